@@ -7,9 +7,12 @@ gradient all-reduce when N > 1) on BASELINE.json's configs[1]: FUNSD-like one-ho
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
-Prints ONE JSON line on rank 0 (contract in the task statement) with two extra objects:
+Prints ONE JSON line on rank 0 (contract in the task statement).  A plain run sets up, warms up, times the steps and
+prints it; with --full it also fills three extra objects (null otherwise):
   roofline     -- the dominant kernel symbol: algorithmic bytes per launch / HIP-event launch time
   cpu_baseline -- the CPU oracle (port of the reference path) timed on this host's cores, N=1 only
+  secondary    -- other configurations of the same step, N=1 only
+--dump-outputs DIR writes what the last timed step computed (loss, updated parameters, gradient, gradient norm) as .npy.
 """
 import argparse
 import json
@@ -41,6 +44,8 @@ def parse():
     ap.add_argument("--graph", action="store_true",
                     help="replay the step as HIP graphs instead of launching eagerly (measured slower on ROCm 7.2: "
                          "6.08 vs 5.73 ms/step; the host keeps up with ~450 launches of ~10 us)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline: roofline, secondary configurations and CPU baseline (each can be left out below)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-roofline", action="store_true")
     ap.add_argument("--no-secondary", action="store_true",
@@ -49,8 +54,34 @@ def parse():
     ap.add_argument("--secondary-steps", type=int, default=30)
     ap.add_argument("--cpu-steps", type=int, default=200)
     ap.add_argument("--cpu-seconds", type=float, default=15.0, help="time budget of the CPU baseline sample")
-    ap.add_argument("--dump-kernels", default="", help="write the per-kernel HIP-event table to this file")
-    return ap.parse_args()
+    ap.add_argument("--dump-kernels", default="", help="write the per-kernel HIP-event table to this file (needs --full)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="write the loss, parameters, gradient and gradient norm of the last timed step to DIR/<name>.npy")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_kernels and not (args.full and not args.no_roofline):
+        ap.error("--dump-kernels needs --full (and the roofline pass)")
+    return args
+
+
+DUMP_MAX_ELEMS = 1 << 21       # per array (8 MB of fp32); the four arrays stay far below 64 MB
+
+
+def dump_outputs(dirname, loss, model, eng):
+    """What the timed step hands its caller, as float32 .npy: the loss it returns, the parameters it updated, and the
+    engine's gradient and gradient norm of that step.  An array longer than DUMP_MAX_ELEMS is written as a fixed, seeded
+    sample of its elements (same length, same positions in every run); `<name>_index.npy` names the positions."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    arrays = {"loss": loss, "parameters": model.flat_parameters, "gradient": eng.flat_grad, "grad_norm": eng.grad_norm}
+    for name, t in arrays.items():
+        a = t.detach().reshape(-1).float().cpu()
+        if a.numel() > DUMP_MAX_ELEMS:
+            idx = torch.randperm(a.numel(), generator=torch.Generator().manual_seed(0))[:DUMP_MAX_ELEMS].sort().values
+            np.save(os.path.join(dirname, name + "_index.npy"), idx.double().numpy())
+            a = a[idx]
+        np.save(os.path.join(dirname, name + ".npy"), a.numpy())
 
 
 def synthetic(B, C, H, W, n_class, seed, device):
@@ -387,9 +418,11 @@ def main():
     tiles = world * args.batch * args.steps
     value = tiles / dt
     loss_val = float(loss)
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, loss, model, eng)     # before the roofline passes below step the model again
 
     roof = None
-    if rank == 0 and not args.no_roofline:
+    if rank == 0 and args.full and not args.no_roofline:
         # the measuring passes below run on rank 0 only: take the gradient exchange out of the step (a collective that
         # only one rank enters would hang); the other ranks wait at the barrier before the process group is torn down
         eng.sync.active = False
@@ -486,13 +519,13 @@ def main():
             roof["whole_step"]["compulsory_mfma_frac"] = round(ach["mfma_frac"], 4)
 
     secondary = None
-    if rank == 0 and world == 1 and not args.no_secondary:
+    if rank == 0 and world == 1 and args.full and not args.no_secondary:
         del eng, model
         torch.cuda.empty_cache()
         secondary = secondary_measurements(args, L, MSAUWrapper, TrainEngine, dev, n_class)
 
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         cpu = cpu_baseline(args, n_class)
 
     if rank == 0:

@@ -80,8 +80,15 @@ def test_attention(tag):
     y, gx, gp = _grad(lambda x, p: O.self_attention(x, p, "attention_block"),
                       g[f"{tag}.x"], g[f"{tag}.gy"], _params(g, tag))
     assert rel_err(y, g[f"{tag}.y"]) < TOL and rel_err(gx, g[f"{tag}.gx"]) < TOL
+    # the f-projection bias adds g_i . b_f to every score of row i of s, a shift the row softmax cancels: its gradient is zero in exact
+    # arithmetic and both sides hold only summation-order noise (~1e-8 of the block's gradients, which the CPU's thread count
+    # and vector width decide) -- it is held to zero on the scale of the block's gradients instead of to the reference's noise
+    scale = max(float(np.abs(g[f"{tag}.g.{k}"]).max()) for k in gp)
     for k, v in gp.items():
-        assert rel_err(v, g[f"{tag}.g.{k}"]) < TOL
+        if k == "attention_block.f.conv.bias":
+            assert float(np.abs(g[f"{tag}.g.{k}"]).max()) < 1e-6 * scale and float(v.abs().max()) < TOL * scale, k
+        else:
+            assert rel_err(v, g[f"{tag}.g.{k}"]) < TOL, k
 
 
 def test_pool():

@@ -5,7 +5,7 @@
 set -o pipefail
 R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/r02cfg4
 mkdir -p "$O" && cd "$R" || exit 1
-A="--channels 768 --stages 2 --no-secondary --no-cpu-baseline"
+A="--channels 768 --stages 2 --full --no-secondary --no-cpu-baseline"
 python bench.py $A --steps 60 --warmup 10 --dump-kernels "$O/r02_cfg4_hip_events.csv" > "$O/r02_cfg4_bench.json" 2> "$O/bench.err" || { tail -5 "$O/bench.err"; exit 1; }
 cut -c1-600 "$O/r02_cfg4_bench.json"
 cd /tmp && export TMPDIR=/tmp
