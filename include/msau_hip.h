@@ -121,6 +121,12 @@ enum {
                                    and MSAU_CONV_MASK_B (the tensor's own stored output y) means v *= (y > 0 ? 1 : y + 1), the derivative of ELU at
                                    the pre-activation.  MSAU_CONV_RELU_IN / MASK_A stay ReLU: the reference's residual block starts with a
                                    hard-wired torch.nn.ReLU (model/model.py:35,39).  Generic kernel only (no fused / row / lean instance). */
+    MSAU_CONV_EXTENT   = 65536, /* ragged batch: `extent` ([B][2] int32 (h, w) of each sample on the OUTPUT grid) -- applied LAST, after bias, masks,
+                                   add, accumulate and activation: a pixel (oy, ox) with oy >= h or ox >= w of its sample is stored as 0.  For
+                                   forward convs, transposed convs (ups = 2) and data gradients (stride = 2 included: its output is the deconv
+                                   input's grid).  Implemented by the generic tile kernel (conv.hip) only: every other instance refuses the flag,
+                                   so it does not combine with HEAD / DOUT / LRN / POOL / IDS / OWNER / NCHW / WGRAD (msau_conv2d_launch_info
+                                   info[7] bit 7 says whether the instance taking the descriptor implements it). */
     MSAU_CONV_HEAD     = 64     /* inference head (kv_model.py:305-313): besides y, write softmax over the Cout real
                                    channels of the (storage-rounded) result to head_probs (fp32 [B][Hout][Wout][Cout],
                                    dense) and the index of its first maximum to head_argmax (uint8 [B][Hout][Wout]).
@@ -160,6 +166,7 @@ typedef struct {
     float* wg_slabs;            /* MSAU_CONV_WGRAD only: [msau_conv2d_rider_slabs()][2][8][16] partial sums, one slab per workgroup */
     int32_t wg_nslabs;          /* MSAU_CONV_WGRAD only: the slab count the caller allocated: the launch refuses to write another number */
     int32_t reserved1;
+    const int32_t* extent;      /* MSAU_CONV_EXTENT only: [B][2] (h, w) of every sample on the output grid (ABI v11)        */
 } msau_conv_desc;
 /* number of slabs an MSAU_CONV_WGRAD launch of this descriptor writes (= its workgroups); 0 if no instance takes the flag */
 int msau_conv2d_rider_slabs(int dtype, const msau_conv_desc* d);
@@ -184,7 +191,8 @@ int msau_conv2d(void* stream, int dtype, const msau_conv_desc* d);
  * info[6] = 1 if a compile-time-specialised "lean" instance (conv_lean.hip) takes the launch, 2 if the chunked-K instance does,
  *           3 if a row-streaming instance (conv_rows.hip) does,
  * info[7] = bit 0: that instance implements MSAU_CONV_HEAD for this descriptor, bit 1: MSAU_CONV_DOUT,
- *           bit 2: MSAU_CONV_LRN, bit 3: MSAU_CONV_POOL, bit 4: MSAU_CONV_IDS, bit 5: MSAU_CONV_OWNER, bit 6: MSAU_CONV_NCHW */
+ *           bit 2: MSAU_CONV_LRN, bit 3: MSAU_CONV_POOL, bit 4: MSAU_CONV_IDS, bit 5: MSAU_CONV_OWNER, bit 6: MSAU_CONV_NCHW,
+ *           bit 7: MSAU_CONV_EXTENT (the instance that takes the descriptor with the flag added implements it) */
 int msau_conv2d_launch_info(int dtype, const msau_conv_desc* d, int32_t* info8);
 
 /* ------------------------------------------------------------------------------------------
@@ -405,6 +413,10 @@ int msau_lrn_bwd(void* stream, int dtype, const void* a, const void* dy, void* d
 int msau_maxpool2x2_fwd(void* stream, int dtype, const void* x, void* y, uint8_t* idx, int B, int H, int W, int Cs);
 int msau_maxpool2x2_bwd(void* stream, int dtype, const void* dy, const uint8_t* idx, void* dx, const void* mask,
                         int B, int H, int W, int Cs, int accumulate);
+/* as msau_maxpool2x2_bwd, for a ragged batch: extent [B][2] (h, w) of every sample on the pool's INPUT grid; dx is written as 0
+ * at the pixels outside it (the gradient a window sends to its zero padding, which an ELU's MASK_B would not remove) */
+int msau_maxpool2x2_bwd_ext(void* stream, int dtype, const void* dy, const uint8_t* idx, void* dx, const void* mask,
+                            int B, int H, int W, int Cs, int accumulate, const int32_t* extent);
 
 /* ------------------------------------------------------------------------------------------
  * Bottleneck self-attention core (model/layers/attention.py:156-162), given the 1x1 projections
@@ -416,6 +428,20 @@ int msau_selfattn_fwd(void* stream, int dtype, const void* f, const void* g, con
                       float* stats /* [B][N][2] */, int B, int N, int Ds, int Cs);
 int msau_selfattn_bwd(void* stream, int dtype, const void* f, const void* g, const void* h, const void* dy,
                       const float* stats, void* df, void* dg, void* dh, float* ws, int B, int N, int Ds, int Cs);
+/* Ragged batch: the bottleneck grid is [H][W] = N positions per sample and sample b covers (h_b, w_b) = extent[b] of it.  Keys
+ * j = (j / W, j % W) outside the sample's extent are excluded from the softmax (P[i][j] = 0: statistics and all four sweeps),
+ * y = x at those columns and dh = 0 at rows outside the extent.  f, g, h, x, dy must be 0 outside the extents (the plan's
+ * invariant); then every output is 0 there.  Masked instances of the same kernels; extent = NULL is msau_selfattn_fwd / _bwd. */
+int msau_selfattn_fwd_ext(void* stream, int dtype, const void* f, const void* g, const void* h, const void* x, void* y,
+                          float* stats, int B, int N, int Ds, int Cs, const int32_t* extent, int W);
+int msau_selfattn_bwd_ext(void* stream, int dtype, const void* f, const void* g, const void* h, const void* dy,
+                          const float* stats, void* df, void* dg, void* dh, float* ws, int B, int N, int Ds, int Cs,
+                          const int32_t* extent, int W);
+
+/* Ragged batch: dst[b][p][y][x][:] = (y < h_b && x < w_b) ? src[b][p][y][x][:] : 0 for a tensor of `planes` planes of H x W pixels of
+ * `pixel_bytes` bytes each per sample (NHWC activation: planes 1, pixel_bytes Cs * esz; int64 labels: 1, 8; NCHW fp32: C, 4).
+ * extent [B][2] int32 (h, w).  src == dst is allowed (in place).  pixel_bytes must be a multiple of 4. */
+int msau_extent_copy(void* stream, const void* src, void* dst, int B, int planes, int H, int W, int pixel_bytes, const int32_t* extent);
 
 /* The data gradients of the attention block's three 1x1 projections (model/layers/attention.py:152-154: f, g: C -> C/8, h: C -> C, all
  * reading the same tensor x) as ONE launch instead of three accumulating msau_conv2d launches:
@@ -586,9 +612,12 @@ enum {
 };
 typedef struct { int32_t kind; int32_t dtype; const void* args; } msau_op;
 typedef struct { const void* a; const void* dy; void* out; int64_t npix; int32_t C, Cs, n; float alpha, beta, k; } msau_lrn_args;
-typedef struct { const void* x_or_dy; void* y_or_dx; uint8_t* idx; const void* mask; int32_t B, H, W, Cs, accumulate; } msau_pool_args;
+/* extent (ABI v11): NULL, or the ragged batch's [B][2] (h, w) of the pool input grid (backward: msau_maxpool2x2_bwd_ext) / of the
+ * attention's bottleneck grid, W columns wide (msau_selfattn_*_ext) */
+typedef struct { const void* x_or_dy; void* y_or_dx; uint8_t* idx; const void* mask; int32_t B, H, W, Cs, accumulate;
+                 const int32_t* extent; } msau_pool_args;
 typedef struct { const void* f; const void* g; const void* h; const void* x_or_dy; void* y; float* stats;
-                 void* df; void* dg; void* dh; float* ws; int32_t B, N, Ds, Cs; } msau_attn_args;
+                 void* df; void* dg; void* dh; float* ws; int32_t B, N, Ds, Cs; const int32_t* extent; int32_t W, reserved0; } msau_attn_args;
 typedef struct { const void* g; int64_t npix; int32_t Cs; float* partials; int32_t nblk; } msau_csum_args;
 typedef struct { const float* slab_arena; float* flat_grads; const msau_unpack_entry* table_dev; int32_t n_entries, max_elems; } msau_reduce_args;
 typedef struct { void* comm; float* buf; int64_t count; } msau_allreduce_args;

@@ -15,6 +15,7 @@ F32, BF16 = 0, 1
 
 CONV_RELU_IN, CONV_RELU_OUT, CONV_ADD, CONV_ACCUM, CONV_MASK_A, CONV_MASK_B, CONV_HEAD, CONV_DOUT = 1, 2, 4, 8, 16, 32, 64, 128
 CONV_LRN, CONV_POOL, CONV_IDS, CONV_OWNER, CONV_NCHW, CONV_WGRAD, CONV_ELU = 256, 512, 1024, 2048, 4096, 8192, 32768
+CONV_EXTENT = 65536
 
 i32, i64, vp, f32 = C.c_int32, C.c_int64, C.c_void_p, C.c_float
 
@@ -25,7 +26,7 @@ class ConvDesc(C.Structure):
                [(n, vp) for n in ("x1", "x2", "wpack", "bias", "add", "mask_a", "mask_b", "y", "head_probs", "head_argmax")] + \
                [("head_classes", i32), ("flags2", i32), ("y2", vp), ("mask_b2", vp)] + \
                [("lrn_alpha_over_n", f32), ("lrn_beta", f32), ("lrn_k", f32), ("reserved0", i32), ("pool_y", vp), ("pool_idx", vp)] + \
-               [("wg_x1", vp), ("wg_slabs", vp), ("wg_nslabs", i32), ("reserved1", i32)]
+               [("wg_x1", vp), ("wg_slabs", vp), ("wg_nslabs", i32), ("reserved1", i32), ("extent", vp)]
 
 
 class ConvPairDesc(C.Structure):
@@ -87,12 +88,12 @@ class LrnArgs(C.Structure):
 
 class PoolArgs(C.Structure):
     _fields_ = [("x_or_dy", vp), ("y_or_dx", vp), ("idx", vp), ("mask", vp)] + \
-               [(n, i32) for n in ("B", "H", "W", "Cs", "accumulate")]
+               [(n, i32) for n in ("B", "H", "W", "Cs", "accumulate")] + [("extent", vp)]
 
 
 class AttnArgs(C.Structure):
     _fields_ = [(n, vp) for n in ("f", "g", "h", "x_or_dy", "y", "stats", "df", "dg", "dh", "ws")] + \
-               [(n, i32) for n in ("B", "N", "Ds", "Cs")]
+               [(n, i32) for n in ("B", "N", "Ds", "Cs")] + [("extent", vp), ("W", i32), ("reserved0", i32)]
 
 
 class CsumArgs(C.Structure):
@@ -176,6 +177,10 @@ _SIGNATURES = {
     "msau_maxpool2x2_bwd": (C.c_int, [vp, C.c_int, vp, vp, vp, vp] + [C.c_int] * 5),
     "msau_selfattn_fwd": (C.c_int, [vp, C.c_int, vp, vp, vp, vp, vp, vp] + [C.c_int] * 4),
     "msau_selfattn_bwd": (C.c_int, [vp, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp, vp] + [C.c_int] * 4),
+    "msau_maxpool2x2_bwd_ext": (C.c_int, [vp, C.c_int, vp, vp, vp, vp] + [C.c_int] * 5 + [vp]),
+    "msau_selfattn_fwd_ext": (C.c_int, [vp, C.c_int, vp, vp, vp, vp, vp, vp] + [C.c_int] * 4 + [vp, C.c_int]),
+    "msau_selfattn_bwd_ext": (C.c_int, [vp, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp, vp] + [C.c_int] * 4 + [vp, C.c_int]),
+    "msau_extent_copy": (C.c_int, [vp, vp, vp] + [C.c_int] * 5 + [vp]),
     "msau_label_counts": (C.c_int, [vp, vp, vp, C.c_int, i64]),
     "msau_label_counts_split": (C.c_int, [vp, vp, vp, C.c_int, i64, C.c_int]),
     "msau_ce_ws_floats": (i64, [i64]),

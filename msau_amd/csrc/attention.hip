@@ -4,6 +4,8 @@
 // (m_i, Z_i) come first (stats kernel) and every other pass recomputes exp(s - m_i)/Z_i on the fly.
 // Round-1 implementation: fp32 VALU, one "own" row per lane, the "other" side staged through LDS and
 // read as broadcasts, rows of the other side split over the 4 waves of a workgroup.
+// EXT instances (ragged batch, msau_selfattn_*_ext): keys j outside the sample's extent on the W-wide grid get P = 0, and the
+// outputs of own positions outside it are the unmasked formula's value at P = 0 (y = x, dh = df = 0).
 #include "msau_common.h"
 
 namespace {
@@ -12,11 +14,12 @@ constexpr int TI = 128;          // rows of the other side staged per step (32 p
 
 enum { MODE_FWD_OUT = 0, MODE_BWD_DH = 1, MODE_BWD_DG = 2, MODE_BWD_DF = 3 };
 
-template <typename T, int DS>
+template <typename T, int DS, bool EXT>
 __global__ __launch_bounds__(256) void attn_stats_kernel(const T* __restrict__ f, const T* __restrict__ g,
-                                                         float* __restrict__ stats, int N) {
+                                                         float* __restrict__ stats, int N, const int32_t* __restrict__ extent, int W) {
     __shared__ float fs[256 * DS];
     const int b = blockIdx.y, i = blockIdx.x * 256 + threadIdx.x;
+    const int eh = EXT ? extent[2 * b] : 0, ew = EXT ? extent[2 * b + 1] : 0;
     float gi[DS];
 #pragma unroll
     for (int d = 0; d < DS; ++d) gi[d] = 0.f;
@@ -44,6 +47,7 @@ __global__ __launch_bounds__(256) void attn_stats_kernel(const T* __restrict__ f
         __syncthreads();
         const int nj = min(256, N - j0);
         for (int jj = 0; jj < nj; ++jj) {
+            if (EXT && !pos_in_extent(j0 + jj, W, eh, ew)) continue;       // (uniform over the workgroup)
             float s = 0.f;
 #pragma unroll
             for (int d = 0; d < DS; ++d) s += gi[d] * fs[jj * DS + d];
@@ -56,11 +60,11 @@ __global__ __launch_bounds__(256) void attn_stats_kernel(const T* __restrict__ f
 }
 
 // LDS row of the "other" side: [DS] vector | m, 1/Z, delta, pad | [CS] vector   (all fp32)
-template <typename T, int DS, int CS, int MODE>
+template <typename T, int DS, int CS, int MODE, bool EXT>
 __global__ __launch_bounds__(256) void attn_pass_kernel(const T* __restrict__ f, const T* __restrict__ g, const T* __restrict__ h,
                                                         const T* __restrict__ xdy,       // x (FWD_OUT) or dy (BWD_*)
                                                         const float* __restrict__ stats, float* __restrict__ delta,
-                                                        T* __restrict__ out, int N) {
+                                                        T* __restrict__ out, int N, const int32_t* __restrict__ extent, int W) {
     constexpr bool OWN_IS_I = (MODE == MODE_BWD_DH || MODE == MODE_BWD_DG);   // own row index is i (a row of s)
     constexpr bool ACC_CS = (MODE == MODE_FWD_OUT || MODE == MODE_BWD_DH);    // accumulate a CS vector (else a DS vector)
     constexpr int ROW = DS + 4 + CS;
@@ -70,6 +74,8 @@ __global__ __launch_bounds__(256) void attn_pass_kernel(const T* __restrict__ f,
     const int b = blockIdx.y, own = blockIdx.x * 64 + lane;
     const bool valid = own < N;
     const size_t ob = (size_t)b * N + (valid ? own : 0);
+    const int eh = EXT ? extent[2 * b] : 0, ew = EXT ? extent[2 * b + 1] : 0;
+    const bool own_in = !EXT || (valid && pos_in_extent(own, W, eh, ew));     // own position inside the sample's extent
 
     // ---- own-side registers
     float ov[DS];                         // f_j (own = j) or g_i (own = i)
@@ -132,6 +138,7 @@ __global__ __launch_bounds__(256) void attn_pass_kernel(const T* __restrict__ f,
         __syncthreads();
         const int rend = min(TI, N - r0);
         for (int r = w * (TI / 4); r < (w + 1) * (TI / 4) && r < rend; ++r) {
+            if (EXT && OWN_IS_I && !pos_in_extent(r0 + r, W, eh, ew)) continue;    // key j outside the extent: P = 0 (uniform over the wave)
             const float* row = sm + r * ROW;
             float s = 0.f;
 #pragma unroll
@@ -167,7 +174,7 @@ __global__ __launch_bounds__(256) void attn_pass_kernel(const T* __restrict__ f,
         float s = 0.f;
 #pragma unroll
         for (int ww = 0; ww < 4; ++ww) s += red[(ww * 64 + lane) * (NACC + 1) + w * PER + c];
-        fin[c] = s;
+        fin[c] = own_in ? s : 0.f;                       // EXT: an own key j outside has P = 0 (y = x, df = 0); an own row i outside: dh = 0
     }
     if constexpr (MODE == MODE_BWD_DH) {
         // delta_i = sum_c h[i][c] * dH[i][c]
@@ -191,43 +198,57 @@ __global__ __launch_bounds__(256) void attn_pass_kernel(const T* __restrict__ f,
     }
 }
 
-template <typename T, int DS, int CS, int MODE>
+template <typename T, int DS, int CS, int MODE, bool EXT>
 int launch_pass(hipStream_t s, const T* f, const T* g, const T* h, const T* xdy, const float* stats, float* delta, T* out,
-                int B, int N) {
+                int B, int N, const int32_t* extent, int W) {
     constexpr int ROW = DS + 4 + CS;
     constexpr int NACC = (MODE == MODE_FWD_OUT || MODE == MODE_BWD_DH) ? CS : DS;
     size_t lds = sizeof(float) * (size_t)max(TI * ROW, 256 * (NACC + 1));
     static bool attr_set = false;
     if (!attr_set) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_pass_kernel<T, DS, CS, MODE>),
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_pass_kernel<T, DS, CS, MODE, EXT>),
                                            hipFuncAttributeMaxDynamicSharedMemorySize, MSAU_LDS_LIMIT);
         if (e != hipSuccess) return msau_set_error(MSAU_ERR_HIP, "attn: hipFuncSetAttribute: %s", hipGetErrorString(e));
         attr_set = true;
     }
-    hipLaunchKernelGGL((attn_pass_kernel<T, DS, CS, MODE>), dim3(cdiv(N, 64), B), dim3(256), lds, s, f, g, h, xdy, stats, delta, out, N);
+    hipLaunchKernelGGL((attn_pass_kernel<T, DS, CS, MODE, EXT>), dim3(cdiv(N, 64), B), dim3(256), lds, s, f, g, h, xdy, stats, delta, out, N,
+                       extent, W);
     MSAU_CHECK_LAUNCH("attn_pass_kernel");
     return 0;
 }
 
-template <typename T, int DS, int CS>
-int attn_fwd_t(hipStream_t s, const void* f, const void* g, const void* h, const void* x, void* y, float* stats, int B, int N) {
+template <typename T, int DS, int CS, bool EXT>
+int attn_fwd_e(hipStream_t s, const void* f, const void* g, const void* h, const void* x, void* y, float* stats, int B, int N,
+               const int32_t* extent, int W) {
     const T* fp = static_cast<const T*>(f); const T* gp = static_cast<const T*>(g);
-    hipLaunchKernelGGL((attn_stats_kernel<T, DS>), dim3(cdiv(N, 256), B), dim3(256), 0, s, fp, gp, stats, N);
+    hipLaunchKernelGGL((attn_stats_kernel<T, DS, EXT>), dim3(cdiv(N, 256), B), dim3(256), 0, s, fp, gp, stats, N, extent, W);
     MSAU_CHECK_LAUNCH("attn_stats_kernel");
-    return launch_pass<T, DS, CS, MODE_FWD_OUT>(s, fp, gp, static_cast<const T*>(h), static_cast<const T*>(x), stats, nullptr,
-                                                static_cast<T*>(y), B, N);
+    return launch_pass<T, DS, CS, MODE_FWD_OUT, EXT>(s, fp, gp, static_cast<const T*>(h), static_cast<const T*>(x), stats, nullptr,
+                                                     static_cast<T*>(y), B, N, extent, W);
+}
+template <typename T, int DS, int CS>
+int attn_fwd_t(hipStream_t s, const void* f, const void* g, const void* h, const void* x, void* y, float* stats, int B, int N,
+               const int32_t* extent, int W) {
+    return extent ? attn_fwd_e<T, DS, CS, true>(s, f, g, h, x, y, stats, B, N, extent, W)
+                  : attn_fwd_e<T, DS, CS, false>(s, f, g, h, x, y, stats, B, N, nullptr, 0);
 }
 
-template <typename T, int DS, int CS>
-int attn_bwd_t(hipStream_t s, const void* f, const void* g, const void* h, const void* dy, const float* stats,
-               void* df, void* dg, void* dh, float* ws, int B, int N) {
+template <typename T, int DS, int CS, bool EXT>
+int attn_bwd_e(hipStream_t s, const void* f, const void* g, const void* h, const void* dy, const float* stats,
+               void* df, void* dg, void* dh, float* ws, int B, int N, const int32_t* extent, int W) {
     const T* fp = static_cast<const T*>(f); const T* gp = static_cast<const T*>(g);
     const T* hp = static_cast<const T*>(h); const T* dyp = static_cast<const T*>(dy);
-    int rc = launch_pass<T, DS, CS, MODE_BWD_DH>(s, fp, gp, hp, dyp, stats, ws, static_cast<T*>(dh), B, N);
+    int rc = launch_pass<T, DS, CS, MODE_BWD_DH, EXT>(s, fp, gp, hp, dyp, stats, ws, static_cast<T*>(dh), B, N, extent, W);
     if (rc) return rc;
-    rc = launch_pass<T, DS, CS, MODE_BWD_DG>(s, fp, gp, hp, dyp, stats, ws, static_cast<T*>(dg), B, N);
+    rc = launch_pass<T, DS, CS, MODE_BWD_DG, EXT>(s, fp, gp, hp, dyp, stats, ws, static_cast<T*>(dg), B, N, extent, W);
     if (rc) return rc;
-    return launch_pass<T, DS, CS, MODE_BWD_DF>(s, fp, gp, hp, dyp, stats, ws, static_cast<T*>(df), B, N);
+    return launch_pass<T, DS, CS, MODE_BWD_DF, EXT>(s, fp, gp, hp, dyp, stats, ws, static_cast<T*>(df), B, N, extent, W);
+}
+template <typename T, int DS, int CS>
+int attn_bwd_t(hipStream_t s, const void* f, const void* g, const void* h, const void* dy, const float* stats,
+               void* df, void* dg, void* dh, float* ws, int B, int N, const int32_t* extent, int W) {
+    return extent ? attn_bwd_e<T, DS, CS, true>(s, f, g, h, dy, stats, df, dg, dh, ws, B, N, extent, W)
+                  : attn_bwd_e<T, DS, CS, false>(s, f, g, h, dy, stats, df, dg, dh, ws, B, N, nullptr, 0);
 }
 
 // ---- any (Ds, Cs): one workgroup per score row / column, run-time channel counts.  O(N^2 (Ds + Cs)) like the tiled
@@ -235,13 +256,16 @@ int attn_bwd_t(hipStream_t s, const void* f, const void* g, const void* h, const
 // of the reference's constructor defaults, where N is a handful of positions).  Same two-pass softmax arithmetic.
 constexpr int kAnyChunk = 2048;            // score-vector chunk held in LDS
 
-template <typename T>
-__global__ __launch_bounds__(256) void attn_any_stats_kernel(const T* __restrict__ f, const T* __restrict__ g, float* __restrict__ stats, int N, int Ds) {
+template <typename T, bool EXT>
+__global__ __launch_bounds__(256) void attn_any_stats_kernel(const T* __restrict__ f, const T* __restrict__ g, float* __restrict__ stats, int N, int Ds,
+                                                             const int32_t* __restrict__ extent, int W) {
     __shared__ float red[256];
     const int b = blockIdx.y, i = blockIdx.x;
+    const int eh = EXT ? extent[2 * b] : 0, ew = EXT ? extent[2 * b + 1] : 0;
     const T* gi = g + ((size_t)b * N + i) * Ds;
     float m = -INFINITY;
     for (int j = threadIdx.x; j < N; j += 256) {
+        if (EXT && !pos_in_extent(j, W, eh, ew)) continue;
         const T* fj = f + ((size_t)b * N + j) * Ds;
         float sc = 0.f;
         for (int d = 0; d < Ds; ++d) sc += (float)gi[d] * (float)fj[d];
@@ -252,6 +276,7 @@ __global__ __launch_bounds__(256) void attn_any_stats_kernel(const T* __restrict
     m = red[0]; __syncthreads();
     float Z = 0.f;
     for (int j = threadIdx.x; j < N; j += 256) {
+        if (EXT && !pos_in_extent(j, W, eh, ew)) continue;
         const T* fj = f + ((size_t)b * N + j) * Ds;
         float sc = 0.f;
         for (int d = 0; d < Ds; ++d) sc += (float)gi[d] * (float)fj[d];
@@ -264,13 +289,15 @@ __global__ __launch_bounds__(256) void attn_any_stats_kernel(const T* __restrict
 
 // MODE 0: y[j] = x[j] + sum_i beta[i,j] h[i]      (block = column j)
 // MODE 1: dh[i] = sum_j beta[i,j] dy[j], delta[i] = h[i] . dh[i]   (block = row i)
-template <typename T, int MODE>
+template <typename T, int MODE, bool EXT>
 __global__ __launch_bounds__(256) void attn_any_mix_kernel(const T* __restrict__ f, const T* __restrict__ g, const T* __restrict__ h,
                                                            const T* __restrict__ xdy, const float* __restrict__ stats, float* __restrict__ delta,
-                                                           T* __restrict__ out, int N, int Ds, int Cs) {
+                                                           T* __restrict__ out, int N, int Ds, int Cs, const int32_t* __restrict__ extent, int W) {
     __shared__ float beta[kAnyChunk];
     __shared__ float red[256];
     const int b = blockIdx.y, me = blockIdx.x;
+    const int eh = EXT ? extent[2 * b] : 0, ew = EXT ? extent[2 * b + 1] : 0;
+    const bool me_in = !EXT || pos_in_extent(me, W, eh, ew);        // EXT: column j (MODE 0) / row i (MODE 1) inside the extent
     const size_t base = (size_t)b * N;
     const T* mine = (MODE == 0 ? f : g) + (base + me) * Ds;          // f_j (column) or g_i (row)
     float acc[4] = {0.f, 0.f, 0.f, 0.f};                             // channels tid, tid + 256, ... (Cs <= 1024)
@@ -284,6 +311,7 @@ __global__ __launch_bounds__(256) void attn_any_mix_kernel(const T* __restrict__
             float sc = 0.f;
             for (int d = 0; d < Ds; ++d) sc += (float)mine[d] * (float)other[d];
             beta[t] = __expf(sc - stats[(base + row) * 2]) / stats[(base + row) * 2 + 1];
+            if (EXT && !(MODE == 0 ? me_in : pos_in_extent(o, W, eh, ew))) beta[t] = 0.f;     // key j outside: P = 0
         }
         __syncthreads();
         const T* src = MODE == 0 ? h : xdy;                            // h[i] or dy[j]
@@ -301,6 +329,7 @@ __global__ __launch_bounds__(256) void attn_any_mix_kernel(const T* __restrict__
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
         const int c = threadIdx.x + 256 * k;
+        if (EXT && !me_in) acc[k] = 0.f;                               // (MODE 1: dh = 0 at rows outside the extent)
         if (c < Cs) {
             if (MODE == 0) out[(base + me) * Cs + c] = (T)((float)xdy[(base + me) * Cs + c] + acc[k]);
             else { out[(base + me) * Cs + c] = (T)acc[k]; dot += (float)h[(base + me) * Cs + c] * acc[k]; }
@@ -315,12 +344,14 @@ __global__ __launch_bounds__(256) void attn_any_mix_kernel(const T* __restrict__
 
 // MODE 2: dg[i] = sum_j dS[i,j] f[j]   (block = row i)      MODE 3: df[j] = sum_i dS[i,j] g[i]   (block = column j)
 //   dS[i,j] = beta[i,j] (h[i] . dy[j] - delta[i])
-template <typename T, int MODE>
+template <typename T, int MODE, bool EXT>
 __global__ __launch_bounds__(256) void attn_any_dscore_kernel(const T* __restrict__ f, const T* __restrict__ g, const T* __restrict__ h,
                                                               const T* __restrict__ dy, const float* __restrict__ stats, const float* __restrict__ delta,
-                                                              T* __restrict__ out, int N, int Ds, int Cs) {
+                                                              T* __restrict__ out, int N, int Ds, int Cs, const int32_t* __restrict__ extent, int W) {
     __shared__ float ds[kAnyChunk];
     const int b = blockIdx.y, me = blockIdx.x;
+    const int eh = EXT ? extent[2 * b] : 0, ew = EXT ? extent[2 * b + 1] : 0;
+    const bool me_in = !EXT || pos_in_extent(me, W, eh, ew);
     const size_t base = (size_t)b * N;
     const T* mine = (MODE == 2 ? g : f) + (base + me) * Ds;
     const T* hv = (MODE == 2 ? h : dy) + (base + me) * Cs;            // h[i] (row) or dy[j] (column)
@@ -338,6 +369,7 @@ __global__ __launch_bounds__(256) void attn_any_dscore_kernel(const T* __restric
             for (int c = 0; c < Cs; ++c) hd += (float)hv[c] * (float)ov[c];
             const float bt = __expf(sc - stats[(base + row) * 2]) / stats[(base + row) * 2 + 1];
             ds[t] = bt * (hd - delta[base + row]);
+            if (EXT && !(MODE == 3 ? me_in : pos_in_extent(o, W, eh, ew))) ds[t] = 0.f;       // key j outside: P = 0
         }
         __syncthreads();
         if ((int)threadIdx.x < Ds) {
@@ -348,28 +380,41 @@ __global__ __launch_bounds__(256) void attn_any_dscore_kernel(const T* __restric
     if ((int)threadIdx.x < Ds) out[(base + me) * Ds + threadIdx.x] = (T)acc;
 }
 
-template <typename T>
-int attn_any_fwd(hipStream_t s, const void* f, const void* g, const void* h, const void* x, void* y, float* stats, int B, int N, int Ds, int Cs) {
+template <typename T, bool EXT>
+int attn_any_fwd_e(hipStream_t s, const void* f, const void* g, const void* h, const void* x, void* y, float* stats, int B, int N, int Ds, int Cs,
+                   const int32_t* extent, int W) {
     MSAU_CHECK_ARG(Ds % 8 == 0 && Cs % 8 == 0 && Ds <= 256 && Cs <= 1024 && N <= 65535 && B <= 65535, "selfattn: unsupported (Ds,Cs,N)=(%d,%d,%d)", Ds, Cs, N);
     const T* fp = static_cast<const T*>(f); const T* gp = static_cast<const T*>(g);
-    hipLaunchKernelGGL(attn_any_stats_kernel<T>, dim3(N, B), dim3(256), 0, s, fp, gp, stats, N, Ds);
-    hipLaunchKernelGGL((attn_any_mix_kernel<T, 0>), dim3(N, B), dim3(256), 0, s, fp, gp, static_cast<const T*>(h), static_cast<const T*>(x), stats,
-                       nullptr, static_cast<T*>(y), N, Ds, Cs);
+    hipLaunchKernelGGL((attn_any_stats_kernel<T, EXT>), dim3(N, B), dim3(256), 0, s, fp, gp, stats, N, Ds, extent, W);
+    hipLaunchKernelGGL((attn_any_mix_kernel<T, 0, EXT>), dim3(N, B), dim3(256), 0, s, fp, gp, static_cast<const T*>(h), static_cast<const T*>(x), stats,
+                       nullptr, static_cast<T*>(y), N, Ds, Cs, extent, W);
     MSAU_CHECK_LAUNCH("attn_any_fwd");
     return 0;
 }
-
 template <typename T>
-int attn_any_bwd(hipStream_t s, const void* f, const void* g, const void* h, const void* dy, const float* stats, void* df, void* dg, void* dh,
-                 float* ws, int B, int N, int Ds, int Cs) {
+int attn_any_fwd(hipStream_t s, const void* f, const void* g, const void* h, const void* x, void* y, float* stats, int B, int N, int Ds, int Cs,
+                 const int32_t* extent, int W) {
+    return extent ? attn_any_fwd_e<T, true>(s, f, g, h, x, y, stats, B, N, Ds, Cs, extent, W)
+                  : attn_any_fwd_e<T, false>(s, f, g, h, x, y, stats, B, N, Ds, Cs, nullptr, 0);
+}
+
+template <typename T, bool EXT>
+int attn_any_bwd_e(hipStream_t s, const void* f, const void* g, const void* h, const void* dy, const float* stats, void* df, void* dg, void* dh,
+                   float* ws, int B, int N, int Ds, int Cs, const int32_t* extent, int W) {
     MSAU_CHECK_ARG(Ds % 8 == 0 && Cs % 8 == 0 && Ds <= 256 && Cs <= 1024 && N <= 65535 && B <= 65535, "selfattn: unsupported (Ds,Cs,N)=(%d,%d,%d)", Ds, Cs, N);
     const T* fp = static_cast<const T*>(f); const T* gp = static_cast<const T*>(g);
     const T* hp = static_cast<const T*>(h); const T* dyp = static_cast<const T*>(dy);
-    hipLaunchKernelGGL((attn_any_mix_kernel<T, 1>), dim3(N, B), dim3(256), 0, s, fp, gp, hp, dyp, stats, ws, static_cast<T*>(dh), N, Ds, Cs);
-    hipLaunchKernelGGL((attn_any_dscore_kernel<T, 2>), dim3(N, B), dim3(256), 0, s, fp, gp, hp, dyp, stats, ws, static_cast<T*>(dg), N, Ds, Cs);
-    hipLaunchKernelGGL((attn_any_dscore_kernel<T, 3>), dim3(N, B), dim3(256), 0, s, fp, gp, hp, dyp, stats, ws, static_cast<T*>(df), N, Ds, Cs);
+    hipLaunchKernelGGL((attn_any_mix_kernel<T, 1, EXT>), dim3(N, B), dim3(256), 0, s, fp, gp, hp, dyp, stats, ws, static_cast<T*>(dh), N, Ds, Cs, extent, W);
+    hipLaunchKernelGGL((attn_any_dscore_kernel<T, 2, EXT>), dim3(N, B), dim3(256), 0, s, fp, gp, hp, dyp, stats, ws, static_cast<T*>(dg), N, Ds, Cs, extent, W);
+    hipLaunchKernelGGL((attn_any_dscore_kernel<T, 3, EXT>), dim3(N, B), dim3(256), 0, s, fp, gp, hp, dyp, stats, ws, static_cast<T*>(df), N, Ds, Cs, extent, W);
     MSAU_CHECK_LAUNCH("attn_any_bwd");
     return 0;
+}
+template <typename T>
+int attn_any_bwd(hipStream_t s, const void* f, const void* g, const void* h, const void* dy, const float* stats, void* df, void* dg, void* dh,
+                 float* ws, int B, int N, int Ds, int Cs, const int32_t* extent, int W) {
+    return extent ? attn_any_bwd_e<T, true>(s, f, g, h, dy, stats, df, dg, dh, ws, B, N, Ds, Cs, extent, W)
+                  : attn_any_bwd_e<T, false>(s, f, g, h, dy, stats, df, dg, dh, ws, B, N, Ds, Cs, nullptr, 0);
 }
 
 #define ATTN_DISPATCH(FN, ...)                                                                      \
@@ -383,15 +428,15 @@ int attn_any_bwd(hipStream_t s, const void* f, const void* g, const void* h, con
 
 template <typename T>
 int attn_fwd_d(hipStream_t s, const void* f, const void* g, const void* h, const void* x, void* y, float* stats,
-               int B, int N, int Ds, int Cs) {
-    ATTN_DISPATCH(attn_fwd_t, s, f, g, h, x, y, stats, B, N);
-    return attn_any_fwd<T>(s, f, g, h, x, y, stats, B, N, Ds, Cs);
+               int B, int N, int Ds, int Cs, const int32_t* extent, int W) {
+    ATTN_DISPATCH(attn_fwd_t, s, f, g, h, x, y, stats, B, N, extent, W);
+    return attn_any_fwd<T>(s, f, g, h, x, y, stats, B, N, Ds, Cs, extent, W);
 }
 template <typename T>
 int attn_bwd_d(hipStream_t s, const void* f, const void* g, const void* h, const void* dy, const float* stats,
-               void* df, void* dg, void* dh, float* ws, int B, int N, int Ds, int Cs) {
-    ATTN_DISPATCH(attn_bwd_t, s, f, g, h, dy, stats, df, dg, dh, ws, B, N);
-    return attn_any_bwd<T>(s, f, g, h, dy, stats, df, dg, dh, ws, B, N, Ds, Cs);
+               void* df, void* dg, void* dh, float* ws, int B, int N, int Ds, int Cs, const int32_t* extent, int W) {
+    ATTN_DISPATCH(attn_bwd_t, s, f, g, h, dy, stats, df, dg, dh, ws, B, N, extent, W);
+    return attn_any_bwd<T>(s, f, g, h, dy, stats, df, dg, dh, ws, B, N, Ds, Cs, extent, W);
 }
 
 }  // namespace
@@ -399,27 +444,40 @@ int attn_bwd_d(hipStream_t s, const void* f, const void* g, const void* h, const
 // bf16 instances on the matrix cores (attention_mfma.hip)
 int msau_attn_mfma_supported(int Ds, int Cs, int N);
 int msau_attn_mfma_fwd(hipStream_t s, const void* f, const void* g, const void* h, const void* x, void* y, float* stats,
-                       int B, int N, int Ds, int Cs);
+                       int B, int N, int Ds, int Cs, const int32_t* extent, int W);
 int msau_attn_mfma_bwd(hipStream_t s, const void* f, const void* g, const void* h, const void* dy, const float* stats,
-                       void* df, void* dg, void* dh, float* ws, int B, int N, int Ds, int Cs);
+                       void* df, void* dg, void* dh, float* ws, int B, int N, int Ds, int Cs, const int32_t* extent, int W);
 
 extern "C" int msau_selfattn_fwd(void* stream, int dtype, const void* f, const void* g, const void* h, const void* x, void* y,
                                  float* stats, int B, int N, int Ds, int Cs) {
-    MSAU_CHECK_ARG(f && g && h && x && y && stats && B > 0 && N > 0, "selfattn_fwd: bad args");
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    if (dtype == MSAU_F32) return attn_fwd_d<float>(s, f, g, h, x, y, stats, B, N, Ds, Cs);
-    if (dtype == MSAU_BF16 && msau_attn_mfma_supported(Ds, Cs, N)) return msau_attn_mfma_fwd(s, f, g, h, x, y, stats, B, N, Ds, Cs);
-    if (dtype == MSAU_BF16) return attn_fwd_d<bf16_t>(s, f, g, h, x, y, stats, B, N, Ds, Cs);
-    return msau_set_error(MSAU_ERR_ARG, "selfattn_fwd: bad dtype");
+    return msau_selfattn_fwd_ext(stream, dtype, f, g, h, x, y, stats, B, N, Ds, Cs, nullptr, 0);
 }
 
 extern "C" int msau_selfattn_bwd(void* stream, int dtype, const void* f, const void* g, const void* h, const void* dy,
                                  const float* stats, void* df, void* dg, void* dh, float* ws, int B, int N, int Ds, int Cs) {
-    MSAU_CHECK_ARG(f && g && h && dy && stats && df && dg && dh && ws && B > 0 && N > 0, "selfattn_bwd: bad args");
+    return msau_selfattn_bwd_ext(stream, dtype, f, g, h, dy, stats, df, dg, dh, ws, B, N, Ds, Cs, nullptr, 0);
+}
+
+extern "C" int msau_selfattn_fwd_ext(void* stream, int dtype, const void* f, const void* g, const void* h, const void* x, void* y,
+                                     float* stats, int B, int N, int Ds, int Cs, const int32_t* extent, int W) {
+    MSAU_CHECK_ARG(f && g && h && x && y && stats && B > 0 && N > 0, "selfattn_fwd: bad args");
+    MSAU_CHECK_ARG(!extent || (W > 0 && N % W == 0), "selfattn_fwd: extent needs the grid width W (N = %d, W = %d)", N, W);
     hipStream_t s = static_cast<hipStream_t>(stream);
-    if (dtype == MSAU_F32) return attn_bwd_d<float>(s, f, g, h, dy, stats, df, dg, dh, ws, B, N, Ds, Cs);
+    if (dtype == MSAU_F32) return attn_fwd_d<float>(s, f, g, h, x, y, stats, B, N, Ds, Cs, extent, W);
+    if (dtype == MSAU_BF16 && msau_attn_mfma_supported(Ds, Cs, N)) return msau_attn_mfma_fwd(s, f, g, h, x, y, stats, B, N, Ds, Cs, extent, W);
+    if (dtype == MSAU_BF16) return attn_fwd_d<bf16_t>(s, f, g, h, x, y, stats, B, N, Ds, Cs, extent, W);
+    return msau_set_error(MSAU_ERR_ARG, "selfattn_fwd: bad dtype");
+}
+
+extern "C" int msau_selfattn_bwd_ext(void* stream, int dtype, const void* f, const void* g, const void* h, const void* dy,
+                                     const float* stats, void* df, void* dg, void* dh, float* ws, int B, int N, int Ds, int Cs,
+                                     const int32_t* extent, int W) {
+    MSAU_CHECK_ARG(f && g && h && dy && stats && df && dg && dh && ws && B > 0 && N > 0, "selfattn_bwd: bad args");
+    MSAU_CHECK_ARG(!extent || (W > 0 && N % W == 0), "selfattn_bwd: extent needs the grid width W (N = %d, W = %d)", N, W);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (dtype == MSAU_F32) return attn_bwd_d<float>(s, f, g, h, dy, stats, df, dg, dh, ws, B, N, Ds, Cs, extent, W);
     if (dtype == MSAU_BF16 && msau_attn_mfma_supported(Ds, Cs, N))
-        return msau_attn_mfma_bwd(s, f, g, h, dy, stats, df, dg, dh, ws, B, N, Ds, Cs);
-    if (dtype == MSAU_BF16) return attn_bwd_d<bf16_t>(s, f, g, h, dy, stats, df, dg, dh, ws, B, N, Ds, Cs);
+        return msau_attn_mfma_bwd(s, f, g, h, dy, stats, df, dg, dh, ws, B, N, Ds, Cs, extent, W);
+    if (dtype == MSAU_BF16) return attn_bwd_d<bf16_t>(s, f, g, h, dy, stats, df, dg, dh, ws, B, N, Ds, Cs, extent, W);
     return msau_set_error(MSAU_ERR_ARG, "selfattn_bwd: bad dtype");
 }

@@ -14,6 +14,9 @@
 //   mode DG (own i, sweep j): ds = P (dy_j . h_i - delta_i) ; acc[d][i] += f^T[d][j] ds   -> dg
 //   mode DF (own j, sweep i): ds = P (h_i . dy_j - delta_i) ; acc[d][j] += g^T[d][i] ds   -> df
 // plus a statistics kernel (row max m_i and row sum Z_i of exp).
+// EXT instances (ragged batch, msau_selfattn_*_ext): keys j outside the sample's extent on the W-wide grid get P = 0 -- left out of
+// the statistics, and in the own-i sweeps (DH, DG) a sweep row j outside carries lse2 = 3e38 like a row beyond N; the outputs of
+// own positions outside the extent are the value at P = 0 (y = x, dh = dg = df = 0).
 #include "msau_common.h"
 #include <type_traits>
 
@@ -78,9 +81,9 @@ __device__ __forceinline__ float max3f(float a, float b, float c) { return max2f
 
 constexpr int kStatOG = 6, kStatNT = 64 * kStatOG * 2;
 
-template <int DS>
+template <int DS, bool EXT>
 __global__ __launch_bounds__(kStatNT) void attn_stats_mfma(const bf16_t* __restrict__ f, const bf16_t* __restrict__ g,
-                                                           float* __restrict__ stats, int N) {
+                                                           float* __restrict__ stats, int N, const int32_t* __restrict__ extent, int W) {
     extern __shared__ __align__(16) unsigned char smem[];
     constexpr int OG = kStatOG, NT = kStatNT, KG = DS / 8, RB = DS * 2;
     const int b = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wave_all = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -108,7 +111,8 @@ __global__ __launch_bounds__(kStatNT) void attn_stats_mfma(const bf16_t* __restr
         return __builtin_amdgcn_mfma_f32_16x16x32_bf16(afrag, bfrag, f32x4{0.f, 0.f, 0.f, 0.f}, 0, 0, 0);
     };
     const bool tail = (N & 15) != 0;                                 // the LAST tile has columns beyond N
-    const int tf = (tail && t1 == T) ? t1 - 1 : t1;                  // full tiles end here
+    const int tf = EXT ? t0 : (tail && t1 == T) ? t1 - 1 : t1;       // full tiles end here (EXT: every tile tests its columns)
+    const int eh = EXT ? extent[2 * b] : 0, ew = EXT ? extent[2 * b + 1] : 0;
     float m[4], Z[4];
 #pragma unroll
     for (int r = 0; r < 4; ++r) { m[r] = -1e30f; Z[r] = 0.f; }
@@ -123,7 +127,7 @@ __global__ __launch_bounds__(kStatNT) void attn_stats_mfma(const bf16_t* __restr
     }
     for (; t < t1; ++t) {
         const f32x4 s = score(t);
-        const bool valid = t * 16 + lr < N;
+        const bool valid = t * 16 + lr < N && (!EXT || pos_in_extent(t * 16 + lr, W, eh, ew));
 #pragma unroll
         for (int r = 0; r < 4; ++r) m[r] = valid ? max2f(m[r], s[r]) : m[r];
     }
@@ -148,7 +152,7 @@ __global__ __launch_bounds__(kStatNT) void attn_stats_mfma(const bf16_t* __restr
     }
     for (; t < t1; ++t) {
         const f32x4 s = score(t);
-        const bool valid = t * 16 + lr < N;
+        const bool valid = t * 16 + lr < N && (!EXT || pos_in_extent(t * 16 + lr, W, eh, ew));
 #pragma unroll
         for (int r = 0; r < 4; ++r) Z[r] += valid ? __builtin_amdgcn_exp2f(__builtin_fmaf(s[r], LOG2E, -ml[r])) : 0.f;
     }
@@ -187,11 +191,11 @@ __global__ __launch_bounds__(kStatNT) void attn_stats_mfma(const bf16_t* __restr
 //   * a full chunk's steps are unrolled phase by phase -- all score tiles, then all exponentials, then all second products --
 //     so that the reads and MFMAs of one step hide behind the arithmetic of another.
 // ---------------------------------------------------------------------------------------------
-template <int DS, int CS, int MODE>
+template <int DS, int CS, int MODE, bool EXT>
 __device__ __forceinline__ void attn_sweep_body(const bf16_t* __restrict__ f, const bf16_t* __restrict__ g,
                                                 const bf16_t* __restrict__ h, const bf16_t* __restrict__ xdy,
                                                 const float* __restrict__ stats, float* __restrict__ delta,
-                                                bf16_t* __restrict__ out, int N) {
+                                                bf16_t* __restrict__ out, int N, const int32_t* __restrict__ extent, int W) {
     constexpr bool OWN_I = (MODE == M_DH || MODE == M_DG);        // own positions are rows of s
     constexpr bool ACC_C = (MODE == M_O || MODE == M_DH);         // second product over the C tensor
     constexpr int CTC = CS / 16, KSC = CS / 32, KG = DS / 8;
@@ -206,7 +210,7 @@ __device__ __forceinline__ void attn_sweep_body(const bf16_t* __restrict__ f, co
     extern __shared__ __align__(16) unsigned char smem[];
     unsigned char* vs = smem;                                     // sweep-side d-vectors  [CHUNK][DS]
     unsigned char* ts = smem + VS_BYTES;                          // sweep-side C tensor   [CHUNK][CS] (padded)
-    float* st_l = reinterpret_cast<float*>(smem + VS_BYTES + TS_BYTES);      // [CHUNK] lse2 of the sweep rows (own = j modes)
+    float* st_l = reinterpret_cast<float*>(smem + VS_BYTES + TS_BYTES);      // [CHUNK] lse2 of the sweep rows (own = j modes; EXT own = i: 0 / 3e38)
     float* st_d = st_l + CHUNK;                                              // [CHUNK] delta of the sweep rows (mode DF)
 
     // SW waves share a group of 16 own positions and split the swept rows between them (wave w takes the 32-row steps
@@ -219,6 +223,8 @@ __device__ __forceinline__ void attn_sweep_body(const bf16_t* __restrict__ f, co
     const int own = o0 + lr;
     const bool own_ok = own < N;
     const size_t ob = (size_t)b * N + (own_ok ? own : 0);
+    const int eh = EXT ? extent[2 * b] : 0, ew = EXT ? extent[2 * b + 1] : 0;
+    const bool own_in = !EXT || (own_ok && pos_in_extent(own, W, eh, ew));      // own position inside the sample's extent
 
     const bf16_t* sweep_v = OWN_I ? f : g;                        // d-vectors of the sweep side
     const bf16_t* own_v = OWN_I ? g : f;
@@ -275,6 +281,8 @@ __device__ __forceinline__ void attn_sweep_body(const bf16_t* __restrict__ f, co
             ptn[it] = zero8<bf16_t>();
             if (idx < CHUNK * (CS / 8) && r0 + r < N) ptn[it] = load8<bf16_t>(sweep_t + ((size_t)b * N + r0 + r) * CS + c * 8);
         }
+        if (OWN_I && EXT && tid < CHUNK)                         // key j outside the extent (or beyond N): P = exp2(-huge) = 0
+            pl = (r0 + tid < N && pos_in_extent(r0 + tid, W, eh, ew)) ? 0.f : 3e38f;
         if (!OWN_I && tid < CHUNK) {
             pl = 3e38f; pdl = 0.f;                                // rows beyond N: P = exp2(-huge) = 0
             if (r0 + tid < N) {
@@ -326,8 +334,12 @@ __device__ __forceinline__ void attn_sweep_body(const bf16_t* __restrict__ f, co
 #pragma unroll
             for (int t = 0; t < 2; ++t) {
                 f32x4 ll;
-                if constexpr (OWN_I) ll = f32x4{olse, olse, olse, olse};
-                else ll = *reinterpret_cast<const f32x4*>(plse + k * SW * 32 + t * 16);
+                if constexpr (OWN_I) {
+                    ll = f32x4{olse, olse, olse, olse};
+                    if constexpr (EXT) ll += *reinterpret_cast<const f32x4*>(plse + k * SW * 32 + t * 16);
+                } else {
+                    ll = *reinterpret_cast<const f32x4*>(plse + k * SW * 32 + t * 16);
+                }
 #pragma unroll
                 for (int r = 0; r < 4; ++r) S[k][t][r] = __builtin_amdgcn_exp2f(__builtin_fmaf(S[k][t][r], LOG2E, -ll[r]));
                 if constexpr (!ACC_C) {
@@ -369,7 +381,7 @@ __device__ __forceinline__ void attn_sweep_body(const bf16_t* __restrict__ f, co
             const int idx = tid + it * NT, r = idx / (CS / 8), c = idx % (CS / 8);
             if (idx < CHUNK * (CS / 8)) *reinterpret_cast<bf16x8*>(ts + r * TS + c * 16) = ptn[it];
         }
-        if (!OWN_I && tid < CHUNK) { st_l[tid] = pl; st_d[tid] = pdl; }
+        if ((!OWN_I || EXT) && tid < CHUNK) { st_l[tid] = pl; st_d[tid] = pdl; }
         __syncthreads();
         if (r0 < 6 * CHUNK) ASTAMP(1 + 2 * (r0 / CHUNK));
         if (r0 + CHUNK < N) issue(r0 + CHUNK);
@@ -407,7 +419,7 @@ __device__ __forceinline__ void attn_sweep_body(const bf16_t* __restrict__ f, co
 #pragma unroll
         for (int ct = 0; ct < CTC; ++ct) {
             const int c = ct * 16 + lg * 4;
-            f32x4 v = acc[ct];
+            f32x4 v = own_in ? acc[ct] : f32x4{0.f, 0.f, 0.f, 0.f};
             if (own_ok) {
                 if (MODE == M_O) {
                     bf16x4 xv = load4<bf16_t>(xdy + ob * CS + c);
@@ -434,83 +446,86 @@ __device__ __forceinline__ void attn_sweep_body(const bf16_t* __restrict__ f, co
         if (own_ok && dd < DS) {
             bf16x4 o;
 #pragma unroll
-            for (int r = 0; r < 4; ++r) o[r] = (bf16_t)acc[0][r];
+            for (int r = 0; r < 4; ++r) o[r] = own_in ? (bf16_t)acc[0][r] : (bf16_t)0.f;
             store4<bf16_t>(out + ob * DS + dd, o);
         }
     }
 }
 
-template <int DS, int CS, int MODE>
+template <int DS, int CS, int MODE, bool EXT>
 __global__ __launch_bounds__(SweepGeom<CS>::NT, CS <= 64 ? SweepGeom<CS>::NT / 256 : 1) void attn_sweep_mfma(const bf16_t* __restrict__ f, const bf16_t* __restrict__ g,
                                                        const bf16_t* __restrict__ h, const bf16_t* __restrict__ xdy,
                                                        const float* __restrict__ stats, float* __restrict__ delta,
-                                                       bf16_t* __restrict__ out, int N) {
-    attn_sweep_body<DS, CS, MODE>(f, g, h, xdy, stats, delta, out, N);
+                                                       bf16_t* __restrict__ out, int N, const int32_t* __restrict__ extent, int W) {
+    attn_sweep_body<DS, CS, MODE, EXT>(f, g, h, xdy, stats, delta, out, N, extent, W);
 }
 
 // dg and df need the same inputs (delta from the DH sweep) and nothing from each other: one launch, blockIdx.z picks
 // the mode, twice the workgroups in flight (the sweeps are latency-bound at 336 workgroups).
-template <int DS, int CS>
+template <int DS, int CS, bool EXT>
 __global__ __launch_bounds__(SweepGeom<CS>::NT, CS <= 64 ? SweepGeom<CS>::NT / 256 : 1) void attn_sweep_dgdf(const bf16_t* __restrict__ f, const bf16_t* __restrict__ g,
                                                        const bf16_t* __restrict__ h, const bf16_t* __restrict__ dy,
                                                        const float* __restrict__ stats, float* __restrict__ delta,
-                                                       bf16_t* __restrict__ dg, bf16_t* __restrict__ df, int N) {
-    if (blockIdx.z == 0) attn_sweep_body<DS, CS, M_DG>(f, g, h, dy, stats, delta, dg, N);
-    else attn_sweep_body<DS, CS, M_DF>(f, g, h, dy, stats, delta, df, N);
+                                                       bf16_t* __restrict__ dg, bf16_t* __restrict__ df, int N,
+                                                       const int32_t* __restrict__ extent, int W) {
+    if (blockIdx.z == 0) attn_sweep_body<DS, CS, M_DG, EXT>(f, g, h, dy, stats, delta, dg, N, extent, W);
+    else attn_sweep_body<DS, CS, M_DF, EXT>(f, g, h, dy, stats, delta, df, N, extent, W);
 }
 
-template <int DS, int CS, int MODE>
+template <int DS, int CS, int MODE, bool EXT>
 int launch_sweep(hipStream_t s, const bf16_t* f, const bf16_t* g, const bf16_t* h, const bf16_t* xdy, const float* stats,
-                 float* delta, bf16_t* out, int B, int N) {
+                 float* delta, bf16_t* out, int B, int N, const int32_t* extent, int W) {
     using G = SweepGeom<CS>;
     constexpr int lds = G::template lds<DS>();
     static bool attr_set = false;
     if (!attr_set && lds > 60 * 1024) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_sweep_mfma<DS, CS, MODE>), hipFuncAttributeMaxDynamicSharedMemorySize, MSAU_LDS_LIMIT);
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_sweep_mfma<DS, CS, MODE, EXT>), hipFuncAttributeMaxDynamicSharedMemorySize, MSAU_LDS_LIMIT);
         if (e != hipSuccess) return msau_set_error(MSAU_ERR_HIP, "attn: hipFuncSetAttribute: %s", hipGetErrorString(e));
         attr_set = true;
     }
-    hipLaunchKernelGGL((attn_sweep_mfma<DS, CS, MODE>), dim3(cdiv(N, G::OG * 16), B), dim3(G::NT), lds, s, f, g, h, xdy, stats, delta, out, N);
+    hipLaunchKernelGGL((attn_sweep_mfma<DS, CS, MODE, EXT>), dim3(cdiv(N, G::OG * 16), B), dim3(G::NT), lds, s, f, g, h, xdy, stats, delta, out, N,
+                       extent, W);
     MSAU_CHECK_LAUNCH("attn_sweep_mfma");
     return 0;
 }
 
-template <int DS, int CS>
-int fwd_t(hipStream_t s, const void* f, const void* g, const void* h, const void* x, void* y, float* stats, int B, int N) {
+template <int DS, int CS, bool EXT>
+int fwd_t(hipStream_t s, const void* f, const void* g, const void* h, const void* x, void* y, float* stats, int B, int N,
+          const int32_t* extent, int W) {
     const bf16_t* fp = static_cast<const bf16_t*>(f); const bf16_t* gp = static_cast<const bf16_t*>(g);
     const int Npad = (N + 15) & ~15;
     const size_t lds = (size_t)Npad * DS * 2 + kStatOG * 16 * 2 * 4;
     if (lds > 150 * 1024) return msau_set_error(MSAU_ERR_LDS, "selfattn: N=%d too large for the statistics kernel", N);
     static bool attr_set = false;
     if (!attr_set) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_stats_mfma<DS>),
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_stats_mfma<DS, EXT>),
                                            hipFuncAttributeMaxDynamicSharedMemorySize, MSAU_LDS_LIMIT);
         if (e != hipSuccess) return msau_set_error(MSAU_ERR_HIP, "attn: hipFuncSetAttribute: %s", hipGetErrorString(e));
         attr_set = true;
     }
-    hipLaunchKernelGGL((attn_stats_mfma<DS>), dim3(cdiv(N, kStatOG * 16), B), dim3(kStatNT), lds, s, fp, gp, stats, N);
+    hipLaunchKernelGGL((attn_stats_mfma<DS, EXT>), dim3(cdiv(N, kStatOG * 16), B), dim3(kStatNT), lds, s, fp, gp, stats, N, extent, W);
     MSAU_CHECK_LAUNCH("attn_stats_mfma");
-    return launch_sweep<DS, CS, M_O>(s, fp, gp, static_cast<const bf16_t*>(h), static_cast<const bf16_t*>(x), stats, nullptr,
-                                     static_cast<bf16_t*>(y), B, N);
+    return launch_sweep<DS, CS, M_O, EXT>(s, fp, gp, static_cast<const bf16_t*>(h), static_cast<const bf16_t*>(x), stats, nullptr,
+                                          static_cast<bf16_t*>(y), B, N, extent, W);
 }
 
-template <int DS, int CS>
+template <int DS, int CS, bool EXT>
 int bwd_t(hipStream_t s, const void* f, const void* g, const void* h, const void* dy, const float* stats, void* df, void* dg,
-          void* dh, float* ws, int B, int N) {
+          void* dh, float* ws, int B, int N, const int32_t* extent, int W) {
     const bf16_t* fp = static_cast<const bf16_t*>(f); const bf16_t* gp = static_cast<const bf16_t*>(g);
     const bf16_t* hp = static_cast<const bf16_t*>(h); const bf16_t* dyp = static_cast<const bf16_t*>(dy);
-    int rc = launch_sweep<DS, CS, M_DH>(s, fp, gp, hp, dyp, stats, ws, static_cast<bf16_t*>(dh), B, N);
+    int rc = launch_sweep<DS, CS, M_DH, EXT>(s, fp, gp, hp, dyp, stats, ws, static_cast<bf16_t*>(dh), B, N, extent, W);
     if (rc) return rc;
     using G = SweepGeom<CS>;
     constexpr int lds = G::template lds<DS>();
     static bool attr_set = false;
     if (!attr_set && lds > 60 * 1024) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_sweep_dgdf<DS, CS>), hipFuncAttributeMaxDynamicSharedMemorySize, MSAU_LDS_LIMIT);
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_sweep_dgdf<DS, CS, EXT>), hipFuncAttributeMaxDynamicSharedMemorySize, MSAU_LDS_LIMIT);
         if (e != hipSuccess) return msau_set_error(MSAU_ERR_HIP, "attn: hipFuncSetAttribute: %s", hipGetErrorString(e));
         attr_set = true;
     }
-    hipLaunchKernelGGL((attn_sweep_dgdf<DS, CS>), dim3(cdiv(N, G::OG * 16), B, 2), dim3(G::NT), lds, s, fp, gp, hp, dyp, stats, ws,
-                       static_cast<bf16_t*>(dg), static_cast<bf16_t*>(df), N);
+    hipLaunchKernelGGL((attn_sweep_dgdf<DS, CS, EXT>), dim3(cdiv(N, G::OG * 16), B, 2), dim3(G::NT), lds, s, fp, gp, hp, dyp, stats, ws,
+                       static_cast<bf16_t*>(dg), static_cast<bf16_t*>(df), N, extent, W);
     MSAU_CHECK_LAUNCH("attn_sweep_dgdf");
     return 0;
 }
@@ -524,18 +539,20 @@ int msau_attn_mfma_supported(int Ds, int Cs, int N) {
     return (size_t)((N + 15) & ~15) * Ds * 2 + kStatOG * 16 * 2 * 4 <= 150 * 1024;
 }
 
+#define ATTN_MFMA_CASE(FN, DS, CS, ...) \
+    if (Ds == DS && Cs == CS) return extent ? FN<DS, CS, true>(__VA_ARGS__, extent, W) : FN<DS, CS, false>(__VA_ARGS__, nullptr, 0);
 int msau_attn_mfma_fwd(hipStream_t s, const void* f, const void* g, const void* h, const void* x, void* y, float* stats,
-                       int B, int N, int Ds, int Cs) {
-    if (Ds == 8 && Cs == 32) return fwd_t<8, 32>(s, f, g, h, x, y, stats, B, N);
-    if (Ds == 8 && Cs == 64) return fwd_t<8, 64>(s, f, g, h, x, y, stats, B, N);
-    if (Ds == 16 && Cs == 128) return fwd_t<16, 128>(s, f, g, h, x, y, stats, B, N);
+                       int B, int N, int Ds, int Cs, const int32_t* extent, int W) {
+    ATTN_MFMA_CASE(fwd_t, 8, 32, s, f, g, h, x, y, stats, B, N)
+    ATTN_MFMA_CASE(fwd_t, 8, 64, s, f, g, h, x, y, stats, B, N)
+    ATTN_MFMA_CASE(fwd_t, 16, 128, s, f, g, h, x, y, stats, B, N)
     return msau_set_error(MSAU_ERR_ARG, "selfattn mfma: unsupported (Ds,Cs)=(%d,%d)", Ds, Cs);
 }
 
 int msau_attn_mfma_bwd(hipStream_t s, const void* f, const void* g, const void* h, const void* dy, const float* stats,
-                       void* df, void* dg, void* dh, float* ws, int B, int N, int Ds, int Cs) {
-    if (Ds == 8 && Cs == 32) return bwd_t<8, 32>(s, f, g, h, dy, stats, df, dg, dh, ws, B, N);
-    if (Ds == 8 && Cs == 64) return bwd_t<8, 64>(s, f, g, h, dy, stats, df, dg, dh, ws, B, N);
-    if (Ds == 16 && Cs == 128) return bwd_t<16, 128>(s, f, g, h, dy, stats, df, dg, dh, ws, B, N);
+                       void* df, void* dg, void* dh, float* ws, int B, int N, int Ds, int Cs, const int32_t* extent, int W) {
+    ATTN_MFMA_CASE(bwd_t, 8, 32, s, f, g, h, dy, stats, df, dg, dh, ws, B, N)
+    ATTN_MFMA_CASE(bwd_t, 8, 64, s, f, g, h, dy, stats, df, dg, dh, ws, B, N)
+    ATTN_MFMA_CASE(bwd_t, 16, 128, s, f, g, h, dy, stats, df, dg, dh, ws, B, N)
     return msau_set_error(MSAU_ERR_ARG, "selfattn mfma: unsupported (Ds,Cs)=(%d,%d)", Ds, Cs);
 }

@@ -243,10 +243,13 @@ __global__ __launch_bounds__(256) void conv_kernel(const ConvArgs a) {
     const T* mask_a = static_cast<const T*>(d.mask_a);
     const T* mask_b = static_cast<const T*>(d.mask_b);
     const int flags = d.flags;
+    int ext_h = d.Hout, ext_w = d.Wout;                 // MSAU_CONV_EXTENT: this sample's (h, w) on the output grid
+    if (flags & MSAU_CONV_EXTENT) { ext_h = d.extent[2 * b]; ext_w = d.extent[2 * b + 1]; }
 #pragma unroll
     for (int pt = 0; pt < PT; ++pt) {
         const int oy = oy0 + wave * PT + pt, ox = ox0 + lr;
         if (oy >= d.Hout || ox >= d.Wout) continue;
+        const bool outside = oy >= ext_h || ox >= ext_w;
         const size_t pbase = (((size_t)b * d.Hout + oy) * d.Wout + ox) * a.ystride;
 #pragma unroll
         for (int ct = 0; ct < CT; ++ct) {
@@ -291,6 +294,7 @@ __global__ __launch_bounds__(256) void conv_kernel(const ConvArgs a) {
                     for (int j = 0; j < 4; ++j) v[j] = ((float)m[j] > 0.f) ? v[j] : 0.f;
                 }
             }
+            if (outside) v = f32x4{0.f, 0.f, 0.f, 0.f};                    // MSAU_CONV_EXTENT: last, after every other epilogue step
             V4 o;
 #pragma unroll
             for (int j = 0; j < 4; ++j) o[j] = (T)v[j];
@@ -358,6 +362,18 @@ int msau_conv_chunked_capable(int dtype, const msau_conv_desc* d, int cch, int n
 int msau_firstconv_takes(int dtype, const msau_conv_desc* d);
 int msau_firstconv_launch(hipStream_t s, int dtype, const msau_conv_desc* d, int real_channels);
 
+// 1 if msau_conv2d runs the generic tile kernel for `d` (MSAU_CONV_EXTENT set): no flag that only other instances implement, and
+// none of them takes it (each refuses the flag itself)
+static int conv_takes_extent(int dtype, const msau_conv_desc* d, const ConvGeom& g) {
+    const int only_others = MSAU_CONV_HEAD | MSAU_CONV_DOUT | MSAU_CONV_LRN | MSAU_CONV_POOL | MSAU_CONV_IDS | MSAU_CONV_OWNER |
+                            MSAU_CONV_NCHW | MSAU_CONV_WGRAD;
+    if (d->flags & only_others) return 0;
+    if (g.nslices == 1 && (msau_rowconv_takes(dtype, d) || msau_conv_chunked_capable(dtype, d, g.cch, g.nchunks, g.CT) ||
+                           msau_conv_lean_applicable(dtype, d, g.nchunks, g.CT)))
+        return 0;
+    return 1;
+}
+
 extern "C" int msau_conv2d_launch_info(int dtype, const msau_conv_desc* d, int32_t* info) {
     MSAU_CHECK_ARG(d && info, "conv2d_launch_info: null pointer");
     ConvGeom g; TileGeom t; int PT; int64_t nb;
@@ -381,6 +397,11 @@ extern "C" int msau_conv2d_launch_info(int dtype, const msau_conv_desc* d, int32
         msau_conv_desc p = *d;
         p.flags |= MSAU_CONV_NCHW;
         if (msau_firstconv_takes(dtype, &p)) info[7] |= 64;
+    }
+    {                                                    // MSAU_CONV_EXTENT: the generic tile kernel is the one instance with it
+        msau_conv_desc p = *d;
+        p.flags |= MSAU_CONV_EXTENT;
+        if (conv_takes_extent(dtype, &p, g)) info[7] |= 128;
     }
     if (g.nslices == 1 && !(info[7] & 4)) {              // would a row-streaming instance take this launch with MSAU_CONV_LRN added?
         msau_conv_desc p = *d;
@@ -415,6 +436,15 @@ extern "C" int msau_conv2d(void* stream, int dtype, const msau_conv_desc* d) {
     MSAU_CHECK_ARG(!(d->flags & MSAU_CONV_ADD) || d->add, "conv2d: ADD without pointer");
     MSAU_CHECK_ARG(!(d->flags & MSAU_CONV_MASK_A) || d->mask_a, "conv2d: MASK_A without pointer");
     MSAU_CHECK_ARG(!(d->flags & MSAU_CONV_MASK_B) || d->mask_b, "conv2d: MASK_B without pointer");
+    if (d->flags & MSAU_CONV_EXTENT) {                                         // ragged batch: the generic tile kernel only
+        MSAU_CHECK_ARG(d->extent, "conv2d: MSAU_CONV_EXTENT without extent pointer");
+        ConvGeom g;
+        int rc = conv_geom(dtype, d->C1, d->C2, d->Cout, d->KH, d->KW, d->dil, d->stride, d->ups, &g);
+        if (rc) return rc;
+        if (!conv_takes_extent(dtype, d, g))
+            return msau_set_error(MSAU_ERR_ARG, "conv2d: MSAU_CONV_EXTENT is not implemented for this launch (flags 0x%x; see "
+                                  "msau_conv2d_launch_info info[7] & 128): only the generic tile kernel has it", d->flags);
+    }
     if (d->flags & MSAU_CONV_WGRAD)                                            // a rider only the row-streaming coupling instance carries
         MSAU_CHECK_ARG(msau_conv2d_rider_slabs(dtype, d) > 0, "conv2d: MSAU_CONV_WGRAD is not implemented for this launch (msau_conv2d_rider_slabs says 0)");
     if (d->flags & MSAU_CONV_OWNER) {                                          // ownerconv.hip: box lists instead of a painted input tensor

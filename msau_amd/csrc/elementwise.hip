@@ -372,9 +372,10 @@ __global__ void pool_fwd_kernel(const T* __restrict__ x, T* __restrict__ y, uint
 // window: dy and the positions are read ONCE (rounds 1-4 ran a thread per input pixel -- the four pixels of a window sat in two
 // workgroup rows and each fetched the window's 16 + 8 bytes again: PMC x1.27 the algorithmic bytes, profiles/r04_traffic.json),
 // the two pixels of a window row are 32 contiguous bytes per lane.  No 64-bit divisions.
-template <typename T>
+template <typename T, bool EXT = false>
 __global__ __launch_bounds__(256) void pool_bwd_kernel(const T* __restrict__ dy, const uint8_t* __restrict__ idx, T* __restrict__ dx,
-                                                       const T* __restrict__ mask, int orows, int H, int W, int Ho, int Wo, int Cs, int accumulate) {
+                                                       const T* __restrict__ mask, int orows, int H, int W, int Ho, int Wo, int Cs, int accumulate,
+                                                       const int32_t* __restrict__ extent) {
     const int cgs = Cs >> 3;
     // flat index over (pooled row, pooled x, channel group): every thread of every workgroup but the last has a window (with one
     // pooled ROW per workgroup half of the 256 threads had none at the net's sizes: Wo * cgs = 128); 32-bit divisions only
@@ -392,11 +393,13 @@ __global__ __launch_bounds__(256) void pool_bwd_kernel(const T* __restrict__ dy,
     const bool elu = accumulate & 2;                                 // bit 1: `mask` is the output of an ELU, not of a ReLU
     accumulate &= 1;
     V8 old[4], m[4];
-    bool ok[4];
+    bool ok[4], in_ext[4];
+    const int eh = EXT ? extent[2 * b] : H, ew = EXT ? extent[2 * b + 1] : W;           // ragged batch: the sample's (h, w)
 #pragma unroll
     for (int pos = 0; pos < 4; ++pos) {
         const int iy = 2 * oy + (pos >> 1), ix = 2 * ox + (pos & 1);
         ok[pos] = iy < H && ix < W;
+        in_ext[pos] = iy < eh && ix < ew;
         const int64_t i = (((int64_t)b * H + iy) * W + ix) * cgs + cg;
         old[pos] = accumulate && ok[pos] ? load8<T>(dx + i * 8) : zero8<T>();
         if (mask && ok[pos]) m[pos] = load8<T>(mask + i * 8);
@@ -411,7 +414,7 @@ __global__ __launch_bounds__(256) void pool_bwd_kernel(const T* __restrict__ dy,
         for (int j = 0; j < 8; ++j) {
             float v = (float)old[pos][j] + ((int)((packed >> (8 * j)) & 0xff) == pos ? (float)g[j] : 0.f);
             if (mask && !((float)m[pos][j] > 0.f)) v = elu ? v * ((float)m[pos][j] + 1.f) : 0.f;       // (ELU: y <= 0 -> d/dz = y + 1)
-            r[j] = (T)v;
+            r[j] = (!EXT || in_ext[pos]) ? (T)v : (T)0.f;
         }
         store8<T>(dx + i * 8, r);
     }
@@ -941,16 +944,53 @@ extern "C" int msau_maxpool2x2_fwd(void* stream, int dtype, const void* x, void*
 
 extern "C" int msau_maxpool2x2_bwd(void* stream, int dtype, const void* dy, const uint8_t* idx, void* dx, const void* mask,
                                    int B, int H, int W, int Cs, int accumulate) {
+    return msau_maxpool2x2_bwd_ext(stream, dtype, dy, idx, dx, mask, B, H, W, Cs, accumulate, nullptr);
+}
+
+extern "C" int msau_maxpool2x2_bwd_ext(void* stream, int dtype, const void* dy, const uint8_t* idx, void* dx, const void* mask,
+                                       int B, int H, int W, int Cs, int accumulate, const int32_t* extent) {
     MSAU_CHECK_ARG(dy && dx && idx && B > 0 && H > 0 && W > 0 && Cs % 8 == 0, "maxpool_bwd: bad args");
     hipStream_t s = static_cast<hipStream_t>(stream);
     int Ho = (H + 1) / 2, Wo = (W + 1) / 2;
     MSAU_CHECK_ARG((int64_t)B * Ho * Wo * (Cs / 8) < (1ll << 31) - 256, "maxpool_bwd: image too large");
     const int rows = B * Ho;                                         // pooled rows: a thread owns a 2x2 window
     const dim3 grid((unsigned)(((int64_t)rows * Wo * (Cs / 8) + 255) / 256));
-    DISPATCH_T(dtype,
-               hipLaunchKernelGGL(pool_bwd_kernel<float>, grid, dim3(256), 0, s, static_cast<const float*>(dy), idx, static_cast<float*>(dx), static_cast<const float*>(mask), rows, H, W, Ho, Wo, Cs, accumulate),
-               hipLaunchKernelGGL(pool_bwd_kernel<bf16_t>, grid, dim3(256), 0, s, static_cast<const bf16_t*>(dy), idx, static_cast<bf16_t*>(dx), static_cast<const bf16_t*>(mask), rows, H, W, Ho, Wo, Cs, accumulate));
+    if (extent)
+        DISPATCH_T(dtype,
+                   hipLaunchKernelGGL((pool_bwd_kernel<float, true>), grid, dim3(256), 0, s, static_cast<const float*>(dy), idx, static_cast<float*>(dx), static_cast<const float*>(mask), rows, H, W, Ho, Wo, Cs, accumulate, extent),
+                   hipLaunchKernelGGL((pool_bwd_kernel<bf16_t, true>), grid, dim3(256), 0, s, static_cast<const bf16_t*>(dy), idx, static_cast<bf16_t*>(dx), static_cast<const bf16_t*>(mask), rows, H, W, Ho, Wo, Cs, accumulate, extent));
+    else
+        DISPATCH_T(dtype,
+                   hipLaunchKernelGGL(pool_bwd_kernel<float>, grid, dim3(256), 0, s, static_cast<const float*>(dy), idx, static_cast<float*>(dx), static_cast<const float*>(mask), rows, H, W, Ho, Wo, Cs, accumulate, extent),
+                   hipLaunchKernelGGL(pool_bwd_kernel<bf16_t>, grid, dim3(256), 0, s, static_cast<const bf16_t*>(dy), idx, static_cast<bf16_t*>(dx), static_cast<const bf16_t*>(mask), rows, H, W, Ho, Wo, Cs, accumulate, extent));
     MSAU_CHECK_LAUNCH("pool_bwd");
+    return 0;
+}
+
+// =============================================================================================
+// Ragged batch: zero a tensor outside every sample's extent (the inputs the network does not produce itself: the NHWC input, the
+// label canvas, external logit gradients).  [B][planes][H][W] pixels of `pixel_bytes` bytes; one thread per 4-byte word.
+// =============================================================================================
+__global__ void extent_copy_kernel(const uint32_t* __restrict__ src, uint32_t* __restrict__ dst, int planes, int H, int W, int words,
+                                   const int32_t* __restrict__ extent, int64_t total) {
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
+        int64_t p = i / words;
+        const int x = (int)(p % W); p /= W;
+        const int y = (int)(p % H); p /= H;
+        const int b = (int)(p / planes);
+        dst[i] = (y < extent[2 * b] && x < extent[2 * b + 1]) ? src[i] : 0u;
+    }
+}
+
+extern "C" int msau_extent_copy(void* stream, const void* src, void* dst, int B, int planes, int H, int W, int pixel_bytes,
+                                const int32_t* extent) {
+    MSAU_CHECK_ARG(src && dst && extent && B > 0 && planes > 0 && H > 0 && W > 0 && pixel_bytes > 0 && pixel_bytes % 4 == 0,
+                   "extent_copy: bad args");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const int64_t total = (int64_t)B * planes * H * W * (pixel_bytes / 4);
+    hipLaunchKernelGGL(extent_copy_kernel, dim3(grid_for(total)), dim3(kThreads), 0, s, static_cast<const uint32_t*>(src),
+                       static_cast<uint32_t*>(dst), planes, H, W, pixel_bytes / 4, extent, total);
+    MSAU_CHECK_LAUNCH("extent_copy");
     return 0;
 }
 

@@ -78,6 +78,9 @@ template <typename T> struct Vec4;
 template <> struct Vec4<float>  { typedef f32x4 type; };
 template <> struct Vec4<bf16_t> { typedef bf16x4 type; };
 
+// ragged batch: is position j of a W-wide grid inside a sample's extent (eh, ew)?
+__device__ __forceinline__ bool pos_in_extent(int j, int W, int eh, int ew) { const int y = j / W; return y < eh && j - y * W < ew; }
+
 template <typename T> __device__ __forceinline__ float to_f32(T v) { return (float)v; }
 template <typename T> __device__ __forceinline__ T from_f32(float v) { return (T)v; }
 

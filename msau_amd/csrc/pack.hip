@@ -15,7 +15,7 @@ int msau_set_error(int code, const char* fmt, ...) {
 }
 
 extern "C" const char* msau_last_error(void) { return g_err; }
-extern "C" int msau_version(void) { return 10; }
+extern "C" int msau_version(void) { return 11; }
 
 extern "C" int msau_lds_pixel_stride(int raw_bytes, int esz, int c8_per_chunk, int read_stride) { return lds_pixel_stride(raw_bytes, esz, c8_per_chunk, read_stride); }
 extern "C" int msau_lds_wrow_stride(int nks, int esz) { return lds_wrow_stride(nks, esz); }

@@ -259,18 +259,20 @@ static int run_one_raw(void* stream, const msau_op& o, int i) {
             }
             case MSAU_OP_POOL_BWD: {
                 const msau_pool_args* a = static_cast<const msau_pool_args*>(o.args);
-                rc = msau_maxpool2x2_bwd(stream, o.dtype, a->x_or_dy, a->idx, a->y_or_dx, a->mask, a->B, a->H, a->W, a->Cs, a->accumulate);
+                rc = msau_maxpool2x2_bwd_ext(stream, o.dtype, a->x_or_dy, a->idx, a->y_or_dx, a->mask, a->B, a->H, a->W, a->Cs, a->accumulate,
+                                             a->extent);
                 break;
             }
             case MSAU_OP_ATTN_FWD: {
                 const msau_attn_args* a = static_cast<const msau_attn_args*>(o.args);
-                rc = msau_selfattn_fwd(stream, o.dtype, a->f, a->g, a->h, a->x_or_dy, a->y, a->stats, a->B, a->N, a->Ds, a->Cs);
+                rc = msau_selfattn_fwd_ext(stream, o.dtype, a->f, a->g, a->h, a->x_or_dy, a->y, a->stats, a->B, a->N, a->Ds, a->Cs,
+                                           a->extent, a->W);
                 break;
             }
             case MSAU_OP_ATTN_BWD: {
                 const msau_attn_args* a = static_cast<const msau_attn_args*>(o.args);
-                rc = msau_selfattn_bwd(stream, o.dtype, a->f, a->g, a->h, a->x_or_dy, a->stats, a->df, a->dg, a->dh, a->ws,
-                                       a->B, a->N, a->Ds, a->Cs);
+                rc = msau_selfattn_bwd_ext(stream, o.dtype, a->f, a->g, a->h, a->x_or_dy, a->stats, a->df, a->dg, a->dh, a->ws,
+                                           a->B, a->N, a->Ds, a->Cs, a->extent, a->W);
                 break;
             }
             case MSAU_OP_CHANNEL_SUM: {

@@ -1,0 +1,83 @@
+"""Ragged batches: documents of different chargrid sizes in one training step.
+
+The reference trains with batch 1 and one H x W per document (train_chargrid_funsd_msau.py:45-59,
+data_generator_funsd_bert.py:216-222).  `pack` places B documents at the origin of one zero canvas and returns their sizes;
+`MSAUWrapper.forward(x, sizes)` / `TrainEngine.step(x, labels, sizes)` then compute, for every document, what it would compute
+alone ("Ragged batches").  `unpack` crops the canvas outputs back, `batches` groups documents of similar size.
+
+    for idx in batches(docs, 16):
+        x, labels, sizes = pack([docs[i] for i in idx])
+        loss = engine.step(x.cuda(), labels.cuda(), sizes)
+"""
+from __future__ import annotations
+
+from typing import Iterator, List, Sequence, Tuple
+
+import torch
+
+
+def _hw(doc) -> Tuple[int, int]:
+    m = doc["mask"]
+    return int(m.shape[-2]), int(m.shape[-1])
+
+
+def pack(docs: Sequence[dict], round_to: int = 16) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """`docs`: the {"mask": [1, C, h, w] (or [C, h, w]), "label": [1, h, w] (or [h, w])} items of the FUNSD loader.
+    -> (x fp32 [B, C, H, W], labels int64 [B, H, W], sizes int64 CPU [B, 2] of (h, w)), every document at the canvas origin and
+    zeros elsewhere.  The canvas is the batch's largest h and w, each rounded up to a multiple of `round_to`, so that few
+    distinct canvases (= plans, = captured graphs) occur over an epoch."""
+    if len(docs) == 0:
+        raise ValueError("pack: no documents")
+    if round_to < 1:
+        raise ValueError(f"pack: round_to must be >= 1, got {round_to}")
+    sizes = torch.tensor([_hw(d) for d in docs], dtype=torch.int64)
+    C = int(docs[0]["mask"].shape[-3])
+    H = -(-int(sizes[:, 0].max()) // round_to) * round_to
+    W = -(-int(sizes[:, 1].max()) // round_to) * round_to
+    x = torch.zeros((len(docs), C, H, W), dtype=torch.float32)
+    labels = torch.zeros((len(docs), H, W), dtype=torch.int64)
+    for b, d in enumerate(docs):
+        h, w = int(sizes[b, 0]), int(sizes[b, 1])
+        m = d["mask"].reshape(-1, h, w)
+        if int(m.shape[0]) != C:
+            raise ValueError(f"pack: document {b} has {int(m.shape[0])} channels, document 0 has {C}")
+        x[b, :, :h, :w] = m
+        labels[b, :h, :w] = d["label"].reshape(h, w).long()
+    return x, labels, sizes
+
+
+def unpack(t: torch.Tensor, sizes: torch.Tensor) -> List[torch.Tensor]:
+    """crop a canvas tensor [B, ..., H, W] back to the per-document tensors [..., h_b, w_b] (views)"""
+    sizes = torch.as_tensor(sizes)
+    if tuple(sizes.shape) != (int(t.shape[0]), 2):
+        raise ValueError(f"unpack: sizes must have shape ({int(t.shape[0])}, 2), got {tuple(sizes.shape)}")
+    H, W = int(t.shape[-2]), int(t.shape[-1])
+    out = []
+    for b in range(int(t.shape[0])):
+        h, w = int(sizes[b, 0]), int(sizes[b, 1])
+        if not (1 <= h <= H and 1 <= w <= W):
+            raise ValueError(f"unpack: size ({h}, {w}) of sample {b} is outside the {H} x {W} canvas")
+        out.append(t[b, ..., :h, :w])
+    return out
+
+
+def batches(docs: Sequence[dict], batch_size: int, round_to: int = 16) -> Iterator[List[int]]:
+    """Indices of `docs` in groups of at most `batch_size`, documents of similar size together (sorted by area, then by the
+    rounded canvas they need) to limit the padding a canvas adds.  Every index appears exactly once."""
+    if batch_size < 1:
+        raise ValueError(f"batches: batch_size must be >= 1, got {batch_size}")
+
+    def key(i):
+        h, w = _hw(docs[i])
+        return (-(-h // round_to), -(-w // round_to), h * w)
+
+    order = sorted(range(len(docs)), key=lambda i: (_hw(docs[i])[0] * _hw(docs[i])[1], key(i)))
+    for k in range(0, len(order), batch_size):
+        yield order[k:k + batch_size]
+
+
+def padded_fraction(sizes: torch.Tensor, H: int, W: int) -> float:
+    """share of the canvas pixels that belong to no document"""
+    sizes = torch.as_tensor(sizes)
+    used = int((sizes[:, 0] * sizes[:, 1]).sum())
+    return 1.0 - used / float(int(sizes.shape[0]) * H * W)

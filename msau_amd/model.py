@@ -140,8 +140,10 @@ class _MSAUFunction(torch.autograd.Function):
     """The whole network as one autograd node: forward / backward are the plan's kernel sequences."""
 
     @staticmethod
-    def forward(ctx, wrapper, x, *params):
-        plan = wrapper._plan_for(x, training=True)
+    def forward(ctx, wrapper, x, sizes, *params):
+        plan = wrapper._plan_for(x, training=True, ragged=sizes is not None)
+        if sizes is not None:
+            plan.set_extents(sizes)
         # The saved activations are the plan's own buffers: a second grad-mode forward of the same shape overwrites them.
         # backward() checks that it still belongs to the latest forward instead of returning silently wrong gradients.
         plan.generation += 1
@@ -167,7 +169,7 @@ class _MSAUFunction(torch.autograd.Function):
         for key, p in w._named:
             off, n = w._poff[key], p.numel()
             grads.append(flat_g[off:off + n].view(p.shape) if key not in w._dead else None)
-        return (None, None, *grads)
+        return (None, None, None, *grads)
 
 
 class _MaskedCEFunction(torch.autograd.Function):
@@ -324,22 +326,22 @@ class MSAUWrapper(nn.Module):
         return self._flat
 
     # ---- plans ----------------------------------------------------------------------------------
-    def _plan_for(self, x: torch.Tensor, training: bool) -> Plan:
+    def _plan_for(self, x: torch.Tensor, training: bool, ragged: bool = False) -> Plan:
         if not x.is_cuda:
             raise RuntimeError("MSAUWrapper runs on an MI355X through libmsau_hip.so; input must be a CUDA/HIP tensor "
                                "(there is no CPU fallback)")
         B, C, H, W = x.shape
         if C != self.channels:
             raise ValueError(f"expected {self.channels} input channels, got {C}")
-        return self._plan_for_shape(B, H, W, x.device, training)
+        return self._plan_for_shape(B, H, W, x.device, training, ragged)
 
-    def _plan_for_shape(self, B: int, H: int, W: int, device, training: bool) -> Plan:
+    def _plan_for_shape(self, B: int, H: int, W: int, device, training: bool, ragged: bool = False) -> Plan:
         if self._flat.device != device:
             raise RuntimeError(f"model is on {self._flat.device}, input on {device}")
-        key = (B, H, W, training)
+        key = (B, H, W, training, bool(ragged))
         plan = self._plans.get(key)
         if plan is None:
-            plan = Plan(self.cfg, B, H, W, self._dtype, device, self._poff, self._pshape, training=training)
+            plan = Plan(self.cfg, B, H, W, self._dtype, device, self._poff, self._pshape, training=training, ragged=ragged)
             plan.generation = 0                 # bumped by every grad-mode forward (see _MSAUFunction)
             self._plans[key] = plan
             while len(self._plans) > 1 and (len(self._plans) > self.max_cached_plans or
@@ -350,15 +352,22 @@ class MSAUWrapper(nn.Module):
         return plan
 
     # ---- reference API ----------------------------------------------------------------------------
-    def forward(self, inp):
+    def forward(self, inp, sizes=None):
+        """`sizes` (ragged batch): a CPU integer tensor [B, 2] of every document's (h, w), placed at the origin of the H x W canvas
+        of `inp`; each sample then computes what the document alone would (its crop of the outputs), and the outputs are 0
+        outside the documents.  None: the dense batch."""
         x = inp.contiguous().float()
+        if sizes is not None:
+            sizes = self._check_sizes(x, sizes)
         need_grad = torch.is_grad_enabled() and any(p.requires_grad for _, p in self._named)
         if need_grad:
-            outs = _MSAUFunction.apply(self, x, *[p for _, p in self._named])
+            outs = _MSAUFunction.apply(self, x, sizes, *[p for _, p in self._named])
             logits = outs[0]
             aux = outs[1] if len(outs) > 1 else None
         else:
-            plan = self._plan_for(x, training=False)
+            plan = self._plan_for(x, training=False, ragged=sizes is not None)
+            if sizes is not None:
+                plan.set_extents(sizes)
             lg, ax = plan.forward(self._flat, x)
             logits, aux = lg.clone(), (ax.clone() if ax is not None else None)
         if self.final_act == "softmax":
@@ -370,6 +379,11 @@ class MSAUWrapper(nn.Module):
         else:
             pred = logits
         return pred, logits, aux
+
+    def _check_sizes(self, x: torch.Tensor, sizes) -> torch.Tensor:
+        """host-side check of a ragged batch's sizes against the canvas of x (no device sync)"""
+        B, _, H, W = x.shape
+        return Plan.check_sizes(sizes, B, H, W)
 
     @torch.no_grad()
     def predict_nhwc(self, inp: Optional[torch.Tensor] = None, ids: Optional[torch.Tensor] = None, graph: bool = False):
@@ -623,12 +637,18 @@ class TrainEngine:
                 self.sync.start_all()
             self.sync.finish()
 
-    def step(self, x: torch.Tensor, labels: torch.Tensor) -> torch.Tensor:
-        """One optimisation step.  Returns the (local) loss as a 1-element device tensor (no host sync)."""
+    def step(self, x: torch.Tensor, labels: torch.Tensor, sizes=None) -> torch.Tensor:
+        """One optimisation step.  Returns the (local) loss as a 1-element device tensor (no host sync).
+        `sizes` (ragged batch): CPU integer [B, 2] of every document's (h, w) at the origin of the canvas; the loss is then the
+        mean of the per-document losses and the gradient the mean of the per-document gradients.  None: the dense batch."""
         x = x.contiguous().float()
         labels = labels.reshape(x.shape[0], x.shape[2], x.shape[3]).contiguous().long()
-        plan = self.model._plan_for(x, training=True)
+        if sizes is not None:
+            sizes = self.model._check_sizes(x, sizes)
+        plan = self.model._plan_for(x, training=True, ragged=sizes is not None)
         if not self.use_graph:
+            if sizes is not None:
+                plan.set_extents(sizes)
             loss = self._fwd_bwd(plan, x, labels)
             self._allreduce()
             self._optim()
@@ -642,6 +662,8 @@ class TrainEngine:
         gs = self._gstream
         gs.wait_stream(cur)
         with torch.cuda.stream(gs):
+            if sizes is not None:
+                plan.set_extents(sizes)          # (one graph per canvas: the extents buffer is refreshed before every replay)
             if key not in graphs:
                 sx, sl = x.clone(), labels.clone()
                 # warm up outside capture (hipFuncSetAttribute calls, lazy allocations)

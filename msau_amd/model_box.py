@@ -38,6 +38,10 @@ class BMSAUWrapper(MSAUWrapper):
         return dict(variant="box", num_box_convs=int(self.num_box_convs), num_box_per_channels=int(self.num_box_per_channels),
                     max_box_sizes=float(self.max_box_sizes))
 
+    def _check_sizes(self, x, sizes):
+        raise NotImplementedError("BMSAUWrapper: ragged batches (sizes=...) are not implemented for the box variant -- its box "
+                                  "convolutions have no per-document extents; run one document per step or MSAUWrapper")
+
     def load_state_dict(self, state_dict, strict: bool = True, assign: bool = False):
         """Loads like MSAUWrapper -- and says what cannot be promised.  The stored box borders `x_min / x_max / y_min / y_max`
         are read HERE as fractions of `max_box_sizes` (msau_box_params, oracle/box_oracle.py).  The `box_convolution` package

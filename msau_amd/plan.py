@@ -10,6 +10,17 @@ Gradient bookkeeping: every activation knows how many consumers contribute to it
 Contributions run in reverse forward order; the first one to run writes, later ones accumulate
 (MSAU_CONV_ACCUM) and the last one multiplies by the ReLU mask of the activation's producer
 (MSAU_CONV_MASK_B), so that a gradient buffer always ends up holding dL/d(pre-activation).
+
+Ragged batches (`Plan(..., ragged=True)`): every sample b has its own document size (h_b, w_b) inside the shared H x W canvas,
+placed at the origin.  Level l of the net (l poolings deep) sees the extent (ceil(h_b / 2^l), ceil(w_b / 2^l)); the plan owns
+those per-level extents as one device buffer int32 [levels][B][2] (`extents`, refreshed by `set_extents`).  The invariant:
+every activation and every activation gradient is exactly 0 outside its sample's extent at its level, after every write.
+Every launch that writes one carries its level's extents -- the convs and their data gradients (MSAU_CONV_EXTENT: the generic
+tile kernel, which stores 0 there), the pool backward and the attention core -- and the tensors the net does not produce itself
+(the NHWC input, the label canvas, external logit gradients) are zeroed outside the extents as they enter (msau_extent_copy).
+SAME convs, the zero-padded 2x2 max pool and the transposed conv then read exactly the zeros the document alone would be padded
+with, so each sample computes what it would compute alone ("Ragged batches").  Fused instances that do not
+implement the extent step aside through the same predicate as activation_name="elu" (`generic_only`).
 """
 from __future__ import annotations
 
@@ -195,7 +206,7 @@ class ConvOp(Op):
         self.uentry = None
         self.dd_off = None           # one launch for both sources of a concat conv (MSAU_CONV_DOUT) when an instance has it
         if P.training and conv and x2 is not None and None not in self.slots and x1.C == x1.Cs == x2.C == x2.Cs \
-                and x1.Cs + x2.Cs <= 128 and os.environ.get("MSAU_FUSE_DGRAD", "1") != "0" and not P.act_flag:
+                and x1.Cs + x2.Cs <= 128 and os.environ.get("MSAU_FUSE_DGRAD", "1") != "0" and not P.generic_only:
             proto = L.ConvDesc()
             proto.B, proto.Hin, proto.Win, proto.Hout, proto.Wout = P.B, out.H, out.W, x1.H, x1.W
             proto.C1, proto.C2, proto.Cout = out.Cs, 0, x1.Cs + x2.Cs
@@ -215,7 +226,7 @@ class ConvOp(Op):
         # residual pair's backward launch only needs the packed weights
         self.dcp_off = self.dd_off
         if P.training and conv and self.k == 1 and x2 is not None and self.dd_off is None and None not in self.slots \
-                and x1.C == x1.Cs == x2.C == x2.Cs == out.Cs == 32 and P.dtype == L.BF16 and not P.act_flag \
+                and x1.C == x1.Cs == x2.C == x2.Cs == out.Cs == 32 and P.dtype == L.BF16 and not P.generic_only \
                 and any(pr.c2.cpl is self for pr in P.pairs):
             gd = self._geom(out.Cs, 0, x1.Cs + x2.Cs, self.dil, 1, 1)
             self.dcp_off = P.alloc_pack(gd.bytes)
@@ -250,7 +261,8 @@ class ConvOp(Op):
         d.KH = d.KW = self.k
         d.dil, d.pad_t, d.pad_l, d.stride, d.ups = self.dil, self.pad_t, self.pad_l, 1, (1 if conv else 2)
         d.flags = (L.CONV_RELU_IN if self.relu_in else 0) | ((L.CONV_RELU_OUT | P.act_flag) if self.relu_out else 0) | \
-                  (L.CONV_ADD if self.fwd_add is not None else 0)
+                  (L.CONV_ADD if self.fwd_add is not None else 0) | P.extent_flag
+        d.extent = P.extent_ptr(out)
         d.x1, d.x2 = _ptr(x1.data), _ptr(x2.data if x2 is not None else None)
         d.wpack, d.bias = P.pack_ptr(self.w_off), P.pack_ptr(self.b_off)
         d.add = _ptr(self.fwd_add.data) if self.fwd_add is not None else None
@@ -337,7 +349,8 @@ class ConvOp(Op):
             if maskb:
                 fl |= L.CONV_MASK_B | P.act_flag
                 dd.mask_b = _ptr(x.data)
-            dd.flags = fl
+            dd.flags = fl | P.extent_flag
+            dd.extent = P.extent_ptr(x)
             dd.x1, dd.wpack, dd.bias, dd.y = _ptr(out.grad), P.pack_ptr(self.d_off[si]), None, _ptr(x.grad)
             self.ddesc[si] = dd
         # a 1x1 conv over concat(x1, x2) at 64 + 64 channels (the bottleneck level's coupling conv): both data gradients in one launch
@@ -345,7 +358,7 @@ class ConvOp(Op):
         self.dgrad2 = None
         d1, d2 = self.ddesc
         if conv and self.k == 1 and x2 is not None and self.dd_off is None and d1 is not None and d2 is not None \
-                and P.dtype == L.BF16 and not P.act_flag and x1.C == x1.Cs == x2.C == x2.Cs == out.Cs == 64 \
+                and P.dtype == L.BF16 and not P.generic_only and x1.C == x1.Cs == x2.C == x2.Cs == out.Cs == 64 \
                 and not ((d1.flags | d2.flags) & ~(L.CONV_ACCUM | L.CONV_MASK_B)) and os.environ.get("MSAU_DGRAD2", "1") != "0":
             geo = [self._geom(out.Cs, 0, x.Cs, 1, 1, 1) for x in (x1, x2)]
             if all((gq.nchunks, gq.rows, gq.kchunk) == (1, 64, 64) for gq in geo):
@@ -611,7 +624,7 @@ class PairOp:
         """after both ConvOps are bound: build the fused descriptors if an instance takes the shape"""
         P, c1, c2 = self.plan, self.c1, self.c2
         x0, r1, out = c1.x1, c1.out, c2.out
-        if os.environ.get("MSAU_FUSE_PAIR", "1") == "0" or not P.cfg.get("fuse_pair", True) or P.act_flag:
+        if os.environ.get("MSAU_FUSE_PAIR", "1") == "0" or not P.cfg.get("fuse_pair", True) or P.generic_only:
             return
         ok = (c1.kind == c2.kind == "conv" and c1.k == c2.k == 3 and c1.dil == c2.dil == 1 and c1.x2 is None and c2.x2 is None
               and c1.relu_in and c1.relu_out and c1.fwd_add is None and not c2.relu_in and c2.relu_out and c2.fwd_add is x0
@@ -992,7 +1005,7 @@ class PoolOp(Op):
         x, y = self.x, self.y
         if self.fused_into is not None:
             return []
-        self._fa = L.PoolArgs(_ptr(x.data), _ptr(y.data), _ptr(self.idx), None, self.plan.B, x.H, x.W, x.Cs, 0)
+        self._fa = L.PoolArgs(_ptr(x.data), _ptr(y.data), _ptr(self.idx), None, self.plan.B, x.H, x.W, x.Cs, 0, None)
         self.plan.rec_meta[C.addressof(self._fa)] = (self.fkey, self.fbytes)
         return [(L.OP_POOL_FWD, self._fa)]
 
@@ -1002,7 +1015,8 @@ class PoolOp(Op):
             return []
         accum, maskb = x.slot_flags(self.slot)
         self._ba = L.PoolArgs(_ptr(y.grad), _ptr(x.grad), _ptr(self.idx), _ptr(x.data) if maskb else None,
-                              self.plan.B, x.H, x.W, x.Cs, int(accum) | (2 if maskb and self.plan.act_flag else 0))
+                              self.plan.B, x.H, x.W, x.Cs, int(accum) | (2 if maskb and self.plan.act_flag else 0),
+                              self.plan.extent_ptr(x))
         self.plan.rec_meta[C.addressof(self._ba)] = (self.bkey, self.bbytes)
         return [(L.OP_POOL_BWD, self._ba)]
 
@@ -1018,9 +1032,9 @@ class PoolOp(Op):
         if y.grad is None or x.grad is None:
             return
         accum, maskb = x.slot_flags(self.slot)
-        L.call("msau_maxpool2x2_bwd", s, self.plan.dtype, _ptr(y.grad), _ptr(self.idx), _ptr(x.grad),
+        L.call("msau_maxpool2x2_bwd_ext", s, self.plan.dtype, _ptr(y.grad), _ptr(self.idx), _ptr(x.grad),
                _ptr(x.data) if maskb else None, self.plan.B, x.H, x.W, x.Cs, int(accum) | (2 if maskb and self.plan.act_flag else 0),
-               key=self.bkey)
+               self.plan.extent_ptr(x), key=self.bkey)
 
 
 class AttnCoreOp(Op):
@@ -1047,7 +1061,7 @@ class AttnCoreOp(Op):
         return L.AttnArgs(_ptr(self.f.data), _ptr(self.g.data), _ptr(self.h.data),
                           _ptr(self.y.grad) if bwd else _ptr(self.x.data), _ptr(self.y.data), _ptr(self.stats),
                           _ptr(self.f.grad), _ptr(self.g.grad), _ptr(self.h.grad), _ptr(self.ws),
-                          self.plan.B, self.N, self.f.Cs, self.h.Cs)
+                          self.plan.B, self.N, self.f.Cs, self.h.Cs, self.plan.extent_ptr(self.x), self.x.W)
 
     def note(self):
         """forward: f, g, h, x read, y written (two sweeps: stats, output); backward: f, g, h, dy read, df, dg, dh written.
@@ -1080,15 +1094,16 @@ class AttnCoreOp(Op):
         return [(L.OP_ATTN_BWD, self._ba)]
 
     def fwd(self, s):
-        L.call("msau_selfattn_fwd", s, self.plan.dtype, _ptr(self.f.data), _ptr(self.g.data), _ptr(self.h.data),
-               _ptr(self.x.data), _ptr(self.y.data), _ptr(self.stats), self.plan.B, self.N, self.f.Cs, self.h.Cs, key=self.fkey)
+        L.call("msau_selfattn_fwd_ext", s, self.plan.dtype, _ptr(self.f.data), _ptr(self.g.data), _ptr(self.h.data),
+               _ptr(self.x.data), _ptr(self.y.data), _ptr(self.stats), self.plan.B, self.N, self.f.Cs, self.h.Cs,
+               self.plan.extent_ptr(self.x), self.x.W, key=self.fkey)
 
     def bwd(self, s):
         if self.y.grad is None:
             return
-        L.call("msau_selfattn_bwd", s, self.plan.dtype, _ptr(self.f.data), _ptr(self.g.data), _ptr(self.h.data),
+        L.call("msau_selfattn_bwd_ext", s, self.plan.dtype, _ptr(self.f.data), _ptr(self.g.data), _ptr(self.h.data),
                _ptr(self.y.grad), _ptr(self.stats), _ptr(self.f.grad), _ptr(self.g.grad), _ptr(self.h.grad),
-               _ptr(self.ws), self.plan.B, self.N, self.f.Cs, self.h.Cs, key=self.bkey)
+               _ptr(self.ws), self.plan.B, self.N, self.f.Cs, self.h.Cs, self.plan.extent_ptr(self.x), self.x.W, key=self.bkey)
 
 
 class ProjBwd:
@@ -1110,7 +1125,7 @@ class ProjBwd:
         P, f, g, h = self.plan, self.f, self.g, self.h
         x = f.x1
         df, dg, dh = f.ddesc[0], g.ddesc[0], h.ddesc[0]
-        if P.dtype != L.BF16 or P.act_flag or os.environ.get("MSAU_ATTN_PROJ_FUSE", "1") == "0" or None in (df, dg, dh):
+        if P.dtype != L.BF16 or P.generic_only or os.environ.get("MSAU_ATTN_PROJ_FUSE", "1") == "0" or None in (df, dg, dh):
             return
         if not (x.C == x.Cs == 64 and f.out.Cs == g.out.Cs == 8 and h.out.Cs == 64 and f.k == g.k == h.k == 1
                 and g.x1 is x and h.x1 is x and f.x2 is None and g.x2 is None and h.x2 is None
@@ -1153,7 +1168,7 @@ class ProjBwd:
 
 class Plan:
     def __init__(self, cfg: dict, B: int, H: int, W: int, dtype: int, device, poff: Dict[str, int],
-                 pshape: Dict[str, Tuple[int, ...]], training: bool = True, builder=None):
+                 pshape: Dict[str, Tuple[int, ...]], training: bool = True, builder=None, ragged: bool = False):
         self.cfg, self.B, self.H, self.W, self.dtype, self.device = cfg, B, H, W, dtype, device
         self.tdtype = torch.float32 if dtype == L.F32 else torch.bfloat16
         self.poff, self.pshape, self.training = poff, pshape, training
@@ -1163,6 +1178,15 @@ class Plan:
         # (MSAU_CONV_ELU); the residual block's leading activation stays ReLU as in the reference (model.py:35,39)
         assert cfg.get("activation", "relu") in ("relu", "elu"), cfg.get("activation")
         self.act_flag = L.CONV_ELU if cfg.get("activation", "relu") == "elu" else 0
+        # ragged batch (module docstring): per-level extents of every sample, the flag every activation-writing conv carries
+        self.ragged = bool(ragged)
+        self.extent_flag = L.CONV_EXTENT if self.ragged else 0
+        self.levels = [(-(-H // 2 ** l), -(-W // 2 ** l)) for l in range(max(1, int(cfg.get("scale_space_num", 1))))]
+        self.extents = torch.ones((len(self.levels), B, 2), dtype=torch.int32, device=device) if self.ragged else None
+        self._ext_host = None
+        # the one "generic instances only" predicate: fusions that keep an intermediate inside one launch, or that run instances
+        # without the ELU epilogue / the extent step, are off (ELU and ragged plans both set it)
+        self.generic_only = bool(self.act_flag) or self.ragged
         self.head_probs = self.head_argmax = None
         self.head_fused = False
         self.acts: List[Act] = []
@@ -1202,6 +1226,49 @@ class Plan:
         else:
             builder(self)               # custom graph (op-level tests): must set self.logits (and maybe self.aux)
         self._finish()
+
+    # ---- ragged batches ----------------------------------------------------------------------
+    def extent_ptr(self, a: Act) -> Optional[int]:
+        """device pointer of the [B][2] extents of the level whose grid `a` lives on (None for a dense plan)"""
+        if not self.ragged:
+            return None
+        lv = self.levels.index((a.H, a.W))
+        return self.extents.data_ptr() + lv * self.B * 2 * 4
+
+    @staticmethod
+    def level_extents(sizes: torch.Tensor, levels: int) -> torch.Tensor:
+        """int32 [levels][B][2]: level l of a document of (h, w) is (ceil(h / 2^l), ceil(w / 2^l)) -- what its zero-padded 2x2 pools
+        produce alone (model/model.py:158-160)"""
+        s = sizes.to(torch.int64)
+        return torch.stack([-((-s) // (2 ** l)) for l in range(levels)]).to(torch.int32).contiguous()
+
+    @staticmethod
+    def check_sizes(sizes, B: int, H: int, W: int) -> torch.Tensor:
+        """validate a CPU int [B, 2] tensor of (h, w) with 1 <= h <= H, 1 <= w <= W -- on the host, no device sync"""
+        if not isinstance(sizes, torch.Tensor):
+            sizes = torch.as_tensor(sizes)
+        if sizes.device.type != "cpu" or sizes.dtype.is_floating_point or sizes.dtype == torch.bool:
+            raise ValueError(f"sizes must be a CPU integer tensor [B, 2] of (h, w), got {sizes.dtype} on {sizes.device}")
+        if tuple(sizes.shape) != (B, 2):
+            raise ValueError(f"sizes must have shape ({B}, 2) for this batch, got {tuple(sizes.shape)}")
+        h, w = sizes[:, 0], sizes[:, 1]
+        if bool((h < 1).any() or (w < 1).any() or (h > H).any() or (w > W).any()):
+            raise ValueError(f"sizes must satisfy 1 <= h <= {H} and 1 <= w <= {W} (the canvas), got {sizes.tolist()}")
+        return sizes
+
+    def set_extents(self, sizes) -> None:
+        """refresh the device extents of a ragged plan from the CPU sizes [B, 2] (an ordinary copy on the current stream: a captured
+        graph reads the new extents at its next replay)"""
+        assert self.ragged
+        host = self.level_extents(self.check_sizes(sizes, self.B, self.H, self.W), len(self.levels))
+        if str(self.device).startswith("cuda"):
+            host = host.pin_memory()
+        self._ext_host = host                                # kept alive until the copy has run
+        self.extents.copy_(host, non_blocking=True)
+
+    def _zero_outside(self, src: torch.Tensor, dst: torch.Tensor, planes: int, H: int, W: int, pixel_bytes: int, level: int = 0):
+        L.call("msau_extent_copy", self._stream(), src.data_ptr(), dst.data_ptr(), self.B, planes, H, W, pixel_bytes,
+               self.extents.data_ptr() + level * self.B * 2 * 4)
 
     # ---- arenas -----------------------------------------------------------------------------
     def alloc_pack(self, nbytes: int) -> int:
@@ -1640,6 +1707,8 @@ class Plan:
             (self.B, self.cfg["channels"], self.H, self.W), (x_nchw.shape, x_nchw.dtype)
         a = self.x_in
         L.call("msau_nchw_to_nhwc", self._stream(), self.dtype, x_nchw.data_ptr(), a.data.data_ptr(), self.B, a.C, a.Cs, self.H, self.W)
+        if self.ragged:                                  # the input is ignored outside the documents
+            self._zero_outside(a.data, a.data, 1, self.H, self.W, a.data.element_size() * a.Cs)
 
     def _nchw_first_conv(self):
         """the net's first conv if msau_conv2d takes it with MSAU_CONV_NCHW (the API's fp32 NCHW tensor as its input), else None"""
@@ -1850,6 +1919,8 @@ class Plan:
         """`ids` (int32 [B,H,W] character ids, -1 = empty) instead of `x_nchw`: the one-hot grid is painted on the device.
         `nhwc_ready`: the input buffer (`input_nhwc`) already holds the grid -- no boundary conversion at all."""
         s = self._stream()
+        assert not self.ragged or (owner is None and ids is None and not nhwc_ready), \
+            "a ragged plan takes the NCHW input tensor (ids / nhwc_ready / box lists are dense-only paths)"
         self.pack(flat_params)
         if owner is not None:
             # box lists instead of a painted input (`owner` as Plan._feed_owner takes it); the caller checked that an instance exists
@@ -1909,6 +1980,8 @@ class Plan:
                 g = g.contiguous().float()
                 L.call("msau_nchw_grad_to_nhwc", s, self.dtype, g.data_ptr(), act.grad.data_ptr(), self.B, act.C, act.Cs,
                        act.H, act.W, 0)
+                if self.ragged:                          # external gradients are ignored outside the documents
+                    self._zero_outside(act.grad, act.grad, 1, act.H, act.W, act.grad.element_size() * act.Cs)
                 if maskb:       # output produced through a ReLU and consumed by nothing else (op-level tests only)
                     act.grad.mul_(act.data > 0)
 
@@ -1918,6 +1991,11 @@ class Plan:
         assert labels.dtype == torch.int64 and labels.is_contiguous() and tuple(labels.shape) == (self.B, self.H, self.W)
         s = self._stream()
         HW = self.H * self.W
+        if self.ragged:                                  # the label canvas: 0 (= not counted) outside the documents
+            if getattr(self, "_labels_buf", None) is None:
+                self._labels_buf = torch.zeros_like(labels)
+            self._zero_outside(labels, self._labels_buf, 1, self.H, self.W, 8)
+            labels = self._labels_buf
         lg, ax = self.logits, self.aux
         if lg.Cs <= 16 and self.B * HW < (1 << 31) and (ax is None or (ax.C, ax.Cs) == (lg.C, lg.Cs)) \
                 and os.environ.get("MSAU_CE_MULTI", "1") != "0":

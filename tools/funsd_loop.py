@@ -9,7 +9,11 @@ document's plan cached; reports, as one JSON object:
   launches_per_step        native launch records of the median-size plan
   graph                    the same with TrainEngine(use_graph=True): one HIP-graph replay per cached plan
 
-    python tools/funsd_loop.py [--docs 120] [--epochs 3] [--channels 64] [--dtype bf16] [--graph]
+  ragged                   with --ragged B: the same documents in ragged batches of B (msau_amd.data.ragged: documents of
+                           similar area together, canvases rounded up to 16), TrainEngine.step(x, labels, sizes) --
+                           docs/s, launches per step, the canvases used and the padded fraction of the canvases
+
+    python tools/funsd_loop.py [--docs 120] [--epochs 3] [--channels 64] [--dtype bf16] [--graph] [--ragged 16]
 """
 import argparse
 import json
@@ -31,25 +35,38 @@ def doc_shapes(n, seed=0):
     return sorted(out, key=lambda s: rng.random())
 
 
-def run(args, use_graph):
+def make_docs(args):
+    """the synthetic documents (CPU): {"mask": [1, C, h, w], "label": [1, h, w]} as the FUNSD loader yields them"""
     import torch
-    from msau_amd import MSAUWrapper, TrainEngine
-    dev = torch.device("cuda", 0)
-    kw = dict(scale_space_num=4, res_depth=2, featRoot=8, filter_size=3, pool_size=2, final_act="softmax", num_blocks=3,
-              dtype=args.dtype, seed=0)
-    m = MSAUWrapper(args.channels, 5, kw).to(dev)
-    shapes = doc_shapes(args.docs)
-    m.max_cached_plans = 2 * len(shapes) + 2
-    eng = TrainEngine(m, lr=1e-4, use_graph=use_graph)
     g = torch.Generator(device="cpu").manual_seed(1)
     docs = []
-    for (H, W) in shapes:
+    for (H, W) in doc_shapes(args.docs):
         occ = torch.rand((1, H, W), generator=g) < 0.1
         ids = torch.randint(0, args.channels, (1, H, W), generator=g)
         x = torch.zeros((1, args.channels, H, W))
         x.scatter_(1, ids.unsqueeze(1), occ.unsqueeze(1).float())
         lab = (occ * torch.randint(1, 5, (1, H, W), generator=g)).long()
-        docs.append((x.to(dev), lab.to(dev)))
+        docs.append({"mask": x, "label": lab})
+    return docs
+
+
+def make_model(args):
+    import torch
+    from msau_amd import MSAUWrapper
+    kw = dict(scale_space_num=4, res_depth=2, featRoot=8, filter_size=3, pool_size=2, final_act="softmax", num_blocks=3,
+              dtype=args.dtype, seed=0)
+    return MSAUWrapper(args.channels, 5, kw).to(torch.device("cuda", 0))
+
+
+def run(args, use_graph):
+    import torch
+    from msau_amd import TrainEngine
+    dev = torch.device("cuda", 0)
+    m = make_model(args)
+    shapes = doc_shapes(args.docs)
+    m.max_cached_plans = 2 * len(shapes) + 2
+    eng = TrainEngine(m, lr=1e-4, use_graph=use_graph)
+    docs = [(d["mask"].to(dev), d["label"].to(dev)) for d in make_docs(args)]
     torch.cuda.synchronize()
     res = {}
     t0 = time.perf_counter()
@@ -82,6 +99,54 @@ def run(args, use_graph):
     return res
 
 
+def run_ragged(args, B, use_graph=False):
+    """the same documents in ragged batches of B: one step per batch, loss = mean of the per-document losses"""
+    import torch
+    from msau_amd import TrainEngine
+    from msau_amd.data.ragged import batches, pack, padded_fraction
+    dev = torch.device("cuda", 0)
+    m = make_model(args)
+    docs = make_docs(args)
+    steps = []
+    for idx in batches(docs, B, round_to=16):
+        x, lab, sizes = pack([docs[i] for i in idx], round_to=16)
+        steps.append((x.to(dev), lab.to(dev), sizes))
+    canvases = sorted({(int(x.shape[0]), int(x.shape[2]), int(x.shape[3])) for x, _, _ in steps})
+    m.max_cached_plans = 2 * len(canvases) + 2
+    eng = TrainEngine(m, lr=1e-4, use_graph=use_graph)
+    torch.cuda.synchronize()
+    res = {}
+    t0 = time.perf_counter()
+    for x, lab, sizes in steps:
+        eng.step(x, lab, sizes)
+    torch.cuda.synchronize()
+    res["first_epoch_ms_per_doc"] = round(1e3 * (time.perf_counter() - t0) / len(docs), 3)
+    times, host = [], []
+    for ep in range(args.epochs):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        th = 0.0
+        for x, lab, sizes in steps:
+            h0 = time.perf_counter()
+            loss = eng.step(x, lab, sizes)
+            th += time.perf_counter() - h0
+        torch.cuda.synchronize()
+        times.append((time.perf_counter() - t0) / len(docs))
+        host.append(th / len(steps))
+    best = min(times)
+    pad = sum(padded_fraction(s, int(x.shape[2]), int(x.shape[3])) * x.shape[0] * x.shape[2] * x.shape[3] for x, _, s in steps) / \
+        sum(x.shape[0] * x.shape[2] * x.shape[3] for x, _, _ in steps)
+    x, _, _ = steps[len(steps) // 2]
+    plan = m._plan_for_shape(int(x.shape[0]), int(x.shape[2]), int(x.shape[3]), dev, True, ragged=True)
+    res.update(batch=B, docs=len(docs), steps_per_epoch=len(steps), epochs=args.epochs, docs_per_s=round(1.0 / best, 1),
+               ms_per_doc=round(1e3 * best, 3), ms_per_step=round(1e3 * best * len(docs) / len(steps), 3),
+               host_ms_per_step=round(1e3 * min(host), 3), loss=round(float(loss), 4), canvases=[list(c) for c in canvases],
+               padded_fraction=round(pad, 4), median_canvas=[int(x.shape[0]), int(x.shape[2]), int(x.shape[3])],
+               # + pack, convert, zero the input outside the documents, label canvas, counts, CE, clip+Adam
+               launches_per_step=sum(seq[1] for seq in (plan._fwd_seq, plan._bwd_seq) if seq is not None) + 7)
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--docs", type=int, default=120)
@@ -89,11 +154,21 @@ def main():
     ap.add_argument("--channels", type=int, default=64)
     ap.add_argument("--dtype", default="bf16")
     ap.add_argument("--graph", action="store_true", help="also run with one HIP-graph replay per cached plan")
+    ap.add_argument("--ragged", type=int, default=0, help="also run the documents in ragged batches of this size")
+    ap.add_argument("--ragged-only", action="store_true", help="skip the batch-1 loop (e.g. under rocprofv3)")
     args = ap.parse_args()
+    if args.ragged_only:
+        print(json.dumps({"ragged": run_ragged(args, args.ragged or 16)}))
+        return
     out = {"eager": run(args, False)}
     if args.graph:
         out["graph"] = run(args, True)
         out["graph_speedup"] = round(out["graph"]["docs_per_s"] / out["eager"]["docs_per_s"], 3)
+    if args.ragged:
+        out["ragged"] = run_ragged(args, args.ragged)
+        out["ragged_speedup"] = round(out["ragged"]["docs_per_s"] / out["eager"]["docs_per_s"], 3)
+        if args.graph:
+            out["ragged_graph"] = run_ragged(args, args.ragged, use_graph=True)
     print(json.dumps(out))
 
 
