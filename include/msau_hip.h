@@ -701,10 +701,22 @@ int msau_softmax_channels_nchw(void* stream, const float* logits, float* pred, i
  *                              (the stand-alone form of MSAU_CONV_HEAD, bit-identical to it; any C <= 255)
  *   msau_onehot_ids          : grid[p][c] = (c == ids[p]) for c < C, 0 for C <= c < Cs -- to_categorical() of the
  *                              character-id mask (generic_util.py:97-98) written straight into the NHWC input
+ *   msau_onehot_ids_ext      : ragged batch: msau_onehot_ids inside every sample's extent, all-zero channels outside it
+ *                              whatever the id there; ids [B][H][W], extent int32 [B][2] = (h, w) at level 0 (not NULL)
+ *   msau_eval_confusion      : evaluation counts.  logits [B][H][W][Cs] in `dtype` storage (C real classes, C <= 64),
+ *                              labels int64 [B][H][W].  A pixel counts when its label is in [1, C) and, with `extent` not
+ *                              NULL, it lies inside its sample's extent; pred = index of the FIRST maximum of the C stored
+ *                              values (as float: torch's argmax of the fp32 export, ties included), a 0 becomes zero_as
+ *                              when zero_as >= 0; then counts[label * C + pred] += 1.  counts int64 [C][C] accumulates
+ *                              across calls (zero it first); integer sums, independent of arrival order
  * ------------------------------------------------------------------------------------------ */
 int msau_softmax_argmax_nhwc(void* stream, int dtype, const void* logits, float* probs, uint8_t* argmax,
                              int64_t npix, int C, int Cs);
 int msau_onehot_ids(void* stream, int dtype, const int32_t* ids, void* grid_nhwc, int64_t npix, int C, int Cs);
+int msau_onehot_ids_ext(void* stream, int dtype, const int32_t* ids, void* grid_nhwc, int B, int H, int W, int C, int Cs,
+                        const int32_t* extent);
+int msau_eval_confusion(void* stream, int dtype, const void* logits, const int64_t* labels, int64_t* counts, int B, int H, int W,
+                        int C, int Cs, int zero_as, const int32_t* extent);
 
 #ifdef __cplusplus
 }

@@ -215,6 +215,8 @@ _SIGNATURES = {
     "msau_probe_overhead": (C.c_int, [vp, C.c_int, vp]),
     "msau_softmax_argmax_nhwc": (C.c_int, [vp, C.c_int, vp, vp, vp, i64, C.c_int, C.c_int]),
     "msau_onehot_ids": (C.c_int, [vp, C.c_int, vp, vp, i64, C.c_int, C.c_int]),
+    "msau_onehot_ids_ext": (C.c_int, [vp, C.c_int, vp, vp] + [C.c_int] * 5 + [vp]),
+    "msau_eval_confusion": (C.c_int, [vp, C.c_int, vp, vp, vp] + [C.c_int] * 6 + [vp]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)

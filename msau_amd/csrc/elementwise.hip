@@ -837,6 +837,75 @@ __global__ void onehot_ids_kernel(const int32_t* __restrict__ ids, T* __restrict
     }
 }
 
+// Ragged batch: onehot_ids_kernel inside every sample's extent, all-zero channels outside it (whatever the id there), so the
+// painted input already satisfies the plan invariant.  ids [B][H][W], extent [B][2] = (h, w) at level 0.
+template <typename T>
+__global__ void onehot_ids_ext_kernel(const int32_t* __restrict__ ids, T* __restrict__ grid, int64_t npix, int H, int W, int C,
+                                      int Cs, const int32_t* __restrict__ extent) {
+    const int cgs = Cs >> 3;
+    const int64_t total = npix * cgs;
+    const int64_t hw = (int64_t)H * W;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
+        const int cg = (int)(i % cgs);
+        const int64_t p = i / cgs;
+        const int b = (int)(p / hw);
+        const int64_t r = p - (int64_t)b * hw;
+        const int y = (int)(r / W), x = (int)(r - (int64_t)y * W);
+        const int id = (y < extent[2 * b] && x < extent[2 * b + 1]) ? ids[p] : -1;
+        typename Vec8<T>::type o = zero8<T>();
+        const int j = id - cg * 8;
+        if (id >= 0 && id < C && j >= 0 && j < 8) o[j] = (T)1.0f;
+        store8<T>(grid + i * 8, o);
+    }
+}
+
+// Evaluation counts (the per-epoch accuracy / classification report of train_chargrid_funsd_msau.py): for every pixel whose
+// label is in [1, C) (and, with `extent`, that lies inside its sample's extent) pred = the first maximum of the C stored logits
+// (torch's argmax of the fp32 export, ties included), 0 -> zero_as when zero_as >= 0, and counts[label * C + pred] += 1.
+// A workgroup histograms into LDS (uint32 bins) and adds each non-empty bin to the int64 matrix with one global atomic:
+// integer sums, so the result does not depend on arrival order.
+constexpr int kConfusionMaxC = 64;
+
+template <typename T>
+__global__ __launch_bounds__(256) void eval_confusion_kernel(const T* __restrict__ logits, const int64_t* __restrict__ labels,
+                                                             unsigned long long* __restrict__ counts, int64_t npix, int H, int W,
+                                                             int C, int Cs, int zero_as, const int32_t* __restrict__ extent) {
+    __shared__ uint32_t hist[kConfusionMaxC * kConfusionMaxC];
+    const int bins = C * C;
+    for (int i = threadIdx.x; i < bins; i += blockDim.x) hist[i] = 0u;
+    __syncthreads();
+    const int64_t hw = (int64_t)H * W;
+    for (int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; p < npix; p += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t lab = labels[p];
+        if (lab < 1 || lab >= C) continue;
+        if (extent) {
+            const int b = (int)(p / hw);
+            const int64_t r = p - (int64_t)b * hw;
+            const int y = (int)(r / W), x = (int)(r - (int64_t)y * W);
+            if (y >= extent[2 * b] || x >= extent[2 * b + 1]) continue;
+        }
+        const T* l = logits + p * Cs;
+        int best = 0;
+        float bv = -INFINITY;
+        for (int c0 = 0; c0 < C; c0 += 8) {
+            const typename Vec8<T>::type v8 = load8<T>(l + c0);
+#pragma unroll
+            for (int j = 0; j < 8; ++j) {
+                const float v = (float)v8[j];
+                // strictly greater: the first maximum wins; a NaN counts as the maximum, as in torch.argmax
+                if (c0 + j < C && (v > bv || (v != v && bv == bv))) { bv = v; best = c0 + j; }
+            }
+        }
+        if (best == 0 && zero_as >= 0) best = zero_as;
+        atomicAdd(&hist[(int)lab * C + best], 1u);
+    }
+    __syncthreads();
+    for (int i = threadIdx.x; i < bins; i += blockDim.x) {
+        const uint32_t n = hist[i];
+        if (n) atomicAdd(counts + i, (unsigned long long)n);
+    }
+}
+
 }  // namespace
 
 #define DISPATCH_T(dtype, CALL_F32, CALL_BF16)                          \
@@ -1255,5 +1324,36 @@ extern "C" int msau_onehot_ids(void* stream, int dtype, const int32_t* ids, void
                hipLaunchKernelGGL(onehot_ids_kernel<float>, dim3(grid_for(npix * (Cs / 8))), dim3(kThreads), 0, s, ids, static_cast<float*>(grid), npix, C, Cs),
                hipLaunchKernelGGL(onehot_ids_kernel<bf16_t>, dim3(grid_for(npix * (Cs / 8))), dim3(kThreads), 0, s, ids, static_cast<bf16_t*>(grid), npix, C, Cs));
     MSAU_CHECK_LAUNCH("onehot_ids");
+    return 0;
+}
+
+extern "C" int msau_onehot_ids_ext(void* stream, int dtype, const int32_t* ids, void* grid, int B, int H, int W, int C, int Cs,
+                                   const int32_t* extent) {
+    MSAU_CHECK_ARG(ids && grid && extent && B > 0 && H > 0 && W > 0 && C > 0 && Cs % 8 == 0 && C <= Cs, "onehot_ids_ext: bad args");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const int64_t npix = (int64_t)B * H * W;
+    DISPATCH_T(dtype,
+               hipLaunchKernelGGL(onehot_ids_ext_kernel<float>, dim3(grid_for(npix * (Cs / 8))), dim3(kThreads), 0, s, ids, static_cast<float*>(grid), npix, H, W, C, Cs, extent),
+               hipLaunchKernelGGL(onehot_ids_ext_kernel<bf16_t>, dim3(grid_for(npix * (Cs / 8))), dim3(kThreads), 0, s, ids, static_cast<bf16_t*>(grid), npix, H, W, C, Cs, extent));
+    MSAU_CHECK_LAUNCH("onehot_ids_ext");
+    return 0;
+}
+
+extern "C" int msau_eval_confusion(void* stream, int dtype, const void* logits, const int64_t* labels, int64_t* counts, int B, int H,
+                                   int W, int C, int Cs, int zero_as, const int32_t* extent) {
+    MSAU_CHECK_ARG(logits && labels && counts && B > 0 && H > 0 && W > 0, "eval_confusion: bad args");
+    MSAU_CHECK_ARG(C >= 1 && C <= kConfusionMaxC && C <= Cs && Cs % 8 == 0, "eval_confusion: C = %d (Cs = %d) must satisfy 1 <= C <= %d, C <= Cs, Cs %% 8 == 0",
+                   C, Cs, kConfusionMaxC);
+    MSAU_CHECK_ARG(zero_as < C, "eval_confusion: zero_as = %d is not a class of %d", zero_as, C);
+    const int64_t npix = (int64_t)B * H * W;
+    MSAU_CHECK_ARG(npix < (1ll << 40), "eval_confusion: too many pixels");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    // at least 4 pixels per lane and at most 512 workgroups: the LDS histogram's clear and flush stay small beside the pixels
+    const dim3 grid(grid_for(cdiv64(npix, 4), 512));
+    unsigned long long* out = reinterpret_cast<unsigned long long*>(counts);
+    DISPATCH_T(dtype,
+               hipLaunchKernelGGL(eval_confusion_kernel<float>, grid, dim3(kThreads), 0, s, static_cast<const float*>(logits), labels, out, npix, H, W, C, Cs, zero_as, extent),
+               hipLaunchKernelGGL(eval_confusion_kernel<bf16_t>, grid, dim3(kThreads), 0, s, static_cast<const bf16_t*>(logits), labels, out, npix, H, W, C, Cs, zero_as, extent));
+    MSAU_CHECK_LAUNCH("eval_confusion");
     return 0;
 }

@@ -3,7 +3,8 @@
 The reference trains with batch 1 and one H x W per document (train_chargrid_funsd_msau.py:45-59,
 data_generator_funsd_bert.py:216-222).  `pack` places B documents at the origin of one zero canvas and returns their sizes;
 `MSAUWrapper.forward(x, sizes)` / `TrainEngine.step(x, labels, sizes)` then compute, for every document, what it would compute
-alone ("Ragged batches").  `unpack` crops the canvas outputs back, `batches` groups documents of similar size.
+alone ("Ragged batches").  `unpack` crops the canvas outputs back, `batches` groups documents of similar size, `pack_ids` packs character-id masks for
+`MSAUWrapper.predict_nhwc(ids=..., sizes=...)`.
 
     for idx in batches(docs, 16):
         x, labels, sizes = pack([docs[i] for i in idx])
@@ -13,6 +14,7 @@ from __future__ import annotations
 
 from typing import Iterator, List, Sequence, Tuple
 
+import numpy as np
 import torch
 
 
@@ -44,6 +46,27 @@ def pack(docs: Sequence[dict], round_to: int = 16) -> Tuple[torch.Tensor, torch.
         x[b, :, :h, :w] = m
         labels[b, :h, :w] = d["label"].reshape(h, w).long()
     return x, labels, sizes
+
+
+def pack_ids(masks: Sequence, round_to: int = 16) -> Tuple[torch.Tensor, torch.Tensor]:
+    """`masks`: [h, w] character-id masks (numpy or torch, e.g. KVModel's uint16 `char_ids`).
+    -> (ids int32 [B, H, W] with -1 (= empty pixel) outside every document, sizes int64 CPU [B, 2] of (h, w)), the canvas rounded
+    as in `pack`.  Feed them to `MSAUWrapper.predict_nhwc(ids=ids.cuda(), sizes=sizes)`."""
+    if len(masks) == 0:
+        raise ValueError("pack_ids: no documents")
+    if round_to < 1:
+        raise ValueError(f"pack_ids: round_to must be >= 1, got {round_to}")
+    ts = [torch.from_numpy(np.asarray(m).astype(np.int64)) if isinstance(m, np.ndarray) else torch.as_tensor(m) for m in masks]
+    for b, t in enumerate(ts):
+        if t.dim() != 2 or t.dtype.is_floating_point or t.dtype == torch.bool:
+            raise ValueError(f"pack_ids: mask {b} must be an integer [h, w] array, got {t.dtype} {tuple(t.shape)}")
+    sizes = torch.tensor([tuple(t.shape) for t in ts], dtype=torch.int64)
+    H = -(-int(sizes[:, 0].max()) // round_to) * round_to
+    W = -(-int(sizes[:, 1].max()) // round_to) * round_to
+    ids = torch.full((len(ts), H, W), -1, dtype=torch.int32)
+    for b, t in enumerate(ts):
+        ids[b, :t.shape[0], :t.shape[1]] = t.to(torch.int32)
+    return ids, sizes
 
 
 def unpack(t: torch.Tensor, sizes: torch.Tensor) -> List[torch.Tensor]:

@@ -225,46 +225,111 @@ class KVModel:
         pred, amax = self.net.predict_nhwc(ids=ids.cuda())
         return pred[0].cpu().numpy(), amax[0].cpu().numpy()
 
-    def predict(self, data, debug_info=None, label_path=None, eval_results=None):
-        """data = (layout JSON path, page image or None) -> ({field: text}, debug image).
-        The debug rendering of the reference (OpenCV + PIL drawing) is not part of this build: the second result is
-        always None; everything that feeds `kv_results` and `eval_results` is computed as in kv_model.py:264-347."""
-        json_path, _debug_im = data
-        input_im, line_mask, char_mask, label_lines, scale, bg_pad, (min_x, min_y, _max_x, _max_y) = \
-            self._generate_masks_from_label(json_path)
+    def _run_net_batch(self, input_masks):
+        """char-id masks [h_b, w_b] -> per document (pred fp32 [h_b, w_b, n_class], argmax uint8 [h_b, w_b]) numpy: ONE ragged
+        forward over the group (msau_amd.data.ragged.pack_ids, MSAUWrapper.predict_nhwc(ids=..., sizes=...)) and one copy of
+        the canvas outputs to the host, then a crop per document"""
+        if not torch.cuda.is_available():
+            raise RuntimeError("KVModel.predict runs the network through libmsau_hip.so on an MI355X; no GPU is "
+                               "visible and there is no CPU fallback")
+        from ..data.ragged import pack_ids
+        ids, sizes = pack_ids(input_masks)
+        pred, amax = self.net.predict_nhwc(ids=ids.cuda(), sizes=sizes)
+        pred, amax = pred.cpu().numpy(), amax.cpu().numpy()
+        return [(np.ascontiguousarray(pred[b, :h, :w]), np.ascontiguousarray(amax[b, :h, :w]))
+                for b, (h, w) in enumerate(sizes.tolist())]
 
+    def _read_answers(self, label_path, scale, offset, eval_results, notes=None):
+        """the ground-truth boxes of a document (None without `label_path`), counted into `eval_results`.  A file that cannot
+        be read is reported at once, or appended to `notes` (the arguments of the print) for the caller to report later."""
         correct_answers = None
         if label_path is not None:
             try:
-                correct_answers = read_json_gt(label_path, scale=scale, offset=(min_x - bg_pad, min_y - bg_pad))
+                correct_answers = read_json_gt(label_path, scale=scale, offset=offset)
             except IOError as e:
-                print("Error reading CA", e)
+                if notes is None:
+                    print("Error reading CA", e)
+                else:
+                    notes.append(("Error reading CA", e))
         if correct_answers is not None:
             for value_id in correct_answers:
                 eval_results[value_id]["num_label"] += 1
+        return correct_answers
 
-        a_pred, a_cls = self._run_net(input_im)
+    def _finish(self, masks, a_pred, a_cls, correct_answers, eval_results):
+        """post-processing of one document's prediction -> kv_results"""
+        _input_im, line_mask, char_mask, label_lines = masks[:4]
         values, _pred_mask = self._extract_value(line_mask, char_mask, label_lines, a_pred, self.n_class,
                                                  pred_class=a_cls.astype(np.int64))
         kv_results = post_process_kv(values)
         if eval_results is not None:
             self._count_predictions(values, self.n_class, eval_results, correct_answers)
-        return kv_results, None
+        return kv_results
 
-    def run_test(self, list_inf, out_dir, label_dir=None, img_dir=None):
+    def predict(self, data, debug_info=None, label_path=None, eval_results=None):
+        """data = (layout JSON path, page image or None) -> ({field: text}, debug image).
+        The debug rendering of the reference (OpenCV + PIL drawing) is not part of this build: the second result is
+        always None; everything that feeds `kv_results` and `eval_results` is computed as in kv_model.py:264-347."""
+        json_path, _debug_im = data
+        masks = self._generate_masks_from_label(json_path)
+        input_im, _line_mask, _char_mask, _label_lines, scale, bg_pad, (min_x, min_y, _max_x, _max_y) = masks
+        correct_answers = self._read_answers(label_path, scale, (min_x - bg_pad, min_y - bg_pad), eval_results)
+        a_pred, a_cls = self._run_net(input_im)
+        return self._finish(masks, a_pred, a_cls, correct_answers, eval_results), None
+
+    def predict_batch(self, json_paths, label_paths=None, eval_results=None):
+        """`predict` for a group of layout JSONs with one network forward: the documents' id masks share a ragged canvas
+        (each is computed as it would be alone).  -> [kv_results] in the order of `json_paths`.  The ground truth of the whole
+        group is read before the forward, so a label file that cannot be read is reported before any result is returned
+        (`run_test` prints each such message next to its own document, as at batch 1)."""
+        results, notes = self._predict_group(json_paths, label_paths, eval_results)
+        for doc_notes in notes:
+            for n in doc_notes:
+                print(*n)
+        return results
+
+    def _predict_group(self, json_paths, label_paths, eval_results):
+        """predict_batch -> ([kv_results], per document the list of its unprinted messages)"""
+        docs, notes = [], []
+        for k, json_path in enumerate(json_paths):
+            masks = self._generate_masks_from_label(json_path)
+            scale, bg_pad, (min_x, min_y, _max_x, _max_y) = masks[4:]
+            label_path = label_paths[k] if label_paths is not None else None
+            notes.append([])
+            docs.append((masks, self._read_answers(label_path, scale, (min_x - bg_pad, min_y - bg_pad), eval_results,
+                                                   notes[-1])))
+        outs = self._run_net_batch([masks[0] for masks, _ in docs])
+        return [self._finish(masks, a_pred, a_cls, correct_answers, eval_results)
+                for (masks, correct_answers), (a_pred, a_cls) in zip(docs, outs)], notes
+
+    def run_test(self, list_inf, out_dir, label_dir=None, img_dir=None, batch_size=1):
         """predict every layout JSON of `list_inf`; with `label_dir`, print per-class counts and precision / recall /
         F1 over region boxes (kv_model.py:350-387).  Unlike the reference a missing page image does not skip the
-        document, because no debug image is drawn."""
+        document, because no debug image is drawn.  batch_size > 1: consecutive groups of `batch_size` documents go through
+        the network as one ragged forward (as in `predict_batch`); results, printing and `eval_results` keep the order of
+        `list_inf`, and the last group may be shorter.  The counts are kept as `self.eval_results`."""
+        if batch_size < 1:
+            raise ValueError(f"batch_size must be >= 1, got {batch_size}")
         eval_results = [{"num_pred": 0, "num_correct": 0, "num_label": 0} for _ in range(self.n_class)]
+        self.eval_results = eval_results
         kv_results = []
-        for file_path in list_inf:
-            basename = os.path.basename(file_path).split(".")[0]
-            label_path = os.path.join(label_dir, basename + ".json") if label_dir is not None else None
-            result, _ = self.predict((file_path, None), debug_info=("", None), label_path=label_path,
-                                     eval_results=eval_results)
-            print(basename)
-            print(result)
-            kv_results.append(result)
+        for k in range(0, len(list_inf), batch_size):
+            group = list_inf[k:k + batch_size]
+            names = [os.path.basename(p).split(".")[0] for p in group]
+            label_paths = [os.path.join(label_dir, n + ".json") for n in names] if label_dir is not None else None
+            if batch_size == 1:
+                results = [self.predict((group[0], None), debug_info=("", None),
+                                        label_path=label_paths[0] if label_paths is not None else None,
+                                        eval_results=eval_results)[0]]
+                notes = [[]]                                     # (printed by predict)
+            else:
+                results, notes = self._predict_group(group, label_paths, eval_results)
+            for basename, result, doc_notes in zip(names, results, notes):
+                for n in doc_notes:
+                    print(*n)
+                print(basename)
+                print(result)
+                kv_results.append(result)
         if label_dir is not None:
             for c, count in enumerate(eval_results):
                 if count["num_pred"] > 0 or count["num_label"] > 0:

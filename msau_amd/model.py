@@ -386,7 +386,8 @@ class MSAUWrapper(nn.Module):
         return Plan.check_sizes(sizes, B, H, W)
 
     @torch.no_grad()
-    def predict_nhwc(self, inp: Optional[torch.Tensor] = None, ids: Optional[torch.Tensor] = None, graph: bool = False):
+    def predict_nhwc(self, inp: Optional[torch.Tensor] = None, ids: Optional[torch.Tensor] = None, graph: bool = False,
+                     sizes=None):
         """Forward-only path for `KVModel.predict` (inference/kv_model.py:305-313): one of
           inp float [B,C,H,W]   -- the dense grid the reference builds with to_categorical, or
           ids int   [B,H,W]     -- the character-id mask itself; the one-hot grid is painted on the device
@@ -395,7 +396,11 @@ class MSAUWrapper(nn.Module):
         No activations are kept (buffers are reused by liveness) and softmax + argmax run in the last conv's epilogue.
         The returned tensors are the plan's buffers: copy them before the next call if they must survive it.
         graph=True replays the sweep as a HIP graph (captured per shape on first use, on a dedicated stream): at
-        batch 1 the ~120 launches are host-bound and the replay is what sets the latency."""
+        batch 1 the ~120 launches are host-bound and the replay is what sets the latency.
+        `sizes` (ragged batch): the CPU integer [B, 2] of `forward` -- every document's (h, w) at the origin of the canvas.
+        Inside each document the outputs are what the document alone produces; outside them they are unspecified (crop them).
+        The ragged plan runs the stand-alone head (msau_softmax_argmax_nhwc); with graph=True one graph per canvas and input
+        kind is captured and the extents are refreshed before every replay."""
         if (inp is None) == (ids is None):
             raise ValueError("give exactly one of inp / ids")
         if self.final_act != "softmax":
@@ -412,11 +417,16 @@ class MSAUWrapper(nn.Module):
             inp = inp.contiguous().float()
             B, C, H, W = inp.shape
             ref = inp
+        if sizes is not None:
+            sizes = Plan.check_sizes(sizes, B, H, W)
         if not ref.is_cuda:
             raise RuntimeError("MSAUWrapper runs on an MI355X through libmsau_hip.so; input must be a CUDA/HIP tensor "
                                "(there is no CPU fallback)")
-        plan = self._plan_for(inp, False) if ids is None else self._plan_for_shape(B, H, W, ref.device, False)
+        ragged = sizes is not None
+        plan = self._plan_for(inp, False, ragged) if ids is None else self._plan_for_shape(B, H, W, ref.device, False, ragged)
         if not graph:
+            if ragged:
+                plan.set_extents(sizes)
             return plan.predict(self._flat, x_nchw=inp, ids=ids)
         kind = "ids" if ids is not None else "dense"
         if getattr(self, "_pstream", None) is None:
@@ -424,6 +434,8 @@ class MSAUWrapper(nn.Module):
         cur, gs = torch.cuda.current_stream(), self._pstream
         gs.wait_stream(cur)
         with torch.cuda.stream(gs):
+            if ragged:
+                plan.set_extents(sizes)                               # read by the captured sweep at every replay
             cache = plan.__dict__.setdefault("_pgraphs", {})
             if kind not in cache:
                 static = ref.clone()
@@ -440,6 +452,49 @@ class MSAUWrapper(nn.Module):
             g.replay()
         cur.wait_stream(gs)
         return plan.head_probs, plan.head_argmax
+
+    @torch.no_grad()
+    def confusion_matrix(self, inp: torch.Tensor, labels: torch.Tensor, sizes=None, zero_as: Optional[int] = None,
+                         out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """Evaluation counts on the device: int64 [n_class, n_class], rows = labels, columns = predictions, over the pixels whose
+        label is in [1, n_class) (and, with `sizes`, that lie inside their document).  The prediction is the first maximum of the
+        logits, exactly `argmax(0)` of the fp32 NCHW logits `forward` returns; with `zero_as`, a predicted 0 counts as that class
+        (the reference's test-split remap, train_chargrid_funsd_msau.py:140).  inp float [B,C,H,W], labels int [B,H,W] (or
+        [B,1,H,W]); `sizes` as in `forward`.  Runs the forward-only plan without exporting the logits and adds into `out` when
+        given (batches of an epoch accumulate on the device; read the matrix once)."""
+        C = self.n_class
+        if C > 64:
+            raise ValueError(f"confusion_matrix counts at most 64 classes, the model has {C}")
+        x = inp.contiguous().float()
+        if x.dim() != 4:
+            raise ValueError("inp must be [B,C,H,W]")
+        B, Cin, H, W = x.shape
+        if int(labels.numel()) != B * H * W:
+            raise ValueError(f"labels must hold [B,H,W] = {(B, H, W)} values, got shape {tuple(labels.shape)}")
+        if zero_as is not None and not (0 <= int(zero_as) < C):
+            raise ValueError(f"zero_as must be a class in [0, {C}), got {zero_as}")
+        if sizes is not None:
+            sizes = self._check_sizes(x, sizes)
+        if labels.device.type == "cpu" and labels.numel() and \
+                bool((labels < 0).any() or (labels >= C).any()):
+            raise ValueError(f"labels must lie in [0, {C})")
+        if not x.is_cuda:
+            raise RuntimeError("MSAUWrapper runs on an MI355X through libmsau_hip.so; input must be a CUDA/HIP tensor "
+                               "(there is no CPU fallback)")
+        if out is None:
+            out = torch.zeros((C, C), dtype=torch.int64, device=x.device)
+        elif out.dtype != torch.int64 or tuple(out.shape) != (C, C) or out.device != x.device or not out.is_contiguous():
+            raise ValueError(f"out must be a contiguous int64 [{C}, {C}] tensor on {x.device}")
+        lab = labels.to(device=x.device, dtype=torch.int64).reshape(B, H, W).contiguous()
+        plan = self._plan_for(x, training=False, ragged=sizes is not None)
+        if sizes is not None:
+            plan.set_extents(sizes)
+        plan.forward(self._flat, x, export=False)
+        lg = plan.logits
+        L.call("msau_eval_confusion", torch.cuda.current_stream().cuda_stream, plan.dtype, lg.data.data_ptr(), lab.data_ptr(),
+               out.data_ptr(), B, H, W, lg.C, lg.Cs, -1 if zero_as is None else int(zero_as),
+               plan.extent_ptr(lg) if sizes is not None else None)
+        return out
 
     def save(self, path):
         torch.save(self.state_dict(), path)

@@ -1859,6 +1859,10 @@ class Plan:
         H*W*4 bytes cross PCIe instead of the dense H*W*C float grid."""
         assert ids.dtype == torch.int32 and ids.is_contiguous() and tuple(ids.shape) == (self.B, self.H, self.W), (ids.shape, ids.dtype)
         a = self.x_in
+        if self.ragged:                                  # all-zero channels outside the documents, whatever the ids there
+            L.call("msau_onehot_ids_ext", self._stream(), self.dtype, ids.data_ptr(), a.data.data_ptr(), self.B, self.H, self.W,
+                   a.C, a.Cs, self.extents.data_ptr())
+            return
         L.call("msau_onehot_ids", self._stream(), self.dtype, ids.data_ptr(), a.data.data_ptr(), a.npix, a.C, a.Cs)
 
     def predict(self, flat_params: torch.Tensor, x_nchw: Optional[torch.Tensor] = None, ids: Optional[torch.Tensor] = None):
@@ -1919,8 +1923,8 @@ class Plan:
         """`ids` (int32 [B,H,W] character ids, -1 = empty) instead of `x_nchw`: the one-hot grid is painted on the device.
         `nhwc_ready`: the input buffer (`input_nhwc`) already holds the grid -- no boundary conversion at all."""
         s = self._stream()
-        assert not self.ragged or (owner is None and ids is None and not nhwc_ready), \
-            "a ragged plan takes the NCHW input tensor (ids / nhwc_ready / box lists are dense-only paths)"
+        assert not self.ragged or (owner is None and not nhwc_ready), \
+            "a ragged plan takes the NCHW input tensor or an id mask (nhwc_ready / box lists are dense-only paths)"
         self.pack(flat_params)
         if owner is not None:
             # box lists instead of a painted input (`owner` as Plan._feed_owner takes it); the caller checked that an instance exists

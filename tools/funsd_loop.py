@@ -13,7 +13,12 @@ document's plan cached; reports, as one JSON object:
                            similar area together, canvases rounded up to 16), TrainEngine.step(x, labels, sizes) --
                            docs/s, launches per step, the canvases used and the padded fraction of the canvases
 
-    python tools/funsd_loop.py [--docs 120] [--epochs 3] [--channels 64] [--dtype bf16] [--graph] [--ragged 16]
+  eval                     with --eval B: evaluation of the same documents (train_chargrid_funsd_msau.evaluate) two ways --
+                           the per-document loop (forward, NCHW fp32 logit export, torch argmax, .cpu() per document) and
+                           MSAUWrapper.confusion_matrix on ragged batches of B (counts on the device, one host read) --
+                           docs/s of each and launches per forward
+
+    python tools/funsd_loop.py [--docs 120] [--epochs 3] [--channels 64] [--dtype bf16] [--graph] [--ragged 16] [--eval 16]
 """
 import argparse
 import json
@@ -147,6 +152,67 @@ def run_ragged(args, B, use_graph=False):
     return res
 
 
+def run_eval(args, B):
+    """evaluation of the documents: today's per-document loop against ragged confusion counts (same model, same documents)"""
+    import numpy as np
+    import torch
+    from msau_amd.data.ragged import batches, pack
+    dev = torch.device("cuda", 0)
+    m = make_model(args).eval()
+    docs = make_docs(args)
+    C = m.n_class
+    steps = []
+    for idx in batches(docs, B, round_to=16):
+        x, lab, sizes = pack([docs[i] for i in idx], round_to=16)
+        steps.append((x.to(dev), lab, sizes))
+    m.max_cached_plans = len(docs) + len({tuple(x.shape) for x, _, _ in steps}) + 2
+    single = [(d["mask"].to(dev), d["label"]) for d in docs]
+
+    def loop():
+        labels, preds = [], []
+        with torch.no_grad():
+            for x, lab in single:
+                lab = np.squeeze(lab.numpy())
+                _, ypred, _ = m(x)
+                idx = ypred.squeeze(0).argmax(0).cpu().numpy()
+                labels.append(lab[lab != 0])
+                preds.append(idx[lab != 0])
+        cm = np.zeros((C, C), np.int64)
+        np.add.at(cm, (np.hstack(labels), np.hstack(preds)), 1)
+        return cm
+
+    def ragged():
+        cm = torch.zeros((C, C), dtype=torch.int64, device=dev)
+        for x, lab, sizes in steps:
+            m.confusion_matrix(x, lab, sizes=sizes, out=cm)
+        return cm.cpu().numpy()
+
+    res = {}
+    for name, fn in (("loop", loop), ("ragged", ragged)):
+        fn()                                                 # plans built, first launches done
+        torch.cuda.synchronize()
+        times = []
+        for _ in range(args.epochs):
+            t0 = time.perf_counter()
+            cm = fn()
+            times.append(time.perf_counter() - t0)
+        best = min(times)
+        res[name] = {"docs_per_s": round(len(docs) / best, 1), "ms_per_doc": round(1e3 * best / len(docs), 3),
+                     "acc": round(float(np.trace(cm)) / max(int(cm.sum()), 1), 6)}
+    shapes = doc_shapes(args.docs)
+    med = sorted(shapes, key=lambda s: s[0] * s[1])[len(shapes) // 2]
+    p1 = m._plan_for_shape(1, med[0], med[1], dev, False)
+    # + convert the input, export the logits, argmax, copy to the host
+    res["loop"]["launches_per_forward"] = p1._fwd_seq[1] + 4
+    x, _, _ = steps[len(steps) // 2]
+    pr = m._plan_for_shape(int(x.shape[0]), int(x.shape[2]), int(x.shape[3]), dev, False, ragged=True)
+    # + convert the input, zero it outside the documents, the counts
+    res["ragged"].update(batch=B, forwards=len(steps), launches_per_forward=pr._fwd_seq[1] + 3,
+                         median_canvas=[int(x.shape[0]), int(x.shape[2]), int(x.shape[3])])
+    res["speedup"] = round(res["ragged"]["docs_per_s"] / res["loop"]["docs_per_s"], 3)
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--docs", type=int, default=120)
@@ -156,7 +222,12 @@ def main():
     ap.add_argument("--graph", action="store_true", help="also run with one HIP-graph replay per cached plan")
     ap.add_argument("--ragged", type=int, default=0, help="also run the documents in ragged batches of this size")
     ap.add_argument("--ragged-only", action="store_true", help="skip the batch-1 loop (e.g. under rocprofv3)")
+    ap.add_argument("--eval", type=int, default=0, help="also compare the per-document evaluation loop with ragged batches of this size")
+    ap.add_argument("--eval-only", action="store_true", help="only the evaluation comparison (e.g. under rocprofv3)")
     args = ap.parse_args()
+    if args.eval_only:
+        print(json.dumps({"eval": run_eval(args, args.eval or 16)}))
+        return
     if args.ragged_only:
         print(json.dumps({"ragged": run_ragged(args, args.ragged or 16)}))
         return
@@ -169,6 +240,8 @@ def main():
         out["ragged_speedup"] = round(out["ragged"]["docs_per_s"] / out["eager"]["docs_per_s"], 3)
         if args.graph:
             out["ragged_graph"] = run_ragged(args, args.ragged, use_graph=True)
+    if args.eval:
+        out["eval"] = run_eval(args, args.eval)
     print(json.dumps(out))
 
 

@@ -7,6 +7,10 @@ Same flow and defaults: pickles written by funsd_preprocessing_word_level.py -> 
 clip 1.0 -> accuracy / micro precision / recall over labelled pixels after every epoch -> state_dict saved
 every 10 epochs under ckpt/<dataset>_<method>_h<hidden>_o<out>/<epoch>.pth.tar.
 
+--batch-size N trains ragged batches (msau_amd.data.ragged: each document computes what it would alone, the loss is the mean of
+the documents' losses); --eval-batch-size N evaluates in ragged batches.  The evaluation counts a confusion matrix on the device
+(MSAUWrapper.confusion_matrix) and prints sklearn's classification report for the test split, as the reference does.
+
 Two step implementations, selected with --loop:
   engine     (default) msau_amd.TrainEngine: fused masked-CE + clip + Adam, no per-step host sync
   reference  model(V) -> model.loss -> loss.backward() -> clip_grad_norm_ -> optimizer.step(), line for line
@@ -23,7 +27,8 @@ import torch
 from msau_amd import MSAUWrapper as MSAU
 from msau_amd import TrainEngine
 from msau_amd.data import FUNSDCharGridDataLoaderBoxMaskBoxLabel
-from msau_amd.training import save_checkpoint
+from msau_amd.data import ragged
+from msau_amd.training import metrics, save_checkpoint
 
 
 def ckpt_filename(save_dir, args, epoch=-1, isbest=False):
@@ -37,28 +42,48 @@ def ckpt_filename(save_dir, args, epoch=-1, isbest=False):
     return d + ".pth.tar"
 
 
-def evaluate(dataset, model, args, name="Validation", testing=False, max_num_examples=None, labels_map=None):
+def eval_count(n_docs, max_num_examples=None):
+    """how many documents, from the start of the dataset, `evaluate` looks at: the reference stops after the batch for which
+    `(batch_idx + 1) * batch_size > max_num_examples` (train_chargrid_funsd_msau.py:144-146) and evaluates at batch 1, so the
+    first max_num_examples + 1 -- whatever batch size the evaluation runs at here"""
+    return n_docs if max_num_examples is None else min(n_docs, max_num_examples + 1)
+
+
+def canvases(docs, batch_size, round_to=16):
+    """the (B, H, W) inputs a pass over `docs` feeds the model: the documents' own shapes at batch 1, else the ragged canvases of
+    msau_amd.data.ragged.batches + pack (every one is a plan)"""
+    if batch_size == 1:
+        return {(1,) + tuple(d["mask"].shape[2:]) for d in docs}
+    out = set()
+    for idx in ragged.batches(docs, batch_size, round_to):
+        hw = [tuple(docs[i]["mask"].shape[2:]) for i in idx]
+        out.add((len(idx), -(-max(h for h, _ in hw) // round_to) * round_to, -(-max(w for _, w in hw) // round_to) * round_to))
+    return out
+
+
+def evaluate(dataset, model, args, name="Validation", testing=False, max_num_examples=None, labels_map=None, batch_size=None):
+    """accuracy over the labelled pixels (reference :121-163) from a confusion matrix that the device accumulates
+    (MSAUWrapper.confusion_matrix): no logits leave the device and the host reads the matrix once.  batch_size (default
+    --eval-batch-size) > 1 runs the documents in ragged batches.  The test split also prints the classification report."""
     model.eval()
     device = model.flat_parameters.device
-    labels, preds = [], []
+    bs = batch_size if batch_size is not None else getattr(args, "eval_batch_size", 1)
+    docs = dataset[:eval_count(len(dataset), max_num_examples)]
+    zero_as = labels_map["other"] if testing and labels_map is not None and "other" in labels_map else None   # reference :140
+    cm = torch.zeros((model.n_class, model.n_class), dtype=torch.int64, device=device)
     with torch.no_grad():
-        for batch_idx, data in enumerate(dataset):
-            lab = np.squeeze(data["label"].long().numpy())
-            _, ypred, _ = model(data["mask"].float().to(device))
-            idx = ypred.squeeze(0).argmax(0).cpu().numpy()
-            idx = idx[lab != 0]
-            lab = lab[lab != 0]
-            if testing and labels_map is not None and "other" in labels_map:
-                idx[idx == 0] = labels_map["other"]
-            labels.append(lab)
-            preds.append(idx)
-            if max_num_examples is not None and (batch_idx + 1) * args.batch_size > max_num_examples:
-                break
-    labels, preds = np.hstack(labels), np.hstack(preds)
-    acc = float((labels == preds).mean()) if labels.size else 0.0
-    # single-label multi-class: micro precision == micro recall == accuracy (sklearn semantics)
-    result = {"prec": acc, "recall": acc, "acc": acc}
+        if bs == 1:
+            for data in docs:
+                model.confusion_matrix(data["mask"].float().to(device), data["label"].long(), zero_as=zero_as, out=cm)
+        else:
+            for idx in ragged.batches(docs, bs):
+                x, lab, sizes = ragged.pack([docs[i] for i in idx])
+                model.confusion_matrix(x.to(device), lab, sizes=sizes, zero_as=zero_as, out=cm)
+    cm = cm.cpu().numpy()
+    result = metrics.scores(cm)
     print(name, " accuracy:", result["acc"])
+    if testing:
+        print(metrics.classification_report(cm, list(labels_map.keys()) if labels_map is not None else None))
     return result
 
 
@@ -71,26 +96,36 @@ def train(dataset, model, args, val_dataset=None, test_dataset=None, labels_map=
         optimizer = torch.optim.Adam(filter(lambda p: p.requires_grad, model.parameters()), lr=args.lr)
     best_val = {"epoch": 0, "loss": 0, "acc": 0}
     val_accs = []
+    bs = getattr(args, "batch_size", 1)
     for epoch in range(args.num_epochs):
         t0 = time.time()
         model.train()
         avg_loss = torch.zeros((), device=device)
         print("Epoch: ", epoch)
-        for batch_idx, data in enumerate(dataset):
-            V = data["mask"].float().to(device)
-            label = data["label"].long().to(device)
+        # batch 1: one document per step; --batch-size N: ragged batches of documents of similar size
+        steps = ([i] for i in range(len(dataset))) if bs == 1 else ragged.batches(dataset, bs)
+        for batch_idx, idx in enumerate(steps):
+            if bs == 1:
+                data = dataset[idx[0]]
+                V = data["mask"].float().to(device)
+                label = data["label"].long().to(device)
+                sizes = None
+            else:
+                x, lab, sizes = ragged.pack([dataset[i] for i in idx])
+                V, label = x.to(device), lab.to(device)
             if args.loop == "engine":
-                loss = engine.step(V, label).reshape(())
+                loss = engine.step(V, label, sizes).reshape(())
             else:
                 model.zero_grad()
-                _, ypred, ypred_aux = model(V)
+                _, ypred, ypred_aux = model(V, sizes)
                 loss = model.loss(ypred, ypred_aux, label)
                 loss.backward()
                 torch.nn.utils.clip_grad_norm_(model.parameters(), float(args.clip))
                 optimizer.step()
             if batch_idx % 10 == 0:
                 print("Batch {} optimized. Loss: {}".format(batch_idx, float(loss)))
-            avg_loss += loss.detach()
+            # the step's loss is the mean of its documents' losses: weight it by their number
+            avg_loss += loss.detach() if bs == 1 else loss.detach() * len(idx)
         avg_loss = float(avg_loss) / max(len(dataset), 1)
         print("Avg loss: ", avg_loss, "; epoch time: ", time.time() - t0)
         evaluate(dataset, model, args, name="Train", max_num_examples=100)
@@ -110,7 +145,8 @@ def train(dataset, model, args, val_dataset=None, test_dataset=None, labels_map=
     return model, val_accs
 
 
-def main():
+def parse_args(argv=None):
+    """the command line (None: sys.argv) and the fixed settings of the reference's run (train_chargrid_funsd_msau.py:175-200)"""
     ap = argparse.ArgumentParser()
     ap.add_argument("--train-pickle", default="./funsd_preprocess.pkl")
     ap.add_argument("--test-pickle", default="./funsd_preprocess_test.pkl")
@@ -122,8 +158,18 @@ def main():
     ap.add_argument("--model-kwargs-path", default=None)
     ap.add_argument("--loop", choices=["engine", "reference"], default="engine")
     ap.add_argument("--dtype", choices=["fp32", "bf16"], default="bf16")
-    args = ap.parse_args()
-    args.batch_size, args.bmname, args.hidden_dim, args.dataset, args.method = 1, None, 500, "invoice", "GCN"
+    ap.add_argument("--batch-size", type=int, default=1,
+                    help="documents per training step; > 1 trains ragged batches of documents of similar size")
+    ap.add_argument("--eval-batch-size", type=int, default=1, help="documents per evaluation forward (ragged batches when > 1)")
+    args = ap.parse_args(argv)
+    if args.batch_size < 1 or args.eval_batch_size < 1:
+        ap.error("--batch-size and --eval-batch-size must be >= 1")
+    args.bmname, args.hidden_dim, args.dataset, args.method = None, 500, "invoice", "GCN"
+    return args
+
+
+def main(argv=None):
+    args = parse_args(argv)
     random.seed(777)
     data_loader = FUNSDCharGridDataLoaderBoxMaskBoxLabel(args.train_pickle)
     data_loader_test = FUNSDCharGridDataLoaderBoxMaskBoxLabel(args.test_pickle, data_loader.labels)
@@ -148,10 +194,13 @@ def main():
     print("Num training instances: ", len(train_instances), "; Num validation instances: ", len(val_instances),
           "; Num testing instances: ", len(test_instances))
     # batch 1 with a different H x W per document (data_generator_funsd_bert.py:216-222): every shape has its own static
-    # plan (buffers + launch list).  Keep them all -- one training and one forward-only plan per distinct shape, bounded
-    # by model.max_plan_bytes -- instead of rebuilding a plan on every step of every epoch.
+    # plan (buffers + launch list); ragged batches have one per canvas.  Keep them all -- the training plans and the forward-only
+    # plans of the evaluation passes, bounded by model.max_plan_bytes -- instead of rebuilding a plan on every step of every epoch.
     shapes = {tuple(d["mask"].shape[2:]) for d in train_instances + val_instances + test_instances}
-    model.max_cached_plans = max(model.max_cached_plans, 2 * len(shapes))
+    evaluated = train_instances[:eval_count(len(train_instances), 100)]
+    n_plans = len(canvases(train_instances, args.batch_size)) + \
+        len(set().union(*(canvases(d, args.eval_batch_size) for d in (evaluated, val_instances, test_instances) if d)))
+    model.max_cached_plans = max(model.max_cached_plans, 2 * len(shapes), n_plans)
     print("Distinct document shapes: ", len(shapes))
     train(train_instances, model, args, val_dataset=val_instances, test_dataset=test_instances,
           labels_map=data_loader.labels)
