@@ -652,7 +652,7 @@ class TrainEngine:
         # issued while the earlier stages' backward still runs (fewer launches and joins, no overlap)
         self._ar_native = False
         # the native sequence needs one bucket per backward segment + the end-conv tail (stage_buckets drops EMPTY buckets: then
-        # the counts differ and the exchange stays with GradSync), and the per-launch profiling path does not run sequences at all
+        # the counts differ and the exchange stays with GradSync), and a profiled sweep runs its records one by one on one stream
         native = self._comm is not None and self.sync.active and plan.overlap_wgrad and L._profiler is None \
             and len(self.sync.buckets) == len(plan._bwd_segs) + 1
         if native:

@@ -27,7 +27,7 @@ from __future__ import annotations
 import ctypes as C
 import math
 import os
-from typing import Dict, List, Optional, Tuple
+from typing import Dict, List, NamedTuple, Optional, Tuple
 
 import torch
 
@@ -48,6 +48,17 @@ def _ru(a: int, b: int) -> int:
 
 def _ptr(t: Optional[torch.Tensor]) -> Optional[int]:
     return None if t is None else t.data_ptr()
+
+
+class Launch(NamedTuple):
+    """One record of a launch sequence, carrying its own description: `kind` (MSAU_OP_* + stream flags) and `args` are what
+    msau_run_ops* executes; `key` (the kernel instance), `nbytes` and `flops` (algorithmic, per launch) are what the profiler,
+    the in-place probes and `Plan.launch_meta` (bench.py's roofline) call it and charge it with."""
+    kind: int
+    args: Optional[C.Structure]
+    key: str
+    nbytes: float
+    flops: float = 0.0
 
 
 class Act:
@@ -95,14 +106,11 @@ class Op:
     def finalize(self):
         pass
 
-    def note(self):
-        pass
-
-    def fwd(self, s):
+    def fwd_recs(self) -> List[Launch]:
         raise NotImplementedError
 
-    def bwd(self, s):
-        pass
+    def bwd_recs(self) -> List[Launch]:
+        return []
 
 
 class ConvOp(Op):
@@ -477,20 +485,16 @@ class ConvOp(Op):
             return name, (nin + nout * (1 + extra)) * esz + pooled
 
         self.fkey, self.fbytes = conv_meta(self.fdesc)
-        P.note_launch(self.fkey, self.fbytes, self.flops)
-        self.dmeta = [None, None]
+        self.dmeta = [None, None]                        # (key, bytes, flops) of the data-gradient launches
         for si, dd in enumerate(self.ddesc):
             if dd is not None:
                 src_c = (self.x1.C + self.x2.C) if self.dd_off is not None else (self.x1, self.x2)[si].C
                 fl = 2.0 * P.B * (self.out.H * self.out.W if self.kind == "conv" else self.x1.H * self.x1.W) * taps * src_c * self.out.C
-                self.dmeta[si] = conv_meta(dd)
-                if (self.proj is None or not self.proj.active) and self.dgrad2 is None and self.dgrad_in_pair is None:
-                    P.note_launch(self.dmeta[si][0], self.dmeta[si][1], fl)
+                self.dmeta[si] = conv_meta(dd) + (fl,)
         if self.dgrad2 is not None:
             a = self.dgrad2
             nops = 3 + a.accumulate1 + a.accumulate2 + (1 if a.mask1 else 0) + (1 if a.mask2 else 0)
-            self.d2meta = ("dgrad2_1x1<bf16,C64>", self.out.npix * 64 * nops * esz)
-            P.note_launch(self.d2meta[0], self.d2meta[1], 2.0 * self.out.npix * 128 * self.out.C)
+            self.d2meta = ("dgrad2_1x1<bf16,C64>", self.out.npix * 64 * nops * esz, 2.0 * self.out.npix * 128 * self.out.C)
         if self.wdesc is not None:
             w, wg = self.wdesc, self.wgeom
             ctn = -(-w.Cout // 16)
@@ -505,31 +509,13 @@ class ConvOp(Op):
                 self.wkey = f"wgrad_kernel<{T},CT{ctn},NK{nkw}>"
             self.wbytes = (w.B * w.Hin * w.Win * (w.C1 + w.C2) * wg.nchunks // wg.nchunks + w.B * w.Hout * w.Wout * w.Cout) * esz \
                 + w.nslabs * wg.slab_bytes
-            if not self.wg_fused:
-                P.note_launch(self.wkey, self.wbytes, self.flops)
-            if self.kind != "conv":                      # bias gradient of the transposed conv: one pass over its output gradient
-                P.note_launch("msau_channel_sum", self.out.npix * self.out.Cs * esz, 0.0)
-
-    def fwd(self, s):
-        if self.pair is not None and self.pair.active:
-            if self is self.pair.c2:
-                L.call("msau_conv_pair", s, self.plan.dtype, C.byref(self.pair.fdesc), key=self.pair.key)
-            return
-        if self.cpl_fused_into is not None:
-            return
-        L.call("msau_conv2d", s, self.plan.dtype, C.byref(self.fdesc), key=self.fkey)
 
     def fwd_recs(self):
-        rm = self.plan.rec_meta
         if self.cpl_fused_into is not None:             # computed by the residual pair's forward launch
             return []
         if self.pair is not None and self.pair.active:
-            if self is not self.pair.c2:
-                return []
-            rm[C.addressof(self.pair.fdesc)] = (self.pair.key, self.pair.fbytes)
-            return [(L.OP_CONV_PAIR, self.pair.fdesc)]
-        rm[C.addressof(self.fdesc)] = (self.fkey, self.fbytes)
-        return [(L.OP_CONV2D, self.fdesc)]
+            return [self.pair.fwd_rec()] if self is self.pair.c2 else []
+        return [Launch(L.OP_CONV2D, self.fdesc, self.fkey, self.fbytes, self.flops)]
 
     def bwd_recs(self):
         if self.wdesc is None:
@@ -538,72 +524,24 @@ class ConvOp(Op):
         if self.x1 is self.plan.x_in:
             side = 0        # the net's first conv has no data gradient: nothing is left on the main stream to run beside,
                             # and the side stream is still busy with the two weight gradients enqueued before this one
-        recs = [] if self.wg_fused else [(L.OP_WGRAD | side, self.wdesc)]
-        if self.kind != "conv":
-            P = self.plan
-            self._csum = L.CsumArgs(_ptr(self.out.grad), self.out.npix, self.out.Cs, P.slab_ptr(self.csum_off), self.csum_blocks)
-            recs.append((L.OP_CHANNEL_SUM | side, self._csum))
-        rm = self.plan.rec_meta
-        if not self.wg_fused:
-            rm[C.addressof(self.wdesc)] = (self.wkey, self.wbytes)
+        recs = [] if self.wg_fused else [Launch(L.OP_WGRAD | side, self.wdesc, self.wkey, self.wbytes, self.flops)]
+        if self.kind != "conv":                         # bias gradient of the transposed conv: one pass over its output gradient
+            P, g = self.plan, self.out.grad
+            self._csum = L.CsumArgs(_ptr(g), self.out.npix, self.out.Cs, P.slab_ptr(self.csum_off), self.csum_blocks)
+            recs.append(Launch(L.OP_CHANNEL_SUM | side, self._csum, "msau_channel_sum", g.numel() * g.element_size()))
         if self.pair is not None and self.pair.active and self.pair.bdesc is not None:
             if self is self.pair.c2:                    # both data gradients in one launch, behind the second conv's wgrad
-                rm[C.addressof(self.pair.bdesc)] = (self.pair.key, self.pair.bbytes)
                 if self.pair.dcp is not None:           # (MSAU_PAIR_DCOUPLE: that launch WRITES the gradient this conv's wgrad reads)
-                    return [(L.OP_CONV_PAIR, self.pair.bdesc)] + recs
-                recs.append((L.OP_CONV_PAIR, self.pair.bdesc))
+                    return [self.pair.bwd_rec()] + recs
+                recs.append(self.pair.bwd_rec())
             return recs
         if self.dgrad_in_pair is not None:              # a coupling conv whose data gradients are the prologue of the pair's backward launch
             return recs
         if self.proj is not None and self.proj.active:  # f, g, h of an attention block: one launch, behind the last of the three
             return recs + (self.proj.recs() if self is self.proj.f else [])
         if self.dgrad2 is not None:
-            rm[C.addressof(self.dgrad2)] = self.d2meta
-            return recs + [(L.OP_DGRAD2_1X1, self.dgrad2)]
-        for si, dd in enumerate(self.ddesc):
-            if dd is not None:
-                rm[C.addressof(dd)] = self.dmeta[si]
-                recs.append((L.OP_CONV2D, dd))
-        return recs
-
-    def bwd_wgrad(self, s):
-        """weight / bias gradient: reads out.grad and the saved inputs, writes only this op's slabs"""
-        if self.wdesc is None or self.wg_fused:
-            return
-        P = self.plan
-        L.call("msau_conv2d_wgrad", s, P.dtype, C.byref(self.wdesc), key=self.wkey)
-        if self.kind != "conv":
-            L.call("msau_channel_sum", s, P.dtype, _ptr(self.out.grad), self.out.npix, self.out.Cs,
-                   P.slab_ptr(self.csum_off), self.csum_blocks)
-
-    def bwd_dgrad(self, s):
-        if self.wdesc is None:
-            return
-        P = self.plan
-        if self.pair is not None and self.pair.active and self.pair.bdesc is not None:
-            if self is self.pair.c2:
-                L.call("msau_conv_pair", s, P.dtype, C.byref(self.pair.bdesc), key=self.pair.key)
-            return
-        if self.proj is not None and self.proj.active:
-            if self is self.proj.f:
-                self.proj.launch(s)
-            return
-        if self.dgrad2 is not None:
-            L.call("msau_dgrad2_1x1", s, P.dtype, C.byref(self.dgrad2), key=self.d2meta[0])
-            return
-        if self.dgrad_in_pair is not None:
-            return
-        for si, dd in enumerate(self.ddesc):
-            if dd is not None:
-                L.call("msau_conv2d", s, P.dtype, C.byref(dd), key=self.dmeta[si][0])
-
-    def bwd(self, s):
-        if self.pair is not None and self.pair.active and self.pair.dcp is not None and self is self.pair.c2:
-            self.bwd_dgrad(s)                           # (MSAU_PAIR_DCOUPLE: the pair launch writes the gradient the wgrad reads)
-            self.bwd_wgrad(s)
-            return
-        self.bwd_wgrad(s)
-        self.bwd_dgrad(s)
+            return recs + [Launch(L.OP_DGRAD2_1X1, self.dgrad2, *self.d2meta)]
+        return recs + [Launch(L.OP_CONV2D, dd, *self.dmeta[si]) for si, dd in enumerate(self.ddesc) if dd is not None]
 
 
 class PairOp:
@@ -780,22 +718,13 @@ class PairOp:
         if self.bdesc is not None and self.c1.wg_fused:
             self.bdesc.wg1_slabs = self.plan.slab_ptr(self.wg_slab_off)
 
-    def note(self):
-        """replace the two convs' launch accounting by the fused launches' (bench.py roofline)"""
-        P, c1, c2 = self.plan, self.c1, self.c2
-        if not self.active:
-            return
-        for c in (c1, c2):
-            P.unnote_launch(c.fkey, c.fbytes, c.flops)
-        cflops = 0.0
-        if self.cpl is not None:
-            P.unnote_launch(self.cpl.fkey, self.cpl.fbytes, self.cpl.flops)
-            cflops = self.cpl.flops
-        P.note_launch(self.key, self.fbytes, c1.flops + c2.flops + cflops)
-        if self.bdesc is not None:
-            for c in (c1, c2):
-                P.unnote_launch(c.dmeta[0][0], c.dmeta[0][1], c.flops)
-            P.note_launch(self.key, self.bbytes, c1.flops + c2.flops + (2.0 * self.dcp.flops if self.dcp is not None else 0.0))
+    def fwd_rec(self) -> Launch:
+        flops = self.c1.flops + self.c2.flops + (self.cpl.flops if self.cpl is not None else 0.0)
+        return Launch(L.OP_CONV_PAIR, self.fdesc, self.key, self.fbytes, flops)
+
+    def bwd_rec(self) -> Launch:
+        flops = self.c1.flops + self.c2.flops + (2.0 * self.dcp.flops if self.dcp is not None else 0.0)
+        return Launch(L.OP_CONV_PAIR, self.bdesc, self.key, self.bbytes, flops)
 
 
 class BoxOp(Op):
@@ -831,20 +760,15 @@ class BoxOp(Op):
         if P.training and self.y.grad is not None:
             self.ws = torch.zeros((int(L.load().msau_box_pgrad_ws_floats(P.B, x.H, x.W, x.C, self.F)),), dtype=torch.float32, device=P.device)
 
-    def note(self):
+    def _meta(self, bwd: bool) -> Tuple[str, float]:
         P, x, y = self.plan, self.x, self.y
         esz = 4 if P.dtype == L.F32 else 2
         T = "f32" if P.dtype == L.F32 else "bf16"
         nii = P.B * x.C * (x.H + 1) * (x.W + 1) * 4
-        self.fkey, self.bkey = f"box_fwd<{T},C{x.C}>", f"box_bwd<{T},C{x.C}>"
-        # forward: x read, II written + scanned in place (3 passes) + gathered once, y written
-        self.fbytes = x.npix * x.Cs * esz + 4 * nii + y.npix * y.Cs * esz
-        P.note_launch(self.fkey, self.fbytes, 0.0)
-        self.bbytes = 0
-        if self.ws is not None:
-            # backward: g(y) read twice (parameter gradient, integral), II read, II of g(y) (F x larger) written / scanned / gathered, g(x) written
-            self.bbytes = 2 * y.npix * y.Cs * esz + nii + 4 * self.F * nii + x.npix * x.Cs * esz
-            P.note_launch(self.bkey, self.bbytes, 0.0)
+        if not bwd:     # x read, II written + scanned in place (3 passes) + gathered once, y written
+            return f"box_fwd<{T},C{x.C}>", x.npix * x.Cs * esz + 4 * nii + y.npix * y.Cs * esz
+        # g(y) read twice (parameter gradient, integral), II read, II of g(y) (F x larger) written / scanned / gathered, g(x) written
+        return f"box_bwd<{T},C{x.C}>", 2 * y.npix * y.Cs * esz + nii + 4 * self.F * nii + x.npix * x.Cs * esz
 
     def _args(self):
         P, x, y = self.plan, self.x, self.y
@@ -862,8 +786,7 @@ class BoxOp(Op):
 
     def fwd_recs(self):
         self._fa = self._args()
-        self.plan.rec_meta[C.addressof(self._fa)] = (self.fkey, self.fbytes)
-        return [(L.OP_BOX_FWD, self._fa)]
+        return [Launch(L.OP_BOX_FWD, self._fa, *self._meta(False))]
 
     def bwd_recs(self):
         P, x, y = self.plan, self.x, self.y
@@ -878,17 +801,8 @@ class BoxOp(Op):
             a.mask_a = _ptr(x.data) if self.relu_in else None
             a.add = _ptr(self.bwd_add.grad) if self.bwd_add is not None else None
             a.mask_b = _ptr(x.data) if maskb else None
-        self._ba = a
         P._box_bwd_args.append(a)
-        P.rec_meta[C.addressof(a)] = (self.bkey, self.bbytes)
-        return [(L.OP_BOX_BWD, a)]
-
-    def fwd(self, s):
-        L.call("msau_box_fwd", s, self.plan.dtype, C.byref(self._fa), key=self.fkey)
-
-    def bwd(self, s):
-        if self.ws is not None:
-            L.call("msau_box_bwd", s, self.plan.dtype, C.byref(self._ba), key=self.bkey)
+        return [Launch(L.OP_BOX_BWD, a, *self._meta(True))]
 
     def load_params(self, s, flat_params: torch.Tensor):
         a = self._fa
@@ -917,51 +831,28 @@ class LrnOp(Op):
     def writes(self):
         return [self.y]
 
-    def note(self):
+    def _meta(self, bwd: bool) -> Tuple[str, float]:
         """algorithmic bytes: forward reads a, writes y; backward reads a and dy, writes da"""
         P, a = self.plan, self.a
-        esz = 4 if P.dtype == L.F32 else 2
-        T = "f32" if P.dtype == L.F32 else "bf16"
-        n = a.npix * a.Cs * esz
-        self.fkey, self.bkey = f"lrn_fwd<{T},C{a.Cs}>", f"lrn_bwd<{T},C{a.Cs}>"
-        self.fbytes, self.bbytes = 2 * n, 3 * n
-        if self.fused_into is None:
-            P.note_launch(self.fkey, self.fbytes, 0.0)
-        if P.training and self.y.grad is not None and a.grad is not None and self.bwd_fused_into is None:
-            P.note_launch(self.bkey, self.bbytes, 0.0)
+        n = a.npix * a.Cs * (4 if P.dtype == L.F32 else 2)
+        return f"lrn_{'bwd' if bwd else 'fwd'}<{'f32' if P.dtype == L.F32 else 'bf16'},C{a.Cs}>", (3 if bwd else 2) * n
 
     def fwd_recs(self):
         a, y = self.a, self.y
         if self.fused_into is not None:
             return []
         self._fa = L.LrnArgs(_ptr(a.data), None, _ptr(y.data), a.npix, a.C, a.Cs, a.C, 1e-4, 0.75, 1.0)
-        self.plan.rec_meta[C.addressof(self._fa)] = (self.fkey, self.fbytes)
-        return [(L.OP_LRN_FWD, self._fa)]
+        return [Launch(L.OP_LRN_FWD, self._fa, *self._meta(False))]
 
     def bwd_recs(self):
         a, y = self.a, self.y
         if y.grad is None or a.grad is None or self.bwd_fused_into is not None:
             return []
         self._ba = L.LrnArgs(_ptr(a.data), _ptr(y.grad), _ptr(a.grad), a.npix, a.C, a.Cs, a.C, 1e-4, 0.75, 1.0)
-        self.plan.rec_meta[C.addressof(self._ba)] = (self.bkey, self.bbytes)
         # (round 1 tagged this launch MSAU_OP_JOIN in deterministic mode: its results varied from run to run beside a
         # side-stream kernel.  Root cause found in round 2 -- packed-fp32 instructions, msau_amd/build.py -- so the join,
         # and its 4 % cost, are gone.)
-        return [(L.OP_LRN_BWD, self._ba)]
-
-    def fwd(self, s):
-        a, y = self.a, self.y
-        if self.fused_into is not None:
-            return
-        L.call("msau_lrn_fwd", s, self.plan.dtype, _ptr(a.data), _ptr(y.data), a.npix, a.C, a.Cs, a.C, 1e-4, 0.75, 1.0, key=self.fkey)
-
-    def bwd(self, s):
-        a, y = self.a, self.y
-        if y.grad is None or a.grad is None or self.bwd_fused_into is not None:
-            return
-        assert a.n_contrib == 1 and not a.relu_out
-        L.call("msau_lrn_bwd", s, self.plan.dtype, _ptr(a.data), _ptr(y.grad), _ptr(a.grad), a.npix, a.C, a.Cs, a.C,
-               1e-4, 0.75, 1.0, key=self.bkey)
+        return [Launch(L.OP_LRN_BWD, self._ba, *self._meta(True))]
 
 
 class PoolOp(Op):
@@ -985,29 +876,23 @@ class PoolOp(Op):
     def writes(self):
         return [self.y]
 
-    def note(self):
+    def _meta(self, bwd: bool) -> Tuple[str, float]:
         """forward: x read, y (+ 1-byte argmax) written; backward: dy + argmax read, dx written (+ mask / accumulate reads)"""
         P, x, y = self.plan, self.x, self.y
         esz = 4 if P.dtype == L.F32 else 2
         T = "f32" if P.dtype == L.F32 else "bf16"
         nx, ny = x.npix * x.Cs, y.npix * y.Cs
-        self.fkey, self.bkey = f"pool_fwd<{T},C{x.Cs}>", f"pool_bwd<{T},C{x.Cs}>"
-        self.fbytes = (nx + ny) * esz + (ny if P.training else 0)
-        if self.fused_into is None:
-            P.note_launch(self.fkey, self.fbytes, 0.0)
-        self.bbytes = 0
-        if P.training and y.grad is not None and x.grad is not None:
-            accum, maskb = x.slot_flags(self.slot)
-            self.bbytes = (ny + nx * (1 + int(accum) + int(maskb))) * esz + ny
-            P.note_launch(self.bkey, self.bbytes, 0.0)
+        if not bwd:
+            return f"pool_fwd<{T},C{x.Cs}>", (nx + ny) * esz + (ny if P.training else 0)
+        accum, maskb = x.slot_flags(self.slot)
+        return f"pool_bwd<{T},C{x.Cs}>", (ny + nx * (1 + int(accum) + int(maskb))) * esz + ny
 
     def fwd_recs(self):
         x, y = self.x, self.y
         if self.fused_into is not None:
             return []
         self._fa = L.PoolArgs(_ptr(x.data), _ptr(y.data), _ptr(self.idx), None, self.plan.B, x.H, x.W, x.Cs, 0, None)
-        self.plan.rec_meta[C.addressof(self._fa)] = (self.fkey, self.fbytes)
-        return [(L.OP_POOL_FWD, self._fa)]
+        return [Launch(L.OP_POOL_FWD, self._fa, *self._meta(False))]
 
     def bwd_recs(self):
         x, y = self.x, self.y
@@ -1017,24 +902,7 @@ class PoolOp(Op):
         self._ba = L.PoolArgs(_ptr(y.grad), _ptr(x.grad), _ptr(self.idx), _ptr(x.data) if maskb else None,
                               self.plan.B, x.H, x.W, x.Cs, int(accum) | (2 if maskb and self.plan.act_flag else 0),
                               self.plan.extent_ptr(x))
-        self.plan.rec_meta[C.addressof(self._ba)] = (self.bkey, self.bbytes)
-        return [(L.OP_POOL_BWD, self._ba)]
-
-    def fwd(self, s):
-        x, y = self.x, self.y
-        if self.fused_into is not None:
-            return
-        L.call("msau_maxpool2x2_fwd", s, self.plan.dtype, _ptr(x.data), _ptr(y.data), _ptr(self.idx), self.plan.B, x.H, x.W, x.Cs,
-               key=self.fkey)
-
-    def bwd(self, s):
-        x, y = self.x, self.y
-        if y.grad is None or x.grad is None:
-            return
-        accum, maskb = x.slot_flags(self.slot)
-        L.call("msau_maxpool2x2_bwd_ext", s, self.plan.dtype, _ptr(y.grad), _ptr(self.idx), _ptr(x.grad),
-               _ptr(x.data) if maskb else None, self.plan.B, x.H, x.W, x.Cs, int(accum) | (2 if maskb and self.plan.act_flag else 0),
-               self.plan.extent_ptr(x), key=self.bkey)
+        return [Launch(L.OP_POOL_BWD, self._ba, *self._meta(True))]
 
 
 class AttnCoreOp(Op):
@@ -1063,7 +931,7 @@ class AttnCoreOp(Op):
                           _ptr(self.f.grad), _ptr(self.g.grad), _ptr(self.h.grad), _ptr(self.ws),
                           self.plan.B, self.N, self.f.Cs, self.h.Cs, self.plan.extent_ptr(self.x), self.x.W)
 
-    def note(self):
+    def _meta(self, bwd: bool) -> Tuple[str, float, float]:
         """forward: f, g, h, x read, y written (two sweeps: stats, output); backward: f, g, h, dy read, df, dg, dh written.
         flops: the N x N score matrix (2*N*N*d) is formed twice per sweep pair, h . beta costs 2*N*N*C."""
         P = self.plan
@@ -1071,44 +939,27 @@ class AttnCoreOp(Op):
         T = "f32" if P.dtype == L.F32 else "bf16"
         npx = P.B * self.N
         small, big = npx * self.f.Cs * esz, npx * self.h.Cs * esz
-        self.fkey, self.bkey = f"selfattn_fwd<{T}>", f"selfattn_bwd<{T}>"
-        self.fbytes = 2 * small + 3 * big
         ffl = 2.0 * P.B * self.N * self.N * (self.f.C + self.h.C)
-        P.note_launch(self.fkey, self.fbytes, ffl)
-        self.bbytes = 4 * small + 4 * big
-        if P.training and self.y.grad is not None:
-            P.note_launch(self.bkey, self.bbytes, 2.0 * ffl)
+        if not bwd:
+            return f"selfattn_fwd<{T}>", 2 * small + 3 * big, ffl
+        return f"selfattn_bwd<{T}>", 4 * small + 4 * big, 2.0 * ffl
 
     def fwd_recs(self):
         self._fa = self._args(False)
-        self.plan.rec_meta[C.addressof(self._fa)] = (self.fkey, self.fbytes)
-        return [(L.OP_ATTN_FWD, self._fa)]
+        return [Launch(L.OP_ATTN_FWD, self._fa, *self._meta(False))]
 
     def bwd_recs(self):
         if self.y.grad is None:
             return []
         self._ba = self._args(True)
-        self.plan.rec_meta[C.addressof(self._ba)] = (self.bkey, self.bbytes)
         # (round 4: the core's backward as a side branch too -- released at the start of its stage's backward, the level-3 data gradients
         #  waiting for an event right behind it -- made the step 65 us SLOWER: in the backward the side queue is as loaded as the main one)
-        return [(L.OP_ATTN_BWD, self._ba)]
-
-    def fwd(self, s):
-        L.call("msau_selfattn_fwd_ext", s, self.plan.dtype, _ptr(self.f.data), _ptr(self.g.data), _ptr(self.h.data),
-               _ptr(self.x.data), _ptr(self.y.data), _ptr(self.stats), self.plan.B, self.N, self.f.Cs, self.h.Cs,
-               self.plan.extent_ptr(self.x), self.x.W, key=self.fkey)
-
-    def bwd(self, s):
-        if self.y.grad is None:
-            return
-        L.call("msau_selfattn_bwd_ext", s, self.plan.dtype, _ptr(self.f.data), _ptr(self.g.data), _ptr(self.h.data),
-               _ptr(self.y.grad), _ptr(self.stats), _ptr(self.f.grad), _ptr(self.g.grad), _ptr(self.h.grad),
-               _ptr(self.ws), self.plan.B, self.N, self.f.Cs, self.h.Cs, self.plan.extent_ptr(self.x), self.x.W, key=self.bkey)
+        return [Launch(L.OP_ATTN_BWD, self._ba, *self._meta(True))]
 
 
 class ProjBwd:
     """The data gradients of an attention block's f, g, h projections (attention.py:152-154: three 1x1 convs reading the same
-    tensor) as ONE launch (msau_attn_proj_bwd, csrc/attention_mfma.hip) instead of three accumulating msau_conv2d launches.
+    tensor) as ONE launch (msau_attn_proj_bwd, csrc/pointwise.hip) instead of three accumulating msau_conv2d launches.
     Like PairOp not an entry of plan.ops: the ConvOps keep their packed images, weight-gradient launches and bookkeeping; the
     LAST of the three in backward order (f) emits the fused record, the other two emit no data gradient."""
 
@@ -1121,7 +972,7 @@ class ProjBwd:
         plan.projs.append(self)
 
     def bind(self):
-        """after ConvOp.bind (the three descriptors say what the launches would have done), before late_bind (launch accounting)"""
+        """after ConvOp.bind (the three descriptors say what the launches would have done)"""
         P, f, g, h = self.plan, self.f, self.g, self.h
         x = f.x1
         df, dg, dh = f.ddesc[0], g.ddesc[0], h.ddesc[0]
@@ -1147,23 +998,11 @@ class ProjBwd:
         a.dx, a.npix, a.C, a.accumulate = _ptr(x.grad), x.npix, x.Cs, int(bool(dh.flags & A))
         self.args, self.active = a, True
 
-    def late_bind(self):
-        if not self.active:
-            return
-        P, x = self.plan, self.f.x1
-        esz = 2
-        nops = 1 + (1 if self.args.add else 0) + self.args.accumulate + (1 if self.args.mask_b else 0)
-        self.key = "attn_proj_bwd<bf16,C64>"
-        self.bytes = x.npix * (self.f.out.Cs + self.g.out.Cs + self.h.out.Cs + nops * x.Cs) * esz
-        self.flops = 2.0 * x.npix * x.C * (self.f.out.C + self.g.out.C + self.h.out.C)
-        P.note_launch(self.key, self.bytes, self.flops)
-
     def recs(self):
-        self.plan.rec_meta[C.addressof(self.args)] = (self.key, self.bytes)
-        return [(L.OP_ATTN_PROJ_BWD, self.args)]
-
-    def launch(self, s):
-        L.call("msau_attn_proj_bwd", s, self.plan.dtype, C.byref(self.args), key=self.key)
+        x, outs = self.f.x1, (self.f.out, self.g.out, self.h.out)
+        nops = 1 + (1 if self.args.add else 0) + self.args.accumulate + (1 if self.args.mask_b else 0)
+        nbytes = x.npix * (sum(o.Cs for o in outs) + nops * x.Cs) * 2
+        return [Launch(L.OP_ATTN_PROJ_BWD, self.args, "attn_proj_bwd<bf16,C64>", nbytes, 2.0 * x.npix * x.C * sum(o.C for o in outs))]
 
 
 class Plan:
@@ -1206,8 +1045,8 @@ class Plan:
         self._unpack_stage: List[int] = []
         self._pack_max = 1
         self._unpack_max = 1
-        self.launch_meta: Dict[str, Tuple[int, float, float]] = {}
-        self.rec_meta: Dict[int, Tuple[str, float]] = {}       # address of a launch record's args -> (kernel key, bytes)
+        self.launch_meta: Dict[str, Tuple[int, float, float]] = {}     # kernel key -> (launches, bytes, flops) of one step (_finish)
+        self.rec_meta: Dict[int, Tuple[str, float]] = {}       # address of a launch record's args -> (kernel key, bytes) (_make_seq)
         self._cur_stage = 0
         # The weight gradients form no dependency chain (each reads a finished out.grad and writes its own slabs),
         # so they run on a side stream beside the data-gradient chain.  Measured 2026-10-03 with the lean kernels:
@@ -1289,18 +1128,6 @@ class Plan:
         self._unpack_entries.append(e)
         self._unpack_stage.append(stage)
         self._unpack_max = max(self._unpack_max, int(nelems))
-
-    def note_launch(self, key: str, nbytes: float, flops: float):
-        """algorithmic bytes / flops of one launch, accumulated per kernel symbol for one train step"""
-        c, b, f = self.launch_meta.get(key, (0, 0.0, 0.0))
-        self.launch_meta[key] = (c + 1, b + nbytes, f + flops)
-
-    def unnote_launch(self, key: str, nbytes: float, flops: float):
-        c, b, f = self.launch_meta[key]
-        if c <= 1:
-            del self.launch_meta[key]
-        else:
-            self.launch_meta[key] = (c - 1, b - nbytes, f - flops)
 
     def pack_ptr(self, off: int) -> int:
         return self.pack_arena.data_ptr() + off
@@ -1457,15 +1284,9 @@ class Plan:
         for op in self.ops:
             if isinstance(op, ConvOp):
                 op.late_bind()
-        for pj in self.projs:
-            pj.late_bind()
         for pr in self.pairs:
             pr.late_bind()
-            pr.note()
-        for op in self.ops:
-            if not isinstance(op, ConvOp):
-                op.note()
-        self._note_boundary()
+        boundary = self._boundary_launches()
         # The bottleneck attention of a stage (f, g, h projections + core: model/layers/attention.py:152-162) feeds ONLY the next stage's
         # level-3 coupling (model/model.py:149-150: the decoder consumes the pre-attention tensor), so in the forward sweep it is a side
         # branch: its launches go to the side stream -- idle during the forward -- beside the stage's decoder, and the consumer of its
@@ -1488,13 +1309,13 @@ class Plan:
                         join_ops.add(id(first))
         frecs = []
         for op in self.ops:
-            for kind, args in op.fwd_recs():
+            for r in op.fwd_recs():
                 if id(op) in side_ops:
-                    kind |= L.OP_SIDE
+                    r = r._replace(kind=r.kind | L.OP_SIDE)
                 elif id(op) in join_ops:
-                    kind |= L.OP_JOIN
+                    r = r._replace(kind=r.kind | L.OP_JOIN)
                     join_ops.discard(id(op))                 # (a fused pair emits one record; only the first record of an op joins)
-                frecs.append((kind, args))
+                frecs.append(r)
         assert not join_ops, "a side-stream attention branch lost its join: its first reader emitted no launch record"
         self._fwd_side = bool(side_ops)
 
@@ -1508,6 +1329,8 @@ class Plan:
             recs = []
             stages = sorted({op.stage for op in self.ops}, reverse=True)
             esz = C.sizeof(L.UnpackEntry)
+            slabs = [e.nslabs * e.slab_elems for e in self._unpack_entries]
+
             def reduce_rec(group):
                 idx = [i for i, st in enumerate(self._unpack_stage) if st == group]
                 if not idx:
@@ -1516,7 +1339,9 @@ class Plan:
                 ra = L.ReduceArgs(self.slab_arena.data_ptr(), None, self.unpack_table.data_ptr() + idx[0] * esz,
                                   len(idx), self._unpack_max)
                 self._reduce_args.append(ra)
-                recs.append((L.OP_WGRAD_REDUCE | (L.OP_SIDE if self.overlap_wgrad else 0), ra))
+                # (the step's reduction bytes, shared out by the slab elements each group reads)
+                recs.append(Launch(L.OP_WGRAD_REDUCE | (L.OP_SIDE if self.overlap_wgrad else 0), ra, "msau_wgrad_reduce",
+                                   self.reduce_bytes * sum(slabs[i] for i in idx) / sum(slabs)))
 
             for b in stages:
                 start = len(recs)
@@ -1531,6 +1356,10 @@ class Plan:
                     reduce_rec(-1)
                 self._bwd_segs.append((b, start, len(recs) - start))
             self._bwd_seq = self._make_seq(recs)
+        # one step's launches per kernel key: the records of both sequences + the launches outside them
+        for r in frecs + (recs if self.training else []) + boundary:
+            n, nbytes, flops = self.launch_meta.get(r.key, (0, 0.0, 0.0))
+            self.launch_meta[r.key] = (n + 1, nbytes + r.nbytes, flops + r.flops)
         HW = self.H * self.W
         lg = self.logits
         self.out_logits = torch.zeros((self.B, lg.C, lg.H, lg.W), dtype=torch.float32, device=self.device)
@@ -1569,6 +1398,7 @@ class Plan:
 
         def release(a: Act):
             if id(a) not in keep and a.data is not None:
+                keep.add(id(a))                   # (at most once: a riding coupling conv's outputs are listed by two ops)
                 free[a._buf.numel()].append(a._buf)
 
         take(self.x_in)
@@ -1583,35 +1413,34 @@ class Plan:
             if a.data is None:
                 take(a)
 
-    def _note_boundary(self):
-        """launches outside the op list: parameter packing, NCHW fp32 -> NHWC conversion of the API input, masked CE (+ label
-        counting), slab reduction, clip + Adam -- so that `launch_meta` sums to the whole step"""
+    def _boundary_launches(self) -> List[Launch]:
+        """launches outside the two sequences: parameter packing, NCHW fp32 -> NHWC conversion of the API input, masked CE (+ label
+        counting), clip + Adam -- so that `launch_meta` sums to the whole step.  Runs before the records are made: it also
+        names the first conv's launch when that conv reads the API tensor itself."""
         esz = 4 if self.dtype == L.F32 else 2
         a = self.x_in
-        self.in_bytes = self.B * a.C * a.H * a.W * 4 + a.npix * a.Cs * esz
+        api_bytes = self.B * a.C * a.H * a.W * 4
+        out = []
         c = self._nchw_first_conv()
         if c is None:
-            self.note_launch("msau_nchw_to_nhwc", self.in_bytes, 0.0)
+            out.append(Launch(0, None, "msau_nchw_to_nhwc", api_bytes + a.npix * a.Cs * esz))
         else:
             # the first conv reads the API tensor itself (MSAU_CONV_NCHW, csrc/conv_first.hip): the conversion launch and the conv's
             # read of the converted copy disappear; the copy is still written for the backward's weight gradient (training plans)
-            self.unnote_launch(c.fkey, c.fbytes, c.flops)
             T = "f32" if self.dtype == L.F32 else "bf16"
             c.fkey = f"first_conv_nchw<{T},CIN{a.Cs},CO{c.out.Cs}>"
-            c.fbytes = self.B * a.C * a.H * a.W * 4 + (a.npix * a.Cs * esz if self.training else 0) + c.out.npix * c.out.Cs * esz
-            self.note_launch(c.fkey, c.fbytes, c.flops)
+            c.fbytes = api_bytes + (a.npix * a.Cs * esz if self.training else 0) + c.out.npix * c.out.Cs * esz
         nparam = sum(int(math.prod(shp)) for shp in self.pshape.values())
-        self.note_launch("msau_pack_params", nparam * 4 + self._pack_bytes, 0.0)
+        out.append(Launch(0, None, "msau_pack_params", nparam * 4 + self._pack_bytes))
         if self.training:
             HW = self.H * self.W
             lg = self.logits
             nl = 2 if self.aux is not None else 1
-            self.note_launch("msau_label_counts", self.B * HW * 8, 0.0)
-            self.ce_bytes = self.B * HW * (8 + nl * 2 * lg.Cs * esz)
-            self.note_launch("msau_masked_ce_multi" if lg.Cs <= 16 else "msau_masked_ce", self.ce_bytes, 0.0)
-            self.reduce_bytes = self._slab_elems * 4 + nparam * 4
-            self.note_launch("msau_wgrad_reduce", self.reduce_bytes, 0.0)
-            self.note_launch("msau_clip_adam_step", nparam * 4 * 8, 0.0)       # g twice, p, m, v read; p, m, v written
+            out.append(Launch(0, None, "msau_label_counts", self.B * HW * 8))
+            out.append(Launch(0, None, "msau_masked_ce_multi" if lg.Cs <= 16 else "msau_masked_ce", self.B * HW * (8 + nl * 2 * lg.Cs * esz)))
+            self.reduce_bytes = self._slab_elems * 4 + nparam * 4          # (charged to the reduce records of the backward)
+            out.append(Launch(0, None, "msau_clip_adam_step", nparam * 4 * 8))       # g twice, p, m, v read; p, m, v written
+        return out
 
     def set_probe_keys(self, keys, side: bool = False) -> List[Tuple[str, float]]:
         """Mark every launch of ONE stream (main, or with side=True the weight-gradient side stream) whose kernel key is in
@@ -1633,37 +1462,6 @@ class Plan:
                     arr[i].kind &= ~L.OP_PROBE
         return order
 
-    def set_probe(self, key: Optional[str]) -> int:
-        """Mark (or with None: unmark) every conv launch whose kernel symbol is `key` with MSAU_OP_PROBE in the forward
-        and backward sequences; the next sweeps then time those launches in place (read with `read_probe`).
-        Returns the number of marked launches per step."""
-        want = set()
-        if key is not None:
-            for op in self.ops:
-                if isinstance(op, ConvOp):
-                    if op.fkey == key:
-                        want.add(C.addressof(op.fdesc))
-                    for si, dd in enumerate(op.ddesc):
-                        if dd is not None and op.dmeta[si][0] == key:
-                            want.add(C.addressof(dd))
-            for pr in self.pairs:
-                if pr.active and pr.key == key:
-                    want.add(C.addressof(pr.fdesc))
-                    if pr.bdesc is not None:
-                        want.add(C.addressof(pr.bdesc))
-        n = 0
-        for seq in (self._fwd_seq, self._bwd_seq):
-            if seq is None:
-                continue
-            arr, cnt, _ = seq
-            for i in range(cnt):
-                if arr[i].args in want:
-                    arr[i].kind |= L.OP_PROBE
-                    n += 1
-                else:
-                    arr[i].kind &= ~L.OP_PROBE
-        return n
-
     @staticmethod
     def read_probe(cap: int = 1 << 16):
         """durations (us) of the probed launches since the last read, in launch order"""
@@ -1672,15 +1470,30 @@ class Plan:
         L.call("msau_probe_read", buf, cap, C.byref(n))
         return list(buf[:n.value])
 
-    def _make_seq(self, recs):
-        """(kind, args struct) records -> (msau_op array, n); the structs are kept alive by the ops / this list"""
+    def _make_seq(self, recs: List[Launch]):
+        """records -> (msau_op array, n, records); the structs are kept alive by the ops / this list"""
         arr = (L.Op * max(len(recs), 1))()
-        for i, (kind, args) in enumerate(recs):
-            arr[i].kind, arr[i].dtype, arr[i].args = kind, self.dtype, C.addressof(args)
+        for i, r in enumerate(recs):
+            arr[i].kind, arr[i].dtype, arr[i].args = r.kind, self.dtype, C.addressof(r.args)
+            self.rec_meta[arr[i].args] = (r.key, r.nbytes)
         return arr, len(recs), recs
 
     def _run_seq(self, seq, s):
-        L.call("msau_run_ops", s, seq[0], seq[1])
+        """enqueue a whole sequence on ONE stream: one C call -- or, under a profiler, one call per record of the same array, so
+        that every launch of the step is bracketed by the profiler's events under the key `launch_meta` counts it by"""
+        arr, n, recs = seq
+        if L._profiler is None:
+            L.call("msau_run_ops", s, arr, n)
+            return
+        for i in range(n):
+            L.call("msau_run_ops", s, C.cast(C.byref(arr, i * C.sizeof(L.Op)), C.POINTER(L.Op)), 1, key=recs[i].key)
+
+    def _one_stream(self, single_stream: bool) -> bool:
+        """a sweep stays on ONE stream when the caller says so, when it is being captured into a HIP graph whoever the caller is (a
+        captured fork onto the side stream is the configuration of profiles/r04_graph_destroy.md; creating the side stream
+        synchronises the device, which is illegal during capture), and when its launches are being timed one by one"""
+        return single_stream or L._profiler is not None or \
+            (str(self.device).startswith("cuda") and torch.cuda.is_current_stream_capturing())
 
     def _upload(self, entries, ctype):
         n = len(entries)
@@ -1946,20 +1759,12 @@ class Plan:
             self._feed_ids(None)
             if not self._feed_nchw(x_nchw):
                 self.load_input(x_nchw)
-        if L._profiler is None:
-            # a sweep that is being captured into a HIP graph stays on ONE stream whoever the caller is (a captured fork onto the
-            # side stream is the configuration of profiles/r04_graph_destroy.md; creating the side stream synchronises the device,
-            # which is illegal during capture)
-            single_stream = single_stream or (str(self.device).startswith("cuda") and torch.cuda.is_current_stream_capturing())
-            if self._fwd_side and not single_stream:
-                if self._side is None:
-                    self._side = L.concurrent_stream(self.device)
-                L.call("msau_run_ops_overlap", s, self._side.cuda_stream, self._fwd_seq[0], self._fwd_seq[1], 1)
-            else:
-                self._run_seq(self._fwd_seq, s)      # one C call enqueues the whole forward sweep
+        if self._fwd_side and not self._one_stream(single_stream):
+            if self._side is None:
+                self._side = L.concurrent_stream(self.device)
+            L.call("msau_run_ops_overlap", s, self._side.cuda_stream, self._fwd_seq[0], self._fwd_seq[1], 1)
         else:
-            for op in self.ops:
-                op.fwd(s)
+            self._run_seq(self._fwd_seq, s)      # one C call enqueues the whole forward sweep
         if export:
             self.export_logits()
         return self.out_logits, self.out_aux
@@ -2055,23 +1860,13 @@ class Plan:
         enqueued (its slab reduction is the last thing on `side_stream`): the data-parallel engine starts that
         stage's all-reduce bucket there."""
         s = self._stream()
-        if L._profiler is not None:                      # per-launch timing path (bench roofline pass)
-            for ba in self._box_bwd_args:
-                ba.flat_grads = flat_grads.data_ptr()
-            for op in reversed(self.ops):
-                op.bwd(s)
-            if self.unpack_table is not None:
-                L.call("msau_wgrad_reduce", s, self.slab_arena.data_ptr(), flat_grads.data_ptr(), self.unpack_table.data_ptr(),
-                       len(self._unpack_entries), self._unpack_max)
-            return
         for ra in self._reduce_args:
             ra.flat_grads = flat_grads.data_ptr()
         for ba in self._box_bwd_args:
             ba.flat_grads = flat_grads.data_ptr()
         arr, n, _ = self._bwd_seq
-        single_stream = single_stream or (str(self.device).startswith("cuda") and torch.cuda.is_current_stream_capturing())
-        if not self.overlap_wgrad or single_stream:         # (single_stream: a sweep that is being captured into a HIP graph)
-            L.call("msau_run_ops", s, arr, n)
+        if not self.overlap_wgrad or self._one_stream(single_stream):
+            self._run_seq(self._bwd_seq, s)
             if on_stage_done is not None:
                 for b, _, _ in self._bwd_segs:
                     on_stage_done(b, torch.cuda.current_stream())

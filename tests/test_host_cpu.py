@@ -137,6 +137,44 @@ def test_plans_build_for_baseline_configs(case, dtype):
     assert plan.logits.C == 5 and (plan.aux is not None) == (case["num_blocks"] >= 2)
 
 
+def test_launch_accounting_is_a_fold_over_the_records_the_step_runs():
+    """A launch is stated once, as a record of the forward / backward sequence (cfg 2, bf16, training): every entry of the
+    msau_op arrays the step executes has a `rec_meta` entry with a key; `launch_meta`, restricted to the keys that occur in the
+    sequences, is the per-key sum over those records; and the op classes have no second (per-op launch methods) or third
+    (`note`) statement of the launches that could drift from the records."""
+    import ctypes as C
+    from msau_amd import plan as PL
+    cfg = dict(O.DEFAULT_CFG)
+    shapes = param_shapes(cfg)
+    poff, off = {}, 0
+    for k, s in shapes.items():
+        poff[k] = off
+        off += -(-int(np.prod(s)) // 4) * 4
+    plan = Plan(cfg, 2, 336, 256, L.BF16, torch.device("cpu"), poff, dict(shapes), training=True)
+    fold = {}
+    for arr, n, recs in (plan._fwd_seq, plan._bwd_seq):
+        assert n == len(recs) > 0
+        for i, r in enumerate(recs):
+            assert (arr[i].kind, arr[i].args) == (r.kind, C.addressof(r.args))
+            assert plan.rec_meta[arr[i].args] == (r.key, r.nbytes) and isinstance(r.key, str) and r.key, (i, r)
+            c, b, f = fold.get(r.key, (0, 0.0, 0.0))
+            fold[r.key] = (c + 1, b + r.nbytes, f + r.flops)
+    assert any(r.kind & 0xff == L.OP_WGRAD_REDUCE for r in plan._bwd_seq[2]) and any(r.kind & 0xff == L.OP_CHANNEL_SUM for r in plan._bwd_seq[2])
+    inseq = {k: v for k, v in plan.launch_meta.items() if k in fold}
+    assert sorted(inseq) == sorted(fold)
+    for k, (c, b, f) in fold.items():
+        assert inseq[k][0] == c and inseq[k][1] == pytest.approx(b, rel=1e-12) and inseq[k][2] == pytest.approx(f, rel=1e-12), k
+    assert fold["msau_wgrad_reduce"][1] == pytest.approx(plan.reduce_bytes, rel=1e-12)
+    # what is left are the launches outside the sequences, once each
+    rest = {k: v[0] for k, v in plan.launch_meta.items() if k not in fold}
+    assert rest == {"msau_pack_params": 1, "msau_label_counts": 1, "msau_masked_ce_multi": 1, "msau_clip_adam_step": 1}, rest
+    for cls in (PL.Op, PL.ConvOp, PL.PairOp, PL.BoxOp, PL.LrnOp, PL.PoolOp, PL.AttnCoreOp, PL.ProjBwd):
+        for name in ("fwd", "bwd", "bwd_wgrad", "bwd_dgrad", "launch", "note"):
+            assert not hasattr(cls, name), (cls.__name__, name)
+    for name in ("note_launch", "unnote_launch", "set_probe"):
+        assert not hasattr(Plan, name), name
+
+
 def test_dead_parameters_are_the_last_stage_attention():
     m = MSAUWrapper(64, 5, dict(scale_space_num=4, res_depth=2, featRoot=8, final_act="softmax"))
     assert len(m._dead) == 6 and sum(int(np.prod(m._pshape[k])) for k in m._dead) == 5200      # SURVEY F7 / 2.1

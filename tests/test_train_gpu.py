@@ -484,6 +484,43 @@ def test_train_step_is_bit_reproducible_beside_the_side_stream():
             assert cur[0] == ref[0] and torch.equal(cur[1], ref[1]), f"step {it} differs from step 0"
 
 
+def test_profiled_step_runs_the_records_of_the_step():
+    """A step under `L.Profiler()` enqueues the very msau_op arrays of the step, one record per call: with `overlap_wgrad=False`
+    (both steps then go through msau_run_ops on one stream: the same launches in the same order) loss, gradient and updated
+    parameters are bit-identical to the unprofiled step's, and the profiler's keys and counts are those of `plan.launch_meta`.
+    A profiled step with the default `overlap_wgrad` (one stream too, while it is being timed) leaves the same keys and counts."""
+    from msau_amd import _lib as L
+    g, cfg, sd, x, label = load_net_case("net_f8_c13_33x26")
+    assert cfg["num_blocks"] == 3
+    xb, lb = x.cuda(), label.cuda()
+
+    def step(profiled, **extra):
+        m = _model(cfg, sd, "bf16", **extra)
+        eng = TrainEngine(m)
+        plan = m._plan_for(xb, True)                 # built, and its lazily resolved input feed settled, outside the profiled
+        plan._feed_ids(None)                         # region: their host-side queries of the library are no launches
+        prof = L.Profiler() if profiled else None
+        L.set_profiler(prof)
+        try:
+            loss = eng.step(xb, lb)
+        finally:
+            L.set_profiler(None)
+        torch.cuda.synchronize()
+        counts = {k: n for k, (n, _) in prof.summary().items()} if profiled else None
+        assert m._plan_for(xb, True) is plan
+        meta = {k: n for k, (n, _, _) in plan.launch_meta.items()}
+        return (float(loss), eng.flat_grad.clone(), m.flat_parameters.clone()), counts, meta
+
+    plain, _, _ = step(False, overlap_wgrad=False)
+    prof, counts, meta = step(True, overlap_wgrad=False)
+    assert plain[0] == prof[0] and torch.equal(plain[1], prof[1]) and torch.equal(plain[2], prof[2])
+    assert float(plain[1].abs().max()) > 0.0
+    print("profiled:", counts, "\nlaunch_meta:", meta)
+    assert counts == meta, {k: (counts.get(k), meta.get(k)) for k in set(counts) | set(meta) if counts.get(k) != meta.get(k)}
+    _, counts2, meta2 = step(True)
+    assert counts2 == meta2 == counts, {k: (counts2.get(k), meta2.get(k)) for k in set(counts2) | set(meta2) if counts2.get(k) != meta2.get(k)}
+
+
 @pytest.mark.parametrize("dense", [True, False])
 def test_prefetched_box_batches_train_exactly_like_step_boxes(dense, monkeypatch):
     """TrainEngine.prefetch_boxes / step_prefetched: the next batch is painted into the plan's SECOND input buffer on the side
