@@ -718,6 +718,34 @@ int msau_onehot_ids_ext(void* stream, int dtype, const int32_t* ids, void* grid_
 int msau_eval_confusion(void* stream, int dtype, const void* logits, const int64_t* labels, int64_t* counts, int B, int H, int W,
                         int C, int Cs, int zero_as, const int32_t* extent);
 
+/* ------------------------------------------------------------------------------------------
+ * Region extraction for key-value inference (the per-pixel part of inference/kv_model.py:150-261), one workgroup per
+ * (document, class c in [2, n_class)), the document in LDS.
+ *   msau_kv_regions_limits : out int32 [6] = (pixels a document may have, regions per (document, class), pairs per (document,
+ *                            class), int32 per region record, int32 per pair record, lines per document)
+ *   msau_kv_regions        : argmax uint8 [B][H][W] (the head's class map), line_ids / char_pos uint16 [B][H][W], boxes int32 [n][4] =
+ *                            (x1, y1, x2, y2) of every document's lines in grid coordinates, box_off int32 [B + 1] (document b owns
+ *                            boxes[box_off[b] .. box_off[b + 1]); line id v means box v - 1 of its document), extent int32 [B][2] =
+ *                            (h, w) or NULL for a dense batch (h, w = H, W).  All device memory.  Per class: M = closing of
+ *                            (argmax == c) with a 1 x 3 element, zero outside the document; its 4-connected components in
+ *                            raster order of their first pixel.
+ *                              header  int32 [B][n_class][4]: row c >= 2 = (region offset, regions, pair offset, pairs) of class c
+ *                                      inside the document's slices; row 0 = (region cursor, pair cursor, 0, 0); zeroed here
+ *                              regions int32 [B][cap_regions][8] = (first_y, first_x, y0, y1, x0, x1, pixels, c), box half-open
+ *                              pairs   int32 [B][cap_pairs][4]   = ((k << 16) | v, n_under, cp_min, cp_max) sorted by the key:
+ *                                      n_under = pixels of component k with line id v, cp_min / cp_max = extremes of the non-zero
+ *                                      char_pos under k inside box v - 1 clipped to the document (65535 / 0 when there is none)
+ *                              overflow int32 [B], zeroed here: 1 the document has more pixels than the LDS form holds (or its
+ *                                      extent is outside the canvas), 2 the labelling did not converge within its bound,
+ *                                      4 more regions / 8 more pairs than a table or the document's slice holds, 16 a line id
+ *                                      beyond the document's boxes.  A flagged document's rows are to be ignored; the others'
+ *                                      are complete.  Integers only, independent of arrival order but for the slice offsets.
+ * ------------------------------------------------------------------------------------------ */
+int msau_kv_regions_limits(int32_t* out);
+int msau_kv_regions(void* stream, const uint8_t* argmax, const uint16_t* line_ids, const uint16_t* char_pos, const int32_t* boxes,
+                    const int32_t* box_off, const int32_t* extent, int B, int H, int W, int n_class, int32_t* header,
+                    int32_t* regions, int cap_regions, int32_t* pairs, int cap_pairs, int32_t* overflow);
+
 #ifdef __cplusplus
 }
 #endif

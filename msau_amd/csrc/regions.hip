@@ -1,0 +1,449 @@
+// Region extraction for key-value inference (inference/kv_model.py `_extract_value`, the per-pixel part): from the uint8 class
+// map the head writes, per document and per field class c >= 2
+//   M_c   = closing of (argmax == c) with a 1 x 3 element, zero outside the DOCUMENT (morph_util.r_closing(mask, (1, 3)))
+//   comps = the 4-connected components of M_c, numbered by the raster position of their first pixel (scipy.ndimage.label),
+//           each with its first pixel, its half-open bounding box (find_objects) and its pixel count
+//   pairs = for (component k, text line v >= 1): n_under = pixels of k whose line id is v; cp_min / cp_max = smallest / largest
+//           non-zero character position over the pixels of k inside line v's box
+// One workgroup per (document, class); the whole document lives in LDS:
+//   labels   int32 [RG_MAXPIX]      union-find forest, parent <= child, so a root is its component's smallest linear index
+//   pairs    4 x uint32 [RG_HASH]   open-addressing hash keyed (k << 16) | v, sorted in place (bitonic) before it is written
+//   comps    6 x int32 [RG_MAXK]    first pixel, box, count
+// Every loop is a counted loop whose bound follows from the document's pixel count (or from the sizes of the LDS tables); a
+// document that does not fit, a table that is full and a labelling that has not converged set the document's overflow flag
+// and end the workgroup.  The results are integers and do not depend on arrival order: the component numbers are ranks of root
+// indices, the pair list is sorted by key; only the position of a class's slice inside its document's lists (header) depends on
+// which workgroup reserved first.
+//
+// The body is written as phases between workgroup barriers; with -DMSAU_REGIONS_CPU the same phases compile as plain C++ and
+// the lanes of a phase run one after another (tests/test_regions_cpu.py builds that form with the host compiler).
+#ifdef MSAU_REGIONS_CPU
+#include <stdint.h>
+#include <stdlib.h>
+#include <string.h>
+#define RG_DEV static inline
+#define RG_PHASE(fn, ...) do { for (int t__ = 0; t__ < RG_THREADS; ++t__) fn(c, s, t__, ##__VA_ARGS__); } while (0)
+RG_DEV int rg_amin(int* p, int v) { int o = *p; if (v < o) *p = v; return o; }
+RG_DEV int rg_amax(int* p, int v) { int o = *p; if (v > o) *p = v; return o; }
+RG_DEV int rg_aadd(int* p, int v) { int o = *p; *p = o + v; return o; }
+RG_DEV int rg_aor(int* p, int v) { int o = *p; *p = o | v; return o; }
+RG_DEV unsigned rg_acas(unsigned* p, unsigned cmp, unsigned v) { unsigned o = *p; if (o == cmp) *p = v; return o; }
+RG_DEV int rg_ld(const int* p) { return *p; }
+#define RG_SYNC() do { } while (0)
+#else
+#include "msau_common.h"
+#define RG_DEV __device__ __forceinline__
+#define RG_PHASE(fn, ...) do { fn(c, s, (int)threadIdx.x, ##__VA_ARGS__); __syncthreads(); } while (0)
+RG_DEV int rg_amin(int* p, int v) { return atomicMin(p, v); }
+RG_DEV int rg_amax(int* p, int v) { return atomicMax(p, v); }
+RG_DEV int rg_aadd(int* p, int v) { return atomicAdd(p, v); }
+RG_DEV int rg_aor(int* p, int v) { return atomicOr(p, v); }
+RG_DEV unsigned rg_acas(unsigned* p, unsigned cmp, unsigned v) { return atomicCAS(p, cmp, v); }
+RG_DEV int rg_ld(const int* p) { return *(const volatile int*)p; }
+#define RG_SYNC() __syncthreads()
+#endif
+// a uniform exit: every lane reads the flags, THEN a barrier, so that no lane of the next phase can change them under a reader
+#define RG_CHECK() do { const int f__ = s.misc[RG_FAIL]; RG_SYNC(); if (f__) return f__; } while (0)
+
+#define RG_THREADS 1024
+#define RG_MAXPIX 24576
+#define RG_MAXK 1024
+#define RG_HASH 2048
+#define RG_REGION_INTS 8
+#define RG_PAIR_INTS 4
+#define RG_MAXLINES 65535
+#define RG_EMPTY 0xFFFFFFFFu
+#define RG_BG (-1)
+enum { RG_OVF_PIXELS = 1, RG_OVF_LABEL = 2, RG_OVF_REGIONS = 4, RG_OVF_PAIRS = 8, RG_OVF_LINES = 16 };
+enum { RG_FAIL = 0, RG_NCOMP = 1, RG_NPAIR = 2, RG_ROFF = 3, RG_POFF = 4, RG_MISC = 8 };
+
+struct RgCtx {                      // one (document, class)
+    const uint8_t* cls;             // the document's planes on the canvas: pixel (y, x) at y * W + x
+    const uint16_t* line;
+    const uint16_t* chr;
+    const int32_t* boxes;           // the document's lines [n_lines][4] = (x1, y1, x2, y2)
+    int n_lines, h, w, W, c;
+    int32_t* hdr;                   // the document's header [n_class][4]; row 0 holds the two cursors
+    int32_t* regions;               // the document's slices of the output lists
+    int32_t* pairs;
+    int cap_regions, cap_pairs;
+};
+
+struct RgLds {
+    int* L;                                          // [RG_MAXPIX]
+    unsigned* hk; int* hn; int* hmn; int* hmx;       // [RG_HASH]
+    int* cfirst; int* cy0; int* cy1; int* cx0; int* cx1; int* ccnt;   // [RG_MAXK]
+    int* scan;                                       // [RG_THREADS]
+    int* part;                                       // [32]
+    int* misc;                                       // [RG_MISC]
+};
+#define RG_LDS_INTS (RG_MAXPIX + 4 * RG_HASH + 6 * RG_MAXK + RG_THREADS + 32 + RG_MISC)
+
+RG_DEV void rg_carve(RgLds& s, int* base) {
+    s.L = base; base += RG_MAXPIX;
+    s.hk = (unsigned*)base; base += RG_HASH;
+    s.hn = base; base += RG_HASH;
+    s.hmn = base; base += RG_HASH;
+    s.hmx = base; base += RG_HASH;
+    s.cfirst = base; base += RG_MAXK;
+    s.cy0 = base; base += RG_MAXK;
+    s.cy1 = base; base += RG_MAXK;
+    s.cx0 = base; base += RG_MAXK;
+    s.cx1 = base; base += RG_MAXK;
+    s.ccnt = base; base += RG_MAXK;
+    s.scan = base; base += RG_THREADS;
+    s.part = base; base += 32;
+    s.misc = base;
+}
+
+// closing with a 1 x 3 element, zero outside [0, w): D(x) = m(x-1) | m(x) | m(x+1), M(x) = D(x-1) & D(x) & D(x+1) with D = 0
+// outside, so M(0) = M(w-1) = 0 and M(x) reads m(x-2 .. x+2)
+RG_DEV bool rg_closed(const RgCtx& c, int y, int x) {
+    if (x < 1 || x > c.w - 2) return false;
+    const uint8_t* row = c.cls + (size_t)y * c.W;
+    const bool m1 = row[x - 1] == c.c, m2 = row[x] == c.c, m3 = row[x + 1] == c.c;
+    const bool m0 = x >= 2 && row[x - 2] == c.c, m4 = x + 2 < c.w && row[x + 2] == c.c;
+    return (m0 | m1 | m2) & (m1 | m2 | m3) & (m2 | m3 | m4);
+}
+
+// root of a; parents never exceed their children, so the walk is at most npix long
+RG_DEV int rg_find(const RgLds& s, int a, int npix) {
+    for (int it = 0; it < npix; ++it) {
+        const int p = rg_ld(s.L + a);
+        if (p == a) break;
+        a = p;
+    }
+    return a;
+}
+
+// lock-free union: hang the larger root under the smaller one; a + b decreases with every retry
+RG_DEV void rg_union(const RgLds& s, int a, int b, int npix) {
+    for (int it = 0; it < 2 * npix + 2; ++it) {
+        a = rg_find(s, a, npix);
+        b = rg_find(s, b, npix);
+        if (a == b) return;
+        if (a < b) { const int t = a; a = b; b = t; }
+        const int old = rg_amin(s.L + a, b);
+        if (old == a) return;
+        a = old;
+    }
+    rg_aor(s.misc + RG_FAIL, RG_OVF_LABEL);
+}
+
+// component number of a mask pixel after rg_ph_assign: roots hold -2 - rank, the others their root
+RG_DEV int rg_comp(const RgLds& s, int p) {
+    const int l = s.L[p];
+    return l < RG_BG ? -2 - l : -2 - s.L[l];
+}
+
+RG_DEV unsigned rg_hash(unsigned key) { return (key * 2654435761u) >> 21; }        // 11 bits: RG_HASH = 2048
+
+// slot of `key`, inserted if absent; -1 (and the overflow bit) when the table is full
+RG_DEV int rg_slot(const RgLds& s, unsigned key) {
+    unsigned slot = rg_hash(key) & (RG_HASH - 1);
+    for (int it = 0; it < RG_HASH; ++it) {
+        const unsigned old = rg_acas(s.hk + slot, RG_EMPTY, key);
+        if (old == RG_EMPTY) { rg_aadd(s.misc + RG_NPAIR, 1); return (int)slot; }
+        if (old == key) return (int)slot;
+        slot = (slot + 1) & (RG_HASH - 1);
+    }
+    rg_aor(s.misc + RG_FAIL, RG_OVF_PAIRS);
+    return -1;
+}
+
+// ---- phases ------------------------------------------------------------------------------------------------------
+RG_DEV void rg_ph_init(const RgCtx& c, const RgLds& s, int tid) {
+    const int npix = c.h * c.w;
+    for (int p = tid; p < npix; p += RG_THREADS) {
+        const int y = p / c.w, x = p - y * c.w;
+        s.L[p] = rg_closed(c, y, x) ? p : RG_BG;
+    }
+    for (int i = tid; i < RG_HASH; i += RG_THREADS) { s.hk[i] = RG_EMPTY; s.hn[i] = 0; s.hmn[i] = 65535; s.hmx[i] = 0; }
+    if (tid < RG_MISC) s.misc[tid] = 0;
+}
+
+// every mask pixel with a mask pixel on its left points at it ...
+RG_DEV void rg_ph_link_left(const RgCtx& c, const RgLds& s, int tid) {
+    const int npix = c.h * c.w;
+    for (int p = tid; p < npix; p += RG_THREADS) {
+        const int x = p % c.w;
+        if (x > 0 && rg_ld(s.L + p) != RG_BG && rg_ld(s.L + p - 1) != RG_BG) s.L[p] = p - 1;
+    }
+}
+
+// ... and pointer jumping (ceil(log2 w) rounds) brings it to the start of its row run
+RG_DEV void rg_ph_jump(const RgCtx& c, const RgLds& s, int tid) {
+    const int npix = c.h * c.w;
+    for (int p = tid; p < npix; p += RG_THREADS) {
+        const int l = rg_ld(s.L + p);
+        if (l != RG_BG) s.L[p] = rg_ld(s.L + l);
+    }
+}
+
+// join the runs of neighbouring rows (a pixel whose left, upper and upper-left neighbours are all set adds nothing)
+RG_DEV void rg_ph_union_up(const RgCtx& c, const RgLds& s, int tid) {
+    const int npix = c.h * c.w;
+    for (int p = c.w + tid; p < npix; p += RG_THREADS) {
+        if (rg_ld(s.L + p) == RG_BG || rg_ld(s.L + p - c.w) == RG_BG) continue;
+        const int x = p % c.w;
+        if (x > 0 && rg_ld(s.L + p - 1) != RG_BG && rg_ld(s.L + p - c.w - 1) != RG_BG) continue;
+        rg_union(s, p, p - c.w, npix);
+    }
+}
+
+RG_DEV void rg_ph_flatten(const RgCtx& c, const RgLds& s, int tid) {
+    const int npix = c.h * c.w;
+    for (int p = tid; p < npix; p += RG_THREADS)
+        if (rg_ld(s.L + p) != RG_BG) s.L[p] = rg_find(s, p, npix);
+}
+
+// rank the roots by linear index: lane t owns pixels [t * chunk, (t + 1) * chunk)
+RG_DEV void rg_ph_count(const RgCtx& c, const RgLds& s, int tid) {
+    const int npix = c.h * c.w, chunk = (npix + RG_THREADS - 1) / RG_THREADS;
+    int n = 0;
+    for (int i = 0; i < chunk; ++i) {
+        const int p = tid * chunk + i;
+        if (p < npix && s.L[p] == p) ++n;
+    }
+    s.scan[tid] = n;
+}
+
+RG_DEV void rg_ph_scan_parts(const RgCtx& c, const RgLds& s, int tid) {
+    if (tid >= 32) return;
+    int n = 0;
+    for (int i = 0; i < RG_THREADS / 32; ++i) n += s.scan[tid * (RG_THREADS / 32) + i];
+    s.part[tid] = n;
+}
+
+RG_DEV void rg_ph_scan_top(const RgCtx& c, const RgLds& s, int tid) {
+    if (tid != 0) return;
+    int run = 0;
+    for (int i = 0; i < 32; ++i) { const int n = s.part[i]; s.part[i] = run; run += n; }
+    s.misc[RG_NCOMP] = run;
+    if (run > RG_MAXK) s.misc[RG_FAIL] |= RG_OVF_REGIONS;
+}
+
+RG_DEV void rg_ph_assign(const RgCtx& c, const RgLds& s, int tid) {
+    const int npix = c.h * c.w, chunk = (npix + RG_THREADS - 1) / RG_THREADS, per = RG_THREADS / 32;
+    int rank = s.part[tid / per];
+    for (int i = (tid / per) * per; i < tid; ++i) rank += s.scan[i];
+    for (int i = 0; i < chunk; ++i) {
+        const int p = tid * chunk + i;
+        if (p < npix && s.L[p] == p) {
+            if (rank < RG_MAXK) {
+                s.cfirst[rank] = p;
+                s.cy0[rank] = c.h; s.cy1[rank] = -1; s.cx0[rank] = c.w; s.cx1[rank] = -1; s.ccnt[rank] = 0;
+            }
+            s.L[p] = -2 - rank;
+            ++rank;
+        }
+    }
+}
+
+RG_DEV void rg_ph_stats(const RgCtx& c, const RgLds& s, int tid) {
+    const int npix = c.h * c.w;
+    for (int p = tid; p < npix; p += RG_THREADS) {
+        if (s.L[p] == RG_BG) continue;
+        const int k = rg_comp(s, p), y = p / c.w, x = p - y * c.w;
+        rg_amin(s.cy0 + k, y); rg_amax(s.cy1 + k, y);
+        rg_amin(s.cx0 + k, x); rg_amax(s.cx1 + k, x);
+        rg_aadd(s.ccnt + k, 1);
+    }
+}
+
+// n_under: by the line-id mask
+RG_DEV void rg_ph_pairs_pix(const RgCtx& c, const RgLds& s, int tid) {
+    const int npix = c.h * c.w;
+    for (int p = tid; p < npix; p += RG_THREADS) {
+        if (s.L[p] == RG_BG) continue;
+        const int y = p / c.w, x = p - y * c.w;
+        const int v = c.line[(size_t)y * c.W + x];
+        if (v == 0) continue;
+        if (v > c.n_lines) { rg_aor(s.misc + RG_FAIL, RG_OVF_LINES); continue; }
+        const int slot = rg_slot(s, ((unsigned)rg_comp(s, p) << 16) | (unsigned)v);
+        if (slot >= 0) rg_aadd(s.hn + slot, 1);
+    }
+}
+
+// cp_min / cp_max: by the line's box, clipped to the document; one wavefront per line, its lanes over the box
+RG_DEV void rg_ph_pairs_box(const RgCtx& c, const RgLds& s, int tid) {
+    const int wv = tid >> 6, lane = tid & 63;
+    for (int li = wv; li < c.n_lines; li += RG_THREADS / 64) {
+        const int32_t* b = c.boxes + 4 * (size_t)li;
+        const int x1 = b[0] > 0 ? b[0] : 0, y1 = b[1] > 0 ? b[1] : 0;
+        const int x2 = b[2] < c.w ? b[2] : c.w, y2 = b[3] < c.h ? b[3] : c.h;
+        if (x2 <= x1 || y2 <= y1) continue;
+        const int bw = x2 - x1, area = bw * (y2 - y1);               // <= npix
+        for (int i = lane; i < area; i += 64) {
+            const int y = y1 + i / bw, x = x1 + i % bw, p = y * c.w + x;
+            if (s.L[p] == RG_BG) continue;
+            const int cp = c.chr[(size_t)y * c.W + x];
+            if (cp == 0) continue;
+            const int slot = rg_slot(s, ((unsigned)rg_comp(s, p) << 16) | (unsigned)(li + 1));
+            if (slot >= 0) { rg_amin(s.hmn + slot, cp); rg_amax(s.hmx + slot, cp); }
+        }
+    }
+}
+
+// one compare-exchange step of the bitonic network over the RG_HASH entries (empty keys are the largest: they end up last)
+RG_DEV void rg_ph_bitonic(const RgCtx& c, const RgLds& s, int tid, int k, int j) {
+    const int i = ((tid & ~(j - 1)) << 1) | (tid & (j - 1)), o = i | j;      // the pair (i, i + j) of lane tid
+    const bool up = (i & k) == 0;
+    const unsigned a = s.hk[i], b = s.hk[o];
+    if ((a > b) == up) {
+        s.hk[i] = b; s.hk[o] = a;
+        int t;
+        t = s.hn[i]; s.hn[i] = s.hn[o]; s.hn[o] = t;
+        t = s.hmn[i]; s.hmn[i] = s.hmn[o]; s.hmn[o] = t;
+        t = s.hmx[i]; s.hmx[i] = s.hmx[o]; s.hmx[o] = t;
+    }
+}
+
+// reserve this class's slices of the document's lists: one 32-bit atomic each
+RG_DEV void rg_ph_reserve(const RgCtx& c, const RgLds& s, int tid) {
+    if (tid != 0) return;
+    const int nc = s.misc[RG_NCOMP], np = s.misc[RG_NPAIR];
+    const int roff = rg_aadd(c.hdr + 0, nc), poff = rg_aadd(c.hdr + 1, np);
+    s.misc[RG_ROFF] = roff; s.misc[RG_POFF] = poff;
+    if (roff + nc > c.cap_regions) s.misc[RG_FAIL] |= RG_OVF_REGIONS;
+    if (poff + np > c.cap_pairs) s.misc[RG_FAIL] |= RG_OVF_PAIRS;
+}
+
+RG_DEV void rg_ph_write(const RgCtx& c, const RgLds& s, int tid) {
+    const int nc = s.misc[RG_NCOMP], np = s.misc[RG_NPAIR], roff = s.misc[RG_ROFF], poff = s.misc[RG_POFF];
+    for (int k = tid; k < nc; k += RG_THREADS) {
+        int32_t* r = c.regions + (size_t)(roff + k) * RG_REGION_INTS;
+        const int first = s.cfirst[k];
+        r[0] = first / c.w; r[1] = first % c.w;
+        r[2] = s.cy0[k]; r[3] = s.cy1[k] + 1; r[4] = s.cx0[k]; r[5] = s.cx1[k] + 1;
+        r[6] = s.ccnt[k]; r[7] = c.c;
+    }
+    for (int i = tid; i < np; i += RG_THREADS) {
+        int32_t* q = c.pairs + (size_t)(poff + i) * RG_PAIR_INTS;
+        q[0] = (int32_t)s.hk[i]; q[1] = s.hn[i]; q[2] = s.hmn[i]; q[3] = s.hmx[i];
+    }
+    if (tid == 0) {
+        int32_t* hd = c.hdr + 4 * c.c;
+        hd[0] = roff; hd[1] = nc; hd[2] = poff; hd[3] = np;
+    }
+}
+
+// -> the overflow bits of this (document, class); 0 = its slices and its header row are written
+RG_DEV int rg_body(const RgCtx& c, const RgLds& s) {
+    RG_PHASE(rg_ph_init);
+    RG_PHASE(rg_ph_link_left);
+    for (int span = 1; span < c.w; span *= 2) RG_PHASE(rg_ph_jump);
+    RG_PHASE(rg_ph_union_up);
+    RG_CHECK();
+    RG_PHASE(rg_ph_flatten);
+    RG_PHASE(rg_ph_count);
+    RG_PHASE(rg_ph_scan_parts);
+    RG_PHASE(rg_ph_scan_top);
+    RG_CHECK();
+    RG_PHASE(rg_ph_assign);
+    RG_PHASE(rg_ph_stats);
+    RG_PHASE(rg_ph_pairs_pix);
+    RG_PHASE(rg_ph_pairs_box);
+    RG_CHECK();
+    if (s.misc[RG_NPAIR] > 0)
+        for (int k = 2; k <= RG_HASH; k *= 2)
+            for (int j = k / 2; j >= 1; j /= 2) RG_PHASE(rg_ph_bitonic, k, j);
+    RG_PHASE(rg_ph_reserve);
+    RG_CHECK();
+    RG_PHASE(rg_ph_write);
+    return 0;
+}
+
+// the checks that need no LDS: a document the LDS form does not hold, an extent outside the canvas, a line list too long
+RG_DEV int rg_precheck(int h, int w, int H, int W, int n_lines) {
+    if (h < 1 || w < 1 || h > H || w > W || (int64_t)h * w > RG_MAXPIX) return RG_OVF_PIXELS;
+    if (n_lines < 0 || n_lines > RG_MAXLINES) return RG_OVF_LINES;
+    return 0;
+}
+
+#ifdef MSAU_REGIONS_CPU
+// the launch, lane by lane on the host: same arguments as msau_kv_regions without the stream
+extern "C" int msau_kv_regions_cpu(const uint8_t* argmax, const uint16_t* line_ids, const uint16_t* char_pos, const int32_t* boxes,
+                                   const int32_t* box_off, const int32_t* extent, int B, int H, int W, int n_class, int32_t* header,
+                                   int32_t* regions, int cap_regions, int32_t* pairs, int cap_pairs, int32_t* overflow) {
+    int* lds = (int*)malloc(sizeof(int) * RG_LDS_INTS);
+    if (!lds) return 1;
+    memset(header, 0, sizeof(int32_t) * 4 * (size_t)B * n_class);
+    memset(overflow, 0, sizeof(int32_t) * B);
+    for (int b = 0; b < B; ++b)
+        for (int cc = 2; cc < n_class; ++cc) {
+            RgCtx c;
+            const size_t plane = (size_t)b * H * W;
+            c.cls = argmax + plane; c.line = line_ids + plane; c.chr = char_pos + plane;
+            c.boxes = boxes + 4 * (size_t)box_off[b]; c.n_lines = box_off[b + 1] - box_off[b];
+            c.h = extent ? extent[2 * b] : H; c.w = extent ? extent[2 * b + 1] : W; c.W = W; c.c = cc;
+            c.hdr = header + 4 * (size_t)b * n_class;
+            c.regions = regions + (size_t)b * cap_regions * RG_REGION_INTS; c.cap_regions = cap_regions;
+            c.pairs = pairs + (size_t)b * cap_pairs * RG_PAIR_INTS; c.cap_pairs = cap_pairs;
+            RgLds s;
+            rg_carve(s, lds);
+            int f = rg_precheck(c.h, c.w, H, W, c.n_lines);
+            if (!f) f = rg_body(c, s);
+            overflow[b] |= f;
+        }
+    free(lds);
+    return 0;
+}
+extern "C" int msau_kv_regions_limits(int32_t* out) {
+    out[0] = RG_MAXPIX; out[1] = RG_MAXK; out[2] = RG_HASH; out[3] = RG_REGION_INTS; out[4] = RG_PAIR_INTS; out[5] = RG_MAXLINES;
+    return 0;
+}
+#else
+
+__global__ void __launch_bounds__(RG_THREADS)
+kv_regions_kernel(const uint8_t* argmax, const uint16_t* line_ids, const uint16_t* char_pos, const int32_t* boxes, const int32_t* box_off,
+                  const int32_t* extent, int H, int W, int n_class, int32_t* header, int32_t* regions, int cap_regions, int32_t* pairs,
+                  int cap_pairs, int32_t* overflow) {
+    extern __shared__ int rg_lds[];
+    const int b = blockIdx.y;
+    RgCtx c;
+    const size_t plane = (size_t)b * H * W;
+    c.cls = argmax + plane; c.line = line_ids + plane; c.chr = char_pos + plane;
+    c.boxes = boxes + 4 * (size_t)box_off[b]; c.n_lines = box_off[b + 1] - box_off[b];
+    c.h = extent ? extent[2 * b] : H; c.w = extent ? extent[2 * b + 1] : W; c.W = W; c.c = 2 + (int)blockIdx.x;
+    c.hdr = header + 4 * (size_t)b * n_class;
+    c.regions = regions + (size_t)b * cap_regions * RG_REGION_INTS; c.cap_regions = cap_regions;
+    c.pairs = pairs + (size_t)b * cap_pairs * RG_PAIR_INTS; c.cap_pairs = cap_pairs;
+    RgLds s;
+    rg_carve(s, rg_lds);
+    int f = rg_precheck(c.h, c.w, H, W, c.n_lines);           // uniform over the workgroup, like every exit of rg_body
+    if (!f) f = rg_body(c, s);
+    if (f && threadIdx.x == 0) atomicOr(overflow + b, f);
+}
+
+extern "C" int msau_kv_regions_limits(int32_t* out) {
+    MSAU_CHECK_ARG(out, "kv_regions_limits: null");
+    out[0] = RG_MAXPIX; out[1] = RG_MAXK; out[2] = RG_HASH; out[3] = RG_REGION_INTS; out[4] = RG_PAIR_INTS; out[5] = RG_MAXLINES;
+    return 0;
+}
+
+extern "C" int msau_kv_regions(void* stream, const uint8_t* argmax, const uint16_t* line_ids, const uint16_t* char_pos, const int32_t* boxes,
+                               const int32_t* box_off, const int32_t* extent, int B, int H, int W, int n_class, int32_t* header,
+                               int32_t* regions, int cap_regions, int32_t* pairs, int cap_pairs, int32_t* overflow) {
+    MSAU_CHECK_ARG(argmax && line_ids && char_pos && boxes && box_off && header && regions && pairs && overflow, "kv_regions: null pointer");
+    MSAU_CHECK_ARG(B > 0 && B <= 65535 && H > 0 && W > 0 && (int64_t)H * W < (1ll << 31), "kv_regions: bad shape B = %d, H = %d, W = %d", B, H, W);
+    MSAU_CHECK_ARG(n_class >= 1 && n_class <= 255, "kv_regions: n_class = %d, must be in [1, 255]", n_class);
+    MSAU_CHECK_ARG(cap_regions >= 1 && cap_pairs >= 1 && cap_regions < (1 << 24) && cap_pairs < (1 << 24), "kv_regions: bad capacities");
+    static_assert(sizeof(int) * RG_LDS_INTS <= MSAU_LDS_LIMIT, "kv_regions: the tables must fit the LDS");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    hipError_t e = hipMemsetAsync(header, 0, sizeof(int32_t) * 4 * (size_t)B * n_class, s);
+    if (e == hipSuccess) e = hipMemsetAsync(overflow, 0, sizeof(int32_t) * (size_t)B, s);
+    if (e != hipSuccess) return msau_set_error(MSAU_ERR_HIP, "kv_regions: hipMemsetAsync: %s", hipGetErrorString(e));
+    if (n_class < 3) return 0;
+    static bool attr_set = false;
+    if (!attr_set) {
+        e = hipFuncSetAttribute(reinterpret_cast<const void*>(&kv_regions_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, MSAU_LDS_LIMIT);
+        if (e != hipSuccess) return msau_set_error(MSAU_ERR_HIP, "kv_regions: hipFuncSetAttribute: %s", hipGetErrorString(e));
+        attr_set = true;
+    }
+    hipLaunchKernelGGL(kv_regions_kernel, dim3(n_class - 2, B), dim3(RG_THREADS), sizeof(int) * RG_LDS_INTS, s, argmax, line_ids, char_pos, boxes,
+                       box_off, extent, H, W, n_class, header, regions, cap_regions, pairs, cap_pairs, overflow);
+    MSAU_CHECK_LAUNCH("kv_regions");
+    return 0;
+}
+#endif

@@ -4,7 +4,7 @@ The reference trains with batch 1 and one H x W per document (train_chargrid_fun
 data_generator_funsd_bert.py:216-222).  `pack` places B documents at the origin of one zero canvas and returns their sizes;
 `MSAUWrapper.forward(x, sizes)` / `TrainEngine.step(x, labels, sizes)` then compute, for every document, what it would compute
 alone ("Ragged batches").  `unpack` crops the canvas outputs back, `batches` groups documents of similar size, `pack_ids` packs character-id masks for
-`MSAUWrapper.predict_nhwc(ids=..., sizes=...)`.
+`MSAUWrapper.predict_nhwc(ids=..., sizes=...)`, `pack_masks` the line-id / character-position masks of the region stage.
 
     for idx in batches(docs, 16):
         x, labels, sizes = pack([docs[i] for i in idx])
@@ -67,6 +67,27 @@ def pack_ids(masks: Sequence, round_to: int = 16) -> Tuple[torch.Tensor, torch.T
     for b, t in enumerate(ts):
         ids[b, :t.shape[0], :t.shape[1]] = t.to(torch.int32)
     return ids, sizes
+
+
+def pack_masks(masks: Sequence, round_to: int = 16) -> Tuple[torch.Tensor, torch.Tensor]:
+    """`masks`: [h, w] uint16 masks (KVModel's `line_ids` / `char_pos`), the documents in the order given to `pack_ids`.
+    -> (int16 [B, H, W] holding the uint16 bits, zero outside every document; sizes int64 CPU [B, 2]) on the canvas of `pack_ids`,
+    for the region stage behind the forward (`MSAUWrapper.predict_regions`)."""
+    if len(masks) == 0:
+        raise ValueError("pack_masks: no documents")
+    if round_to < 1:
+        raise ValueError(f"pack_masks: round_to must be >= 1, got {round_to}")
+    arrs = [np.asarray(m) for m in masks]
+    for b, a in enumerate(arrs):
+        if a.ndim != 2 or a.dtype.kind not in "iu" or (a.size and (int(a.min()) < 0 or int(a.max()) > 65535)):
+            raise ValueError(f"pack_masks: mask {b} must be an integer [h, w] array of values in [0, 65535], got {a.dtype} {a.shape}")
+    sizes = torch.tensor([a.shape for a in arrs], dtype=torch.int64)
+    H = -(-int(sizes[:, 0].max()) // round_to) * round_to
+    W = -(-int(sizes[:, 1].max()) // round_to) * round_to
+    canvas = np.zeros((len(arrs), H, W), dtype=np.uint16)
+    for b, a in enumerate(arrs):
+        canvas[b, :a.shape[0], :a.shape[1]] = a
+    return torch.from_numpy(canvas.view(np.int16)), sizes
 
 
 def unpack(t: torch.Tensor, sizes: torch.Tensor) -> List[torch.Tensor]:

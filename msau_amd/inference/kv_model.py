@@ -10,6 +10,11 @@ by the forward-only HIP plan:
     softmax, transpose to NHWC, .cpu()                    softmax + argmax in the end conv's epilogue, NHWC output
 
 There is no CPU network path: without the HIP library / a GPU `predict` raises (msau_amd.model).
+
+`device_post=True` (predict, predict_batch, run_test) keeps the class map on the device as well: the line-id and
+character-position masks and the line boxes go up with the ids, a kernel behind the forward extracts the field regions
+(csrc/regions.hip, msau_amd.inference.regions), and the host selects the fields from that table.  Same results; the default
+(False) is the path above, unchanged.
 """
 from __future__ import annotations
 
@@ -256,6 +261,46 @@ class KVModel:
                 eval_results[value_id]["num_label"] += 1
         return correct_answers
 
+    def _run_regions(self, docs_masks):
+        """`device_post`: the masks of a group of documents -> per document its region table.  One forward (dense at one
+        document, ragged otherwise) with the region kernel behind it; a document whose overflow flag is set (more pixels, regions
+        or pairs than the kernel's tables hold) gets its table from `regions_host` on its crop of the class map, copied back for
+        that document alone -- the same table, never an approximation."""
+        if not torch.cuda.is_available():
+            raise RuntimeError("KVModel.predict runs the network through libmsau_hip.so on an MI355X; no GPU is "
+                               "visible and there is no CPU fallback")
+        from ..data.ragged import pack_ids, pack_masks
+        from . import regions as R
+        boxes = [[l["box"] for l in m[3]] for m in docs_masks]
+        if len(docs_masks) == 1:
+            m = docs_masks[0]
+            ids, sizes = torch.from_numpy(m[0].astype(np.int32))[None], None
+            line_ids = torch.from_numpy(np.ascontiguousarray(m[1]).view(np.int16))[None]
+            char_pos = torch.from_numpy(np.ascontiguousarray(m[2]).view(np.int16))[None]
+        else:
+            ids, sizes = pack_ids([m[0] for m in docs_masks])
+            line_ids, _ = pack_masks([m[1] for m in docs_masks])
+            char_pos, _ = pack_masks([m[2] for m in docs_masks])
+        tables, flags, amax = self.net.predict_regions(ids=ids.cuda(), sizes=sizes, line_ids=line_ids, char_pos=char_pos,
+                                                       boxes=boxes)
+        for b, m in enumerate(docs_masks):
+            if flags[b] != 0:
+                h, w = m[0].shape
+                cls = amax[b, :h, :w].cpu().numpy()
+                R.STATS["fallbacks"] += 1
+                R.STATS["d2h_bytes"] += cls.nbytes
+                tables[b] = R.regions_host(cls, m[1], m[2], boxes[b], self.n_class)
+        return tables
+
+    def _finish_regions(self, masks, table, correct_answers, eval_results):
+        """`_finish` from a region table"""
+        from .regions import fields_from_regions
+        values = fields_from_regions(table, masks[3], self.n_class)
+        kv_results = post_process_kv(values)
+        if eval_results is not None:
+            self._count_predictions(values, self.n_class, eval_results, correct_answers)
+        return kv_results
+
     def _finish(self, masks, a_pred, a_cls, correct_answers, eval_results):
         """post-processing of one document's prediction -> kv_results"""
         _input_im, line_mask, char_mask, label_lines = masks[:4]
@@ -266,29 +311,32 @@ class KVModel:
             self._count_predictions(values, self.n_class, eval_results, correct_answers)
         return kv_results
 
-    def predict(self, data, debug_info=None, label_path=None, eval_results=None):
+    def predict(self, data, debug_info=None, label_path=None, eval_results=None, device_post=False):
         """data = (layout JSON path, page image or None) -> ({field: text}, debug image).
         The debug rendering of the reference (OpenCV + PIL drawing) is not part of this build: the second result is
-        always None; everything that feeds `kv_results` and `eval_results` is computed as in kv_model.py:264-347."""
+        always None; everything that feeds `kv_results` and `eval_results` is computed as in kv_model.py:264-347.
+        device_post=True: the field regions are extracted on the device (module docstring); the results are the same."""
         json_path, _debug_im = data
         masks = self._generate_masks_from_label(json_path)
         input_im, _line_mask, _char_mask, _label_lines, scale, bg_pad, (min_x, min_y, _max_x, _max_y) = masks
         correct_answers = self._read_answers(label_path, scale, (min_x - bg_pad, min_y - bg_pad), eval_results)
+        if device_post:
+            return self._finish_regions(masks, self._run_regions([masks])[0], correct_answers, eval_results), None
         a_pred, a_cls = self._run_net(input_im)
         return self._finish(masks, a_pred, a_cls, correct_answers, eval_results), None
 
-    def predict_batch(self, json_paths, label_paths=None, eval_results=None):
+    def predict_batch(self, json_paths, label_paths=None, eval_results=None, device_post=False):
         """`predict` for a group of layout JSONs with one network forward: the documents' id masks share a ragged canvas
         (each is computed as it would be alone).  -> [kv_results] in the order of `json_paths`.  The ground truth of the whole
         group is read before the forward, so a label file that cannot be read is reported before any result is returned
-        (`run_test` prints each such message next to its own document, as at batch 1)."""
-        results, notes = self._predict_group(json_paths, label_paths, eval_results)
+        (`run_test` prints each such message next to its own document, as at batch 1).  device_post=True: as in `predict`."""
+        results, notes = self._predict_group(json_paths, label_paths, eval_results, device_post)
         for doc_notes in notes:
             for n in doc_notes:
                 print(*n)
         return results
 
-    def _predict_group(self, json_paths, label_paths, eval_results):
+    def _predict_group(self, json_paths, label_paths, eval_results, device_post=False):
         """predict_batch -> ([kv_results], per document the list of its unprinted messages)"""
         docs, notes = [], []
         for k, json_path in enumerate(json_paths):
@@ -298,16 +346,21 @@ class KVModel:
             notes.append([])
             docs.append((masks, self._read_answers(label_path, scale, (min_x - bg_pad, min_y - bg_pad), eval_results,
                                                    notes[-1])))
+        if device_post:
+            tables = self._run_regions([masks for masks, _ in docs])
+            return [self._finish_regions(masks, table, correct_answers, eval_results)
+                    for (masks, correct_answers), table in zip(docs, tables)], notes
         outs = self._run_net_batch([masks[0] for masks, _ in docs])
         return [self._finish(masks, a_pred, a_cls, correct_answers, eval_results)
                 for (masks, correct_answers), (a_pred, a_cls) in zip(docs, outs)], notes
 
-    def run_test(self, list_inf, out_dir, label_dir=None, img_dir=None, batch_size=1):
+    def run_test(self, list_inf, out_dir, label_dir=None, img_dir=None, batch_size=1, device_post=False):
         """predict every layout JSON of `list_inf`; with `label_dir`, print per-class counts and precision / recall /
         F1 over region boxes (kv_model.py:350-387).  Unlike the reference a missing page image does not skip the
         document, because no debug image is drawn.  batch_size > 1: consecutive groups of `batch_size` documents go through
         the network as one ragged forward (as in `predict_batch`); results, printing and `eval_results` keep the order of
-        `list_inf`, and the last group may be shorter.  The counts are kept as `self.eval_results`."""
+        `list_inf`, and the last group may be shorter.  The counts are kept as `self.eval_results`.  device_post=True: the
+        field regions of every document are extracted on the device (module docstring); results and printing are the same."""
         if batch_size < 1:
             raise ValueError(f"batch_size must be >= 1, got {batch_size}")
         eval_results = [{"num_pred": 0, "num_correct": 0, "num_label": 0} for _ in range(self.n_class)]
@@ -320,10 +373,10 @@ class KVModel:
             if batch_size == 1:
                 results = [self.predict((group[0], None), debug_info=("", None),
                                         label_path=label_paths[0] if label_paths is not None else None,
-                                        eval_results=eval_results)[0]]
+                                        eval_results=eval_results, device_post=device_post)[0]]
                 notes = [[]]                                     # (printed by predict)
             else:
-                results, notes = self._predict_group(group, label_paths, eval_results)
+                results, notes = self._predict_group(group, label_paths, eval_results, device_post)
             for basename, result, doc_notes in zip(names, results, notes):
                 for n in doc_notes:
                     print(*n)

@@ -3,6 +3,10 @@
 the size KVModel really runs at (text lines scaled to 3 px), dense input vs the device-painted id mask.
 With --ragged B: ms per document of predict_nhwc(ids) one document at a time against ragged batches of B (pack_ids +
 predict_nhwc(ids=..., sizes=...)) on id masks of varied sizes around KVModel's 70 x 128 scale (60 tokens, 17 classes).
+With --post B: ms per document of KVModel's post-processing on the host against device_post=True (the region kernel of
+csrc/regions.hip), interleaved in one process: (a) predict_batch end to end on the golden layouts with the golden (seeded,
+random-weight) net, (b) the region stage alone on the reference's clean class maps, both arms starting from class maps on the
+device.  Reads tests/golden/kv only.
 Not the headline metric (bench.py is); numbers are quoted in DESIGN.md."""
 import argparse
 import json
@@ -74,13 +78,132 @@ def run_ragged(B, n_docs, dtype, iters, warmup, C=60, n_class=17):
     return out
 
 
+def run_post(B, dtype, repeats, n_docs=48):
+    import copy
+    import numpy as np
+    from msau_amd.data.ragged import pack_masks
+    from msau_amd.inference import KVModel
+    from msau_amd.inference import regions as R
+    from oracle import msau_oracle as O
+    import tempfile
+    KV = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests", "golden", "kv")
+    g, meta = np.load(os.path.join(KV, "kv.npz")), json.load(open(os.path.join(KV, "kv.json")))
+    n_class, cfg = meta["n_class"], meta["net"]["cfg"]
+    km = KVModel()
+    with tempfile.TemporaryDirectory() as tmp:
+        wpath = os.path.join(tmp, "w.pt")
+        torch.save(O.init_params(cfg, meta["net"]["seed"]), wpath)
+        km.load(model_weight=wpath, charset=os.path.join(KV, "charset.txt"), n_class=n_class, dtype=dtype,
+                model_kwargs=dict(featRoot=cfg["featRoot"], scale_space_num=cfg["scale_space_num"], res_depth=cfg["res_depth"],
+                                  filter_size=cfg["filter_size"], pool_size=cfg["pool_size"], final_act="softmax"))
+    files = [os.path.join(KV, f"layout{i % 3}.json") for i in range(n_docs)]
+    groups = [files[k:k + B] for k in range(0, n_docs, B)]
+    out = {"batch": B, "dtype": dtype, "n_docs": n_docs, "repeats": repeats, "n_class": n_class}
+
+    def reset():
+        for k in R.STATS:
+            R.STATS[k] = 0
+
+    def timed(fn):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        fn()
+        torch.cuda.synchronize()
+        return round((time.perf_counter() - t0) / n_docs * 1e3, 4)
+
+    # (a) end to end, layout JSON -> kv_results
+    arms = {"host": lambda: [km.predict_batch(gr) for gr in groups],
+            "device": lambda: [km.predict_batch(gr, device_post=True) for gr in groups]}
+    same = arms["host"]() == arms["device"]()                              # (the warm-up)
+    reset()
+    ms = {"host": [], "device": []}
+    for _ in range(repeats):
+        for name in ("host", "device"):
+            ms[name].append(timed(arms[name]))
+    sizes = [g[f"d{i}.line_mask"].shape for i in range(3)]
+    canvas = (-(-max(h for h, _ in sizes) // 16) * 16) * (-(-max(w for _, w in sizes) // 16) * 16) if B > 1 else None
+    out["a_end_to_end"] = {"host_ms_per_doc": ms["host"], "device_ms_per_doc": ms["device"], "same_results": same,
+                           "host_d2h_bytes_per_doc": (canvas if B > 1 else int(np.mean([h * w for h, w in sizes]))) * (4 * n_class + 1),
+                           "device_d2h_bytes_per_doc": round(R.STATS["d2h_bytes"] / max(R.STATS["documents"], 1)),
+                           "fallbacks": R.STATS["fallbacks"]}
+    t0 = time.perf_counter()
+    for f in files:
+        km._generate_masks_from_label(f)
+    out["a_end_to_end"]["masks_from_label_ms_per_doc"] = round((time.perf_counter() - t0) / n_docs * 1e3, 4)
+
+    # (b) the region stage on the reference's clean class maps, already on the device
+    docs = []
+    for i in range(n_docs):
+        di = i % 3
+        docs.append((np.argmax(g[f"d{di}.pred"].astype(np.float32), -1).astype(np.uint8), g[f"d{di}.line_mask"], g[f"d{di}.char_mask"],
+                     meta[f"d{di}"]["lines"]))
+    batches = []
+    for k in range(0, n_docs, B):
+        grp = docs[k:k + B]
+        am, szs = pack_masks([d[0] for d in grp], round_to=16 if B > 1 else 1)
+        am = torch.from_numpy(am.numpy().view(np.uint16).astype(np.uint8)).cuda()
+        batches.append((grp, am, szs, [np.zeros(d[0].shape + (n_class,), np.float32) for d in grp]))
+
+    def host_arm(keep=None):
+        for grp, am, szs, preds in batches:
+            a = am.cpu().numpy()
+            for b, (d, pred) in enumerate(zip(grp, preds)):
+                h, w = d[0].shape
+                v, _ = KVModel._extract_value(d[1], d[2], copy.deepcopy(d[3]), pred, n_class, pred_class=a[b, :h, :w].astype(np.int64))
+                if keep is not None:
+                    keep.append(v)
+
+    def device_arm(keep=None):
+        for grp, am, szs, _preds in batches:
+            lm, _ = pack_masks([d[1] for d in grp], round_to=16 if B > 1 else 1)
+            cm, _ = pack_masks([d[2] for d in grp], round_to=16 if B > 1 else 1)
+            tables, flags = R.regions_device(am, lm.cuda(), cm.cuda(), [[l["box"] for l in d[3]] for d in grp], n_class,
+                                             sizes=szs if B > 1 else None)
+            for d, t, f in zip(grp, tables, flags):
+                if f:
+                    R.STATS["fallbacks"] += 1
+                    t = R.regions_host(d[0], d[1], d[2], [l["box"] for l in d[3]], n_class)
+                v = R.fields_from_regions(t, copy.deepcopy(d[3]), n_class)
+                if keep is not None:
+                    keep.append(v)
+
+    hv, dv = [], []
+    host_arm(hv)
+    device_arm(dv)
+    norm = lambda o: json.loads(json.dumps(o, default=lambda v: v.item() if hasattr(v, "item") else list(v)))
+    same = norm(hv) == norm(dv)
+    reset()
+    ms = {"host": [], "device": []}
+    for _ in range(repeats):
+        ms["host"].append(timed(host_arm))
+        ms["device"].append(timed(device_arm))
+    out["b_region_stage"] = {"host_ms_per_doc": ms["host"], "device_ms_per_doc": ms["device"], "same_results": same,
+                             "device_faster_in_every_repeat": all(d < h for d, h in zip(ms["device"], ms["host"])),
+                             "host_d2h_bytes_per_doc": round(sum(int(b[1].numel()) for b in batches) / n_docs),
+                             "device_d2h_bytes_per_doc": round(R.STATS["d2h_bytes"] / max(R.STATS["documents"], 1)),
+                             "fallbacks": R.STATS["fallbacks"]}
+    tables = [R.regions_host(d[0], d[1], d[2], [l["box"] for l in d[3]], n_class) for d in docs]
+    t0 = time.perf_counter()
+    for d, t in zip(docs, tables):
+        R.fields_from_regions(t, copy.deepcopy(d[3]), n_class)
+    out["b_region_stage"]["fields_from_regions_ms_per_doc"] = round((time.perf_counter() - t0) / n_docs * 1e3, 4)
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--iters", type=int, default=30)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--ragged", type=int, default=0, help="only the ragged comparison, in batches of this size")
     ap.add_argument("--docs", type=int, default=48, help="documents of the ragged comparison")
+    ap.add_argument("--post", type=int, default=0, help="only the post-processing comparison (host against device_post=True), "
+                                                        "in batches of this size")
+    ap.add_argument("--repeats", type=int, default=5, help="interleaved repeats per arm of --post")
     a = ap.parse_args()
+    if a.post:
+        for dtype in ("bf16", "fp32"):
+            print(json.dumps(run_post(a.post, dtype, a.repeats, a.docs)), flush=True)
+        return
     if a.ragged:
         for dtype in ("bf16", "fp32"):
             print(json.dumps(run_ragged(a.ragged, a.docs, dtype, max(1, a.iters // 10), 1)), flush=True)
