@@ -746,6 +746,26 @@ int msau_kv_regions(void* stream, const uint8_t* argmax, const uint16_t* line_id
                     const int32_t* box_off, const int32_t* extent, int B, int H, int W, int n_class, int32_t* header,
                     int32_t* regions, int cap_regions, int32_t* pairs, int cap_pairs, int32_t* overflow);
 
+/* ------------------------------------------------------------------------------------------
+ * Mask painter for key-value inference (inference/kv_model.py:83-148 `_generate_masks_from_label`, the per-pixel part):
+ * the three canvases the forward and msau_kv_regions read, painted from the documents' glyph tables
+ * (msau_amd/inference/glyphs.py) in one launch.  Every canvas pixel is written, so nothing has to be cleared before.
+ *   msau_kv_paint : lines int32 [n][8] = (x1, y1, x2, y2, first glyph, glyphs, xl, xr) per text line in document order: the box in
+ *                   grid coordinates, its glyphs glyphs[first .. first + glyphs) counted from the document's first glyph, and the
+ *                   columns [xl, xr) that the box and the glyph spans reach; glyphs = 0 is a line without text, which paints
+ *                   nothing.  glyphs [m] of 8 bytes = (int16 a, int16 b, uint16 token, uint16 0): character k of its line covers
+ *                   the columns [a, b); within a line the spans are disjoint and their starts increase (a_k <= b_k <= a_k+1, a_k < a_k+1).
+ *                   line_off / glyph_off int32 [B + 1]: document b owns lines[line_off[b] .. line_off[b + 1]) and
+ *                   glyphs[glyph_off[b] .. glyph_off[b + 1]); sizes int32 [B][2] = (h, w) <= (H, W).  All device memory, the
+ *                   canvases 16-byte aligned.  Pixel (y, x) of document b:
+ *                     line_ids = li + 1 of the LAST line li with text, y1 <= y < y2, and x1 <= x < x2 or x in one of its spans
+ *                     ids / char_pos = token / k + 1 of glyph k of the LAST line with y1 <= y < y2 that has a span holding x
+ *                     0 where there is none; outside the document ids = -1 and both masks 0 (ragged.pack_ids / pack_masks)
+ *                   ids int32 [B][H][W], line_ids / char_pos uint16 [B][H][W].  Integers only, no atomics, no pixel limit.
+ * ------------------------------------------------------------------------------------------ */
+int msau_kv_paint(void* stream, const int32_t* lines, const void* glyphs, const int32_t* line_off, const int32_t* glyph_off,
+                  const int32_t* sizes, int B, int H, int W, int32_t* ids, uint16_t* line_ids, uint16_t* char_pos);
+
 #ifdef __cplusplus
 }
 #endif

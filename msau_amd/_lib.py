@@ -219,6 +219,7 @@ _SIGNATURES = {
     "msau_eval_confusion": (C.c_int, [vp, C.c_int, vp, vp, vp] + [C.c_int] * 6 + [vp]),
     "msau_kv_regions_limits": (C.c_int, [C.POINTER(i32)]),
     "msau_kv_regions": (C.c_int, [vp] * 7 + [C.c_int] * 4 + [vp, vp, C.c_int, vp, C.c_int, vp]),
+    "msau_kv_paint": (C.c_int, [vp] * 6 + [C.c_int] * 3 + [vp, vp, vp]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)

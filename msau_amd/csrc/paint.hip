@@ -1,0 +1,242 @@
+// Mask painter for key-value inference (inference/kv_model.py `_generate_masks_from_label`, the per-pixel part): the
+// character-id, line-id and character-position canvases of a group of documents from their glyph tables
+// (msau_amd/inference/glyphs.py), as a GATHER: every pixel looks its answers up, nothing is painted over.
+//   line_ids(y, x) = li + 1 of the last line li with text whose rows hold y and whose box or one of whose glyph spans holds x
+//   ids / char_pos = token / k + 1 of glyph k of the last line whose rows hold y and that has a span holding x
+// A glyph hit gives both answers, so a pixel is finished exactly when its character position is known; until then the lines are
+// walked from last to first.  The glyph holding x is found by binary search: within a line the spans are disjoint and their
+// starts strictly increasing (the table builder checks it), so the last span that starts at or before x is the only one that can
+// hold it.
+// One workgroup per band of PT_ROWS canvas rows of one document; a wavefront owns whole rows, so the row test of a line is the
+// same for all its lanes; a lane owns 8 consecutive pixels of a row and stores them as 16 bytes per 16-bit canvas and 32 bytes
+// of ids where the row start allows it.  The document's line records are staged in LDS PT_CHUNK at a time, last chunk first; a
+// line that misses the band is staged as a line without text.  With more than PT_CHUNK lines a lane takes the state of its
+// pixels back from the canvases (its own stores of the pass before).  Every loop is counted by the line / glyph counts or the
+// canvas; every canvas pixel is written once per pass, outside the documents with -1 / 0 / 0.  Integers only, no atomics.
+//
+// The body is written as phases between workgroup barriers; with -DMSAU_PAINT_CPU the same phases compile as plain C++ and the
+// lanes of a phase run one after another (tests/test_glyphs_cpu.py builds that form with the host compiler).
+#ifdef MSAU_PAINT_CPU
+#include <stdint.h>
+#include <stdlib.h>
+#include <string.h>
+#define PT_DEV static inline
+#define PT_PHASE(fn, ...) do { for (int t__ = 0; t__ < PT_THREADS; ++t__) fn(c, s, t__, ##__VA_ARGS__); } while (0)
+#define PT_UNIFORM(v) (v)
+#else
+#include "msau_common.h"
+#define PT_DEV __device__ __forceinline__
+#define PT_PHASE(fn, ...) do { fn(c, s, (int)threadIdx.x, ##__VA_ARGS__); __syncthreads(); } while (0)
+#define PT_UNIFORM(v) __builtin_amdgcn_readfirstlane(v)
+#endif
+
+#define PT_THREADS 256
+#define PT_WAVES (PT_THREADS / 64)
+#define PT_ROWS 4                   // canvas rows per workgroup: one per wavefront
+#define PT_CHUNK 256                // line records in LDS at a time: one per lane
+#define PT_LINE_INTS 8
+#define PT_SEARCH_STEPS 17          // a line has at most 65535 glyphs
+
+struct PtGlyph { int16_t a, b; uint16_t tok, zero; };
+
+struct PtCtx {                      // one band of one document
+    const int32_t* lines;           // the document's records [n_lines][PT_LINE_INTS]
+    const PtGlyph* glyphs;          // the document's glyphs [n_glyphs]
+    int n_lines, n_glyphs, h, w, H, W, r0;
+    int32_t* ids;                   // the document's planes on the canvas: pixel (y, x) at y * W + x
+    uint16_t* line;
+    uint16_t* chr;
+    bool aligned;                   // the planes start at a multiple of 8 pixels (the canvases are 16-byte aligned)
+};
+
+struct PtLds { int* x1; int* y1; int* x2; int* y2; int* g0; int* n; int* xl; int* xr; };     // [PT_CHUNK] each
+#define PT_LDS_INTS (8 * PT_CHUNK)
+
+PT_DEV void pt_carve(PtLds& s, int* base) {
+    s.x1 = base; s.y1 = base + PT_CHUNK; s.x2 = base + 2 * PT_CHUNK; s.y2 = base + 3 * PT_CHUNK;
+    s.g0 = base + 4 * PT_CHUNK; s.n = base + 5 * PT_CHUNK; s.xl = base + 6 * PT_CHUNK; s.xr = base + 7 * PT_CHUNK;
+}
+
+// lane t stages line first + t; n = 0 for a line without text, outside the band, with no rows, or whose glyphs are not the document's
+PT_DEV void pt_ph_stage(const PtCtx& c, const PtLds& s, int tid, int first) {
+    const int li = first + tid;
+    int n = 0;
+    if (li < c.n_lines) {
+        const int32_t* r = c.lines + (size_t)li * PT_LINE_INTS;
+        const int y1 = r[1], y2 = r[3], g0 = r[4], cnt = r[5];
+        const bool glyphs_ok = cnt > 0 && cnt <= 65535 && g0 >= 0 && g0 <= c.n_glyphs - cnt;
+        if (glyphs_ok && y1 < y2 && y1 < c.r0 + PT_ROWS && y2 > c.r0) n = cnt;
+        s.x1[tid] = r[0]; s.y1[tid] = y1; s.x2[tid] = r[2]; s.y2[tid] = y2; s.g0[tid] = g0; s.xl[tid] = r[6]; s.xr[tid] = r[7];
+    }
+    s.n[tid] = n;
+}
+
+// the last glyph of g[0 .. n) that starts at or before x, -1 if none
+PT_DEV int pt_last_at_or_before(const PtGlyph* g, int n, int x) {
+    int lo = 0, hi = n;
+    for (int it = 0; it < PT_SEARCH_STEPS && lo < hi; ++it) {
+        const int mid = (lo + hi) >> 1;
+        if (g[mid].a <= x) lo = mid + 1; else hi = mid;
+    }
+    return lo - 1;
+}
+
+// the 8 pixels (y, X .. X + 8) of the canvas against the staged lines, last to first
+PT_DEV void pt_pixels(const PtCtx& c, const PtLds& s, int y, int X, int first, int count, bool first_pass) {
+    int32_t id[8];
+    uint16_t lid[8], cp[8];
+    const size_t at = (size_t)y * c.W + X;
+    const bool vec = c.aligned && (at & 7) == 0 && X + 8 <= c.W;
+    unsigned need = 0;                                              // pixels of the document without a character so far
+    if (first_pass) {
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+            const bool in = y < c.h && X + i < c.w;
+            id[i] = in ? 0 : -1; lid[i] = 0; cp[i] = 0;
+            if (in) need |= 1u << i;
+        }
+    } else {
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+            const bool on = X + i < c.W;
+            id[i] = on ? c.ids[at + i] : -1; lid[i] = on ? c.line[at + i] : 0; cp[i] = on ? c.chr[at + i] : 0;
+            if (y < c.h && X + i < c.w && cp[i] == 0) need |= 1u << i;
+        }
+    }
+    for (int j = count - 1; j >= 0 && need; --j) {
+        const int n = s.n[j];
+        if (n == 0 || y < s.y1[j] || y >= s.y2[j]) continue;        // the same for every lane of the wavefront
+        if (X >= s.xr[j] || X + 8 <= s.xl[j]) continue;
+        const int x1 = s.x1[j], x2 = s.x2[j];
+        const PtGlyph* g = c.glyphs + s.g0[j];
+        const uint16_t v = (uint16_t)(first + j + 1);
+        // one search per lane and line: the starts are strictly increasing integers, so the last glyph that starts at or before
+        // X + i is one of k0 .. k0 + i.  The 9 records that the 8 pixels can need are loaded together, not one after another.
+        const int k0 = pt_last_at_or_before(g, n, X);
+        int ca[9], cb[9], ct[9];
+#pragma unroll
+        for (int t = 0; t < 9; ++t) {
+            const int k = k0 + t;
+            const bool has = k >= 0 && k < n;
+            const PtGlyph r = g[has ? k : 0];
+            ca[t] = has ? r.a : 0x7fffffff; cb[t] = r.b; ct[t] = r.tok;
+        }
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+            if (!(need >> i & 1)) continue;
+            const int x = X + i;
+            int sel = -1;
+#pragma unroll
+            for (int t = 0; t <= i; ++t) if (ca[t] <= x) sel = t;
+            int b = 0, tok = 0;
+#pragma unroll
+            for (int t = 0; t <= i; ++t) if (t == sel) { b = cb[t]; tok = ct[t]; }
+            if (sel >= 0 && x < b) {
+                id[i] = tok; cp[i] = (uint16_t)(k0 + sel + 1);
+                if (lid[i] == 0) lid[i] = v;
+                need &= ~(1u << i);
+            } else if (lid[i] == 0 && x >= x1 && x < x2) {
+                lid[i] = v;
+            }
+        }
+    }
+    if (vec) {
+#ifdef MSAU_PAINT_CPU
+        memcpy(c.ids + at, id, sizeof(id)); memcpy(c.line + at, lid, sizeof(lid)); memcpy(c.chr + at, cp, sizeof(cp));
+#else
+        typedef int i32x4 __attribute__((ext_vector_type(4)));
+        typedef unsigned short u16x8 __attribute__((ext_vector_type(8)));
+        i32x4 lo = {id[0], id[1], id[2], id[3]}, hi = {id[4], id[5], id[6], id[7]};
+        u16x8 l = {lid[0], lid[1], lid[2], lid[3], lid[4], lid[5], lid[6], lid[7]};
+        u16x8 p = {cp[0], cp[1], cp[2], cp[3], cp[4], cp[5], cp[6], cp[7]};
+        *reinterpret_cast<i32x4*>(c.ids + at) = lo;
+        *reinterpret_cast<i32x4*>(c.ids + at + 4) = hi;
+        *reinterpret_cast<u16x8*>(c.line + at) = l;
+        *reinterpret_cast<u16x8*>(c.chr + at) = p;
+#endif
+    } else {
+#pragma unroll
+        for (int i = 0; i < 8; ++i)
+            if (X + i < c.W) { c.ids[at + i] = id[i]; c.line[at + i] = lid[i]; c.chr[at + i] = cp[i]; }
+    }
+}
+
+// wavefront wv owns the band's rows wv, wv + PT_WAVES, ...; its lanes the groups of 8 pixels of a row
+PT_DEV void pt_ph_paint(const PtCtx& c, const PtLds& s, int tid, int first, int count, bool first_pass) {
+    const int wv = PT_UNIFORM(tid >> 6), lane = tid & 63, groups = (c.W + 7) >> 3;
+    for (int r = wv; r < PT_ROWS; r += PT_WAVES) {
+        const int y = c.r0 + r;
+        if (y >= c.H) break;
+        for (int gidx = lane; gidx < groups; gidx += 64) pt_pixels(c, s, y, gidx * 8, first, count, first_pass);
+    }
+}
+
+PT_DEV void pt_body(const PtCtx& c, const PtLds& s) {
+    const int passes = c.n_lines > 0 ? (c.n_lines + PT_CHUNK - 1) / PT_CHUNK : 1;
+    for (int p = 0; p < passes; ++p) {
+        const int first = (passes - 1 - p) * PT_CHUNK;
+        const int count = c.n_lines - first < PT_CHUNK ? (c.n_lines - first > 0 ? c.n_lines - first : 0) : PT_CHUNK;
+        PT_PHASE(pt_ph_stage, first);
+        PT_PHASE(pt_ph_paint, first, count, p == 0);
+    }
+}
+
+// the band `band` of document b.  Offsets that are not ordered make it a document without lines, an extent is clipped to the canvas:
+// whatever the tables hold, nothing outside them is read and nothing outside the canvas is written
+PT_DEV void pt_ctx(PtCtx& c, const int32_t* lines, const PtGlyph* glyphs, const int32_t* line_off, const int32_t* glyph_off,
+                   const int32_t* sizes, int b, int band, int H, int W, int32_t* ids, uint16_t* line_ids, uint16_t* char_pos) {
+    const int l0 = line_off[b], l1 = line_off[b + 1], g0 = glyph_off[b], g1 = glyph_off[b + 1];
+    const bool ok = l0 >= 0 && l1 >= l0 && g0 >= 0 && g1 >= g0;
+    c.lines = lines + (size_t)(ok ? l0 : 0) * PT_LINE_INTS; c.n_lines = ok ? l1 - l0 : 0;
+    c.glyphs = glyphs + (ok ? g0 : 0); c.n_glyphs = ok ? g1 - g0 : 0;
+    const int h = sizes[2 * b], w = sizes[2 * b + 1];
+    c.h = h < 0 ? 0 : (h > H ? H : h); c.w = w < 0 ? 0 : (w > W ? W : w);
+    c.H = H; c.W = W; c.r0 = band * PT_ROWS;
+    const size_t plane = (size_t)b * H * W;
+    c.ids = ids + plane; c.line = line_ids + plane; c.chr = char_pos + plane;
+    c.aligned = (plane & 7) == 0;
+}
+
+#ifdef MSAU_PAINT_CPU
+// the launch, lane by lane on the host: same arguments as msau_kv_paint without the stream
+extern "C" int msau_kv_paint_cpu(const int32_t* lines, const void* glyphs, const int32_t* line_off, const int32_t* glyph_off,
+                                 const int32_t* sizes, int B, int H, int W, int32_t* ids, uint16_t* line_ids, uint16_t* char_pos) {
+    int* lds = (int*)malloc(sizeof(int) * PT_LDS_INTS);
+    if (!lds) return 1;
+    for (int b = 0; b < B; ++b)
+        for (int band = 0; band * PT_ROWS < H; ++band) {
+            PtCtx c;
+            pt_ctx(c, lines, (const PtGlyph*)glyphs, line_off, glyph_off, sizes, b, band, H, W, ids, line_ids, char_pos);
+            PtLds s;
+            pt_carve(s, lds);
+            pt_body(c, s);
+        }
+    free(lds);
+    return 0;
+}
+#else
+
+__global__ void __launch_bounds__(PT_THREADS)
+kv_paint_kernel(const int32_t* lines, const PtGlyph* glyphs, const int32_t* line_off, const int32_t* glyph_off, const int32_t* sizes,
+                int H, int W, int32_t* ids, uint16_t* line_ids, uint16_t* char_pos) {
+    __shared__ int pt_lds[PT_LDS_INTS];
+    PtCtx c;
+    pt_ctx(c, lines, glyphs, line_off, glyph_off, sizes, (int)blockIdx.y, (int)blockIdx.x, H, W, ids, line_ids, char_pos);
+    PtLds s;
+    pt_carve(s, pt_lds);
+    pt_body(c, s);
+}
+
+extern "C" int msau_kv_paint(void* stream, const int32_t* lines, const void* glyphs, const int32_t* line_off, const int32_t* glyph_off,
+                             const int32_t* sizes, int B, int H, int W, int32_t* ids, uint16_t* line_ids, uint16_t* char_pos) {
+    MSAU_CHECK_ARG(lines && glyphs && line_off && glyph_off && sizes && ids && line_ids && char_pos, "kv_paint: null pointer");
+    MSAU_CHECK_ARG(B > 0 && B <= 65535 && H > 0 && W > 0 && (int64_t)B * H * W < (1ll << 31), "kv_paint: bad shape B = %d, H = %d, W = %d", B, H, W);
+    MSAU_CHECK_ARG(((uintptr_t)ids | (uintptr_t)line_ids | (uintptr_t)char_pos) % 16 == 0, "kv_paint: the canvases must be 16-byte aligned");
+    MSAU_CHECK_ARG((uintptr_t)lines % 4 == 0 && (uintptr_t)glyphs % 8 == 0, "kv_paint: the records must be aligned to their size");
+    static_assert(sizeof(PtGlyph) == 8, "kv_paint: a glyph record is 8 bytes");
+    hipLaunchKernelGGL(kv_paint_kernel, dim3(cdiv(H, PT_ROWS), B), dim3(PT_THREADS), 0, static_cast<hipStream_t>(stream), lines,
+                       static_cast<const PtGlyph*>(glyphs), line_off, glyph_off, sizes, H, W, ids, line_ids, char_pos);
+    MSAU_CHECK_LAUNCH("kv_paint");
+    return 0;
+}
+#endif

@@ -4,8 +4,9 @@ the size KVModel really runs at (text lines scaled to 3 px), dense input vs the 
 With --ragged B: ms per document of predict_nhwc(ids) one document at a time against ragged batches of B (pack_ids +
 predict_nhwc(ids=..., sizes=...)) on id masks of varied sizes around KVModel's 70 x 128 scale (60 tokens, 17 classes).
 With --post B: ms per document of KVModel's post-processing on the host against device_post=True (the region kernel of
-csrc/regions.hip), interleaved in one process: (a) predict_batch end to end on the golden layouts with the golden (seeded,
-random-weight) net, (b) the region stage alone on the reference's clean class maps, both arms starting from class maps on the
+csrc/regions.hip) and against device_post=True, device_masks=True (the masks painted on the device as well, csrc/paint.hip),
+interleaved in one process: (a) predict_batch end to end on the golden layouts with the golden (seeded, random-weight) net,
+(b) the region stage alone on the reference's clean class maps, both arms starting from class maps on the
 device.  Reads tests/golden/kv only.
 Not the headline metric (bench.py is); numbers are quoted in DESIGN.md."""
 import argparse
@@ -83,6 +84,7 @@ def run_post(B, dtype, repeats, n_docs=48):
     import numpy as np
     from msau_amd.data.ragged import pack_masks
     from msau_amd.inference import KVModel
+    from msau_amd.inference import glyphs as G
     from msau_amd.inference import regions as R
     from oracle import msau_oracle as O
     import tempfile
@@ -101,8 +103,9 @@ def run_post(B, dtype, repeats, n_docs=48):
     out = {"batch": B, "dtype": dtype, "n_docs": n_docs, "repeats": repeats, "n_class": n_class}
 
     def reset():
-        for k in R.STATS:
-            R.STATS[k] = 0
+        for stats in (R.STATS, G.STATS):
+            for k in stats:
+                stats[k] = 0
 
     def timed(fn):
         torch.cuda.synchronize()
@@ -113,23 +116,33 @@ def run_post(B, dtype, repeats, n_docs=48):
 
     # (a) end to end, layout JSON -> kv_results
     arms = {"host": lambda: [km.predict_batch(gr) for gr in groups],
-            "device": lambda: [km.predict_batch(gr, device_post=True) for gr in groups]}
-    same = arms["host"]() == arms["device"]()                              # (the warm-up)
+            "device": lambda: [km.predict_batch(gr, device_post=True) for gr in groups],
+            "device_masks": lambda: [km.predict_batch(gr, device_post=True, device_masks=True) for gr in groups]}
+    same = arms["host"]() == arms["device"]() == arms["device_masks"]()    # (the warm-up)
     reset()
-    ms = {"host": [], "device": []}
+    ms = {name: [] for name in arms}
     for _ in range(repeats):
-        for name in ("host", "device"):
+        for name in arms:
             ms[name].append(timed(arms[name]))
     sizes = [g[f"d{i}.line_mask"].shape for i in range(3)]
     canvas = (-(-max(h for h, _ in sizes) // 16) * 16) * (-(-max(w for _, w in sizes) // 16) * 16) if B > 1 else None
-    out["a_end_to_end"] = {"host_ms_per_doc": ms["host"], "device_ms_per_doc": ms["device"], "same_results": same,
-                           "host_d2h_bytes_per_doc": (canvas if B > 1 else int(np.mean([h * w for h, w in sizes]))) * (4 * n_class + 1),
+    pixels = canvas if B > 1 else int(np.mean([h * w for h, w in sizes]))
+    out["a_end_to_end"] = {"host_ms_per_doc": ms["host"], "device_ms_per_doc": ms["device"],
+                           "device_masks_ms_per_doc": ms["device_masks"], "same_results": same,
+                           "device_h2d_bytes_per_doc": 8 * pixels,          # int32 ids + two 16-bit masks per canvas pixel
+                           "device_masks_h2d_bytes_per_doc": round(G.STATS["h2d_bytes"] / max(G.STATS["documents"], 1)),
+                           "device_masks_host_painted": G.STATS["host_painted"],
+                           "host_d2h_bytes_per_doc": pixels * (4 * n_class + 1),
                            "device_d2h_bytes_per_doc": round(R.STATS["d2h_bytes"] / max(R.STATS["documents"], 1)),
                            "fallbacks": R.STATS["fallbacks"]}
     t0 = time.perf_counter()
     for f in files:
         km._generate_masks_from_label(f)
     out["a_end_to_end"]["masks_from_label_ms_per_doc"] = round((time.perf_counter() - t0) / n_docs * 1e3, 4)
+    t0 = time.perf_counter()
+    for f in files:
+        G.glyph_table(f, km.tok_to_id, km.blank_idx)
+    out["a_end_to_end"]["glyph_table_ms_per_doc"] = round((time.perf_counter() - t0) / n_docs * 1e3, 4)
 
     # (b) the region stage on the reference's clean class maps, already on the device
     docs = []
@@ -196,7 +209,7 @@ def main():
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--ragged", type=int, default=0, help="only the ragged comparison, in batches of this size")
     ap.add_argument("--docs", type=int, default=48, help="documents of the ragged comparison")
-    ap.add_argument("--post", type=int, default=0, help="only the post-processing comparison (host against device_post=True), "
+    ap.add_argument("--post", type=int, default=0, help="only the post-processing comparison (host against device_post=True and device_masks=True), "
                                                         "in batches of this size")
     ap.add_argument("--repeats", type=int, default=5, help="interleaved repeats per arm of --post")
     a = ap.parse_args()
