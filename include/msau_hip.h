@@ -100,8 +100,11 @@ enum {
                                    box list, the feature table.  The piecewise-constant embedding chargrid (data_generator_funsd_bert.py:
                                    64-93,240; 1536 bytes per pixel at 768 channels) is never painted: the forward gathers per-tap partial
                                    products from a [feature row][tap][co] table, the weight gradient sums the output gradient per box
-                                   and tap.  3x3, stride 1, C1 -> 8; other flags: RELU_OUT only; also on msau_wgrad_desc.flags (x1 =
-                                   the same context; the first msau_owner_slabs(d) slabs are written -- the slab reduction must be told).
+                                   and tap.  3x3, stride 1, C1 -> 8; other flags: RELU_OUT, and EXTENT (ragged batch: a pixel outside its sample's
+                                   extent is stored as 0 and gathers nothing, taps stop at the document's edge; the owner map must come
+                                   from msau_raster_owner_ext, and the weight gradient relies on g being 0 outside the extents); also on
+                                   msau_wgrad_desc.flags (x1 = the same context; EXTENT needs no pointer there; the first
+                                   msau_owner_slabs(d) slabs are written -- the slab reduction must be told).
                                    msau_conv2d_launch_info: info[7] & 32 when the launch can take it. */
     MSAU_CONV_NCHW     = 4096,  /* the net's first conv fed with the API's input tensor itself (csrc/conv_first.hip): x1 is fp32 NCHW
                                    [B][C][Hin][Win] with C = head_classes real channels (<= C1 = 64 stored; the missing ones are zero), and
@@ -124,8 +127,9 @@ enum {
     MSAU_CONV_EXTENT   = 65536, /* ragged batch: `extent` ([B][2] int32 (h, w) of each sample on the OUTPUT grid) -- applied LAST, after bias, masks,
                                    add, accumulate and activation: a pixel (oy, ox) with oy >= h or ox >= w of its sample is stored as 0.  For
                                    forward convs, transposed convs (ups = 2) and data gradients (stride = 2 included: its output is the deconv
-                                   input's grid).  Implemented by the generic tile kernel (conv.hip) only: every other instance refuses the flag,
-                                   so it does not combine with HEAD / DOUT / LRN / POOL / IDS / OWNER / NCHW / WGRAD (msau_conv2d_launch_info
+                                   input's grid).  Implemented by the generic tile kernel (conv.hip) and by the box-list instance (MSAU_CONV_OWNER,
+                                   ownerconv.hip): every other instance refuses the flag, so it does not combine with HEAD / DOUT / LRN /
+                                   POOL / IDS / NCHW / WGRAD (msau_conv2d_launch_info
                                    info[7] bit 7 says whether the instance taking the descriptor implements it). */
     MSAU_CONV_HEAD     = 64     /* inference head (kv_model.py:305-313): besides y, write softmax over the Cout real
                                    channels of the (storage-rounded) result to head_probs (fp32 [B][Hout][Wout][Cout],
@@ -307,7 +311,10 @@ typedef struct {
     int32_t B, Hin, Win, Hout, Wout;
     int32_t C1, C2, Cout;
     int32_t KH, KW, dil, pad_t, pad_l, stride;
-    int32_t flags;              /* MSAU_CONV_RELU_IN; MSAU_CONV_IDS (x1 = int32 id mask, C1 = 64, Cout = 8, 3x3) */
+    int32_t flags;              /* MSAU_CONV_RELU_IN; MSAU_CONV_IDS (x1 = int32 id mask, C1 = 64, Cout = 8, 3x3);
+                                   MSAU_CONV_OWNER (x1 = host msau_owner_ctx), with it MSAU_CONV_EXTENT (no pointer: the
+                                   per-box sums run in an order anchored on the canvas, independent of what a box covers
+                                   outside its document) */
     const void* x1;
     const void* x2;
     const void* g;              /* [B][Hout][Wout][Cout] gradient w.r.t. the conv's pre-activation  */
@@ -533,6 +540,12 @@ int msau_clip_adam_step(void* stream, float* params, const float* grads, float* 
  *   msau_raster_labels : labels[b][y][x]  = value of the owning box, 0 where none
  * ------------------------------------------------------------------------------------------ */
 int msau_raster_owner(void* stream, const int32_t* boxes, int n, int32_t* owner, int B, int H, int W);
+/* Ragged batch (documents of their own (h, w) at the origin of one H x W canvas): every box is in the coordinates of its own
+ * document and is clipped at that DOCUMENT's edge -- what numpy slicing does on the reference's h x w array
+ * (data_generator_funsd_bert.py:64-93) -- not at the canvas edge.  extent: int32 [B][2] = (h, w) of every sample (level 0 of a ragged
+ * plan's extents; not NULL; values beyond the canvas are clipped to it).  owner is -1 everywhere outside the documents, so
+ * msau_raster_onehot / _labels / _dense on it write zeros there, and MSAU_CONV_OWNER | MSAU_CONV_EXTENT gathers nothing there. */
+int msau_raster_owner_ext(void* stream, const int32_t* boxes, int n, int32_t* owner, int B, int H, int W, const int32_t* extent);
 int msau_raster_onehot(void* stream, int dtype, const int32_t* boxes, const int32_t* owner, void* grid_nhwc,
                        int B, int H, int W, int C, int Cs);
 int msau_raster_labels(void* stream, const int32_t* boxes, const int32_t* owner, int64_t* labels, int B, int H, int W);

@@ -192,6 +192,7 @@ _SIGNATURES = {
     "msau_adam_ws_floats": (i64, [i64]),
     "msau_clip_adam_step": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, i64, f32, f32, f32, f32, f32, f32]),
     "msau_raster_owner": (C.c_int, [vp, vp, C.c_int, vp, C.c_int, C.c_int, C.c_int]),
+    "msau_raster_owner_ext": (C.c_int, [vp, vp, C.c_int, vp, C.c_int, C.c_int, C.c_int, vp]),
     "msau_raster_onehot": (C.c_int, [vp, C.c_int, vp, vp, vp] + [C.c_int] * 5),
     "msau_raster_labels": (C.c_int, [vp, vp, vp, vp, C.c_int, C.c_int, C.c_int]),
     "msau_raster_dense": (C.c_int, [vp, C.c_int, vp, vp, vp, vp] + [C.c_int] * 5),

@@ -362,11 +362,13 @@ int msau_conv_chunked_capable(int dtype, const msau_conv_desc* d, int cch, int n
 int msau_firstconv_takes(int dtype, const msau_conv_desc* d);
 int msau_firstconv_launch(hipStream_t s, int dtype, const msau_conv_desc* d, int real_channels);
 
-// 1 if msau_conv2d runs the generic tile kernel for `d` (MSAU_CONV_EXTENT set): no flag that only other instances implement, and
-// none of them takes it (each refuses the flag itself)
+// 1 if the instance msau_conv2d runs for `d` (MSAU_CONV_EXTENT set) implements the flag: the box-list instance (MSAU_CONV_OWNER,
+// ownerconv.hip) where it takes the launch, else the generic tile kernel -- no flag that only other instances implement, and none of
+// them takes it (each refuses the flag itself)
 static int conv_takes_extent(int dtype, const msau_conv_desc* d, const ConvGeom& g) {
-    const int only_others = MSAU_CONV_HEAD | MSAU_CONV_DOUT | MSAU_CONV_LRN | MSAU_CONV_POOL | MSAU_CONV_IDS | MSAU_CONV_OWNER |
-                            MSAU_CONV_NCHW | MSAU_CONV_WGRAD;
+    if (d->flags & MSAU_CONV_OWNER) return msau_ownerconv_takes(dtype, d);
+    const int only_others = MSAU_CONV_HEAD | MSAU_CONV_DOUT | MSAU_CONV_LRN | MSAU_CONV_POOL | MSAU_CONV_IDS | MSAU_CONV_NCHW |
+                            MSAU_CONV_WGRAD;
     if (d->flags & only_others) return 0;
     if (g.nslices == 1 && (msau_rowconv_takes(dtype, d) || msau_conv_chunked_capable(dtype, d, g.cch, g.nchunks, g.CT) ||
                            msau_conv_lean_applicable(dtype, d, g.nchunks, g.CT)))
@@ -443,12 +445,12 @@ extern "C" int msau_conv2d(void* stream, int dtype, const msau_conv_desc* d) {
         if (rc) return rc;
         if (!conv_takes_extent(dtype, d, g))
             return msau_set_error(MSAU_ERR_ARG, "conv2d: MSAU_CONV_EXTENT is not implemented for this launch (flags 0x%x; see "
-                                  "msau_conv2d_launch_info info[7] & 128): only the generic tile kernel has it", d->flags);
+                                  "msau_conv2d_launch_info info[7] & 128): only the generic tile kernel and the box-list instance have it", d->flags);
     }
     if (d->flags & MSAU_CONV_WGRAD)                                            // a rider only the row-streaming coupling instance carries
         MSAU_CHECK_ARG(msau_conv2d_rider_slabs(dtype, d) > 0, "conv2d: MSAU_CONV_WGRAD is not implemented for this launch (msau_conv2d_rider_slabs says 0)");
     if (d->flags & MSAU_CONV_OWNER) {                                          // ownerconv.hip: box lists instead of a painted input tensor
-        MSAU_CHECK_ARG(msau_ownerconv_takes(dtype, d), "conv2d: MSAU_CONV_OWNER is the 3x3 stride-1 C -> 8 conv, no other flag but RELU_OUT");
+        MSAU_CHECK_ARG(msau_ownerconv_takes(dtype, d), "conv2d: MSAU_CONV_OWNER is the 3x3 stride-1 C -> 8 conv, no other flag but RELU_OUT and EXTENT");
         return msau_ownerconv_fwd(static_cast<hipStream_t>(stream), dtype, d);
     }
     if (d->flags & MSAU_CONV_NCHW) {                                           // conv_first.hip: the fp32 NCHW input tensor itself

@@ -94,25 +94,34 @@ __global__ __launch_bounds__(64) void owner_table_mfma_kernel(const bf16_t* __re
     }
 }
 
-// ---- forward: a thread per pixel, taps in (ky, kx) order
+// ---- forward: a thread per pixel, taps in (ky, kx) order.  `extent` (MSAU_CONV_EXTENT, ragged batch: [B][2] (h, w) of every sample): a pixel
+// outside its sample's extent stores zeros (bias + ReLU would leave a non-zero there) and gathers nothing; inside, the taps stop at the
+// DOCUMENT's edge -- its own zero padding (the owner map of msau_raster_owner_ext is -1 there anyway) -- and nothing else changes
 template <typename T>
 __global__ __launch_bounds__(256) void owner_fwd_kernel(const int32_t* __restrict__ owner, const int32_t* __restrict__ boxes, const float* __restrict__ table,
-                                                        const float* __restrict__ bias, T* __restrict__ y, int B, int H, int W, int n_vec, bool relu_out) {
+                                                        const float* __restrict__ bias, T* __restrict__ y, int B, int H, int W, int n_vec, bool relu_out,
+                                                        const int32_t* __restrict__ extent) {
     const int64_t npix = (int64_t)B * H * W;
     for (int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; p < npix; p += (int64_t)gridDim.x * blockDim.x) {
         const int x = (int)(p % W);
         const int64_t r = p / W;
         const int yy = (int)(r % H);
+        int eh = H, ew = W;
+        if (extent) {
+            const int b = (int)(r / H);
+            eh = min(extent[2 * b], H); ew = min(extent[2 * b + 1], W);
+            if (yy >= eh || x >= ew) { store8<T>(y + p * 8, zero8<T>()); continue; }
+        }
         f32x4 a0 = {0.f, 0.f, 0.f, 0.f}, a1 = a0;
         if (bias) { a0 = *reinterpret_cast<const f32x4*>(bias); a1 = *reinterpret_cast<const f32x4*>(bias + 4); }
 #pragma unroll
         for (int ky = 0; ky < 3; ++ky) {
             const int qy = yy + ky - 1;
-            if ((unsigned)qy >= (unsigned)H) continue;
+            if ((unsigned)qy >= (unsigned)eh) continue;
 #pragma unroll
             for (int kx = 0; kx < 3; ++kx) {
                 const int qx = x + kx - 1;
-                if ((unsigned)qx >= (unsigned)W) continue;
+                if ((unsigned)qx >= (unsigned)ew) continue;
                 const int o = owner[p + (int64_t)(ky - 1) * W + (kx - 1)];
                 if (o < 0) continue;
                 const int v = boxes[(size_t)o * 6 + 5];
@@ -132,8 +141,32 @@ __global__ __launch_bounds__(256) void owner_fwd_kernel(const int32_t* __restric
     }
 }
 
-// ---- S[box][tap * 8 + co]: a wave per box; lanes stride over the box's rectangle, then 72 threads add the 64 lanes up in order
+// ---- S[box][tap * 8 + co]: a wave per box; lanes stride over the box's rectangle, then 72 threads add the 64 lanes up in order.
+// ANCH (MSAU_CONV_EXTENT, ragged batch): a box may reach beyond its document, where it owns nothing; which lane takes a pixel, and in
+// which order, must then not depend on the rectangle's shape, or the part outside the document would change the bits of the sum.  So
+// the lane is the pixel's place in an 8 x 8 tile anchored on the CANVAS and a lane visits its pixels in row-major order: clipping the
+// box anywhere leaves every owned pixel on its lane and in its turn.  The dense launch keeps its order (and its bits).
 template <typename T>
+__device__ __forceinline__ void owner_sums_pixel(const int32_t* __restrict__ owner, const T* __restrict__ g, int i, int b, int qy, int qx,
+                                                 int H, int W, float (&acc)[72]) {
+    const int64_t q = ((int64_t)b * H + qy) * W + qx;
+    if (owner[q] != i) return;
+#pragma unroll
+    for (int ky = 0; ky < 3; ++ky) {
+        const int py = qy - (ky - 1);
+        if ((unsigned)py >= (unsigned)H) continue;
+#pragma unroll
+        for (int kx = 0; kx < 3; ++kx) {
+            const int px = qx - (kx - 1);
+            if ((unsigned)px >= (unsigned)W) continue;
+            const typename Vec8<T>::type gv = load8<T>(g + (((int64_t)b * H + py) * W + px) * 8);
+#pragma unroll
+            for (int c = 0; c < 8; ++c) acc[(ky * 3 + kx) * 8 + c] += (float)gv[c];
+        }
+    }
+}
+
+template <typename T, bool ANCH>
 __global__ __launch_bounds__(64) void owner_sums_kernel(const int32_t* __restrict__ owner, const int32_t* __restrict__ boxes, const T* __restrict__ g,
                                                         float* __restrict__ sums, int n_boxes, int B, int H, int W) {
     __shared__ float part[64][73];
@@ -146,24 +179,13 @@ __global__ __launch_bounds__(64) void owner_sums_kernel(const int32_t* __restric
 #pragma unroll
         for (int k = 0; k < 72; ++k) acc[k] = 0.f;
         if (b >= 0 && b < B && y1 > y0 && x1 > x0) {                       // wave-uniform
-            const int w = x1 - x0, area = w * (y1 - y0);
-            for (int t = lane; t < area; t += 64) {
-                const int qy = y0 + t / w, qx = x0 + t % w;
-                const int64_t q = ((int64_t)b * H + qy) * W + qx;
-                if (owner[q] != i) continue;
-#pragma unroll
-                for (int ky = 0; ky < 3; ++ky) {
-                    const int py = qy - (ky - 1);
-                    if ((unsigned)py >= (unsigned)H) continue;
-#pragma unroll
-                    for (int kx = 0; kx < 3; ++kx) {
-                        const int px = qx - (kx - 1);
-                        if ((unsigned)px >= (unsigned)W) continue;
-                        const typename Vec8<T>::type gv = load8<T>(g + (((int64_t)b * H + py) * W + px) * 8);
-#pragma unroll
-                        for (int c = 0; c < 8; ++c) acc[(ky * 3 + kx) * 8 + c] += (float)gv[c];
-                    }
-                }
+            if (ANCH) {
+                const int ly = lane >> 3, lx = lane & 7;
+                for (int qy = y0 + ((ly - y0) & 7); qy < y1; qy += 8)
+                    for (int qx = x0 + ((lx - x0) & 7); qx < x1; qx += 8) owner_sums_pixel<T>(owner, g, i, b, qy, qx, H, W, acc);
+            } else {
+                const int w = x1 - x0, area = w * (y1 - y0);
+                for (int t = lane; t < area; t += 64) owner_sums_pixel<T>(owner, g, i, b, y0 + t / w, x0 + t % w, H, W, acc);
             }
         }
         __syncthreads();
@@ -242,7 +264,7 @@ __global__ __launch_bounds__(64) void owner_bias_kernel(const float* __restrict_
 }  // namespace
 
 int msau_ownerconv_takes(int dtype, const msau_conv_desc* d) {
-    return (d->flags & MSAU_CONV_OWNER) && !(d->flags & ~(MSAU_CONV_OWNER | MSAU_CONV_RELU_OUT)) && d->Cout == 8 && d->C2 == 0 && d->KH == 3 && d->KW == 3 &&
+    return (d->flags & MSAU_CONV_OWNER) && !(d->flags & ~(MSAU_CONV_OWNER | MSAU_CONV_RELU_OUT | MSAU_CONV_EXTENT)) && d->Cout == 8 && d->C2 == 0 && d->KH == 3 && d->KW == 3 &&
            d->dil == 1 && d->stride == 1 && d->ups == 1 && d->pad_t == 1 && d->pad_l == 1 && d->Hin == d->Hout && d->Win == d->Wout &&
            (dtype == MSAU_F32 || dtype == MSAU_BF16);
 }
@@ -259,6 +281,8 @@ int msau_ownerconv_fwd(hipStream_t s, int dtype, const msau_conv_desc* d) {
     int64_t blocks = cdiv64(npix, 256);
     if (blocks > 16384) blocks = 16384;
     const bool relu = d->flags & MSAU_CONV_RELU_OUT;
+    MSAU_CHECK_ARG(!(d->flags & MSAU_CONV_EXTENT) || d->extent, "conv2d: MSAU_CONV_EXTENT without extent pointer");
+    const int32_t* ext = (d->flags & MSAU_CONV_EXTENT) ? d->extent : nullptr;
     if (c->n_vec > 0) {
         if (dtype == MSAU_F32) {
             const dim3 gw(cdiv(c->C * 72, 256)), gt(cdiv(c->n_vec, 64), 72 / JW);
@@ -273,10 +297,10 @@ int msau_ownerconv_fwd(hipStream_t s, int dtype, const msau_conv_desc* d) {
     }
     if (dtype == MSAU_F32)
         hipLaunchKernelGGL(owner_fwd_kernel<float>, dim3((int)blocks), dim3(256), 0, s, c->owner, c->boxes, c->table, d->bias, static_cast<float*>(d->y),
-                           d->B, d->Hout, d->Wout, c->n_vec, relu);
+                           d->B, d->Hout, d->Wout, c->n_vec, relu, ext);
     else
         hipLaunchKernelGGL(owner_fwd_kernel<bf16_t>, dim3((int)blocks), dim3(256), 0, s, c->owner, c->boxes, c->table, d->bias, static_cast<bf16_t*>(d->y),
-                           d->B, d->Hout, d->Wout, c->n_vec, relu);
+                           d->B, d->Hout, d->Wout, c->n_vec, relu, ext);
     MSAU_CHECK_LAUNCH("owner_fwd");
     return 0;
 }
@@ -293,7 +317,11 @@ int msau_ownerconv_wgrad(hipStream_t s, int dtype, const msau_wgrad_desc* d, int
     MSAU_CHECK_ARG(c && c->owner && c->feats && c->sums && c->csum && c->csum_blocks >= 1 && c->n_boxes >= 0 && (c->n_boxes == 0 || c->boxes) &&
                    c->C > 0 && c->C <= d->C1, "wgrad: bad MSAU_CONV_OWNER context");
     MSAU_CHECK_ARG(d->Cout == 8 && d->C2 == 0 && d->KH == 3 && d->KW == 3 && d->dil == 1 && d->stride == 1 && d->pad_t == 1 && d->pad_l == 1 &&
-                   kext >= 9 * cch + 1 && cch * nchunks >= d->C1 && !(d->flags & MSAU_CONV_RELU_IN), "wgrad: MSAU_CONV_OWNER is the 3x3 C -> 8 conv of the net's input");
+                   kext >= 9 * cch + 1 && cch * nchunks >= d->C1 && !(d->flags & ~(MSAU_CONV_OWNER | MSAU_CONV_EXTENT)),
+                   "wgrad: MSAU_CONV_OWNER is the 3x3 C -> 8 conv of the net's input, no other flag but EXTENT");
+    // MSAU_CONV_EXTENT (ragged batch) needs no extents here: g is 0 outside them (the plan's invariant) and the owner map of
+    // msau_raster_owner_ext is -1 there, so the sums are those of the dense launch; only the ORDER of the per-box sums is anchored on the
+    // canvas (owner_sums_kernel<ANCH>), so that the part of a box outside its document cannot change a bit
     const int64_t npix = (int64_t)d->B * d->Hout * d->Wout;
     int rc = msau_channel_sum(s, dtype, d->g, npix, 8, c->csum, c->csum_blocks);
     if (rc) return rc;
@@ -305,11 +333,12 @@ int msau_ownerconv_wgrad(hipStream_t s, int dtype, const msau_wgrad_desc* d, int
     if (c->n_boxes > 0) {
         const int nb = c->n_boxes < 8192 ? c->n_boxes : 8192;
         const dim3 grid(cdiv(c->C, 64), 72 / JW, ksplit);
+        const bool anch = d->flags & MSAU_CONV_EXTENT;
         if (dtype == MSAU_F32) {
-            hipLaunchKernelGGL(owner_sums_kernel<float>, dim3(nb), dim3(64), 0, s, c->owner, c->boxes, static_cast<const float*>(d->g), c->sums, c->n_boxes, d->B, d->Hout, d->Wout);
+            hipLaunchKernelGGL((anch ? owner_sums_kernel<float, true> : owner_sums_kernel<float, false>), dim3(nb), dim3(64), 0, s, c->owner, c->boxes, static_cast<const float*>(d->g), c->sums, c->n_boxes, d->B, d->Hout, d->Wout);
             hipLaunchKernelGGL(owner_wgrad_kernel<float>, grid, dim3(64), 0, s, c->boxes, c->feats, c->sums, d->slabs, c->n_boxes, c->n_vec, c->C, cch, kext, nchunks, ksplit);
         } else {
-            hipLaunchKernelGGL(owner_sums_kernel<bf16_t>, dim3(nb), dim3(64), 0, s, c->owner, c->boxes, static_cast<const bf16_t*>(d->g), c->sums, c->n_boxes, d->B, d->Hout, d->Wout);
+            hipLaunchKernelGGL((anch ? owner_sums_kernel<bf16_t, true> : owner_sums_kernel<bf16_t, false>), dim3(nb), dim3(64), 0, s, c->owner, c->boxes, static_cast<const bf16_t*>(d->g), c->sums, c->n_boxes, d->B, d->Hout, d->Wout);
             hipLaunchKernelGGL(owner_wgrad_kernel<bf16_t>, grid, dim3(64), 0, s, c->boxes, c->feats, c->sums, d->slabs, c->n_boxes, c->n_vec, c->C, cch, kext, nchunks, ksplit);
         }
         MSAU_CHECK_LAUNCH("owner_wgrad");

@@ -23,6 +23,26 @@ __global__ void raster_owner_kernel(const int32_t* __restrict__ boxes, int n, in
     }
 }
 
+// ragged batch: box i lies in the coordinates of its own document b = boxes[i][0], whose (h, w) = extent[b] sits at the origin of the
+// H x W canvas; the box is clipped at the DOCUMENT's edge (what numpy slicing on the reference's h x w array does), so owner stays
+// -1 everywhere outside the documents and the painters below leave zeros there
+__global__ void raster_owner_ext_kernel(const int32_t* __restrict__ boxes, int n, int32_t* __restrict__ owner, int B, int H, int W,
+                                        const int32_t* __restrict__ extent) {
+    for (int i = blockIdx.x; i < n; i += gridDim.x) {
+        const int32_t* bx = boxes + (size_t)i * 6;
+        const int b = bx[0];
+        if (b < 0 || b >= B) continue;
+        const int eh = min(max(extent[2 * b], 0), H), ew = min(max(extent[2 * b + 1], 0), W);
+        int y0 = max(bx[1], 0), y1 = min(bx[2], eh), x0 = max(bx[3], 0), x1 = min(bx[4], ew);
+        if (y1 <= y0 || x1 <= x0) continue;
+        const int w = x1 - x0, area = w * (y1 - y0);
+        for (int t = threadIdx.x; t < area; t += blockDim.x) {
+            int y = y0 + t / w, x = x0 + t % w;
+            atomicMax(&owner[((size_t)b * H + y) * W + x], i);
+        }
+    }
+}
+
 template <typename T>
 __global__ void raster_onehot_kernel(const int32_t* __restrict__ boxes, const int32_t* __restrict__ owner,
                                      T* __restrict__ grid, int64_t npix, int C, int Cs) {
@@ -119,6 +139,17 @@ extern "C" int msau_raster_owner(void* stream, const int32_t* boxes, int n, int3
     if (n == 0) return 0;
     hipLaunchKernelGGL(raster_owner_kernel, dim3(n < 4096 ? n : 4096), dim3(64), 0, s, boxes, n, owner, B, H, W);
     MSAU_CHECK_LAUNCH("raster_owner");
+    return 0;
+}
+
+extern "C" int msau_raster_owner_ext(void* stream, const int32_t* boxes, int n, int32_t* owner, int B, int H, int W, const int32_t* extent) {
+    MSAU_CHECK_ARG(owner && extent && B > 0 && H > 0 && W > 0 && n >= 0 && (n == 0 || boxes), "raster_owner_ext: bad args");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    hipError_t e = hipMemsetAsync(owner, 0xFF, sizeof(int32_t) * (size_t)B * H * W, s);      // -1
+    if (e != hipSuccess) return msau_set_error(MSAU_ERR_HIP, "raster_owner_ext: memset: %s", hipGetErrorString(e));
+    if (n == 0) return 0;
+    hipLaunchKernelGGL(raster_owner_ext_kernel, dim3(n < 4096 ? n : 4096), dim3(64), 0, s, boxes, n, owner, B, H, W, extent);
+    MSAU_CHECK_LAUNCH("raster_owner_ext");
     return 0;
 }
 

@@ -4,7 +4,9 @@ The reference trains with batch 1 and one H x W per document (train_chargrid_fun
 data_generator_funsd_bert.py:216-222).  `pack` places B documents at the origin of one zero canvas and returns their sizes;
 `MSAUWrapper.forward(x, sizes)` / `TrainEngine.step(x, labels, sizes)` then compute, for every document, what it would compute
 alone ("Ragged batches").  `unpack` crops the canvas outputs back, `batches` groups documents of similar size, `pack_ids` packs character-id masks for
-`MSAUWrapper.predict_nhwc(ids=..., sizes=...)`, `pack_masks` the line-id / character-position masks of the region stage.
+`MSAUWrapper.predict_nhwc(ids=..., sizes=...)`, `pack_masks` the line-id / character-position masks of the region stage,
+`pack_boxes` the box lists (and feature tables) of `msau_amd.data.raster` for `TrainEngine.step_boxes(..., sizes=)`: no canvas is built
+on the host at all.
 
     for idx in batches(docs, 16):
         x, labels, sizes = pack([docs[i] for i in idx])
@@ -67,6 +69,62 @@ def pack_ids(masks: Sequence, round_to: int = 16) -> Tuple[torch.Tensor, torch.T
     for b, t in enumerate(ts):
         ids[b, :t.shape[0], :t.shape[1]] = t.to(torch.int32)
     return ids, sizes
+
+
+def pack_boxes(docs: Sequence, round_to: int = 16):
+    """`docs`: per document `(feat_boxes [n, 6], label_boxes [m, 6], h, w)` or `(feat_boxes, label_boxes, h, w, feats [n_vec, C])`, as
+    `raster.document_boxes` / `raster.document_line_boxes` return them (plus the document's feature table); every document in its
+    own coordinates.
+    -> (grid_boxes int32 [sum n, 6], label_boxes int32 [sum m, 6], feats fp32 [sum n_vec, C] or None, sizes int64 CPU [B, 2] of
+    (h, w), (H, W)): the lists concatenated in document order with the sample column rewritten to the document's place in the batch,
+    with feature tables the value column (= row of the table) offset by the rows of the documents before and the tables stacked; the
+    canvas rounded as in `pack`.  Boxes are NOT clipped here: `TrainEngine.step_boxes(grid_boxes, label_boxes, B, H, W, feats=feats,
+    sizes=sizes)` clips every box to its own document on the device, as the reference's painter does on the document's own array."""
+    if len(docs) == 0:
+        raise ValueError("pack_boxes: no documents")
+    if round_to < 1:
+        raise ValueError(f"pack_boxes: round_to must be >= 1, got {round_to}")
+    with_feats = [len(d) >= 5 and d[4] is not None for d in docs]
+    if any(with_feats) and not all(with_feats):
+        raise ValueError("pack_boxes: either every document brings a feature table or none does")
+    gbs, lbs, tabs, sizes = [], [], [], []
+    base, C = 0, None
+    for b, d in enumerate(docs):
+        if len(d) not in (4, 5):
+            raise ValueError(f"pack_boxes: document {b} must be (feat_boxes, label_boxes, h, w[, feats]), got {len(d)} items")
+        h, w = int(d[2]), int(d[3])
+        if h < 1 or w < 1:
+            raise ValueError(f"pack_boxes: document {b} has size ({h}, {w})")
+        lists = []
+        for nm, bx in (("feature", d[0]), ("label", d[1])):
+            a = np.asarray(bx)
+            if a.size and (a.dtype.kind not in "iu" or a.ndim != 2 or a.shape[1] != 6):
+                raise ValueError(f"pack_boxes: the {nm} boxes of document {b} must be an integer [n, 6] array, got {a.dtype} {a.shape}")
+            a = a.astype(np.int32).reshape(-1, 6).copy()
+            a[:, 0] = b
+            lists.append(a)
+        gb, lb = lists
+        if with_feats[b]:
+            t = np.ascontiguousarray(np.asarray(d[4]), dtype=np.float32)
+            if t.ndim != 2:
+                raise ValueError(f"pack_boxes: the feature table of document {b} must be [n_vec, C], got {t.shape}")
+            if C is None:
+                C = int(t.shape[1])
+            elif int(t.shape[1]) != C:
+                raise ValueError(f"pack_boxes: document {b} has {int(t.shape[1])} channels, document 0 has {C}")
+            if len(gb) and int(gb[:, 5].max()) >= len(t):
+                raise ValueError(f"pack_boxes: a box of document {b} names feature row {int(gb[:, 5].max())}, its table has {len(t)}")
+            gb[:, 5] = np.where(gb[:, 5] >= 0, gb[:, 5] + base, gb[:, 5])
+            base += len(t)
+            tabs.append(t)
+        gbs.append(gb)
+        lbs.append(lb)
+        sizes.append((h, w))
+    sizes = torch.tensor(sizes, dtype=torch.int64)
+    H = -(-int(sizes[:, 0].max()) // round_to) * round_to
+    W = -(-int(sizes[:, 1].max()) // round_to) * round_to
+    feats = np.concatenate(tabs, axis=0) if tabs else None
+    return np.concatenate(gbs, axis=0), np.concatenate(lbs, axis=0), feats, sizes, (H, W)
 
 
 def pack_masks(masks: Sequence, round_to: int = 16) -> Tuple[torch.Tensor, torch.Tensor]:

@@ -42,27 +42,53 @@ def _dev_boxes(boxes, dev):
     return (torch.from_numpy(arr).to(dev) if len(arr) else None), len(arr)
 
 
+def _dev_extent(sizes, B: int, H: int, W: int, dev):
+    """`sizes` of a ragged batch -> the device int32 [B][2] of (h, w) the painters clip to, or None for a dense batch.  A CPU integer
+    [B, 2] (or a nested list) is checked against the canvas on the host and uploaded; a tensor that is already on the device (level 0
+    of a ragged plan's extents) is taken as it is."""
+    if sizes is None:
+        return None
+    if isinstance(sizes, torch.Tensor) and sizes.device.type != "cpu":
+        if sizes.dtype != torch.int32 or tuple(sizes.shape) != (B, 2) or not sizes.is_contiguous() or sizes.device != dev:
+            raise ValueError(f"resident sizes must be a contiguous int32 [{B}, 2] tensor on {dev}, got {sizes.dtype} "
+                             f"{tuple(sizes.shape)} on {sizes.device}")
+        return sizes
+    from ..plan import Plan
+    return Plan.check_sizes(sizes, B, H, W).to(torch.int32).contiguous().to(dev)
+
+
+def _owner(s, bt, n, owner, B, H, W, ext):
+    """the owner map of one box list: clipped to the canvas (dense batch) or to every box's own document (ragged: `ext`)"""
+    if ext is None:
+        L.call("msau_raster_owner", s, bt.data_ptr() if n else None, n, owner.data_ptr(), B, H, W)
+    else:
+        L.call("msau_raster_owner_ext", s, bt.data_ptr() if n else None, n, owner.data_ptr(), B, H, W, ext.data_ptr())
+
+
 def rasterize(char_boxes, label_boxes, B: int, H: int, W: int, C: int,
-              dtype: str = "bf16", device="cuda", out: torch.Tensor = None) -> Tuple[torch.Tensor, torch.Tensor]:
+              dtype: str = "bf16", device="cuda", out: torch.Tensor = None, sizes=None) -> Tuple[torch.Tensor, torch.Tensor]:
     """-> (grid [B,H,W,Cs] one-hot in `dtype` storage, labels int64 [B,H,W]) on `device`.  `out`: paint the grid into this
     buffer (a plan's own input buffer: TrainEngine.input_nhwc) instead of a new tensor.  Box lists may be numpy arrays
-    (uploaded here) or int32 device tensors (nothing crosses PCIe, no host synchronisation)."""
+    (uploaded here) or int32 device tensors (nothing crosses PCIe, no host synchronisation).
+    `sizes` (ragged batch): CPU integer [B, 2] of every document's (h, w) at the origin of the H x W canvas, or the int32 [B, 2]
+    tensor already on the device; every box is then clipped to its own document and grid and labels are 0 outside the documents."""
     dt = L.BF16 if dtype in ("bf16", "bfloat16") else L.F32
     Cs = -(-C // 8) * 8
     dev = torch.device(device)
     if dev.index is None and dev.type == "cuda":
         dev = torch.device("cuda", torch.cuda.current_device())
     s = torch.cuda.current_stream(dev).cuda_stream
+    ext = _dev_extent(sizes, B, H, W, dev)
     owner = torch.empty((B, H, W), dtype=torch.int32, device=dev)
     tdt = torch.bfloat16 if dt == L.BF16 else torch.float32
     grid = out if out is not None else torch.empty((B, H, W, Cs), dtype=tdt, device=dev)
     assert tuple(grid.shape) == (B, H, W, Cs) and grid.dtype == tdt and grid.is_contiguous(), (grid.shape, grid.dtype)
     labels = torch.empty((B, H, W), dtype=torch.int64, device=dev)
-    keep = []
+    keep = [ext]
     for boxes, kind in ((char_boxes, "grid"), (label_boxes, "labels")):
         bt, n = _dev_boxes(boxes, dev)
         keep.append(bt)
-        L.call("msau_raster_owner", s, bt.data_ptr() if n else None, n, owner.data_ptr(), B, H, W)
+        _owner(s, bt, n, owner, B, H, W, ext)
         if kind == "grid":
             L.call("msau_raster_onehot", s, dt, bt.data_ptr() if n else None, owner.data_ptr(), grid.data_ptr(), B, H, W, C, Cs)
         else:
@@ -75,10 +101,11 @@ def rasterize(char_boxes, label_boxes, B: int, H: int, W: int, C: int,
     return grid, labels
 
 
-def owner_maps(feat_boxes, label_boxes, B: int, H: int, W: int, device="cuda"):
+def owner_maps(feat_boxes, label_boxes, B: int, H: int, W: int, device="cuda", sizes=None):
     """-> (owner int32 [B,H,W]: index of the feature box that owns each pixel, -1 = none; the feature boxes as a device
     tensor [n,6] (or None) and n; labels int64 [B,H,W]).  What the dense painters start from -- and all that the net's first
-    conv needs when it is fed with box lists (MSAU_CONV_OWNER, csrc/ownerconv.hip): the grid itself is never painted."""
+    conv needs when it is fed with box lists (MSAU_CONV_OWNER, csrc/ownerconv.hip): the grid itself is never painted.
+    `sizes` (ragged batch, as `rasterize`): owner is -1 and labels are 0 everywhere outside the documents."""
     dev = torch.device(device)
     if dev.index is None and dev.type == "cuda":
         dev = torch.device("cuda", torch.cuda.current_device())
@@ -88,10 +115,11 @@ def owner_maps(feat_boxes, label_boxes, B: int, H: int, W: int, device="cuda"):
     labels = torch.empty((B, H, W), dtype=torch.int64, device=dev)
     fb, nf = _dev_boxes(feat_boxes, dev)
     lb, nl = _dev_boxes(label_boxes, dev)
-    L.call("msau_raster_owner", s, fb.data_ptr() if nf else None, nf, owner.data_ptr(), B, H, W)
-    L.call("msau_raster_owner", s, lb.data_ptr() if nl else None, nl, lown.data_ptr(), B, H, W)
+    ext = _dev_extent(sizes, B, H, W, dev)
+    _owner(s, fb, nf, owner, B, H, W, ext)
+    _owner(s, lb, nl, lown, B, H, W, ext)
     L.call("msau_raster_labels", s, lb.data_ptr() if nl else None, lown.data_ptr(), labels.data_ptr(), B, H, W)
-    for t in (fb, lb, lown):
+    for t in (fb, lb, lown, ext):
         if t is not None:
             t.record_stream(torch.cuda.current_stream(dev))
     return owner, fb, nf, labels
@@ -107,10 +135,10 @@ def document_line_boxes(doc: dict, sample: int = 0, feat_base: int = 0):
 
 
 def rasterize_dense(feat_boxes, label_boxes, feats, B: int, H: int, W: int,
-                    dtype: str = "bf16", device="cuda", out: torch.Tensor = None) -> Tuple[torch.Tensor, torch.Tensor]:
+                    dtype: str = "bf16", device="cuda", out: torch.Tensor = None, sizes=None) -> Tuple[torch.Tensor, torch.Tensor]:
     """-> (grid [B,H,W,Cs] with feats[value] painted over each box in `dtype` storage, labels int64 [B,H,W]); only the
     box list and the [n_lines, C] feature table cross PCIe (at 768 channels the dense fp32 grid is 264 MB per tile).  `out`,
-    device-tensor arguments: as `rasterize`."""
+    device-tensor arguments, `sizes`: as `rasterize`."""
     dt = L.BF16 if dtype in ("bf16", "bfloat16") else L.F32
     dev = torch.device(device)
     if dev.index is None and dev.type == "cuda":
@@ -123,16 +151,17 @@ def rasterize_dense(feat_boxes, label_boxes, feats, B: int, H: int, W: int,
     C = int(ft.shape[1])
     Cs = -(-C // 8) * 8
     s = torch.cuda.current_stream(dev).cuda_stream
+    ext = _dev_extent(sizes, B, H, W, dev)
     owner = torch.empty((B, H, W), dtype=torch.int32, device=dev)
     tdt = torch.bfloat16 if dt == L.BF16 else torch.float32
     grid = out if out is not None else torch.empty((B, H, W, Cs), dtype=tdt, device=dev)
     assert tuple(grid.shape) == (B, H, W, Cs) and grid.dtype == tdt and grid.is_contiguous(), (grid.shape, grid.dtype)
     labels = torch.empty((B, H, W), dtype=torch.int64, device=dev)
-    keep = [ft]
+    keep = [ft, ext]
     for boxes, kind in ((feat_boxes, "grid"), (label_boxes, "labels")):
         bt, n = _dev_boxes(boxes, dev)
         keep.append(bt)
-        L.call("msau_raster_owner", s, bt.data_ptr() if n else None, n, owner.data_ptr(), B, H, W)
+        _owner(s, bt, n, owner, B, H, W, ext)
         if kind == "grid":
             L.call("msau_raster_dense", s, dt, bt.data_ptr() if n else None, owner.data_ptr(), ft.data_ptr(), grid.data_ptr(), B, H, W, C, Cs)
         else:

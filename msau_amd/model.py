@@ -385,6 +385,10 @@ class MSAUWrapper(nn.Module):
         B, _, H, W = x.shape
         return Plan.check_sizes(sizes, B, H, W)
 
+    def _check_sizes_for(self, sizes, B: int, H: int, W: int) -> torch.Tensor:
+        """`_check_sizes` for the entry points that have a canvas shape and no input tensor (box lists, id masks)"""
+        return self._check_sizes(torch.empty((B, 0, H, W)), sizes)
+
     @torch.no_grad()
     def predict_nhwc(self, inp: Optional[torch.Tensor] = None, ids: Optional[torch.Tensor] = None, graph: bool = False,
                      sizes=None):
@@ -509,6 +513,54 @@ class MSAUWrapper(nn.Module):
         if sizes is not None:
             plan.set_extents(sizes)
         plan.forward(self._flat, x, export=False)
+        lg = plan.logits
+        L.call("msau_eval_confusion", torch.cuda.current_stream().cuda_stream, plan.dtype, lg.data.data_ptr(), lab.data_ptr(),
+               out.data_ptr(), B, H, W, lg.C, lg.Cs, -1 if zero_as is None else int(zero_as),
+               plan.extent_ptr(lg) if sizes is not None else None)
+        return out
+
+    @torch.no_grad()
+    def confusion_matrix_boxes(self, grid_boxes, label_boxes, B: int, H: int, W: int, feats=None, sizes=None,
+                               zero_as: Optional[int] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """`confusion_matrix` without a dense grid: the batch comes as BOX LISTS (and, for the embedding grid, a feature table), as
+        `TrainEngine.step_boxes` takes them -- int32 [n][6] = sample, y0, y1, x0, x1, value; numpy arrays or device tensors.  The label
+        mask is painted on the device; with `feats` and a box-list instance of the first conv (MSAU_CONV_OWNER) the grid is never
+        painted, otherwise it is painted into the forward-only plan's input buffer.  `sizes` (ragged batch): the CPU integer [B, 2]
+        of `forward`, every document's boxes in its own coordinates (msau_amd.data.ragged.pack_boxes).  Counts, `zero_as` and `out`
+        as in `confusion_matrix`: rows = painted labels in [1, n_class), columns = first maximum of the logits."""
+        from .data import raster
+        C = self.n_class
+        if C > 64:
+            raise ValueError(f"confusion_matrix counts at most 64 classes, the model has {C}")
+        if zero_as is not None and not (0 <= int(zero_as) < C):
+            raise ValueError(f"zero_as must be a class in [0, {C}), got {zero_as}")
+        if sizes is not None:
+            sizes = self._check_sizes_for(sizes, B, H, W)
+        dev = self._flat.device
+        if dev.type != "cuda":
+            raise RuntimeError("MSAUWrapper runs on an MI355X through libmsau_hip.so; the model must be on the GPU "
+                               "(there is no CPU fallback)")
+        if out is None:
+            out = torch.zeros((C, C), dtype=torch.int64, device=dev)
+        elif out.dtype != torch.int64 or tuple(out.shape) != (C, C) or out.device != dev or not out.is_contiguous():
+            raise ValueError(f"out must be a contiguous int64 [{C}, {C}] tensor on {dev}")
+        plan = self._plan_for_shape(B, H, W, dev, False, ragged=sizes is not None)
+        ext = None
+        if sizes is not None:
+            plan.set_extents(sizes)
+            ext = plan.extents[0]                        # the painters clip to the plan's own level-0 extents
+        if feats is not None and plan._feed_owner(None):
+            ft = feats if isinstance(feats, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(feats, dtype=np.float32)).to(dev)
+            owner, fb, nf, lab = raster.owner_maps(grid_boxes, label_boxes, B, H, W, dev, sizes=ext)
+            plan.forward(self._flat, None, export=False, owner=(owner, fb, nf, ft))
+            plan._feed_owner(None)                       # (Plan.predict of the same plan expects the tensor-fed first conv)
+        else:
+            buf = plan.input_nhwc
+            if feats is None:
+                _, lab = raster.rasterize(grid_boxes, label_boxes, B, H, W, self.channels, self.dtype_name, dev, out=buf, sizes=ext)
+            else:
+                _, lab = raster.rasterize_dense(grid_boxes, label_boxes, feats, B, H, W, self.dtype_name, dev, out=buf, sizes=ext)
+            plan.forward(self._flat, None, export=False, nhwc_ready=True, nhwc_clean=True)
         lg = plan.logits
         L.call("msau_eval_confusion", torch.cuda.current_stream().cuda_stream, plan.dtype, lg.data.data_ptr(), lab.data_ptr(),
                out.data_ptr(), B, H, W, lg.C, lg.Cs, -1 if zero_as is None else int(zero_as),
@@ -664,8 +716,9 @@ class TrainEngine:
         weakref.finalize(self, L.load().msau_comm_destroy, self._comm)
 
     # -- pieces (each is a fixed launch sequence on the current stream) --
-    def _fwd_bwd(self, plan: Plan, x, labels, ids=None, nhwc_ready=False, owner=None):
-        plan.forward(self.model._flat, x, export=False, ids=ids, nhwc_ready=nhwc_ready, owner=owner, single_stream=self.use_graph)
+    def _fwd_bwd(self, plan: Plan, x, labels, ids=None, nhwc_ready=False, owner=None, nhwc_clean=False):
+        plan.forward(self.model._flat, x, export=False, ids=ids, nhwc_ready=nhwc_ready, owner=owner, single_stream=self.use_graph,
+                     nhwc_clean=nhwc_clean)
         loss = plan.loss_grads(labels)
         # MSAU_DP_BUCKETS=1: ONE all-reduce of the whole flat gradient after the backward instead of a bucket per stage
         # issued while the earlier stages' backward still runs (fewer launches and joins, no overlap)
@@ -761,18 +814,26 @@ class TrainEngine:
         cur.wait_stream(gs)
         return loss
 
-    def step_ids(self, ids: torch.Tensor, labels: torch.Tensor) -> torch.Tensor:
+    def step_ids(self, ids: torch.Tensor, labels: torch.Tensor, sizes=None) -> torch.Tensor:
         """One optimisation step fed with the character-id mask int32 [B,H,W] (-1 or any id outside [0, channels) = empty
         pixel) instead of the dense one-hot float tensor: what `to_categorical` / the chargrid painter would have produced
         is painted straight into the NHWC input on the device -- 4 B per pixel cross the boundary instead
         of 4*C, and the 352 MB NCHW -> NHWC conversion of cfg 2 disappears.  Same kernels after that: bit-identical to
-        `step(one_hot(ids), labels)`.  Eager only."""
+        `step(one_hot(ids), labels)`.  Eager only.
+        `sizes` (ragged batch, msau_amd.data.ragged.pack_ids): CPU integer [B, 2] of every document's (h, w) at the origin of the
+        canvas; ids and labels outside the documents are ignored, loss and gradient are those of `step(one_hot(ids), labels, sizes)`."""
         if self.use_graph:
             raise RuntimeError("step_ids is an eager path (use_graph=False)")
+        if ids.dim() != 3:
+            raise ValueError("ids must be [B,H,W]")
         ids = ids.to(dtype=torch.int32).contiguous()
         B, H, W = ids.shape
+        if sizes is not None:
+            sizes = self.model._check_sizes_for(sizes, B, H, W)
         labels = labels.reshape(B, H, W).contiguous().long()
-        plan = self.model._plan_for_shape(B, H, W, ids.device, True)
+        plan = self.model._plan_for_shape(B, H, W, ids.device, True, ragged=sizes is not None)
+        if sizes is not None:
+            plan.set_extents(sizes)
         loss = self._fwd_bwd(plan, None, labels, ids=ids)
         self._allreduce()
         self._optim()
@@ -803,12 +864,21 @@ class TrainEngine:
         self._optim()
         return loss
 
-    def step_boxes(self, grid_boxes, label_boxes, B: int, H: int, W: int, feats=None) -> torch.Tensor:
+    def step_boxes(self, grid_boxes, label_boxes, B: int, H: int, W: int, feats=None, sizes=None) -> torch.Tensor:
         """One optimisation step from BOX LISTS (int32 [n][6] = sample, y0, y1, x0, x1, value; msau_amd/data/raster.py): the
         one-hot grid (feats None: value = character id) or the dense embedding grid (feats fp32 [n_vectors][channels]: value
         = row of feats) and the label mask are painted on the device, the grid straight into the plan's input buffer.
-        Only the lists (KBs) and the feature table cross PCIe.  Arguments may be numpy arrays or device tensors."""
+        Only the lists (KBs) and the feature table cross PCIe.  Arguments may be numpy arrays or device tensors.
+        `sizes` (ragged batch, msau_amd.data.ragged.pack_boxes): CPU integer [B, 2] of every document's (h, w) at the origin of the
+        H x W canvas, every document's boxes in its own coordinates.  Each box is clipped at its own document's edge, the loss is
+        the mean of the documents' losses as `step(x, labels, sizes)` defines it, and with `feats` the grid is still never
+        painted (the box-list instance of the first conv implements the extents).  Eager only."""
         from .data import raster
+        if sizes is not None:
+            if self.use_graph:
+                raise RuntimeError("step_boxes: a ragged batch (sizes=...) is an eager path (use_graph=False); there is no "
+                                   "captured-graph form of it")
+            return self._step_boxes_ragged(grid_boxes, label_boxes, B, H, W, feats, self.model._check_sizes_for(sizes, B, H, W))
         plan = self.model._plan_for_shape(B, H, W, self.model._flat.device, True)
         if feats is not None and not self.use_graph and plan._feed_owner(None):
             # the embedding grid is piecewise constant: the first conv and its weight gradient work from the per-pixel box index
@@ -827,12 +897,39 @@ class TrainEngine:
             _, labels = raster.rasterize_dense(grid_boxes, label_boxes, feats, B, H, W, self.model.dtype_name, buf.device, out=buf)
         return self.step_nhwc(buf, labels)
 
-    def prefetch_boxes(self, grid_boxes, label_boxes, B: int, H: int, W: int, feats=None):
+    def _step_boxes_ragged(self, grid_boxes, label_boxes, B: int, H: int, W: int, feats, sizes) -> torch.Tensor:
+        """`step_boxes` on a ragged plan: the painters clip to the plan's own level-0 extents, so owner map, grid and labels are
+        empty / zero outside the documents -- the plan's invariant holds as they enter, nothing has to be zeroed afterwards"""
+        from .data import raster
+        dev = self.model._flat.device
+        plan = self.model._plan_for_shape(B, H, W, dev, True, ragged=True)
+        plan.set_extents(sizes)
+        ext = plan.extents[0]
+        if feats is not None and plan._feed_owner(None):
+            ft = feats if isinstance(feats, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(feats, dtype=np.float32)).to(dev)
+            owner, fb, nf, labels = raster.owner_maps(grid_boxes, label_boxes, B, H, W, dev, sizes=ext)
+            loss = self._fwd_bwd(plan, None, labels, owner=(owner, fb, nf, ft))
+        else:
+            buf = plan.input_nhwc
+            if feats is None:
+                _, labels = raster.rasterize(grid_boxes, label_boxes, B, H, W, self.model.channels, self.model.dtype_name, dev, out=buf,
+                                             sizes=ext)
+            else:
+                _, labels = raster.rasterize_dense(grid_boxes, label_boxes, feats, B, H, W, self.model.dtype_name, dev, out=buf, sizes=ext)
+            loss = self._fwd_bwd(plan, None, labels, nhwc_ready=True, nhwc_clean=True)
+        self._allreduce()
+        self._optim()
+        return loss
+
+    def prefetch_boxes(self, grid_boxes, label_boxes, B: int, H: int, W: int, feats=None, sizes=None):
         """Paint the NEXT batch (arguments as `step_boxes`) while the current step runs: the grid goes into the input buffer the
         current step does not read (the plan keeps two), on the plan's side stream -- idle during the forward sweep, which is
         when the painter's store (2.1 GB per batch at 768 channels) is absorbed.  `step_prefetched()` then trains on it.  The
         data-loader counterpart of the reference's generator thread (data_generator_funsd_bert.py:216-240)."""
         from .data import raster
+        if sizes is not None:
+            raise NotImplementedError("prefetch_boxes paints dense batches only: a ragged batch (sizes=...) goes through "
+                                      "step_boxes(..., sizes=sizes)")
         if self.use_graph:
             raise RuntimeError("prefetch_boxes is an eager path (use_graph=False)")
         plan = self.model._plan_for_shape(B, H, W, self.model._flat.device, True)

@@ -1606,16 +1606,23 @@ class Plan:
     def _feed_owner(self, src, flat_params: Optional[torch.Tensor] = None) -> bool:
         """Switch the net's first conv (and its weight gradient) between the painted input tensor and BOX LISTS
         (MSAU_CONV_OWNER, csrc/ownerconv.hip): `src` = (owner int32 [B,H,W], boxes int32 [n,6] device tensor or None, n, feats
-        fp32 [n_vec, C] device tensor) or None.  Returns False when no instance takes the conv (paint the tensor instead)."""
+        fp32 [n_vec, C] device tensor) or None.  Returns False when no instance takes the conv (paint the tensor instead).
+        Ragged plan: `owner` must be -1 outside every sample's extent (msau_raster_owner_ext with this plan's level-0 extents)."""
         self._feed_nchw(None)
         if not hasattr(self, "_owner_conv"):
             c = next((op for op in self.ops if isinstance(op, ConvOp) and op.x1 is self.x_in and op.x2 is None), None)
+            # (a ragged plan's conv carries MSAU_CONV_EXTENT: the box-list instance implements it -- info[7] & 128 with both flags set)
             ok = c is not None and os.environ.get("MSAU_OWNER_CONV", "1") != "0" and not (c.pair is not None and c.pair.active) \
-                and not (c.fdesc.flags & ~L.CONV_RELU_OUT)
+                and not (c.fdesc.flags & ~(L.CONV_RELU_OUT | L.CONV_EXTENT))
             if ok:
                 info = (L.i32 * 8)()
                 L.call("msau_conv2d_launch_info", self.dtype, C.byref(c.fdesc), info)
                 ok = bool(info[7] & 32)
+                if ok and self.ragged:
+                    probe = L.ConvDesc.from_buffer_copy(c.fdesc)
+                    probe.flags |= L.CONV_OWNER
+                    L.call("msau_conv2d_launch_info", self.dtype, C.byref(probe), info)
+                    ok = bool(info[7] & 128)
             if ok and self.training and c.wdesc is not None:
                 ok = c.wdesc.flags == 0 and c.uentry is not None and c.kind == "conv"
             self._owner_conv = c if ok else None
@@ -1629,7 +1636,7 @@ class Plan:
                 c.fdesc.flags &= ~L.CONV_OWNER
                 c.fdesc.x1 = _ptr(self.x_in.data)
                 if c.wdesc is not None:
-                    c.wdesc.flags &= ~L.CONV_OWNER
+                    c.wdesc.flags &= ~(L.CONV_OWNER | L.CONV_EXTENT)
                     c.wdesc.x1 = _ptr(self.x_in.data)
                     self._set_unpack_slabs(c, c.wdesc.nslabs)
                 self._owner_keep = None
@@ -1652,7 +1659,8 @@ class Plan:
         c.fdesc.flags |= L.CONV_OWNER
         c.fdesc.x1 = C.addressof(ctx)
         if c.wdesc is not None:
-            c.wdesc.flags |= L.CONV_OWNER
+            # (ragged: the weight gradient needs no extents of its own -- the gradient it sums is 0 outside them, the owner map -1)
+            c.wdesc.flags |= L.CONV_OWNER | self.extent_flag
             c.wdesc.x1 = C.addressof(ctx)
             self._set_unpack_slabs(c, int(L.load().msau_owner_slabs(C.byref(c.wdesc))))     # the slabs the box-list weight gradient writes
         self._owner_keep = (ctx, owner, boxes, feats, wt, table, sums, csum, flat_params)  # read again by the backward
@@ -1732,12 +1740,13 @@ class Plan:
         return self.x_in.data
 
     def forward(self, flat_params: torch.Tensor, x_nchw: Optional[torch.Tensor], export: bool = True,
-                ids: Optional[torch.Tensor] = None, nhwc_ready: bool = False, owner=None, single_stream: bool = False):
+                ids: Optional[torch.Tensor] = None, nhwc_ready: bool = False, owner=None, single_stream: bool = False,
+                nhwc_clean: bool = False):
         """`ids` (int32 [B,H,W] character ids, -1 = empty) instead of `x_nchw`: the one-hot grid is painted on the device.
-        `nhwc_ready`: the input buffer (`input_nhwc`) already holds the grid -- no boundary conversion at all."""
+        `nhwc_ready`: the input buffer (`input_nhwc`) already holds the grid -- no boundary conversion at all.  On a ragged plan the
+        buffer is zeroed outside the extents first, unless `nhwc_clean` says that its producer already left zeros there (the
+        painters of msau_amd.data.raster with this plan's extents do)."""
         s = self._stream()
-        assert not self.ragged or (owner is None and not nhwc_ready), \
-            "a ragged plan takes the NCHW input tensor or an id mask (nhwc_ready / box lists are dense-only paths)"
         self.pack(flat_params)
         if owner is not None:
             # box lists instead of a painted input (`owner` as Plan._feed_owner takes it); the caller checked that an instance exists
@@ -1751,6 +1760,9 @@ class Plan:
         elif nhwc_ready:
             assert x_nchw is None and ids is None
             self._feed_ids(None)
+            if self.ragged and not nhwc_clean:
+                a = self.x_in
+                self._zero_outside(a.data, a.data, 1, self.H, self.W, a.data.element_size() * a.Cs)
         elif ids is not None:
             assert ids.dtype == torch.int32 and ids.is_contiguous() and tuple(ids.shape) == (self.B, self.H, self.W), (ids.shape, ids.dtype)
             if not self._feed_ids(ids):

@@ -18,7 +18,16 @@ document's plan cached; reports, as one JSON object:
                            MSAUWrapper.confusion_matrix on ragged batches of B (counts on the device, one host read) --
                            docs/s of each and launches per forward
 
+  ragged_boxes             with --ragged B --boxes: documents made of text-line boxes with a feature row each (the BERT grid of
+                           data_generator_funsd_bert.py:64-93), in ragged batches of B, three ways, interleaved, --repeats times:
+                           "dense"       pack() on the host, upload of the fp32 NCHW canvas, TrainEngine.step(x, labels, sizes)
+                           "boxes"       pack_boxes(), upload of the lists and the table, step_boxes(..., feats=, sizes=sizes)
+                           "boxes_dense" the same lists through the DENSE step_boxes on the same canvas (no sizes): what the
+                                         extent flag costs on the generic kernels
+                           ms per step and bytes uploaded per step of each arm, every repeat; only this comparison runs
+
     python tools/funsd_loop.py [--docs 120] [--epochs 3] [--channels 64] [--dtype bf16] [--graph] [--ragged 16] [--eval 16]
+    python tools/funsd_loop.py --ragged 16 --boxes --channels 768 --dtype bf16 [--repeats 5]
 """
 import argparse
 import json
@@ -152,6 +161,87 @@ def run_ragged(args, B, use_graph=False):
     return res
 
 
+def make_box_docs(args):
+    """the synthetic documents as box lists (CPU): (feature boxes, label boxes, h, w, feats [n, C]) with one text-line-like box per
+    ~150 pixels, some overlapping, some over the document's edge"""
+    import numpy as np
+    rng = np.random.default_rng(1)
+    docs = []
+    for (h, w) in doc_shapes(args.docs):
+        n = max(4, h * w // 150)
+        fb, lb = [], []
+        for i in range(n):
+            y0, x0 = int(rng.integers(0, h)), int(rng.integers(-2, w - 4))
+            y1, x1 = y0 + int(rng.integers(1, 4)), x0 + int(rng.integers(6, 40))
+            fb.append((0, y0, y1, x0, x1, i))
+            lb.append((0, y0, y1, x0, x1, int(rng.integers(1, 5))))
+        docs.append((np.asarray(fb, np.int32), np.asarray(lb, np.int32), h, w, rng.standard_normal((n, args.channels)).astype(np.float32)))
+    return docs
+
+
+def paint_host(doc):
+    """one document painted on the host as the reference's loader does (numpy slicing on its own array) -> the FUNSD loader's item"""
+    import numpy as np
+    import torch
+    fb, lb, h, w, feats = doc
+    grid, lab = np.zeros((feats.shape[1], h, w), np.float32), np.zeros((h, w), np.int64)
+    for (_, y0, y1, x0, x1, v), (_, _, _, _, _, lv) in zip(fb.tolist(), lb.tolist()):
+        grid[:, max(y0, 0):max(y1, 0), max(x0, 0):max(x1, 0)] = feats[v][:, None, None]
+        lab[max(y0, 0):max(y1, 0), max(x0, 0):max(x1, 0)] = lv
+    return {"mask": torch.from_numpy(grid)[None], "label": torch.from_numpy(lab)[None]}
+
+
+def run_ragged_boxes(args, B):
+    """ragged batches of the same box documents: host-painted canvas + step(x, labels, sizes) against step_boxes(..., sizes=)"""
+    import torch
+    from msau_amd import TrainEngine
+    from msau_amd.data.ragged import batches, pack, pack_boxes
+    dev = torch.device("cuda", 0)
+    bdocs = make_box_docs(args)
+    ddocs = [paint_host(d) for d in bdocs]
+    groups = list(batches(ddocs, B, round_to=16))
+    arms = ("dense", "boxes", "boxes_dense")
+    models = {a: make_model(args) for a in arms}                   # an engine of its own per arm: same seed, same documents
+    engs = {a: TrainEngine(models[a], lr=1e-4) for a in arms}
+    for m in models.values():
+        m.max_cached_plans = 2 * len(groups) + 2
+    up = {a: 0 for a in arms}
+
+    def epoch(arm, count=False):
+        eng = engs[arm]
+        for idx in groups:
+            if arm == "dense":
+                x, lab, sizes = pack([ddocs[i] for i in idx], round_to=16)
+                if count:
+                    up[arm] += x.numel() * 4 + lab.numel() * 8
+                loss = eng.step(x.to(dev), lab.to(dev), sizes)
+            else:
+                gb, lb, feats, sizes, (H, W) = pack_boxes([bdocs[i] for i in idx], round_to=16)
+                if count:
+                    up[arm] += gb.nbytes + lb.nbytes + feats.nbytes
+                loss = eng.step_boxes(gb, lb, len(idx), H, W, feats=feats, sizes=sizes if arm == "boxes" else None)
+            if count and arm != "boxes_dense":
+                plan = models[arm]._plan_for_shape(len(idx), *((int(x.shape[2]), int(x.shape[3])) if arm == "dense" else (H, W)), dev, True, ragged=True)
+                up[arm] += plan.extents.numel() * 4
+        torch.cuda.synchronize()
+        return loss
+
+    for a in arms:                                                 # plans built, first launches done; the uploads counted once
+        loss = epoch(a, count=True)
+    res = {a: {"ms_per_step": [], "bytes_uploaded_per_step": up[a] // len(groups), "loss": round(float(loss), 4)} for a in arms}
+    for _ in range(max(args.repeats, 5)):
+        for a in arms:
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            epoch(a)
+            res[a]["ms_per_step"].append(round(1e3 * (time.perf_counter() - t0) / len(groups), 3))
+    plan = next(p for (b, h, w, tr, rg), p in models["boxes"]._plans.items() if rg)
+    res.update(batch=B, docs=len(bdocs), steps_per_epoch=len(groups), channels=args.channels, dtype=args.dtype,
+               box_fed_first_conv=getattr(plan, "_owner_keep", None) is not None,
+               boxes_faster_in_every_repeat=all(b < d for b, d in zip(res["boxes"]["ms_per_step"], res["dense"]["ms_per_step"])))
+    return res
+
+
 def run_eval(args, B):
     """evaluation of the documents: today's per-document loop against ragged confusion counts (same model, same documents)"""
     import numpy as np
@@ -224,7 +314,14 @@ def main():
     ap.add_argument("--ragged-only", action="store_true", help="skip the batch-1 loop (e.g. under rocprofv3)")
     ap.add_argument("--eval", type=int, default=0, help="also compare the per-document evaluation loop with ragged batches of this size")
     ap.add_argument("--eval-only", action="store_true", help="only the evaluation comparison (e.g. under rocprofv3)")
+    ap.add_argument("--boxes", action="store_true", help="with --ragged: ragged batches from box lists against the host-painted canvas (only this runs)")
+    ap.add_argument("--repeats", type=int, default=5, help="--boxes: interleaved repeats (at least 5)")
     args = ap.parse_args()
+    if args.boxes:
+        if not args.ragged:
+            ap.error("--boxes compares ragged batches: give --ragged B")
+        print(json.dumps({"ragged_boxes": run_ragged_boxes(args, args.ragged)}))
+        return
     if args.eval_only:
         print(json.dumps({"eval": run_eval(args, args.eval or 16)}))
         return
