@@ -779,6 +779,38 @@ int msau_kv_regions(void* stream, const uint8_t* argmax, const uint16_t* line_id
 int msau_kv_paint(void* stream, const int32_t* lines, const void* glyphs, const int32_t* line_off, const int32_t* glyph_off,
                   const int32_t* sizes, int B, int H, int W, int32_t* ids, uint16_t* line_ids, uint16_t* char_pos);
 
+/* ------------------------------------------------------------------------------------------
+ * Key-value training (data_generator/data_generator_text.py:160-250 without its warps, model/training/cost.py:35-65 `UNetLoss`).
+ *   msau_kv_paint_train : the painter of a training batch from the documents' training tables (msau_amd/training/kv_data.py): lines,
+ *                   glyphs, offsets and sizes as msau_kv_paint takes them, line_labels int32 [n][2] = (label, aux label) per line, sharing
+ *                   the lines' offsets.  ids int32 as msau_kv_paint writes them; labels / aux_labels int64 [B][H][W]: the record of
+ *                   the LAST line with text whose box holds the pixel (y1 <= y < y2, x1 <= x < x2; the glyph spans play no part), 0
+ *                   where there is none, -1 outside the document (ids -1 there too).  Every canvas pixel is written.
+ *   msau_label_hist : partial[(b * K + k) * C + c] int32 = the pixels with label c in part k of K of document b, counted inside the
+ *                   extent (h_b, w_b) (extent NULL: the whole H x W) among labels in [0, C); written, no atomics in global memory;
+ *                   the K rows of a document add up to its class histogram.  C <= 256, K <= 64.
+ *   msau_unet_ce  : UNetLoss and its gradient for B documents on one canvas, both heads in one launch, each head with its own
+ *                   labels.  For document b with extent (h_b, w_b) (NULL: (H, W)) and class weights cw (NULL: all ones):
+ *                     L_b(head) = sum_p cw[t_p] * nll_p / D_b(head),  D_b = sum_p cw[t_p]  over pixels inside the extent with t_p in [0, C)
+ *                     loss3[0] = (1/B) sum_b (0.5 L_b(final) + 0.5 L_b(aux))      (aux NULL: L_b(final) alone)
+ *                     loss3[1] = (1/B) sum_b L_b(final),  loss3[2] = (1/B) sum_b L_b(aux)   (aux NULL: 0)
+ *                     dlogits  = head_weight / (B * D_b) * cw[t_p] * (softmax - onehot),  head_weight 0.5 (aux NULL: 1)
+ *                   and 0 outside the extent, at labels outside [0, C) and in padded channels.  Without weights D_b is the extent's
+ *                   area; with weights it is sum_c cw[c] * hist[b][c], classes in index order, hist the K rows of msau_label_hist
+ *                   added up: hist_partial holds [B][K][C] of `labels`, then [B][K][C] of `aux_labels` when aux is given.  A
+ *                   document with D_b = 0 contributes nothing.  loss3 is written; the block partials in ws
+ *                   (>= msau_unet_ce_ws_floats(B*H*W) floats) are added in index order, so the three values are reproducible.
+ *                   B <= 1024, B*H*W < 2^31; Cs <= 32 keeps a pixel's logits in registers.
+ * ------------------------------------------------------------------------------------------ */
+int msau_kv_paint_train(void* stream, const int32_t* lines, const void* glyphs, const int32_t* line_labels, const int32_t* line_off,
+                        const int32_t* glyph_off, const int32_t* sizes, int B, int H, int W, int32_t* ids, int64_t* labels,
+                        int64_t* aux_labels);
+int msau_label_hist(void* stream, const int64_t* labels, const int32_t* extent, int32_t* partial, int B, int H, int W, int C, int K);
+int64_t msau_unet_ce_ws_floats(int64_t npix_total);
+int msau_unet_ce(void* stream, int dtype, const void* logits, const void* aux, const int64_t* labels, const int64_t* aux_labels,
+                 const int32_t* extent, const float* class_w, const int32_t* hist_partial, int K, void* dlogits, void* daux,
+                 float* loss3, float* ws, int B, int H, int W, int C, int Cs);
+
 #ifdef __cplusplus
 }
 #endif

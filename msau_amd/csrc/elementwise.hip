@@ -678,6 +678,193 @@ __global__ __launch_bounds__(256) void ordered_sum_kernel_t(const float* __restr
 }
 
 // =============================================================================================
+// UNetLoss for a (ragged) batch of documents (model/training/cost.py:35-65): plain CE over every pixel of a document, class 0
+// counted, 0.5 * final + 0.5 * auxiliary, optional class weights; every head has its own label map
+// =============================================================================================
+constexpr int kHistMaxC = 256;
+// Class histogram of the labelled pixels of a document: grid K x B, a document's pixels shared out over its K workgroups, one LDS
+// histogram per wavefront (LDS atomics only), partial[(b * K + k) * C + c] is WRITTEN.  The consumer adds the K rows: exact in any order.
+__global__ __launch_bounds__(256) void label_hist_kernel(const int64_t* __restrict__ labels, const int32_t* __restrict__ extent,
+                                                         int32_t* __restrict__ partial, int H, int W, int C, int K) {
+    __shared__ int hist[4][kHistMaxC];
+    const int b = blockIdx.y, k = blockIdx.x, wv = threadIdx.x >> 6;
+    for (int i = threadIdx.x; i < 4 * kHistMaxC; i += 256) (&hist[0][0])[i] = 0;
+    __syncthreads();
+    const int hw = H * W;                                            // B * H * W < 2^31 (checked by the host)
+    const int eh = extent ? min(max(extent[2 * b], 0), H) : H, ew = extent ? min(max(extent[2 * b + 1], 0), W) : W;
+    const int chunk = (hw + K - 1) / K;
+    const int lo = k * chunk, hi = min(lo + chunk, hw);
+    const int64_t* base = labels + (int64_t)b * hw;
+    for (int i = lo + (int)threadIdx.x; i < hi; i += 256) {
+        const int64_t lab = base[i];
+        if (lab >= 0 && lab < C && pos_in_extent(i, W, eh, ew)) atomicAdd(&hist[wv][(int)lab], 1);
+    }
+    __syncthreads();
+    for (int c = threadIdx.x; c < C; c += 256)
+        partial[((int64_t)b * K + k) * C + c] = (hist[0][c] + hist[1][c]) + (hist[2][c] + hist[3][c]);
+}
+
+// inv[t * B + b] = 1 / (B * D_b(head t)), 0 for a document without weight: D_b is the extent's area, or with class weights
+// sum_c cw[c] * hist_t[b][c], the classes added in index order (hist_t = hist + t * B * K * C, its K rows added first)
+__device__ __forceinline__ void unet_ce_denominators(float* inv, const int32_t* __restrict__ extent, const float* __restrict__ cw,
+                                                     const int32_t* __restrict__ hist, int NL, int B, int H, int W, int C, int K) {
+    for (int i = threadIdx.x; i < NL * B; i += blockDim.x) {
+        const int t = i / B, b = i - t * B;
+        float d;
+        if (cw) {
+            const int32_t* h = hist + ((int64_t)t * B + b) * K * C;
+            d = 0.f;
+            for (int c = 0; c < C; ++c) {
+                int n = 0;
+                for (int k = 0; k < K; ++k) n += h[k * C + c];
+                d += cw[c] * (float)n;
+            }
+        } else {
+            const int eh = extent ? min(max(extent[2 * b], 0), H) : H, ew = extent ? min(max(extent[2 * b + 1], 0), W) : W;
+            d = (float)eh * (float)ew;
+        }
+        inv[i] = d > 0.f ? 1.f / ((float)B * d) : 0.f;
+    }
+    __syncthreads();
+}
+
+// the block's two sums -> ws[blockIdx.x] (final), ws[gridDim.x + blockIdx.x] (auxiliary)
+__device__ __forceinline__ void unet_ce_block_sums(float l0, float l1, float* red, float* __restrict__ ws) {
+    for (int o = 32; o > 0; o >>= 1) { l0 += __shfl_down(l0, o, 64); l1 += __shfl_down(l1, o, 64); }
+    if ((threadIdx.x & 63) == 0) { red[threadIdx.x >> 6] = l0; red[kThreads / 64 + (threadIdx.x >> 6)] = l1; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        float s0 = 0.f, s1 = 0.f;
+        for (int i = 0; i < kThreads / 64; ++i) { s0 += red[i]; s1 += red[kThreads / 64 + i]; }
+        ws[blockIdx.x] = s0;
+        ws[gridDim.x + blockIdx.x] = s1;
+    }
+}
+
+// Both heads in one launch, the logits of a pixel in registers (Cs = 8 * CS8 <= 32: every index is a compile-time constant).
+// A thread's weight of head t at pixel p of document b: hw_t * cw[lab] / (B * D_b(t)) inside the extent with lab in [0, C), else 0;
+// the loss partials carry the weight WITHOUT hw_t (loss3[1], loss3[2] are the heads' own losses).
+template <typename T, int NL, int CS8>
+__global__ void unet_ce_kernel(const T* __restrict__ l0, const T* __restrict__ l1, const int64_t* __restrict__ lab0,
+                               const int64_t* __restrict__ lab1, const int32_t* __restrict__ extent, const float* __restrict__ cw,
+                               const int32_t* __restrict__ hist, int K, T* __restrict__ d0, T* __restrict__ d1,
+                               float* __restrict__ ws, int B, int H, int W, int C) {
+    constexpr int Cs = CS8 * 8;
+    __shared__ float red[2 * kThreads / 64];
+    __shared__ float inv[2 * kCeMaxB];
+    unet_ce_denominators(inv, extent, cw, hist, NL, B, H, W, C, K);
+    const float hwt = NL == 2 ? 0.5f : 1.f;
+    const int hw = H * W;
+    float local[2] = {0.f, 0.f};
+    const int64_t total = (int64_t)B * hw;
+    for (int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; p < total; p += (int64_t)gridDim.x * blockDim.x) {
+        const int b = (int)((unsigned)p / (unsigned)hw);               // total < 2^31 (checked by the host)
+        const int j = (int)p - b * hw;
+        const bool in = extent ? pos_in_extent(j, W, extent[2 * b], extent[2 * b + 1]) : true;
+#pragma unroll
+        for (int t = 0; t < NL; ++t) {
+            const T* lg = t ? l1 : l0;
+            T* dg = t ? d1 : d0;
+            const int64_t lab64 = (t ? lab1 : lab0)[p];
+            const bool on = in && lab64 >= 0 && lab64 < C;
+            const int lab = on ? (int)lab64 : -1;
+            const float w = on ? inv[t * B + b] * (cw ? cw[lab] : 1.f) : 0.f;
+            float x[Cs];
+            float mx = -INFINITY, xl = 0.f;
+#pragma unroll
+            for (int c0 = 0; c0 < Cs; c0 += 8) {
+                typename Vec8<T>::type v = load8<T>(lg + p * Cs + c0);
+#pragma unroll
+                for (int jj = 0; jj < 8; ++jj) {
+                    x[c0 + jj] = (float)v[jj];
+                    if (c0 + jj < C) mx = fmaxf(mx, x[c0 + jj]);
+                    xl = (c0 + jj == lab) ? x[c0 + jj] : xl;
+                }
+            }
+            float se = 0.f;
+#pragma unroll
+            for (int c = 0; c < Cs; ++c) se += c < C ? __expf(x[c] - mx) : 0.f;
+            const float lse = mx + __logf(se);
+            if (on && w != 0.f) local[t] += w * (lse - xl);
+            const float wg = hwt * w;
+#pragma unroll
+            for (int c0 = 0; c0 < Cs; c0 += 8) {
+                typename Vec8<T>::type o;
+#pragma unroll
+                for (int jj = 0; jj < 8; ++jj) {
+                    const int c = c0 + jj;
+                    float g = 0.f;
+                    if (on && w != 0.f && c < C) g = wg * (__expf(x[c] - lse) - (c == lab ? 1.f : 0.f));
+                    o[jj] = (T)g;
+                }
+                store8<T>(dg + p * Cs + c0, o);
+            }
+        }
+    }
+    unet_ce_block_sums(local[0], local[1], red, ws);
+}
+
+// Any class count (Cs > 32): the logits of a pixel are read three times from the cache.  Same arithmetic and summation order.
+template <typename T>
+__global__ void unet_ce_wide_kernel(const T* __restrict__ l0, const T* __restrict__ l1, const int64_t* __restrict__ lab0,
+                                    const int64_t* __restrict__ lab1, const int32_t* __restrict__ extent, const float* __restrict__ cw,
+                                    const int32_t* __restrict__ hist, int K, T* __restrict__ d0, T* __restrict__ d1,
+                                    float* __restrict__ ws, int B, int H, int W, int C, int Cs) {
+    __shared__ float red[2 * kThreads / 64];
+    __shared__ float inv[2 * kCeMaxB];
+    const int NL = l1 ? 2 : 1;
+    unet_ce_denominators(inv, extent, cw, hist, NL, B, H, W, C, K);
+    const float hwt = NL == 2 ? 0.5f : 1.f;
+    const int hw = H * W;
+    float local[2] = {0.f, 0.f};
+    const int64_t total = (int64_t)B * hw;
+    for (int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; p < total; p += (int64_t)gridDim.x * blockDim.x) {
+        const int b = (int)((unsigned)p / (unsigned)hw);
+        const int j = (int)p - b * hw;
+        const bool in = extent ? pos_in_extent(j, W, extent[2 * b], extent[2 * b + 1]) : true;
+        for (int t = 0; t < NL; ++t) {
+            const T* l = (t ? l1 : l0) + p * Cs;
+            T* dg = (t ? d1 : d0) + p * Cs;
+            const int64_t lab64 = (t ? lab1 : lab0)[p];
+            const bool on = in && lab64 >= 0 && lab64 < C;
+            const int lab = on ? (int)lab64 : -1;
+            const float w = on ? inv[t * B + b] * (cw ? cw[lab] : 1.f) : 0.f;
+            float mx = -INFINITY;
+            for (int c = 0; c < C; ++c) mx = fmaxf(mx, (float)l[c]);
+            float se = 0.f;
+            for (int c = 0; c < C; ++c) se += __expf((float)l[c] - mx);
+            const float lse = mx + __logf(se);
+            const bool act = on && w != 0.f;
+            if (act) local[t] += w * (lse - (float)l[lab]);
+            const float wg = hwt * w;
+            for (int c = 0; c < Cs; ++c) {
+                float g = 0.f;
+                if (act && c < C) g = wg * (__expf((float)l[c] - lse) - (c == lab ? 1.f : 0.f));
+                dg[c] = (T)g;
+            }
+        }
+    }
+    unet_ce_block_sums(local[0], local[1], red, ws);
+}
+
+// the follow-up: the block partials of each head added in ordered_sum_kernel_t's order -> loss3 = (total, final, auxiliary), written
+__global__ __launch_bounds__(256) void unet_ce_finish_kernel(const float* __restrict__ ws, int n, int two, float* __restrict__ loss3) {
+    __shared__ float red[8];
+    float s0 = 0.f, s1 = 0.f;
+    for (int i = threadIdx.x; i < n; i += 256) { s0 += ws[i]; s1 += ws[n + i]; }
+    for (int o = 32; o > 0; o >>= 1) { s0 += __shfl_down(s0, o, 64); s1 += __shfl_down(s1, o, 64); }
+    if ((threadIdx.x & 63) == 0) { red[threadIdx.x >> 6] = s0; red[4 + (threadIdx.x >> 6)] = s1; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        const float f = (red[0] + red[1]) + (red[2] + red[3]);
+        const float a = two ? (red[4] + red[5]) + (red[6] + red[7]) : 0.f;
+        loss3[0] = two ? 0.5f * f + 0.5f * a : f;
+        loss3[1] = f;
+        loss3[2] = a;
+    }
+}
+
+// =============================================================================================
 // per-channel sums (bias gradient of the transposed conv)
 // =============================================================================================
 template <typename T>
@@ -1127,6 +1314,50 @@ extern "C" int msau_masked_ce_multi(void* stream, int dtype, const void* logits,
     MSAU_CHECK_LAUNCH("masked_ce_multi");
     hipLaunchKernelGGL(ordered_sum_kernel_t<true>, dim3(1), dim3(256), 0, s, ws, nb, loss);
     MSAU_CHECK_LAUNCH("ordered_sum_set");
+    return 0;
+}
+
+extern "C" int msau_label_hist(void* stream, const int64_t* labels, const int32_t* extent, int32_t* partial, int B, int H, int W,
+                               int C, int K) {
+    MSAU_CHECK_ARG(labels && partial, "label_hist: null pointer");
+    MSAU_CHECK_ARG(B > 0 && B <= 65535 && H > 0 && W > 0 && (int64_t)B * H * W < (1ll << 31) && C > 0 && C <= kHistMaxC && K >= 1 && K <= 64,
+                   "label_hist: bad args (B*H*W < 2^31, n_class <= %d, 1 <= K <= 64)", kHistMaxC);
+    hipLaunchKernelGGL(label_hist_kernel, dim3(K, B), dim3(256), 0, static_cast<hipStream_t>(stream), labels, extent, partial, H, W, C, K);
+    MSAU_CHECK_LAUNCH("label_hist");
+    return 0;
+}
+
+static int unet_ce_blocks(int64_t npix) { return grid_for(npix, 2048); }
+extern "C" int64_t msau_unet_ce_ws_floats(int64_t npix_total) { return 2 * unet_ce_blocks(npix_total); }
+
+extern "C" int msau_unet_ce(void* stream, int dtype, const void* logits, const void* aux, const int64_t* labels,
+                            const int64_t* aux_labels, const int32_t* extent, const float* class_w, const int32_t* hist_partial, int K,
+                            void* dlogits, void* daux, float* loss3, float* ws, int B, int H, int W, int C, int Cs) {
+    MSAU_CHECK_ARG(logits && labels && dlogits && loss3 && ws && (!aux || (daux && aux_labels)), "unet_ce: null pointer");
+    MSAU_CHECK_ARG(!class_w || (hist_partial && K >= 1 && K <= 64), "unet_ce: class weights need the label histograms (1 <= K <= 64)");
+    MSAU_CHECK_ARG(B > 0 && B <= kCeMaxB && H > 0 && W > 0 && (int64_t)B * H * W < (1ll << 31) && C > 0 && C <= Cs && Cs % 8 == 0 && Cs <= 256,
+                   "unet_ce: bad dims (B <= %d, B*H*W < 2^31, n_class <= 256)", kCeMaxB);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const int nb = unet_ce_blocks((int64_t)B * H * W);
+#define UNET_CE(T, NL, C8) hipLaunchKernelGGL((unet_ce_kernel<T, NL, C8>), dim3(nb), dim3(kThreads), 0, s, static_cast<const T*>(logits), \
+        static_cast<const T*>(aux), labels, aux_labels, extent, class_w, hist_partial, K, static_cast<T*>(dlogits), static_cast<T*>(daux), \
+        ws, B, H, W, C)
+#define UNET_CE_NL(C8) do { if (aux) { DISPATCH_T(dtype, UNET_CE(float, 2, C8), UNET_CE(bf16_t, 2, C8)); } \
+                            else { DISPATCH_T(dtype, UNET_CE(float, 1, C8), UNET_CE(bf16_t, 1, C8)); } } while (0)
+#define UNET_CE_WIDE(T) hipLaunchKernelGGL((unet_ce_wide_kernel<T>), dim3(nb), dim3(kThreads), 0, s, static_cast<const T*>(logits), \
+        static_cast<const T*>(aux), labels, aux_labels, extent, class_w, hist_partial, K, static_cast<T*>(dlogits), static_cast<T*>(daux), \
+        ws, B, H, W, C, Cs)
+    if (Cs == 8) UNET_CE_NL(1);
+    else if (Cs == 16) UNET_CE_NL(2);
+    else if (Cs == 24) UNET_CE_NL(3);
+    else if (Cs == 32) UNET_CE_NL(4);
+    else { DISPATCH_T(dtype, UNET_CE_WIDE(float), UNET_CE_WIDE(bf16_t)); }
+#undef UNET_CE_WIDE
+#undef UNET_CE_NL
+#undef UNET_CE
+    MSAU_CHECK_LAUNCH("unet_ce");
+    hipLaunchKernelGGL(unet_ce_finish_kernel, dim3(1), dim3(256), 0, s, ws, nb, aux ? 1 : 0, loss3);
+    MSAU_CHECK_LAUNCH("unet_ce_finish");
     return 0;
 }
 

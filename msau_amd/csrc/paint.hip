@@ -197,7 +197,184 @@ PT_DEV void pt_ctx(PtCtx& c, const int32_t* lines, const PtGlyph* glyphs, const 
     c.aligned = (plane & 7) == 0;
 }
 
+// ---- the training painter (data_generator/data_generator_text.py:206-244, the per-pixel part) ------------------------------------
+// ids as above; labels / aux_labels(y, x) = the label record (label, aux label) of the LAST line with text whose box [y1:y2, x1:x2]
+// holds the pixel, 0 if none -- the glyph spans play no part in them.  Character and box owner can come from different lines (a
+// glyph reaches past its line's x2 when the pitch is clamped to 1; an earlier line's glyph shows under a later line's box), so a
+// pixel is finished when BOTH are known and the walk goes on until then.  Same bands, wavefronts, 8 pixels per lane and staging as
+// above, the label records staged beside the line records.  With more than PT_CHUNK lines the passes before the last keep a pixel's
+// two "known" flags in bits 16 / 17 of its id (a token is 16 bits); the last pass stores the plain values.  Every canvas pixel is
+// written once per pass, outside the documents with -1 / -1 / -1.
+#define PT_CHAR_KNOWN 0x10000
+#define PT_BOX_KNOWN 0x20000
+
+struct PtTrainCtx {
+    PtCtx g;                        // lines, glyphs, extents, the ids plane (g.line / g.chr unused)
+    const int32_t* labs;            // the document's label records [n_lines][2]
+    int64_t* lab;                   // the document's planes of the two label canvases
+    int64_t* aux;
+};
+
+struct PtTrainLds { PtLds l; int* lab; int* aux; };                 // [PT_CHUNK] each
+#define PT_TRAIN_LDS_INTS (10 * PT_CHUNK)
+
+PT_DEV void pt_tr_carve(PtTrainLds& s, int* base) {
+    pt_carve(s.l, base);
+    s.lab = base + 8 * PT_CHUNK; s.aux = base + 9 * PT_CHUNK;
+}
+
+PT_DEV void pt_tr_ph_stage(const PtTrainCtx& c, const PtTrainLds& s, int tid, int first) {
+    pt_ph_stage(c.g, s.l, tid, first);
+    const int li = first + tid;
+    if (li < c.g.n_lines) { s.lab[tid] = c.labs[2 * (size_t)li]; s.aux[tid] = c.labs[2 * (size_t)li + 1]; }
+}
+
+PT_DEV void pt_tr_pixels(const PtTrainCtx& c, const PtTrainLds& s, int y, int X, int count, bool first_pass, bool last_pass) {
+    const PtCtx& g_ = c.g;
+    int32_t id[8];
+    int64_t lab[8], aux[8];
+    const size_t at = (size_t)y * g_.W + X;
+    const bool vec = g_.aligned && (at & 7) == 0 && X + 8 <= g_.W;
+    unsigned need_c = 0, need_b = 0;                                // pixels of the document without a character / a box owner so far
+    if (first_pass) {
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+            const bool in = y < g_.h && X + i < g_.w;
+            id[i] = in ? 0 : -1; lab[i] = in ? 0 : -1; aux[i] = in ? 0 : -1;
+            if (in) { need_c |= 1u << i; need_b |= 1u << i; }
+        }
+    } else {
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+            const bool on = X + i < g_.W, in = y < g_.h && X + i < g_.w;
+            const int32_t v = on ? g_.ids[at + i] : -1;
+            lab[i] = on ? c.lab[at + i] : -1; aux[i] = on ? c.aux[at + i] : -1;
+            id[i] = in ? (v & 0xffff) : -1;
+            if (in && !(v & PT_CHAR_KNOWN)) need_c |= 1u << i;
+            if (in && !(v & PT_BOX_KNOWN)) need_b |= 1u << i;
+        }
+    }
+    for (int j = count - 1; j >= 0 && (need_c | need_b); --j) {
+        const int n = s.l.n[j];
+        if (n == 0 || y < s.l.y1[j] || y >= s.l.y2[j]) continue;    // the same for every lane of the wavefront
+        if (X >= s.l.xr[j] || X + 8 <= s.l.xl[j]) continue;
+        const int x1 = s.l.x1[j], x2 = s.l.x2[j];
+        if (need_b) {
+            const int64_t lv = s.lab[j], av = s.aux[j];
+#pragma unroll
+            for (int i = 0; i < 8; ++i) {
+                const int x = X + i;
+                if ((need_b >> i & 1) && x >= x1 && x < x2) { lab[i] = lv; aux[i] = av; need_b &= ~(1u << i); }
+            }
+        }
+        if (!need_c) continue;
+        const PtGlyph* g = g_.glyphs + s.l.g0[j];
+        const int k0 = pt_last_at_or_before(g, n, X);               // as pt_pixels: the glyph of X + i is one of k0 .. k0 + i
+        int ca[9], cb[9], ct[9];
+#pragma unroll
+        for (int t = 0; t < 9; ++t) {
+            const int k = k0 + t;
+            const bool has = k >= 0 && k < n;
+            const PtGlyph r = g[has ? k : 0];
+            ca[t] = has ? r.a : 0x7fffffff; cb[t] = r.b; ct[t] = r.tok;
+        }
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+            if (!(need_c >> i & 1)) continue;
+            const int x = X + i;
+            int sel = -1;
+#pragma unroll
+            for (int t = 0; t <= i; ++t) if (ca[t] <= x) sel = t;
+            int b = 0, tok = 0;
+#pragma unroll
+            for (int t = 0; t <= i; ++t) if (t == sel) { b = cb[t]; tok = ct[t]; }
+            if (sel >= 0 && x < b) { id[i] = tok; need_c &= ~(1u << i); }
+        }
+    }
+    if (!last_pass) {
+#pragma unroll
+        for (int i = 0; i < 8; ++i)
+            if (y < g_.h && X + i < g_.w)
+                id[i] |= ((need_c >> i & 1) ? 0 : PT_CHAR_KNOWN) | ((need_b >> i & 1) ? 0 : PT_BOX_KNOWN);
+    }
+    if (vec) {
 #ifdef MSAU_PAINT_CPU
+        memcpy(g_.ids + at, id, sizeof(id)); memcpy(c.lab + at, lab, sizeof(lab)); memcpy(c.aux + at, aux, sizeof(aux));
+#else
+        typedef int i32x4 __attribute__((ext_vector_type(4)));
+        typedef long long i64x2 __attribute__((ext_vector_type(2)));
+        i32x4 lo = {id[0], id[1], id[2], id[3]}, hi = {id[4], id[5], id[6], id[7]};
+        *reinterpret_cast<i32x4*>(g_.ids + at) = lo;
+        *reinterpret_cast<i32x4*>(g_.ids + at + 4) = hi;
+#pragma unroll
+        for (int i = 0; i < 8; i += 2) {
+            i64x2 l = {lab[i], lab[i + 1]}, a = {aux[i], aux[i + 1]};
+            *reinterpret_cast<i64x2*>(c.lab + at + i) = l;
+            *reinterpret_cast<i64x2*>(c.aux + at + i) = a;
+        }
+#endif
+    } else {
+#pragma unroll
+        for (int i = 0; i < 8; ++i)
+            if (X + i < g_.W) { g_.ids[at + i] = id[i]; c.lab[at + i] = lab[i]; c.aux[at + i] = aux[i]; }
+    }
+}
+
+PT_DEV void pt_tr_ph_paint(const PtTrainCtx& c, const PtTrainLds& s, int tid, int count, bool first_pass, bool last_pass) {
+    const int wv = PT_UNIFORM(tid >> 6), lane = tid & 63, groups = (c.g.W + 7) >> 3;
+    for (int r = wv; r < PT_ROWS; r += PT_WAVES) {
+        const int y = c.g.r0 + r;
+        if (y >= c.g.H) break;
+        for (int gidx = lane; gidx < groups; gidx += 64) pt_tr_pixels(c, s, y, gidx * 8, count, first_pass, last_pass);
+    }
+}
+
+PT_DEV void pt_tr_body(const PtTrainCtx& c, const PtTrainLds& s) {
+    const int n_lines = c.g.n_lines;
+    const int passes = n_lines > 0 ? (n_lines + PT_CHUNK - 1) / PT_CHUNK : 1;
+    for (int p = 0; p < passes; ++p) {
+        const int first = (passes - 1 - p) * PT_CHUNK;
+        const int count = n_lines - first < PT_CHUNK ? (n_lines - first > 0 ? n_lines - first : 0) : PT_CHUNK;
+        PT_PHASE(pt_tr_ph_stage, first);
+        PT_PHASE(pt_tr_ph_paint, count, p == 0, p == passes - 1);
+    }
+}
+
+// as pt_ctx: unordered offsets make a document without lines (the label records share the lines' offsets), extents are clipped
+PT_DEV void pt_tr_ctx(PtTrainCtx& c, const int32_t* lines, const PtGlyph* glyphs, const int32_t* labs, const int32_t* line_off,
+                      const int32_t* glyph_off, const int32_t* sizes, int b, int band, int H, int W, int32_t* ids, int64_t* lab, int64_t* aux) {
+    const int l0 = line_off[b], l1 = line_off[b + 1], g0 = glyph_off[b], g1 = glyph_off[b + 1];
+    const bool ok = l0 >= 0 && l1 >= l0 && g0 >= 0 && g1 >= g0;
+    c.g.lines = lines + (size_t)(ok ? l0 : 0) * PT_LINE_INTS; c.g.n_lines = ok ? l1 - l0 : 0;
+    c.g.glyphs = glyphs + (ok ? g0 : 0); c.g.n_glyphs = ok ? g1 - g0 : 0;
+    c.labs = labs + (size_t)(ok ? l0 : 0) * 2;
+    const int h = sizes[2 * b], w = sizes[2 * b + 1];
+    c.g.h = h < 0 ? 0 : (h > H ? H : h); c.g.w = w < 0 ? 0 : (w > W ? W : w);
+    c.g.H = H; c.g.W = W; c.g.r0 = band * PT_ROWS;
+    const size_t plane = (size_t)b * H * W;
+    c.g.ids = ids + plane; c.g.line = 0; c.g.chr = 0;
+    c.lab = lab + plane; c.aux = aux + plane;
+    c.g.aligned = (plane & 7) == 0;
+}
+
+#ifdef MSAU_PAINT_CPU
+extern "C" int msau_kv_paint_train_cpu(const int32_t* lines, const void* glyphs, const int32_t* labs, const int32_t* line_off,
+                                       const int32_t* glyph_off, const int32_t* sizes, int B, int H, int W, int32_t* ids,
+                                       int64_t* labels, int64_t* aux_labels) {
+    int* lds = (int*)malloc(sizeof(int) * PT_TRAIN_LDS_INTS);
+    if (!lds) return 1;
+    for (int b = 0; b < B; ++b)
+        for (int band = 0; band * PT_ROWS < H; ++band) {
+            PtTrainCtx c;
+            pt_tr_ctx(c, lines, (const PtGlyph*)glyphs, labs, line_off, glyph_off, sizes, b, band, H, W, ids, labels, aux_labels);
+            PtTrainLds s;
+            pt_tr_carve(s, lds);
+            pt_tr_body(c, s);
+        }
+    free(lds);
+    return 0;
+}
+
 // the launch, lane by lane on the host: same arguments as msau_kv_paint without the stream
 extern "C" int msau_kv_paint_cpu(const int32_t* lines, const void* glyphs, const int32_t* line_off, const int32_t* glyph_off,
                                  const int32_t* sizes, int B, int H, int W, int32_t* ids, uint16_t* line_ids, uint16_t* char_pos) {
@@ -237,6 +414,31 @@ extern "C" int msau_kv_paint(void* stream, const int32_t* lines, const void* gly
     hipLaunchKernelGGL(kv_paint_kernel, dim3(cdiv(H, PT_ROWS), B), dim3(PT_THREADS), 0, static_cast<hipStream_t>(stream), lines,
                        static_cast<const PtGlyph*>(glyphs), line_off, glyph_off, sizes, H, W, ids, line_ids, char_pos);
     MSAU_CHECK_LAUNCH("kv_paint");
+    return 0;
+}
+
+__global__ void __launch_bounds__(PT_THREADS)
+kv_paint_train_kernel(const int32_t* lines, const PtGlyph* glyphs, const int32_t* labs, const int32_t* line_off, const int32_t* glyph_off,
+                      const int32_t* sizes, int H, int W, int32_t* ids, int64_t* labels, int64_t* aux_labels) {
+    __shared__ int pt_lds[PT_TRAIN_LDS_INTS];
+    PtTrainCtx c;
+    pt_tr_ctx(c, lines, glyphs, labs, line_off, glyph_off, sizes, (int)blockIdx.y, (int)blockIdx.x, H, W, ids, labels, aux_labels);
+    PtTrainLds s;
+    pt_tr_carve(s, pt_lds);
+    pt_tr_body(c, s);
+}
+
+extern "C" int msau_kv_paint_train(void* stream, const int32_t* lines, const void* glyphs, const int32_t* line_labels,
+                                   const int32_t* line_off, const int32_t* glyph_off, const int32_t* sizes, int B, int H, int W,
+                                   int32_t* ids, int64_t* labels, int64_t* aux_labels) {
+    MSAU_CHECK_ARG(lines && glyphs && line_labels && line_off && glyph_off && sizes && ids && labels && aux_labels, "kv_paint_train: null pointer");
+    MSAU_CHECK_ARG(B > 0 && B <= 65535 && H > 0 && W > 0 && (int64_t)B * H * W < (1ll << 31), "kv_paint_train: bad shape B = %d, H = %d, W = %d", B, H, W);
+    MSAU_CHECK_ARG(((uintptr_t)ids | (uintptr_t)labels | (uintptr_t)aux_labels) % 16 == 0, "kv_paint_train: the canvases must be 16-byte aligned");
+    MSAU_CHECK_ARG((uintptr_t)lines % 4 == 0 && (uintptr_t)line_labels % 4 == 0 && (uintptr_t)glyphs % 8 == 0,
+                   "kv_paint_train: the records must be aligned to their size");
+    hipLaunchKernelGGL(kv_paint_train_kernel, dim3(cdiv(H, PT_ROWS), B), dim3(PT_THREADS), 0, static_cast<hipStream_t>(stream), lines,
+                       static_cast<const PtGlyph*>(glyphs), line_labels, line_off, glyph_off, sizes, H, W, ids, labels, aux_labels);
+    MSAU_CHECK_LAUNCH("kv_paint_train");
     return 0;
 }
 #endif

@@ -85,6 +85,16 @@ def glyph_table(doc_or_path, tok_to_id: dict, blank_idx: int) -> GlyphTable:
     for line, box in zip(lines, boxes.tolist()):
         line["box"] = box
     count = np.array([len(l["text"]) for l in lines], dtype=np.int64)
+    text = "".join(l["text"] for l in lines)
+    line_rec, glyph_rec, why = span_records(boxes, count, shape, lambda: _tokens(text, tok_to_id, blank_idx))
+    return GlyphTable(shape, scale, bg_pad, text_bbox, lines, line_rec, glyph_rec, why)
+
+
+def span_records(boxes: np.ndarray, count: np.ndarray, shape: Tuple[int, int], tokens):
+    """The grid boxes int64 [L, 4] and character counts [L] of a document's lines on a grid of `shape` -> (line_rec, glyph_rec, "") or
+    (None, None, why the table cannot represent the document).  `tokens()` gives the token of every character of the document, in
+    text order; it is asked only when everything else fits.  (Shared with the training tables, msau_amd/training/kv_data.py.)"""
+    L = len(boxes)
     why = ""
     reversed_ = (count > 0) & ((boxes[:, 2] < boxes[:, 0]) | (boxes[:, 3] < boxes[:, 1]))
     if reversed_.any():
@@ -93,11 +103,6 @@ def glyph_table(doc_or_path, tok_to_id: dict, blank_idx: int) -> GlyphTable:
     # pitch = max(1.0 * (x2 - x1) / n, 1.0), glyph_w = min(max(0.9 * pitch, 1.0), int((y2 - y1) * 1.2))
     pitch = np.maximum((boxes[:, 2] - boxes[:, 0]).astype(np.float64) / np.maximum(count, 1), 1.0)
     glyph_w = np.minimum(np.maximum(0.9 * pitch, 1.0), ((boxes[:, 3] - boxes[:, 1]) * 1.2).astype(np.int64))
-    texts = [l["text"] for l in lines]
-
-    def table(line_rec, glyph_rec, reason=""):
-        return GlyphTable(shape, scale, bg_pad, text_bbox, lines, line_rec, glyph_rec, reason)
-
     if not why and (shape[0] < 1 or shape[1] < 1):
         why = f"empty grid {shape}"
     if not why and (L > COUNT_MAX or int(count.max(initial=0)) > COUNT_MAX):
@@ -105,7 +110,7 @@ def glyph_table(doc_or_path, tok_to_id: dict, blank_idx: int) -> GlyphTable:
     if not why and (boxes.min(initial=0) < 0 or max(int(boxes.max(initial=0)), *shape) > COORD_MAX):
         why = "a coordinate outside [0, %d]" % COORD_MAX
     if why:
-        return table(None, None, why)
+        return None, None, why
     # every character of the document at once: its line, its index in the line, its span
     first = np.cumsum(count) - count
     G = int(count.sum())
@@ -115,13 +120,13 @@ def glyph_table(doc_or_path, tok_to_id: dict, blank_idx: int) -> GlyphTable:
     a = xs.astype(np.int64)                                             # int(xs)
     b = (xs + glyph_w[of_line]).astype(np.int64)                        # int(xs + glyph_w)
     if G and (int(a.min()) < 0 or int(b.min()) < 0 or int(b.max()) > COORD_MAX):
-        return table(None, None, "a glyph span outside [0, %d]" % COORD_MAX)
+        return None, None, "a glyph span outside [0, %d]" % COORD_MAX
     same_line = of_line[1:] == of_line[:-1]
     if G and ((a > b).any() or ((b[:-1] > a[1:]) | (a[:-1] >= a[1:]))[same_line].any()):
-        return table(None, None, "glyph spans of a line are not disjoint with increasing starts")
-    tok = _tokens("".join(texts), tok_to_id, blank_idx)
+        return None, None, "glyph spans of a line are not disjoint with increasing starts"
+    tok = np.asarray(tokens(), dtype=np.int64)
     if G and (int(tok.min()) < 0 or int(tok.max()) > COUNT_MAX):
-        return table(None, None, "a token outside uint16")
+        return None, None, "a token outside uint16"
     line_rec = np.zeros((L, LINE_INTS), dtype=np.int32)
     line_rec[:, :4] = boxes
     line_rec[:, 4], line_rec[:, 5] = first, count
@@ -131,7 +136,7 @@ def glyph_table(doc_or_path, tok_to_id: dict, blank_idx: int) -> GlyphTable:
     glyph_rec = np.zeros((G, 4), dtype=np.int16)
     glyph_rec[:, 0], glyph_rec[:, 1] = a, b
     glyph_rec[:, 2] = tok.astype(np.uint16).view(np.int16)
-    return table(line_rec, glyph_rec)
+    return line_rec, glyph_rec, ""
 
 
 def paint_host(table: GlyphTable) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:

@@ -716,10 +716,10 @@ class TrainEngine:
         weakref.finalize(self, L.load().msau_comm_destroy, self._comm)
 
     # -- pieces (each is a fixed launch sequence on the current stream) --
-    def _fwd_bwd(self, plan: Plan, x, labels, ids=None, nhwc_ready=False, owner=None, nhwc_clean=False):
+    def _fwd_bwd(self, plan: Plan, x, labels, ids=None, nhwc_ready=False, owner=None, nhwc_clean=False, loss_grads=None):
         plan.forward(self.model._flat, x, export=False, ids=ids, nhwc_ready=nhwc_ready, owner=owner, single_stream=self.use_graph,
                      nhwc_clean=nhwc_clean)
-        loss = plan.loss_grads(labels)
+        loss = plan.loss_grads(labels) if loss_grads is None else loss_grads(plan)     # (step_unet: another loss, same sweeps)
         # MSAU_DP_BUCKETS=1: ONE all-reduce of the whole flat gradient after the backward instead of a bucket per stage
         # issued while the earlier stages' backward still runs (fewer launches and joins, no overlap)
         self._ar_native = False
@@ -838,6 +838,61 @@ class TrainEngine:
         self._allreduce()
         self._optim()
         return loss
+
+    def _class_weights(self, class_weights, n_class: int) -> Optional[torch.Tensor]:
+        """the class weights on the device, uploaded again only when they change"""
+        if class_weights is None:
+            return None
+        host = torch.as_tensor(class_weights).detach().to(device="cpu", dtype=torch.float32).reshape(-1).contiguous() \
+            if not (isinstance(class_weights, torch.Tensor) and class_weights.is_cuda) else None
+        n = host.numel() if host is not None else class_weights.numel()
+        if n != n_class:
+            raise ValueError(f"class_weights must hold n_class = {n_class} values, got {n}")
+        if host is None:                                 # already on the device: the caller keeps it current
+            return class_weights.detach().to(device=self.model._flat.device, dtype=torch.float32).reshape(-1).contiguous()
+        kept = getattr(self, "_cw", None)
+        if kept is None or not torch.equal(kept[0], host):
+            self._cw = (host.clone(), host.to(self.model._flat.device))
+        return self._cw[1]
+
+    def step_unet(self, ids: torch.Tensor, labels: torch.Tensor, aux_labels: torch.Tensor, sizes=None, class_weights=None) -> torch.Tensor:
+        """`step_ids` with the loss the reference trains the key-value model with (model/training/cost.py `UNetLoss`): cross entropy
+        over EVERY pixel of a document, class 0 counted, 0.5 * final + 0.5 * auxiliary, each head against its OWN label map
+        (`labels` for the last stage, `aux_labels` for the auxiliary one; int64 [B,H,W]), optional `class_weights` (a sequence or
+        tensor of n_class floats).  Returns the 3-float device tensor (total, final, auxiliary), no host sync.
+        `sizes` as `step_ids` takes them: ids and labels outside the documents are ignored, every document computes what it
+        computes alone and loss and gradient are the means over the documents.  Without `sizes` every sample is its whole canvas: at
+        B = 1 exactly UNetLoss.  Backward, gradient exchange and optimiser are those of `step_ids`.  Eager only."""
+        if self.use_graph:
+            raise RuntimeError("step_unet is an eager path (use_graph=False)")
+        if ids.dim() != 3:
+            raise ValueError("ids must be [B,H,W]")
+        cw = self._class_weights(class_weights, self.model.n_class)
+        ids = ids.to(dtype=torch.int32).contiguous()
+        B, H, W = ids.shape
+        if sizes is not None:
+            sizes = self.model._check_sizes_for(sizes, B, H, W)
+        labels = labels.reshape(B, H, W).contiguous().long()
+        plan = self.model._plan_for_shape(B, H, W, ids.device, True, ragged=sizes is not None)
+        aux_labels = aux_labels.reshape(B, H, W).contiguous().long() if plan.aux is not None else None
+        if sizes is not None:
+            plan.set_extents(sizes)
+        loss = self._fwd_bwd(plan, None, None, ids=ids, loss_grads=lambda p: p.loss_grads_unet(labels, aux_labels, cw))
+        self._allreduce()
+        self._optim()
+        return loss
+
+    def step_kv(self, tables, class_weights=None, round_to: int = 16) -> torch.Tensor:
+        """One optimisation step on a group of key-value documents given as their training tables
+        (msau_amd.training.kv_data.train_table / KVTrainBatches): one upload of the packed tables, one launch that paints the id
+        canvas and both label canvases (msau_kv_paint_train), then `step_unet` on them with the documents' sizes.  No per-pixel
+        array is built on the host and nothing waits for the device -- except for a document whose table is not `ok`, which is
+        painted on the host and uploaded (kv_data.STATS counts them)."""
+        if self.use_graph:
+            raise RuntimeError("step_kv is an eager path (use_graph=False)")
+        from .training import kv_data
+        ids, labels, aux_labels, sizes = kv_data.paint_train_device(tables, round_to=round_to, device=self.model._flat.device)
+        return self.step_unet(ids, labels, aux_labels, sizes=sizes, class_weights=class_weights)
 
     def input_nhwc(self, B: int, H: int, W: int) -> torch.Tensor:
         """The training plan's own input buffer for this shape, [B][H][W][Cs] in the storage dtype: the zero-copy target of

@@ -1839,6 +1839,49 @@ class Plan:
                    1.0 / self.B)
         return self.loss_buf
 
+    def unet_launches(self, weighted: bool) -> List[Launch]:
+        """the launches of `loss_grads_unet`, stated as `_boundary_launches` states those of `loss_grads` (which they replace in a
+        key-value training step): key and algorithmic bytes, for the step's accounting and a profiler's attribution"""
+        esz = 4 if self.dtype == L.F32 else 2
+        HW, lg = self.H * self.W, self.logits
+        nl = 2 if self.aux is not None else 1
+        out = [Launch(0, None, "msau_label_hist", self.B * HW * 8)] * (nl if weighted else 0)
+        out.append(Launch(0, None, "msau_unet_ce", self.B * HW * nl * (8 + 2 * lg.Cs * esz)))
+        return out
+
+    def loss_grads_unet(self, labels: torch.Tensor, aux_labels: Optional[torch.Tensor], class_w: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """UNetLoss (model/training/cost.py:35-65: CE over every pixel, class 0 counted, 0.5 final + 0.5 auxiliary, optional class
+        weights) fused with its gradient, under the ragged rule: every document computes what it computes alone, the batch is the
+        mean of the documents.  `labels` / `aux_labels` int64 [B,H,W]: each head has its own map; the kernel reads the extents
+        itself, so the canvases are not copied and whatever they hold outside the documents is ignored.  `class_w`: fp32 [n_class]
+        on the device; only then the per-document class histograms are taken (one launch per head).  Writes d(logits), d(aux) in
+        place and returns the plan's 3-float buffer (total, final, auxiliary)."""
+        lg, ax = self.logits, self.aux
+        for t in (labels,) + ((aux_labels,) if ax is not None else ()):
+            assert t is not None and t.dtype == torch.int64 and t.is_contiguous() and tuple(t.shape) == (self.B, self.H, self.W)
+        assert ax is None or (ax.C, ax.Cs, ax.H, ax.W) == (lg.C, lg.Cs, lg.H, lg.W), "the auxiliary head must have the final head's shape"
+        assert (lg.H, lg.W) == (self.H, self.W)
+        s = self._stream()
+        if getattr(self, "unet_loss_buf", None) is None:
+            self.unet_loss_buf = torch.zeros((3,), dtype=torch.float32, device=self.device)
+            self.unet_ws = torch.zeros((int(L.load().msau_unet_ce_ws_floats(self.B * self.H * self.W)),), dtype=torch.float32, device=self.device)
+            self.unet_hist_k = max(1, min(16, 256 // self.B))
+            self.unet_hist = None
+        ext = self.extents.data_ptr() if self.ragged else None      # level 0: the documents' own (h, w)
+        K, hist = self.unet_hist_k, None
+        if class_w is not None:
+            assert class_w.dtype == torch.float32 and class_w.is_contiguous() and class_w.numel() == lg.C and class_w.device == lg.data.device
+            if self.unet_hist is None:
+                self.unet_hist = torch.zeros((2, self.B, K, lg.C), dtype=torch.int32, device=self.device)
+            hist = self.unet_hist.data_ptr()
+            for t, lab in enumerate((labels, aux_labels) if ax is not None else (labels,)):
+                L.call("msau_label_hist", s, lab.data_ptr(), ext, hist + 4 * t * self.B * K * lg.C, self.B, self.H, self.W, lg.C, K)
+        L.call("msau_unet_ce", s, self.dtype, lg.data.data_ptr(), _ptr(ax.data) if ax is not None else None, labels.data_ptr(),
+               aux_labels.data_ptr() if ax is not None else None, ext, _ptr(class_w), hist, K, lg.grad.data_ptr(),
+               _ptr(ax.grad) if ax is not None else None, self.unet_loss_buf.data_ptr(), self.unet_ws.data_ptr(),
+               self.B, self.H, self.W, lg.C, lg.Cs)
+        return self.unet_loss_buf
+
     def set_native_dp(self, comm: int, comm_stream, buckets, flat_grads: torch.Tensor):
         """Data parallelism through the C ABI (msau_allreduce_bucket, csrc/comm.hip): rebuild the backward sequence with one
         MSAU_OP_ALLREDUCE record behind each stage's slab reduction (bucket order = backward order: last stage first, the
