@@ -811,6 +811,27 @@ int msau_unet_ce(void* stream, int dtype, const void* logits, const void* aux, c
                  const int32_t* extent, const float* class_w, const int32_t* hist_partial, int K, void* dlogits, void* daux,
                  float* loss3, float* ws, int B, int H, int W, int C, int Cs);
 
+/* ------------------------------------------------------------------------------------------
+ * Key-value validation (model/training/trainer.py's epoch print: UNetLoss and cost.py:44-48's accuracy, forward only).
+ *   msau_unet_eval : per document, both heads in one launch, no gradient.  logits / aux / labels / aux_labels / extent / class_w
+ *                   exactly as msau_unet_ce takes them (aux NULL: one head; extent NULL: (H, W); class_w NULL: all ones).
+ *                     doc_loss   fp32  [B][2]    : [b][t] = L_b(head t) as defined for msau_unet_ce, 0 when D_b = 0
+ *                     doc_counts int32 [B][2][2] : [b][t] = (labelled, correct): the pixels inside the extent whose label is in
+ *                                                  [1, C), and those of them whose prediction equals the label; the prediction is
+ *                                                  the index of the FIRST maximum of the C stored values read as float (the rule
+ *                                                  of msau_eval_confusion: torch.argmax of the fp32 export)
+ *                   head 1's entries are 0 when aux is NULL.  Every entry is written, nothing accumulates.  K in [1, 256] workgroups
+ *                   per document each take ceil(h_b / K) rows of the extent and write one partial row into ws
+ *                   (>= msau_unet_eval_ws_bytes(B, K) bytes, 16-byte aligned); a second launch adds a document's K rows in index
+ *                   order and divides, so equal K gives equal bits.  The weighted denominator D_b is summed here, pixel by pixel:
+ *                   no msau_label_hist launch.  Nothing outside the extents is read.  No floating-point atomics.
+ *                   B <= 1024, B*H*W < 2^31, C <= Cs <= 256, Cs % 8 == 0; Cs <= 32 keeps a pixel's logits in registers.
+ * ------------------------------------------------------------------------------------------ */
+int64_t msau_unet_eval_ws_bytes(int B, int K);
+int msau_unet_eval(void* stream, int dtype, const void* logits, const void* aux, const int64_t* labels, const int64_t* aux_labels,
+                   const int32_t* extent, const float* class_w, int K, float* doc_loss, int32_t* doc_counts, void* ws, int B, int H,
+                   int W, int C, int Cs);
+
 #ifdef __cplusplus
 }
 #endif

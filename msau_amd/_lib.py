@@ -225,6 +225,8 @@ _SIGNATURES = {
     "msau_label_hist": (C.c_int, [vp, vp, vp, vp] + [C.c_int] * 5),
     "msau_unet_ce_ws_floats": (i64, [i64]),
     "msau_unet_ce": (C.c_int, [vp, C.c_int] + [vp] * 7 + [C.c_int, vp, vp, vp, vp] + [C.c_int] * 5),
+    "msau_unet_eval_ws_bytes": (i64, [C.c_int, C.c_int]),
+    "msau_unet_eval": (C.c_int, [vp, C.c_int] + [vp] * 6 + [C.c_int, vp, vp, vp] + [C.c_int] * 5),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)

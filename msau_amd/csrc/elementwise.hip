@@ -741,6 +741,40 @@ __device__ __forceinline__ void unet_ce_block_sums(float l0, float l1, float* re
     }
 }
 
+// A pixel's softmax statistics, shared by the training kernels (unet_ce_*) and the forward-only ones (unet_eval_*).
+// Register form: the pixel's Cs = 8 * CS8 stored values -> x[] (every index a compile-time constant), xl = x[lab] (0 when lab is
+// not a channel), returns the log-sum-exp over the C real classes.
+template <typename T, int CS8>
+__device__ __forceinline__ float unet_pixel_lse(const T* __restrict__ px, int C, int lab, float (&x)[CS8 * 8], float& xl) {
+    constexpr int Cs = CS8 * 8;
+    float mx = -INFINITY;
+    xl = 0.f;
+#pragma unroll
+    for (int c0 = 0; c0 < Cs; c0 += 8) {
+        typename Vec8<T>::type v = load8<T>(px + c0);
+#pragma unroll
+        for (int jj = 0; jj < 8; ++jj) {
+            x[c0 + jj] = (float)v[jj];
+            if (c0 + jj < C) mx = fmaxf(mx, x[c0 + jj]);
+            xl = (c0 + jj == lab) ? x[c0 + jj] : xl;
+        }
+    }
+    float se = 0.f;
+#pragma unroll
+    for (int c = 0; c < Cs; ++c) se += c < C ? __expf(x[c] - mx) : 0.f;
+    return mx + __logf(se);
+}
+
+// Cache-read form (any class count): the pixel's C values are read twice, nothing is kept.
+template <typename T>
+__device__ __forceinline__ float unet_pixel_lse_wide(const T* __restrict__ l, int C) {
+    float mx = -INFINITY;
+    for (int c = 0; c < C; ++c) mx = fmaxf(mx, (float)l[c]);
+    float se = 0.f;
+    for (int c = 0; c < C; ++c) se += __expf((float)l[c] - mx);
+    return mx + __logf(se);
+}
+
 // Both heads in one launch, the logits of a pixel in registers (Cs = 8 * CS8 <= 32: every index is a compile-time constant).
 // A thread's weight of head t at pixel p of document b: hw_t * cw[lab] / (B * D_b(t)) inside the extent with lab in [0, C), else 0;
 // the loss partials carry the weight WITHOUT hw_t (loss3[1], loss3[2] are the heads' own losses).
@@ -770,21 +804,8 @@ __global__ void unet_ce_kernel(const T* __restrict__ l0, const T* __restrict__ l
             const int lab = on ? (int)lab64 : -1;
             const float w = on ? inv[t * B + b] * (cw ? cw[lab] : 1.f) : 0.f;
             float x[Cs];
-            float mx = -INFINITY, xl = 0.f;
-#pragma unroll
-            for (int c0 = 0; c0 < Cs; c0 += 8) {
-                typename Vec8<T>::type v = load8<T>(lg + p * Cs + c0);
-#pragma unroll
-                for (int jj = 0; jj < 8; ++jj) {
-                    x[c0 + jj] = (float)v[jj];
-                    if (c0 + jj < C) mx = fmaxf(mx, x[c0 + jj]);
-                    xl = (c0 + jj == lab) ? x[c0 + jj] : xl;
-                }
-            }
-            float se = 0.f;
-#pragma unroll
-            for (int c = 0; c < Cs; ++c) se += c < C ? __expf(x[c] - mx) : 0.f;
-            const float lse = mx + __logf(se);
+            float xl;
+            const float lse = unet_pixel_lse<T, CS8>(lg + p * Cs, C, lab, x, xl);
             if (on && w != 0.f) local[t] += w * (lse - xl);
             const float wg = hwt * w;
 #pragma unroll
@@ -829,11 +850,7 @@ __global__ void unet_ce_wide_kernel(const T* __restrict__ l0, const T* __restric
             const bool on = in && lab64 >= 0 && lab64 < C;
             const int lab = on ? (int)lab64 : -1;
             const float w = on ? inv[t * B + b] * (cw ? cw[lab] : 1.f) : 0.f;
-            float mx = -INFINITY;
-            for (int c = 0; c < C; ++c) mx = fmaxf(mx, (float)l[c]);
-            float se = 0.f;
-            for (int c = 0; c < C; ++c) se += __expf((float)l[c] - mx);
-            const float lse = mx + __logf(se);
+            const float lse = unet_pixel_lse_wide(l, C);
             const bool act = on && w != 0.f;
             if (act) local[t] += w * (lse - (float)l[lab]);
             const float wg = hwt * w;
@@ -862,6 +879,145 @@ __global__ __launch_bounds__(256) void unet_ce_finish_kernel(const float* __rest
         loss3[1] = f;
         loss3[2] = a;
     }
+}
+
+// =============================================================================================
+// UNetLoss and the reference's accuracy, forward only and per document (validation: model/training/trainer.py's epoch print,
+// cost.py:44-48 `non_zero_mask`).  Grid K x B as label_hist_kernel: workgroup k of document b takes rows [k * rpk, (k + 1) * rpk) of
+// the document's extent, rpk = ceil(h_b / K), and WRITES one partial row; nothing outside the extent is read.
+// =============================================================================================
+struct UnetEvalRow { float num[2], den[2]; int32_t cnt[2][2]; };    // per head: sum cw * nll, sum cw; (labelled, correct)
+
+// strictly greater: the first maximum wins; a NaN counts as the maximum, as in torch.argmax
+__device__ __forceinline__ void first_max(float v, int c, float& bv, int& best) {
+    if (v > bv || (v != v && bv == bv)) { bv = v; best = c; }
+}
+
+// one pixel of one head into the thread's sums.  lse / xl: the pixel's log-sum-exp and its logit at the label; pred: its first maximum
+__device__ __forceinline__ void unet_eval_add(int lab, bool on, float lse, float xl, int pred, const float* __restrict__ cw,
+                                              float& num, float& den, int& labelled, int& correct) {
+    if (!on) return;
+    const float w = cw ? cw[lab] : 1.f;
+    den += w;
+    if (w != 0.f) num += w * (lse - xl);
+    if (lab >= 1) { labelled += 1; correct += pred == lab; }
+}
+
+// the workgroup's sums -> its row: lanes, then the four waves in index order (reproducible)
+__device__ __forceinline__ void unet_eval_block_row(float (&num)[2], float (&den)[2], int (&cnt)[2][2], UnetEvalRow* __restrict__ row) {
+    __shared__ float redf[4][4];
+    __shared__ int redi[4][4];
+    float f[4] = {num[0], num[1], den[0], den[1]};
+    int n[4] = {cnt[0][0], cnt[0][1], cnt[1][0], cnt[1][1]};
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+        for (int o = 32; o > 0; o >>= 1) { f[i] += __shfl_down(f[i], o, 64); n[i] += __shfl_down(n[i], o, 64); }
+    if ((threadIdx.x & 63) == 0) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) { redf[threadIdx.x >> 6][i] = f[i]; redi[threadIdx.x >> 6][i] = n[i]; }
+    }
+    __syncthreads();
+    if (threadIdx.x < 4) {
+        const int i = threadIdx.x;
+        const float fs = (redf[0][i] + redf[1][i]) + (redf[2][i] + redf[3][i]);
+        const int ns = (redi[0][i] + redi[1][i]) + (redi[2][i] + redi[3][i]);
+        (i < 2 ? row->num : row->den)[i & 1] = fs;
+        row->cnt[i >> 1][i & 1] = ns;
+    }
+}
+
+// the slab of workgroup k: pixel i of it -> canvas offset of the pixel inside document b, false past the slab's end
+struct UnetEvalSlab {
+    int r0, n, ew;
+    __device__ __forceinline__ UnetEvalSlab(const int32_t* __restrict__ extent, int b, int k, int K, int H, int W) {
+        const int eh = extent ? min(max(extent[2 * b], 0), H) : H;
+        ew = extent ? min(max(extent[2 * b + 1], 0), W) : W;
+        const int rpk = (eh + K - 1) / K;
+        r0 = min(k * rpk, eh);
+        n = (min(r0 + rpk, eh) - r0) * ew;                            // <= H * W < 2^31 (checked by the host)
+    }
+    __device__ __forceinline__ int offset(int i, int W) const { const int y = i / ew; return (r0 + y) * W + (i - y * ew); }
+};
+
+template <typename T, int NL, int CS8>
+__global__ __launch_bounds__(256) void unet_eval_kernel(const T* __restrict__ l0, const T* __restrict__ l1,
+                                                        const int64_t* __restrict__ lab0, const int64_t* __restrict__ lab1,
+                                                        const int32_t* __restrict__ extent, const float* __restrict__ cw,
+                                                        UnetEvalRow* __restrict__ rows, int H, int W, int C) {
+    constexpr int Cs = CS8 * 8;
+    const int b = blockIdx.y, k = blockIdx.x, K = gridDim.x;
+    const UnetEvalSlab slab(extent, b, k, K, H, W);
+    const int64_t base = (int64_t)b * H * W;
+    float num[2] = {0.f, 0.f}, den[2] = {0.f, 0.f};
+    int cnt[2][2] = {{0, 0}, {0, 0}};
+    for (int i = threadIdx.x; i < slab.n; i += 256) {
+        const int64_t p = base + slab.offset(i, W);
+#pragma unroll
+        for (int t = 0; t < NL; ++t) {
+            const int64_t lab64 = (t ? lab1 : lab0)[p];
+            const bool on = lab64 >= 0 && lab64 < C;
+            const int lab = on ? (int)lab64 : -1;
+            float x[Cs];
+            float xl;
+            const float lse = unet_pixel_lse<T, CS8>((t ? l1 : l0) + p * Cs, C, lab, x, xl);
+            int pred = 0;
+            float bv = -INFINITY;
+#pragma unroll
+            for (int c = 0; c < Cs; ++c)
+                if (c < C) first_max(x[c], c, bv, pred);
+            unet_eval_add(lab, on, lse, xl, pred, cw, num[t], den[t], cnt[t][0], cnt[t][1]);
+        }
+    }
+    unet_eval_block_row(num, den, cnt, rows + (int64_t)b * K + k);
+}
+
+// Any class count (Cs > 32): the logits of a pixel are read from the cache.  Same arithmetic and summation order.
+template <typename T>
+__global__ __launch_bounds__(256) void unet_eval_wide_kernel(const T* __restrict__ l0, const T* __restrict__ l1,
+                                                             const int64_t* __restrict__ lab0, const int64_t* __restrict__ lab1,
+                                                             const int32_t* __restrict__ extent, const float* __restrict__ cw,
+                                                             UnetEvalRow* __restrict__ rows, int H, int W, int C, int Cs) {
+    const int b = blockIdx.y, k = blockIdx.x, K = gridDim.x;
+    const int NL = l1 ? 2 : 1;
+    const UnetEvalSlab slab(extent, b, k, K, H, W);
+    const int64_t base = (int64_t)b * H * W;
+    float num[2] = {0.f, 0.f}, den[2] = {0.f, 0.f};
+    int cnt[2][2] = {{0, 0}, {0, 0}};
+    for (int i = threadIdx.x; i < slab.n; i += 256) {
+        const int64_t p = base + slab.offset(i, W);
+        for (int t = 0; t < NL; ++t) {
+            const T* l = (t ? l1 : l0) + p * Cs;
+            const int64_t lab64 = (t ? lab1 : lab0)[p];
+            const bool on = lab64 >= 0 && lab64 < C;
+            const int lab = on ? (int)lab64 : -1;
+            const float lse = unet_pixel_lse_wide(l, C);
+            int pred = 0;
+            float bv = -INFINITY;
+            for (int c = 0; c < C; ++c) first_max((float)l[c], c, bv, pred);
+            unet_eval_add(lab, on, lse, on ? (float)l[lab] : 0.f, pred, cw, num[t], den[t], cnt[t][0], cnt[t][1]);
+        }
+    }
+    unet_eval_block_row(num, den, cnt, rows + (int64_t)b * K + k);
+}
+
+// the follow-up: one thread per (document, head) adds the document's K rows in index order and divides; every output is written
+__global__ __launch_bounds__(256) void unet_eval_finish_kernel(const UnetEvalRow* __restrict__ rows, int B, int K,
+                                                               float* __restrict__ doc_loss, int32_t* __restrict__ doc_counts) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= 2 * B) return;
+    const int b = i >> 1, t = i & 1;
+    float n = 0.f, d = 0.f;
+    int labelled = 0, correct = 0;
+    for (int k = 0; k < K; ++k) {
+        const UnetEvalRow& r = rows[(int64_t)b * K + k];
+        n += r.num[t];
+        d += r.den[t];
+        labelled += r.cnt[t][0];
+        correct += r.cnt[t][1];
+    }
+    doc_loss[i] = d > 0.f ? n / d : 0.f;
+    doc_counts[2 * i] = labelled;
+    doc_counts[2 * i + 1] = correct;
 }
 
 // =============================================================================================
@@ -1078,9 +1234,7 @@ __global__ __launch_bounds__(256) void eval_confusion_kernel(const T* __restrict
             const typename Vec8<T>::type v8 = load8<T>(l + c0);
 #pragma unroll
             for (int j = 0; j < 8; ++j) {
-                const float v = (float)v8[j];
-                // strictly greater: the first maximum wins; a NaN counts as the maximum, as in torch.argmax
-                if (c0 + j < C && (v > bv || (v != v && bv == bv))) { bv = v; best = c0 + j; }
+                if (c0 + j < C) first_max((float)v8[j], c0 + j, bv, best);
             }
         }
         if (best == 0 && zero_as >= 0) best = zero_as;
@@ -1358,6 +1512,40 @@ extern "C" int msau_unet_ce(void* stream, int dtype, const void* logits, const v
     MSAU_CHECK_LAUNCH("unet_ce");
     hipLaunchKernelGGL(unet_ce_finish_kernel, dim3(1), dim3(256), 0, s, ws, nb, aux ? 1 : 0, loss3);
     MSAU_CHECK_LAUNCH("unet_ce_finish");
+    return 0;
+}
+
+extern "C" int64_t msau_unet_eval_ws_bytes(int B, int K) {
+    return B > 0 && K > 0 ? (int64_t)B * K * (int64_t)sizeof(UnetEvalRow) : 0;
+}
+
+extern "C" int msau_unet_eval(void* stream, int dtype, const void* logits, const void* aux, const int64_t* labels,
+                              const int64_t* aux_labels, const int32_t* extent, const float* class_w, int K, float* doc_loss,
+                              int32_t* doc_counts, void* ws, int B, int H, int W, int C, int Cs) {
+    MSAU_CHECK_ARG(logits && labels && doc_loss && doc_counts && ws && (!aux || aux_labels), "unet_eval: null pointer");
+    MSAU_CHECK_ARG(K >= 1 && K <= 256, "unet_eval: K = %d workgroups per document (1 <= K <= 256)", K);
+    MSAU_CHECK_ARG(B > 0 && B <= kCeMaxB && H > 0 && W > 0 && (int64_t)B * H * W < (1ll << 31) && C > 0 && C <= Cs && Cs % 8 == 0 && Cs <= 256,
+                   "unet_eval: bad dims (B <= %d, B*H*W < 2^31, n_class <= 256)", kCeMaxB);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    UnetEvalRow* rows = static_cast<UnetEvalRow*>(ws);
+    const dim3 grid(K, B);
+#define UNET_EVAL(T, NL, C8) hipLaunchKernelGGL((unet_eval_kernel<T, NL, C8>), grid, dim3(256), 0, s, static_cast<const T*>(logits), \
+        static_cast<const T*>(aux), labels, aux_labels, extent, class_w, rows, H, W, C)
+#define UNET_EVAL_NL(C8) do { if (aux) { DISPATCH_T(dtype, UNET_EVAL(float, 2, C8), UNET_EVAL(bf16_t, 2, C8)); } \
+                              else { DISPATCH_T(dtype, UNET_EVAL(float, 1, C8), UNET_EVAL(bf16_t, 1, C8)); } } while (0)
+#define UNET_EVAL_WIDE(T) hipLaunchKernelGGL((unet_eval_wide_kernel<T>), grid, dim3(256), 0, s, static_cast<const T*>(logits), \
+        static_cast<const T*>(aux), labels, aux_labels, extent, class_w, rows, H, W, C, Cs)
+    if (Cs == 8) UNET_EVAL_NL(1);
+    else if (Cs == 16) UNET_EVAL_NL(2);
+    else if (Cs == 24) UNET_EVAL_NL(3);
+    else if (Cs == 32) UNET_EVAL_NL(4);
+    else { DISPATCH_T(dtype, UNET_EVAL_WIDE(float), UNET_EVAL_WIDE(bf16_t)); }
+#undef UNET_EVAL_WIDE
+#undef UNET_EVAL_NL
+#undef UNET_EVAL
+    MSAU_CHECK_LAUNCH("unet_eval");
+    hipLaunchKernelGGL(unet_eval_finish_kernel, dim3((2 * B + 255) / 256), dim3(256), 0, s, rows, B, K, doc_loss, doc_counts);
+    MSAU_CHECK_LAUNCH("unet_eval_finish");
     return 0;
 }
 

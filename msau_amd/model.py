@@ -212,6 +212,24 @@ class _MaskedCEFunction(torch.autograd.Function):
         return g_logits, g_aux, None
 
 
+def _device_class_weights(holder, class_weights, n_class: int, device) -> Optional[torch.Tensor]:
+    """the class weights on the device, uploaded again only when they change; `holder` (a TrainEngine, a MSAUWrapper) keeps the
+    last upload in `_cw`"""
+    if class_weights is None:
+        return None
+    host = torch.as_tensor(class_weights).detach().to(device="cpu", dtype=torch.float32).reshape(-1).contiguous() \
+        if not (isinstance(class_weights, torch.Tensor) and class_weights.is_cuda) else None
+    n = host.numel() if host is not None else class_weights.numel()
+    if n != n_class:
+        raise ValueError(f"class_weights must hold n_class = {n_class} values, got {n}")
+    if host is None:                                 # already on the device: the caller keeps it current
+        return class_weights.detach().to(device=device, dtype=torch.float32).reshape(-1).contiguous()
+    kept = getattr(holder, "_cw", None)
+    if kept is None or kept[1].device != torch.device(device) or not torch.equal(kept[0], host):
+        holder._cw = (host.clone(), host.to(device))
+    return holder._cw[1]
+
+
 class MSAUWrapper(nn.Module):
     """API-compatible with model/model.py:399-459.  Extra model_kwargs: `num_blocks` (stages,
     reference hard-codes 3: model.py:355) and `dtype` ("fp32" | "bf16" activation/weight storage)."""
@@ -567,6 +585,43 @@ class MSAUWrapper(nn.Module):
                plan.extent_ptr(lg) if sizes is not None else None)
         return out
 
+    @torch.no_grad()
+    def eval_unet(self, ids: torch.Tensor, labels: torch.Tensor, aux_labels: torch.Tensor, sizes=None, class_weights=None):
+        """Validation of a group of documents on the device: the forward-only plan fed with the character-id mask (`ids` int32
+        [B,H,W], as `TrainEngine.step_ids` takes it), then UNetLoss and the reference's accuracy per document in one launch
+        (msau_unet_eval) on the logits both heads left in the plan -- nothing is exported, no one-hot tensor exists and nothing
+        waits for the device.  `labels` / `aux_labels` int64 [B,H,W] (each head against its own map), `sizes` and `class_weights`
+        as `TrainEngine.step_unet` takes them.  -> (doc_loss fp32 [B, 2], doc_counts int32 [B, 2, 2]) on the device: per document
+        and head (0 = final, 1 = auxiliary; zeros without an auxiliary head) the loss the document has alone, and (labelled,
+        correct) over its pixels with a label in [1, n_class), the prediction being `argmax` of the fp32 logits `forward` returns.
+        msau_amd.training.kv_trainer.summarize turns rows into the reference's epoch figures.  No training plan is built or
+        touched, parameters and gradients are left alone."""
+        if ids.dim() != 3:
+            raise ValueError("ids must be [B,H,W]")
+        if not ids.is_cuda:
+            raise RuntimeError("MSAUWrapper runs on an MI355X through libmsau_hip.so; input must be a CUDA/HIP tensor "
+                               "(there is no CPU fallback)")
+        cw = _device_class_weights(self, class_weights, self.n_class, self._flat.device)
+        ids = ids.to(dtype=torch.int32).contiguous()
+        B, H, W = ids.shape
+        if sizes is not None:
+            sizes = self._check_sizes_for(sizes, B, H, W)
+        plan = self._plan_for_shape(B, H, W, ids.device, False, ragged=sizes is not None)
+        labels = labels.reshape(B, H, W).contiguous().long()
+        aux_labels = aux_labels.reshape(B, H, W).contiguous().long() if plan.aux is not None else None
+        if sizes is not None:
+            plan.set_extents(sizes)
+        plan.forward(self._flat, None, export=False, ids=ids)
+        return plan.eval_unet(labels, aux_labels, cw)
+
+    def eval_kv(self, tables, class_weights=None, round_to: int = 16):
+        """`eval_unet` on a group of key-value documents given as their training tables (`KVTrainBatches.validation()`): one
+        upload of the packed tables, one painter launch (kv_data.paint_train_device; a table that is not `ok` is painted on the
+        host, as in `TrainEngine.step_kv`), the forward and the evaluation launch."""
+        from .training import kv_data
+        ids, labels, aux_labels, sizes = kv_data.paint_train_device(tables, round_to=round_to, device=self._flat.device)
+        return self.eval_unet(ids, labels, aux_labels, sizes=sizes, class_weights=class_weights)
+
     def save(self, path):
         torch.save(self.state_dict(), path)
 
@@ -841,28 +896,20 @@ class TrainEngine:
 
     def _class_weights(self, class_weights, n_class: int) -> Optional[torch.Tensor]:
         """the class weights on the device, uploaded again only when they change"""
-        if class_weights is None:
-            return None
-        host = torch.as_tensor(class_weights).detach().to(device="cpu", dtype=torch.float32).reshape(-1).contiguous() \
-            if not (isinstance(class_weights, torch.Tensor) and class_weights.is_cuda) else None
-        n = host.numel() if host is not None else class_weights.numel()
-        if n != n_class:
-            raise ValueError(f"class_weights must hold n_class = {n_class} values, got {n}")
-        if host is None:                                 # already on the device: the caller keeps it current
-            return class_weights.detach().to(device=self.model._flat.device, dtype=torch.float32).reshape(-1).contiguous()
-        kept = getattr(self, "_cw", None)
-        if kept is None or not torch.equal(kept[0], host):
-            self._cw = (host.clone(), host.to(self.model._flat.device))
-        return self._cw[1]
+        return _device_class_weights(self, class_weights, n_class, self.model._flat.device)
 
-    def step_unet(self, ids: torch.Tensor, labels: torch.Tensor, aux_labels: torch.Tensor, sizes=None, class_weights=None) -> torch.Tensor:
+    def step_unet(self, ids: torch.Tensor, labels: torch.Tensor, aux_labels: torch.Tensor, sizes=None, class_weights=None,
+                  stats=None) -> torch.Tensor:
         """`step_ids` with the loss the reference trains the key-value model with (model/training/cost.py `UNetLoss`): cross entropy
         over EVERY pixel of a document, class 0 counted, 0.5 * final + 0.5 * auxiliary, each head against its OWN label map
         (`labels` for the last stage, `aux_labels` for the auxiliary one; int64 [B,H,W]), optional `class_weights` (a sequence or
         tensor of n_class floats).  Returns the 3-float device tensor (total, final, auxiliary), no host sync.
         `sizes` as `step_ids` takes them: ids and labels outside the documents are ignored, every document computes what it
         computes alone and loss and gradient are the means over the documents.  Without `sizes` every sample is its whole canvas: at
-        B = 1 exactly UNetLoss.  Backward, gradient exchange and optimiser are those of `step_ids`.  Eager only."""
+        B = 1 exactly UNetLoss.  Backward, gradient exchange and optimiser are those of `step_ids`.  Eager only.
+        `stats`: a pair of device tensors (fp32 [B, 2], int32 [B, 2, 2]); the rows of `MSAUWrapper.eval_unet` -- per document the
+        losses and (labelled, correct) of this step's forward, the training accuracy of the reference's epoch print -- are then
+        written into it by one more launch between the forward and the loss kernel.  None: no such launch."""
         if self.use_graph:
             raise RuntimeError("step_unet is an eager path (use_graph=False)")
         if ids.dim() != 3:
@@ -877,22 +924,28 @@ class TrainEngine:
         aux_labels = aux_labels.reshape(B, H, W).contiguous().long() if plan.aux is not None else None
         if sizes is not None:
             plan.set_extents(sizes)
-        loss = self._fwd_bwd(plan, None, None, ids=ids, loss_grads=lambda p: p.loss_grads_unet(labels, aux_labels, cw))
+        if stats is None:
+            loss_grads = lambda p: p.loss_grads_unet(labels, aux_labels, cw)
+        else:
+            def loss_grads(p):
+                p.eval_unet(labels, aux_labels, cw, out=stats)
+                return p.loss_grads_unet(labels, aux_labels, cw)
+        loss = self._fwd_bwd(plan, None, None, ids=ids, loss_grads=loss_grads)
         self._allreduce()
         self._optim()
         return loss
 
-    def step_kv(self, tables, class_weights=None, round_to: int = 16) -> torch.Tensor:
+    def step_kv(self, tables, class_weights=None, round_to: int = 16, stats=None) -> torch.Tensor:
         """One optimisation step on a group of key-value documents given as their training tables
         (msau_amd.training.kv_data.train_table / KVTrainBatches): one upload of the packed tables, one launch that paints the id
         canvas and both label canvases (msau_kv_paint_train), then `step_unet` on them with the documents' sizes.  No per-pixel
         array is built on the host and nothing waits for the device -- except for a document whose table is not `ok`, which is
-        painted on the host and uploaded (kv_data.STATS counts them)."""
+        painted on the host and uploaded (kv_data.STATS counts them).  `stats` as in `step_unet`."""
         if self.use_graph:
             raise RuntimeError("step_kv is an eager path (use_graph=False)")
         from .training import kv_data
         ids, labels, aux_labels, sizes = kv_data.paint_train_device(tables, round_to=round_to, device=self.model._flat.device)
-        return self.step_unet(ids, labels, aux_labels, sizes=sizes, class_weights=class_weights)
+        return self.step_unet(ids, labels, aux_labels, sizes=sizes, class_weights=class_weights, stats=stats)
 
     def input_nhwc(self, B: int, H: int, W: int) -> torch.Tensor:
         """The training plan's own input buffer for this shape, [B][H][W][Cs] in the storage dtype: the zero-copy target of

@@ -1882,6 +1882,51 @@ class Plan:
                self.B, self.H, self.W, lg.C, lg.Cs)
         return self.unet_loss_buf
 
+    def unet_eval_launches(self) -> List[Launch]:
+        """the launch of `eval_unet`, stated as `unet_launches` states those of `loss_grads_unet`: key and algorithmic bytes (per head
+        the int64 label and the pixel's stored logits, read once; the K partial rows and the finish launch are noise beside them)"""
+        esz = 4 if self.dtype == L.F32 else 2
+        nl = 2 if self.aux is not None else 1
+        return [Launch(0, None, "msau_unet_eval", self.B * self.H * self.W * nl * (8 + self.logits.Cs * esz))]
+
+    def unet_eval_k(self) -> int:
+        """workgroups per document of `eval_unet`: enough to give every compute unit two workgroups, never more than the smallest
+        document has rows (more would only be empty slabs), at most the kernel's 256.  Reasoned, not measured."""
+        if getattr(self, "_cu_count", None) is None:
+            self._cu_count = int(torch.cuda.get_device_properties(self.device).multi_processor_count)
+        rows = int(self._ext_host[0, :, 0].min()) if self.ragged else self.H      # the pinned host copy of set_extents: no sync
+        return max(1, min(256, rows, -(-2 * self._cu_count // self.B)))
+
+    def eval_unet(self, labels: torch.Tensor, aux_labels: Optional[torch.Tensor], class_w: Optional[torch.Tensor] = None, out=None):
+        """UNetLoss and the reference's accuracy per document, forward only (msau_unet_eval): after `forward(export=False)` on a
+        forward-only plan, on the logits both heads left in the plan (`TrainEngine.step_unet(stats=...)` calls it on the training
+        plan's, between the forward and the loss kernel).  `labels` / `aux_labels` / `class_w` as `loss_grads_unet` takes
+        them; the kernel reads the extents itself.  -> (doc_loss fp32 [B, 2], doc_counts int32 [B, 2, 2]) on the device, head 0 =
+        final, head 1 = auxiliary, counts = (labelled, correct); `out`: a pair of such tensors to write instead of fresh ones.  No
+        gradient buffer is touched and nothing waits for the device."""
+        lg, ax = self.logits, self.aux
+        for t in (labels,) + ((aux_labels,) if ax is not None else ()):
+            assert t is not None and t.dtype == torch.int64 and t.is_contiguous() and tuple(t.shape) == (self.B, self.H, self.W)
+        assert ax is None or (ax.C, ax.Cs, ax.H, ax.W) == (lg.C, lg.Cs, lg.H, lg.W), "the auxiliary head must have the final head's shape"
+        assert (lg.H, lg.W) == (self.H, self.W)
+        if class_w is not None:
+            assert class_w.dtype == torch.float32 and class_w.is_contiguous() and class_w.numel() == lg.C and class_w.device == lg.data.device
+        if out is None:
+            out = (torch.empty((self.B, 2), dtype=torch.float32, device=self.device),
+                   torch.empty((self.B, 2, 2), dtype=torch.int32, device=self.device))
+        doc_loss, doc_counts = out
+        assert doc_loss.dtype == torch.float32 and doc_loss.is_contiguous() and tuple(doc_loss.shape) == (self.B, 2) \
+            and doc_counts.dtype == torch.int32 and doc_counts.is_contiguous() and tuple(doc_counts.shape) == (self.B, 2, 2) \
+            and doc_loss.device == doc_counts.device == lg.data.device, "stats: (fp32 [B, 2], int32 [B, 2, 2]) on the model's device"
+        K = self.unet_eval_k()
+        if getattr(self, "unet_eval_ws", None) is None:          # for the largest K: the extents, and with them K, change per batch
+            self.unet_eval_ws = torch.zeros((int(L.load().msau_unet_eval_ws_bytes(self.B, 256)),), dtype=torch.uint8, device=self.device)
+        L.call("msau_unet_eval", self._stream(), self.dtype, lg.data.data_ptr(), _ptr(ax.data) if ax is not None else None,
+               labels.data_ptr(), aux_labels.data_ptr() if ax is not None else None, self.extents.data_ptr() if self.ragged else None,
+               _ptr(class_w), K, doc_loss.data_ptr(), doc_counts.data_ptr(), self.unet_eval_ws.data_ptr(), self.B, self.H, self.W,
+               lg.C, lg.Cs)
+        return doc_loss, doc_counts
+
     def set_native_dp(self, comm: int, comm_stream, buckets, flat_grads: torch.Tensor):
         """Data parallelism through the C ABI (msau_allreduce_bucket, csrc/comm.hip): rebuild the backward sequence with one
         MSAU_OP_ALLREDUCE record behind each stage's slab reduction (bucket order = backward order: last stage first, the

@@ -9,7 +9,19 @@
 Prints for each route the documents per second of the WHOLE step (host work included), the bytes uploaded per document and
 the loss trajectory, and one JSON line.  The two routes see the same jitter settings but not the same draws, and the optimisers
 differ (the engine clips the gradient norm), so the trajectories are to be read side by side, not compared digit for digit.
-Not the headline metric (bench.py is); numbers are quoted in DESIGN.md 5e and profiles/kv_train.md."""
+Not the headline metric (bench.py is); numbers are quoted in DESIGN.md 5e and profiles/kv_train.md.
+
+--eval times VALIDATION instead (forward only, loss and accuracy per document), again two routes over the same deterministic tables
+(`KVTrainBatches.validation()`, repeated to --eval-docs documents):
+
+  eval_kv  MSAUWrapper.eval_kv at batch 1 and at --batch-size: tables up, painter, ragged forward fed with ids, msau_unet_eval; the
+           rows stay on the device and are read once at the end (training.kv_trainer.summarize)
+  trainer  what msau_amd.training.Trainer's validation loop does per document: one-hot input and targets built on the host, forward
+           with fp32 NCHW export, `UNetLoss` (argmax + a host read for the accuracy, two CE launches), float() of the loss
+
+Each route is timed --repeats times, the routes alternating inside one process; the table gives the median and the spread of the
+documents per second (host work included, the window ends in a device synchronise) and the epoch figures of both routes, which
+must agree.  The markdown table goes to --out (profiles/kv_eval.md)."""
 import argparse
 import json
 import os
@@ -94,6 +106,83 @@ def run_trainer(args):
                 loss=[round(float(l), 5) for l in torch.stack(losses).cpu()][::max(1, args.batch_size)])
 
 
+def eval_tables(args, it):
+    groups = it.validation()
+    docs = [t for g in groups for t in g]
+    return [docs[i % len(docs)] for i in range(args.eval_docs)]
+
+
+def run_eval_kv(args, net, docs, batch_size):
+    from msau_amd.training.kv_trainer import summarize
+    groups = [docs[i:i + batch_size] for i in range(0, len(docs), batch_size)]
+    for g in groups[:args.warmup] + groups[-1:]:                          # every canvas of the timed window (the last may be smaller)
+        net.eval_kv(g, round_to=args.round_to)
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    rows = [net.eval_kv(g, round_to=args.round_to) for g in groups]
+    s = summarize(torch.cat([r[0] for r in rows]), torch.cat([r[1] for r in rows]))      # the one read: ends the window
+    return len(docs) / (time.perf_counter() - t0), s
+
+
+def run_eval_trainer(args, net, docs, n_token):
+    crit = UNetLoss({})
+    eye_in, eye_out = np.eye(n_token, dtype="B"), np.eye(args.n_class, dtype="B")
+
+    def one(t):
+        ids, lab, aux = kv_data.paint_train_host(t) if t.ok else kv_data.paint_train_painter(t)
+        maps = [np.ascontiguousarray(e[m].transpose(2, 0, 1))[None] for e, m in ((eye_in, ids), (eye_out, lab), (eye_out, aux))]
+        bx, bt, ba = (torch.from_numpy(m) for m in maps)
+        bx, bt, ba = bx.float().cuda(), bt.long().cuda(), ba.long().cuda()
+        with torch.no_grad():
+            _, logits, logits_aux = net(bx)
+            acc, loss, final = crit(logits, bt, {"aux_logits": logits_aux, "aux_tgt": ba})
+        return acc, float(loss), float(final)
+
+    for t in docs[:max(args.warmup, 3)]:
+        one(t)
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    res = [one(t) for t in docs]
+    torch.cuda.synchronize()
+    dt = time.perf_counter() - t0
+    acc, loss, final = (float(np.mean([r[i] for r in res])) for i in range(3))
+    return len(docs) / dt, dict(loss=loss, final=final, acc=acc, documents=len(docs))
+
+
+def run_eval(args):
+    if not torch.cuda.is_available():
+        raise SystemExit("kv_train_loop --eval measures on an MI355X; no GPU is visible (nothing was measured)")
+    it = batches(args, args.batch_size)
+    net = model(it.n_token, args.n_class, args.dtype)
+    docs = eval_tables(args, it)
+    routes = [("eval_kv", 1), ("eval_kv", args.batch_size), ("trainer", 1)]
+    rates = {r: [] for r in routes}
+    figures = {}
+    for _ in range(args.repeats):                                         # alternating: a drift of the machine hits every route
+        for r in routes:
+            rate, s = run_eval_kv(args, net, docs, r[1]) if r[0] == "eval_kv" else run_eval_trainer(args, net, docs, it.n_token)
+            rates[r].append(rate)
+            figures[r] = s
+    lines = [f"`tools/kv_train_loop.py --eval --dtype {args.dtype} --eval-docs {args.eval_docs} --repeats {args.repeats}` on "
+             f"{torch.cuda.get_device_name(0)}: validation documents per second, host work included, median of {args.repeats} "
+             f"(min .. max), the routes alternating in one process; canvases of the golden layouts at scale 3.", "",
+             "| route | batch | documents/s | loss | final | acc |", "|---|---|---|---|---|---|"]
+    out = []
+    for r in routes:
+        v, s = sorted(rates[r]), figures[r]
+        med = float(np.median(v))
+        lines.append(f"| {r[0]} | {r[1]} | {med:.1f} ({v[0]:.1f} .. {v[-1]:.1f}) | {s['loss']:.6f} | {s['final']:.6f} | {s['acc']:.6f} |")
+        out.append(dict(route=r[0], batch_size=r[1], docs_per_s=med, docs_per_s_min=v[0], docs_per_s_max=v[-1], loss=s["loss"],
+                        final=s["final"], acc=s["acc"]))
+    text = "\n".join(lines) + "\n"
+    print(text)
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as fh:
+            fh.write(text)
+    print(json.dumps(dict(mode="eval", dtype=args.dtype, eval_docs=args.eval_docs, repeats=args.repeats, results=out)))
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("layouts", nargs="*", default=[os.path.join(KV, f"layout{i}.json") for i in range(3)])
@@ -111,7 +200,14 @@ def main():
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--round-to", type=int, default=32, help="canvas sizes are rounded up to a multiple (fewer distinct plans)")
     ap.add_argument("--routes", default="tables,trainer")
+    ap.add_argument("--eval", action="store_true", help="time validation (eval_kv against the Trainer's route) instead of training")
+    ap.add_argument("--eval-docs", type=int, default=96, help="--eval: documents per timed window")
+    ap.add_argument("--repeats", type=int, default=5, help="--eval: timed windows per route")
+    ap.add_argument("--out", default="", help="--eval: write the markdown table here")
     args = ap.parse_args()
+    if args.eval:
+        run_eval(args)
+        return
     out = []
     for route in args.routes.split(","):
         r = run_tables(args) if route == "tables" else run_trainer(args)
