@@ -533,6 +533,34 @@ int msau_clip_adam_step(void* stream, float* params, const float* grads, float* 
                         float grad_scale);
 
 /* ------------------------------------------------------------------------------------------
+ * The optimisers of the reference's get_optimizer (model/training/optimizer.py:4-31) as one fused multi-tensor step on the
+ * flat fp32 buffers; torch.optim's arithmetic, element for element, with g = grads * grad_scale * clip_coef + weight_decay * p:
+ *   MSAU_OPTIM_ADAM      m = c1 m + (1 - c1) g; v = c2 v + (1 - c2) g g; p -= lr / (1 - c1^t) * m / (sqrt(v) / sqrt(1 - c2^t) + eps)
+ *                        (c1, c2 = beta1, beta2; state_a = exp_avg, state_b = exp_avg_sq: msau_clip_adam_step plus weight decay)
+ *   MSAU_OPTIM_RMSPROP   s = c1 s + (1 - c1) g g; p -= lr g / (sqrt(s) + eps)        (c1 = alpha; state_a = square_avg; no momentum,
+ *                        not centered)
+ *   MSAU_OPTIM_MOMENTUM  b = c1 b + g; p -= lr b                                     (c1 = momentum; state_a = momentum_buffer; dampening 0,
+ *                        no Nesterov; eps unused)
+ * c1, c2 are doubles because torch forms 1 - c in double before it rounds to fp32 (1.f - 0.999f is off by 5e-5), and ADAM's bias
+ * corrections 1 - c^t are taken in double as well.  state_b is NULL and c2 unused where the kind has no second buffer.  state: the 8 floats of msau_clip_adam_step, same slots
+ * ([3], [4] are written under ADAM only); step is incremented by the call.
+ * max_norm > 0: global-norm clip as msau_clip_adam_step (a sum-of-squares launch in a fixed order, then the update; state[1] and
+ * state[2] are written); ADAM takes the two launches without clipping as well (coef 1).  max_norm <= 0 under RMSPROP / MOMENTUM:
+ * ONE launch, state[1] / state[2] are left alone and ws may be NULL.  No floating-point atomics: equal inputs, equal bits.
+ * skip: HOST array of n_skip <= MSAU_OPTIM_MAX_SKIP half-open element ranges [begin, end), ascending, not overlapping, inside
+ * [0, n) (read during the call, passed to the kernel by value).  Parameters and state inside a range are left bit-unchanged --
+ * no update, no weight decay: torch's treatment of a parameter whose gradient is None.  grads must be zero there.
+ * ------------------------------------------------------------------------------------------ */
+#define MSAU_OPTIM_ADAM 0
+#define MSAU_OPTIM_RMSPROP 1
+#define MSAU_OPTIM_MOMENTUM 2
+#define MSAU_OPTIM_MAX_SKIP 8
+int64_t msau_optim_ws_floats(int64_t n);
+int msau_optim_step(void* stream, int kind, float* params, const float* grads, float* state_a, float* state_b, float* state,
+                    float* ws, int64_t n, float lr, double c1, double c2, float eps, float weight_decay, float max_norm,
+                    float grad_scale, const int64_t* skip, int n_skip);
+
+/* ------------------------------------------------------------------------------------------
  * Chargrid rasteriser (next row N1; data_generator_funsd_bert.py:149-186 get_box_mask_box_label_word).
  * boxes: int32 [n][6] = {sample, y0, y1, x0, x1, value}, half-open, painted in order (later overwrites
  * earlier), clipped to the grid.  owner: int32 [B][H][W] scratch (index of the last covering box, -1).

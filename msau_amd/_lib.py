@@ -12,6 +12,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("MSAU_HIP_LIB", os.path.join(HERE, "libmsau_hip.so"))
 
 F32, BF16 = 0, 1
+OPTIM_ADAM, OPTIM_RMSPROP, OPTIM_MOMENTUM, OPTIM_MAX_SKIP = 0, 1, 2, 8
 
 CONV_RELU_IN, CONV_RELU_OUT, CONV_ADD, CONV_ACCUM, CONV_MASK_A, CONV_MASK_B, CONV_HEAD, CONV_DOUT = 1, 2, 4, 8, 16, 32, 64, 128
 CONV_LRN, CONV_POOL, CONV_IDS, CONV_OWNER, CONV_NCHW, CONV_WGRAD, CONV_ELU = 256, 512, 1024, 2048, 4096, 8192, 32768
@@ -191,6 +192,8 @@ _SIGNATURES = {
     "msau_softmax_ce_weighted": (C.c_int, [vp, C.c_int, vp, vp, vp, vp, vp, vp, C.c_int, i64, C.c_int, C.c_int]),
     "msau_adam_ws_floats": (i64, [i64]),
     "msau_clip_adam_step": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, i64, f32, f32, f32, f32, f32, f32]),
+    "msau_optim_ws_floats": (i64, [i64]),
+    "msau_optim_step": (C.c_int, [vp, C.c_int, vp, vp, vp, vp, vp, vp, i64, f32, C.c_double, C.c_double, f32, f32, f32, f32, vp, C.c_int]),
     "msau_raster_owner": (C.c_int, [vp, vp, C.c_int, vp, C.c_int, C.c_int, C.c_int]),
     "msau_raster_owner_ext": (C.c_int, [vp, vp, C.c_int, vp, C.c_int, C.c_int, C.c_int, vp]),
     "msau_raster_onehot": (C.c_int, [vp, C.c_int, vp, vp, vp] + [C.c_int] * 5),

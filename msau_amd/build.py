@@ -7,7 +7,7 @@ from concurrent.futures import ThreadPoolExecutor
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libmsau_hip.so")
-SOURCES = ["pack.hip", "conv.hip", "conv_lean.hip", "conv_first.hip", "conv_pair.hip", "conv_rows.hip", "conv_wgrad.hip", "wgrad_lean.hip", "elementwise.hip", "attention.hip", "attention_mfma.hip", "pointwise.hip", "raster.hip", "boxconv.hip", "sequence.hip", "comm.hip", "ownerconv.hip", "regions.hip", "paint.hip"]
+SOURCES = ["pack.hip", "conv.hip", "conv_lean.hip", "conv_first.hip", "conv_pair.hip", "conv_rows.hip", "conv_wgrad.hip", "wgrad_lean.hip", "elementwise.hip", "attention.hip", "attention_mfma.hip", "pointwise.hip", "raster.hip", "boxconv.hip", "sequence.hip", "comm.hip", "ownerconv.hip", "regions.hip", "paint.hip", "optim.hip"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-fPIC", "-std=c++17", "-Wall", "-Wno-unused-function"] + os.environ.get("MSAU_EXTRA_HIPCC_FLAGS", "").split() + [
          "-ffp-contract=fast"]
 
@@ -34,6 +34,8 @@ EXTRA_FLAGS = {"elementwise.hip": ["-Xclang", "-target-feature", "-Xclang", "-pa
                "conv.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
                # the box variant's kernels (cfg 5) run in a bf16 train path beside the same side-stream weight gradients: same rule
                "boxconv.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
+               # the optimiser kernels: built like msau_clip_adam_step's translation unit (elementwise.hip)
+               "optim.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
                # attention on the matrix cores: MFMA results in VGPRs as well (the statistics kernel read every score back with
                # v_accvgpr_read: a quarter of its vector instructions)
                "attention_mfma.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"],

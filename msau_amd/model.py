@@ -675,24 +675,117 @@ def _ru4(n: int) -> int:
     return -(-n // 4) * 4          # keep every parameter 16-byte aligned inside the flat buffer
 
 
+OPTIMIZERS = {"adam": L.OPTIM_ADAM, "rmsprop": L.OPTIM_RMSPROP, "momentum": L.OPTIM_MOMENTUM}
+# the name of a kind's state buffers in TrainEngine.state_dict() and in torch.optim's state (state_a, state_b of msau_optim_step)
+OPTIM_BUFFERS = {"adam": ("exp_avg", "exp_avg_sq"), "rmsprop": ("square_avg",), "momentum": ("momentum_buffer",)}
+
+
+def torch_optim_kind(sd: dict) -> str:
+    """which of the engine's optimisers a `torch.optim.*.state_dict()` belongs to, by the options of its parameter group:
+    Adam has `betas`, RMSprop `alpha`, SGD `nesterov`.  The variants msau_optim_step does not implement are refused."""
+    g0 = sd["param_groups"][0]
+    if "betas" in g0:
+        return "adam"
+    if "alpha" in g0:
+        if g0.get("momentum", 0) != 0 or g0.get("centered", False):
+            raise ValueError("RMSprop state with momentum or centered=True: the engine implements plain RMSprop only")
+        return "rmsprop"
+    if "nesterov" in g0:
+        if g0.get("nesterov", False) or g0.get("dampening", 0) != 0:
+            raise ValueError("SGD state with Nesterov momentum or dampening: the engine implements plain momentum only")
+        return "momentum"
+    raise ValueError(f"optimizer state of an unknown kind (options {sorted(g0)})")
+
+
+def torch_optim_state_to_flat(sd: dict, named, poff: Dict[str, int], total: int, kind: str):
+    """`torch.optim.{Adam,RMSprop,SGD}.state_dict()` over the model's parameters in registration order -> (step, [flat fp32 CPU
+    tensor of `total` elements per buffer of OPTIM_BUFFERS[kind]], the first parameter group).  `named`: [(key, numel)] of the
+    parameters the optimiser was built over, `poff` their offsets in the flat buffer.  Parameters the optimiser never stepped
+    (no gradient: the dead last-stage attention) have no entry and keep zero state.  ValueError when the state is another
+    kind's or does not fit the parameters.  CPU tensors in, CPU tensors out."""
+    have = torch_optim_kind(sd)
+    if have != kind:
+        raise ValueError(f"optimizer state is {have}'s, the engine runs {kind}")
+    groups, state = sd["param_groups"], sd["state"]
+    order = [pid for g in groups for pid in g["params"]]
+    if len(order) != len(named):
+        raise ValueError(f"optimizer state covers {len(order)} parameters, the model has {len(named)}")
+    names = OPTIM_BUFFERS[kind]
+    flats = [torch.zeros(total, dtype=torch.float32) for _ in names]
+    step = 0
+    for pid, (key, n) in zip(order, named):
+        st = state.get(pid)
+        if st is None:
+            continue
+        for name, flat in zip(names, flats):
+            buf = st.get(name)
+            if buf is None:                      # (SGD before its first step with a gradient)
+                continue
+            if buf.numel() != n:
+                raise ValueError(f"optimizer state of {key}: {buf.numel()} elements, parameter has {n}")
+            flat[poff[key]:poff[key] + n] = buf.detach().reshape(-1).to(device="cpu", dtype=torch.float32)
+        if "step" in st:
+            step = max(step, int(round(float(st["step"]))))
+    return step, flats, groups[0]
+
+
+def skip_ranges(dead, poff: Dict[str, int], numel: Dict[str, int]):
+    """the half-open element ranges of the flat buffer that the parameters `dead` occupy (alignment padding included), ascending,
+    adjacent ones merged: the `skip` argument of msau_optim_step"""
+    out = []
+    for b, e in sorted((poff[k], poff[k] + _ru4(numel[k])) for k in dead):
+        if out and out[-1][1] == b:
+            out[-1][1] = e
+        else:
+            out.append([b, e])
+    return [tuple(r) for r in out]
+
+
 class TrainEngine:
     """Fused training step on one GPU (one process per GPU under data parallelism).
 
     forward -> masked CE (+grad) -> backward -> [RCCL all-reduce of the flat gradient] ->
     global-norm clip + Adam, all on the flat fp32 parameter buffer of `model`
-    (train_chargrid_funsd_msau.py:46-59 with lr 1e-4, clip 1.0)."""
+    (train_chargrid_funsd_msau.py:46-59 with lr 1e-4, clip 1.0).
+
+    `optimizer` "adam" | "rmsprop" | "momentum", `weight_decay`, `alpha` (RMSprop), `momentum` (SGD) and `max_norm=None` (or
+    <= 0: no clipping) give the optimisers of the reference's `get_optimizer` (model/training/optimizer.py; `from_opt_kwargs`
+    takes its options): torch.optim's arithmetic in one fused launch (msau_optim_step), two with clipping or under Adam.  The
+    default -- Adam, no weight decay -- is msau_clip_adam_step as ever."""
 
     def __init__(self, model: MSAUWrapper, lr: float = 1e-4, betas=(0.9, 0.999), eps: float = 1e-8,
-                 max_norm: float = 1.0, process_group=None, use_graph: bool = False):
+                 max_norm: Optional[float] = 1.0, process_group=None, use_graph: bool = False, *, optimizer: str = "adam",
+                 weight_decay: float = 0.0, alpha: float = 0.99, momentum: float = 0.9):
+        if optimizer not in OPTIMIZERS:
+            raise ValueError(f"optimizer {optimizer!r}: TrainEngine knows {sorted(OPTIMIZERS)}")
         self.model, self.lr, self.betas, self.eps, self.max_norm = model, lr, betas, eps, max_norm
+        self.optimizer, self.weight_decay, self.alpha, self.momentum = optimizer, float(weight_decay), float(alpha), float(momentum)
         flat = model._flat
         if not flat.is_cuda:
             raise RuntimeError("TrainEngine needs the model on a GPU (model.cuda())")
         self.flat_grad = torch.zeros_like(flat)
-        self.m = torch.zeros_like(flat)
-        self.v = torch.zeros_like(flat)
+        # only the state buffers the kind uses: Adam's two moments, RMSprop's square_avg, SGD's momentum_buffer
+        self.m = self.v = self.square_avg = self.momentum_buffer = None
+        if optimizer == "adam":
+            self.m = torch.zeros_like(flat)
+            self.v = torch.zeros_like(flat)
+        elif optimizer == "rmsprop":
+            self.square_avg = torch.zeros_like(flat)
+        else:
+            self.momentum_buffer = torch.zeros_like(flat)
         self.state = torch.zeros(8, dtype=torch.float32, device=flat.device)
-        self.adam_ws = torch.zeros(int(L.load().msau_adam_ws_floats(flat.numel())), dtype=torch.float32, device=flat.device)
+        # the workspace of both entry points (msau_clip_adam_step: the default; msau_optim_step: everything else), so that
+        # set_hyper may move the engine from one to the other; a few hundred floats
+        lib = L.load()
+        self.adam_ws = torch.zeros(int(max(lib.msau_adam_ws_floats(flat.numel()), lib.msau_optim_ws_floats(flat.numel()))),
+                                   dtype=torch.float32, device=flat.device)
+        # parameters that never receive a gradient (torch.optim leaves a parameter whose .grad is None alone: no weight decay either)
+        import ctypes as C
+        ranges = skip_ranges(model._dead, model._poff, {k: p.numel() for k, p in model._named})
+        if len(ranges) > L.OPTIM_MAX_SKIP:
+            raise RuntimeError(f"{len(ranges)} separate ranges of parameters without a gradient, msau_optim_step takes {L.OPTIM_MAX_SKIP}")
+        self._skip = ranges
+        self._skip_arr = (C.c_int64 * max(2 * len(ranges), 1))(*[v for r in ranges for v in r])
         from .dp import GradSync, stage_buckets
         self.pg = process_group
         self.sync = GradSync(self.flat_grad, stage_buckets(model._poff, model._total, model.num_blocks), process_group)
@@ -731,13 +824,51 @@ class TrainEngine:
         TrainEngine._tokens += 1
         self._token = TrainEngine._tokens
 
-    def set_hyper(self, lr=None, betas=None, eps=None, max_norm=None):
-        """change optimiser hyper-parameters between steps (the lr schedule of model/training/trainer.py:124)"""
+    def set_hyper(self, lr=None, betas=None, eps=None, max_norm=None, weight_decay=None, alpha=None, momentum=None):
+        """change optimiser hyper-parameters between steps (the lr schedule of model/training/trainer.py:124); max_norm <= 0
+        switches the clipping off"""
         if lr is not None: self.lr = float(lr)
         if betas is not None: self.betas = tuple(betas)
         if eps is not None: self.eps = float(eps)
         if max_norm is not None: self.max_norm = float(max_norm)
+        if weight_decay is not None: self.weight_decay = float(weight_decay)
+        if alpha is not None: self.alpha = float(alpha)
+        if momentum is not None: self.momentum = float(momentum)
         self._invalidate_graphs()
+
+    @classmethod
+    def from_opt_kwargs(cls, model: MSAUWrapper, opt_kwargs={}, **engine_kwargs) -> "TrainEngine":
+        """The engine with the optimiser the reference's `get_optimizer(model, opt_kwargs)` builds (model/training/optimizer.py:
+        RMSprop at 1e-3 by default, "momentum" = SGD with momentum 0.9, any other name Adam, `lr_decay_rate` handed over as weight
+        decay) and no gradient clipping, as `Trainer.train` never clips.  Prints the reference's two lines.  `engine_kwargs`
+        (process_group, use_graph, ...) go to the constructor and win over the mapped options."""
+        from .training.optimizer import engine_options
+        opt = engine_options(opt_kwargs)
+        shown = opt.pop("shown")
+        print(f"Optimizer: {shown[0]}")
+        print(f"Learning Rate: {shown[1]}")
+        return cls(model, **{**opt, **engine_kwargs})
+
+    def _clip(self) -> float:
+        """max_norm as the kernels take it: 0 = no clipping"""
+        return float(self.max_norm) if self.max_norm is not None and self.max_norm > 0 else 0.0
+
+    def _default_step(self) -> bool:
+        """clip + Adam without weight decay: msau_clip_adam_step, the launch of the default engine and of bench.py"""
+        return self.optimizer == "adam" and self.weight_decay == 0.0 and self._clip() > 0.0
+
+    def _has_norm(self) -> bool:
+        return self.optimizer == "adam" or self._clip() > 0.0
+
+    def optim_launches(self):
+        """[(key, algorithmic bytes)] of the optimiser launches this engine's step ends in, in order (the plan's boundary record
+        states the default's: Plan._boundary_launches)"""
+        nparam = sum(p.numel() for _, p in self.model._named)
+        if self._default_step():
+            return [("msau_clip_adam_step", nparam * 4 * 8)]             # g twice, p, m, v read; p, m, v written
+        nbuf = len(OPTIM_BUFFERS[self.optimizer])
+        out = [("msau_optim_step<sqsum>", nparam * 4)] if self._has_norm() else []
+        return out + [(f"msau_optim_step<{self.optimizer}>", nparam * 4 * (2 + 2 * nbuf + 1))]    # g, p, state read; p, state written
 
     def _init_native_comm(self, group):
         """The gradient exchange through the C ABI (msau_allreduce_bucket over RCCL, csrc/comm.hip) when the process group is an
@@ -801,11 +932,22 @@ class TrainEngine:
         return loss
 
     def _optim(self):
-        b1, b2 = self.betas
         n = self.model._flat.numel()
-        L.call("msau_clip_adam_step", torch.cuda.current_stream().cuda_stream, self.model._flat.data_ptr(),
-               self.flat_grad.data_ptr(), self.m.data_ptr(), self.v.data_ptr(), self.state.data_ptr(),
-               self.adam_ws.data_ptr(), n, self.lr, b1, b2, self.eps, self.max_norm, 1.0 / self.world)
+        if self._default_step():
+            b1, b2 = self.betas
+            L.call("msau_clip_adam_step", torch.cuda.current_stream().cuda_stream, self.model._flat.data_ptr(),
+                   self.flat_grad.data_ptr(), self.m.data_ptr(), self.v.data_ptr(), self.state.data_ptr(),
+                   self.adam_ws.data_ptr(), n, self.lr, b1, b2, self.eps, self.max_norm, 1.0 / self.world)
+            return
+        if self.optimizer == "adam":
+            a, b, (c1, c2) = self.m, self.v.data_ptr(), self.betas
+        elif self.optimizer == "rmsprop":
+            a, b, c1, c2 = self.square_avg, None, self.alpha, 0.0
+        else:
+            a, b, c1, c2 = self.momentum_buffer, None, self.momentum, 0.0
+        L.call("msau_optim_step", torch.cuda.current_stream().cuda_stream, OPTIMIZERS[self.optimizer], self.model._flat.data_ptr(),
+               self.flat_grad.data_ptr(), a.data_ptr(), b, self.state.data_ptr(), self.adam_ws.data_ptr(), n, self.lr, c1, c2,
+               self.eps, self.weight_decay, self._clip(), 1.0 / self.world, self._skip_arr, len(self._skip))
 
     def _allreduce(self):
         if getattr(self, "_ar_native", False):
@@ -1076,50 +1218,69 @@ class TrainEngine:
 
     @property
     def grad_norm(self) -> torch.Tensor:
+        if not self._has_norm():
+            raise RuntimeError(f"grad_norm: {self.optimizer} without clipping (max_norm {self.max_norm}) is one launch that never "
+                               f"computes the gradient's norm; build the engine with max_norm > 0 to have it")
         return self.state[1]
 
-    # -- optimiser state (resume): the counterpart of torch.optim.Adam.state_dict() for the flat buffers --
+    # -- optimiser state (resume): the counterpart of torch.optim.*.state_dict() for the flat buffers --
+    def _buffers(self):
+        return {"adam": (self.m, self.v), "rmsprop": (self.square_avg,), "momentum": (self.momentum_buffer,)}[self.optimizer]
+
     def state_dict(self) -> dict:
-        """{"engine": 1, "step", "exp_avg", "exp_avg_sq" (flat fp32, the model's parameter order), hyper-parameters}"""
-        return {"engine": 1, "step": int(round(float(self.state[0]))), "exp_avg": self.m.detach().clone(),
-                "exp_avg_sq": self.v.detach().clone(), "lr": self.lr, "betas": tuple(self.betas), "eps": self.eps,
-                "max_norm": self.max_norm, "numel": int(self.m.numel())}
+        """Adam: {"engine": 1, "step", "exp_avg", "exp_avg_sq" (flat fp32, the model's parameter order), hyper-parameters}, plus
+        "weight_decay" when there is one.  RMSprop / momentum SGD: "optimizer": "rmsprop" / "momentum" as well, the buffer under
+        torch's name ("square_avg" / "momentum_buffer"), "alpha" / "momentum", "weight_decay".  max_norm 0.0: no clipping."""
+        sd = {"engine": 1, "step": int(round(float(self.state[0])))}
+        for name, buf in zip(OPTIM_BUFFERS[self.optimizer], self._buffers()):
+            sd[name] = buf.detach().clone()
+        sd["lr"] = self.lr
+        if self.optimizer == "adam":
+            sd.update(betas=tuple(self.betas), eps=self.eps, max_norm=self.max_norm if self.max_norm is not None else 0.0,
+                      numel=int(self.m.numel()))
+            if self.weight_decay != 0.0:
+                sd["weight_decay"] = self.weight_decay
+            return sd
+        sd.update(optimizer=self.optimizer, eps=self.eps, weight_decay=self.weight_decay, max_norm=self._clip(),
+                  numel=int(self.flat_grad.numel()))
+        sd["alpha" if self.optimizer == "rmsprop" else "momentum"] = self.alpha if self.optimizer == "rmsprop" else self.momentum
+        return sd
 
     def load_state_dict(self, sd: dict):
-        """Accepts `TrainEngine.state_dict()` or a `torch.optim.Adam.state_dict()` over the model's parameters in
-        registration order (what the reference's `save_checkpoint` stores: utils/io_utils.py:83-105); parameters Adam
-        never stepped (the dead last-stage attention) have no entry and keep zero moments."""
+        """Accepts `TrainEngine.state_dict()` or a `torch.optim.{Adam,RMSprop,SGD}.state_dict()` over the model's parameters in
+        registration order (what the reference's `save_checkpoint` stores: utils/io_utils.py:83-105); parameters the optimiser
+        never stepped (the dead last-stage attention) have no entry and keep zero state.  ValueError when the state is
+        another optimiser's than this engine's."""
+        bufs = self._buffers()
         if sd.get("engine") == 1:
-            if int(sd["numel"]) != self.m.numel():
-                raise ValueError(f"optimizer state is for {sd['numel']} parameters, the model has {self.m.numel()}")
-            self.m.copy_(sd["exp_avg"])
-            self.v.copy_(sd["exp_avg_sq"])
+            have = sd.get("optimizer", "adam")
+            if have != self.optimizer:
+                raise ValueError(f"optimizer state is {have}'s, the engine runs {self.optimizer}")
+            if int(sd["numel"]) != self.flat_grad.numel():
+                raise ValueError(f"optimizer state is for {sd['numel']} parameters, the model has {self.flat_grad.numel()}")
+            for name, buf in zip(OPTIM_BUFFERS[self.optimizer], bufs):
+                buf.copy_(sd[name])
             self.state.zero_()
             self.state[0] = float(sd["step"])
-            self.lr, self.betas, self.eps = float(sd["lr"]), tuple(sd["betas"]), float(sd["eps"])
+            self.lr, self.eps = float(sd["lr"]), float(sd["eps"])
+            if self.optimizer == "adam":
+                self.betas = tuple(sd["betas"])
             self.max_norm = float(sd.get("max_norm", self.max_norm))
+            self.weight_decay = float(sd.get("weight_decay", 0.0))
+            self.alpha, self.momentum = float(sd.get("alpha", self.alpha)), float(sd.get("momentum", self.momentum))
             self._invalidate_graphs()
             return
-        groups, state = sd["param_groups"], sd["state"]
-        order = [pid for g in groups for pid in g["params"]]
-        named = [(k, p) for k, p in self.model._named if p.requires_grad]
-        if len(order) != len(named):
-            raise ValueError(f"optimizer state covers {len(order)} parameters, the model has {len(named)}")
-        self.m.zero_()
-        self.v.zero_()
-        step = 0
-        for pid, (key, p) in zip(order, named):
-            st = state.get(pid)
-            if st is None:
-                continue
-            off, n = self.model._poff[key], p.numel()
-            if st["exp_avg"].numel() != n:
-                raise ValueError(f"optimizer state of {key}: {st['exp_avg'].numel()} elements, parameter has {n}")
-            self.m[off:off + n] = st["exp_avg"].reshape(-1).to(self.m)
-            self.v[off:off + n] = st["exp_avg_sq"].reshape(-1).to(self.v)
-            step = max(step, int(round(float(st["step"]))))
+        named = [(k, p.numel()) for k, p in self.model._named if p.requires_grad]
+        step, flats, g0 = torch_optim_state_to_flat(sd, named, self.model._poff, self.flat_grad.numel(), self.optimizer)
+        for buf, flat in zip(bufs, flats):
+            buf.copy_(flat)
         self.state.zero_()
         self.state[0] = float(step)
-        g0 = groups[0]
-        self.lr, self.betas, self.eps = float(g0["lr"]), tuple(g0["betas"]), float(g0["eps"])
+        self.lr, self.weight_decay = float(g0["lr"]), float(g0.get("weight_decay", 0.0))
+        if self.optimizer == "adam":
+            self.betas, self.eps = tuple(g0["betas"]), float(g0["eps"])
+        elif self.optimizer == "rmsprop":
+            self.alpha, self.eps = float(g0["alpha"]), float(g0["eps"])
+        else:
+            self.momentum = float(g0["momentum"])
         self._invalidate_graphs()

@@ -52,16 +52,22 @@ class _Rows:
 class KVTrainer:
     """`KVTrainer(model, batches).fit(output_path, epochs, steps_per_epoch)`: `model` a MSAUWrapper on the GPU, `batches` a
     KVTrainBatches (its iterator gives the training groups, its `validation()` the validation groups), `class_weights` as
-    `TrainEngine.step_unet` takes them, `engine_kwargs` for the TrainEngine.  Eager only; under data parallelism every rank would
-    validate every document."""
+    `TrainEngine.step_unet` takes them, `engine_kwargs` for the TrainEngine.  `opt_kwargs` (a dict, `{}` included): the options of
+    the reference's `get_optimizer`; the engine is then `TrainEngine.from_opt_kwargs(model, opt_kwargs, **engine_kwargs)`, the
+    reference `Trainer`'s optimiser -- RMSprop at 1e-3 by default, no gradient clipping.  None: the engine's own default (clip +
+    Adam).  Eager only; under data parallelism every rank would validate every document."""
 
-    def __init__(self, model, batches, class_weights=None, engine_kwargs={}):
+    def __init__(self, model, batches, class_weights=None, engine_kwargs={}, opt_kwargs=None):
         self.model, self.batches, self.class_weights = model, batches, class_weights
-        self.engine = self._engine(dict(engine_kwargs))
+        self.engine = self._engine(dict(engine_kwargs)) if opt_kwargs is None else self._engine_from_opt(dict(opt_kwargs), dict(engine_kwargs))
 
     def _engine(self, kwargs):
         from ..model import TrainEngine
         return TrainEngine(self.model, **kwargs)
+
+    def _engine_from_opt(self, opt_kwargs, kwargs):
+        from ..model import TrainEngine
+        return TrainEngine.from_opt_kwargs(self.model, opt_kwargs, **kwargs)
 
     def _stats(self, n: int):
         dev = self.model.flat_parameters.device

@@ -29,3 +29,22 @@ def get_optimizer(model, kwargs={}):
     print(f"Optimizer: {opt['optimizer']}")
     print(f"Learning Rate: {shown}")
     return made
+
+
+def engine_options(kwargs={}) -> dict:
+    """`get_optimizer`'s options as keyword arguments of `msau_amd.TrainEngine` (the device path's optimiser, `TrainEngine.
+    from_opt_kwargs`): the same table -- "momentum" = SGD with momentum, "rmsprop" (default), any other name Adam; `learning_rate`
+    1e-3, None = Adam with torch's own defaults (the other two need a rate, as torch does); `lr_decay_rate` as weight decay --
+    and `max_norm=None`, because the reference's `Trainer.train` never clips.  "shown": the two values `get_optimizer` prints."""
+    opt = {key: kwargs.get(key, default) for key, default in _DEFAULTS.items()}
+    kind = opt["optimizer"] if opt["optimizer"] in _FACTORIES else "adam"
+    shown = (opt["optimizer"], "" if opt["learning_rate"] is None else str(opt["learning_rate"]))
+    if opt["learning_rate"] is None:
+        if kind != "adam":
+            raise ValueError(f"optimizer {kind!r} needs a learning_rate")
+        return {"optimizer": "adam", "lr": 1e-3, "weight_decay": 0.0, "max_norm": None, "shown": shown}       # torch.optim.Adam()
+    out = {"optimizer": kind, "lr": float(opt["learning_rate"]), "weight_decay": float(opt["lr_decay_rate"]), "max_norm": None,
+           "shown": shown}
+    if kind == "momentum":
+        out["momentum"] = float(opt["momentum"])
+    return out

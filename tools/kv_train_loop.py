@@ -2,9 +2,11 @@
 """Key-value training, two routes over the same documents (layout + OCR JSONs; default: the three golden layouts, repeated):
 
   tables   KVTrainBatches -> TrainEngine.step_kv at --batch-size: the training tables cross the bus, one launch paints the ids and both
-           label canvases, ragged forward, UNetLoss kernel, backward, clip + Adam -- nothing per pixel on the host
+           label canvases, ragged forward, UNetLoss kernel, backward, the optimiser (--optimizer adam: clip + Adam, the default;
+           rmsprop / momentum, --weight-decay, --no-clip: msau_optim_step; `--optimizer rmsprop --no-clip --lr 1e-3` is the
+           reference Trainer's optimiser) -- nothing per pixel on the host
   trainer  msau_amd.training.Trainer's route: one-hot input and one-hot targets built on the host and uploaded, autograd
-           `UNetLoss`, torch.optim.Adam, batch 1
+           `UNetLoss`, the torch.optim counterpart of --optimizer (never clipped), batch 1
 
 Prints for each route the documents per second of the WHOLE step (host work included), the bytes uploaded per document and
 the loss trajectory, and one JSON line.  The two routes see the same jitter settings but not the same draws, and the optimisers
@@ -52,7 +54,9 @@ def batches(args, batch_size):
 
 def run_tables(args):
     it = batches(args, args.batch_size)
-    eng = TrainEngine(model(it.n_token, args.n_class, args.dtype), lr=args.lr)
+    eng = TrainEngine(model(it.n_token, args.n_class, args.dtype), lr=args.lr, optimizer=args.optimizer, weight_decay=args.weight_decay,
+                      max_norm=None if args.no_clip else 1.0)
+    print("optimiser launches:", ", ".join(f"{key} ({nbytes} B)" for key, nbytes in eng.optim_launches()))
     cw = [float(v) for v in args.class_weights.split(",")] if args.class_weights else None
     for _ in range(args.warmup):
         eng.step_kv(next(it), class_weights=cw, round_to=args.round_to)
@@ -65,7 +69,9 @@ def run_tables(args):
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
     docs = args.steps * args.batch_size
-    return dict(route="tables", batch_size=args.batch_size, docs_per_s=docs / dt, h2d_bytes_per_doc=kv_data.STATS["h2d_bytes"] / docs,
+    return dict(route="tables", batch_size=args.batch_size, optimizer=args.optimizer, clip=not args.no_clip, weight_decay=args.weight_decay,
+                optim_launches=[key for key, _ in eng.optim_launches()], docs_per_s=docs / dt,
+                h2d_bytes_per_doc=kv_data.STATS["h2d_bytes"] / docs,
                 host_painted=kv_data.STATS["host_painted"], loss=[round(float(l[0]), 5) for l in torch.stack(losses).cpu()])
 
 
@@ -73,7 +79,9 @@ def run_trainer(args):
     it = batches(args, 1)
     net = model(it.n_token, args.n_class, args.dtype)
     crit = UNetLoss({})
-    opt = torch.optim.Adam(net.parameters(), lr=args.lr)
+    opt = {"adam": lambda ps: torch.optim.Adam(ps, lr=args.lr, weight_decay=args.weight_decay),
+           "rmsprop": lambda ps: torch.optim.RMSprop(ps, lr=args.lr, weight_decay=args.weight_decay),
+           "momentum": lambda ps: torch.optim.SGD(ps, lr=args.lr, momentum=0.9, weight_decay=args.weight_decay)}[args.optimizer](net.parameters())
     eye_in, eye_out = np.eye(it.n_token, dtype="B"), np.eye(args.n_class, dtype="B")
 
     def step():
@@ -193,6 +201,10 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--dtype", default="bf16", choices=["fp32", "bf16"])
     ap.add_argument("--lr", type=float, default=1e-4)
+    ap.add_argument("--optimizer", default="adam", choices=["adam", "rmsprop", "momentum"], help="the engine's optimiser (tables route) "
+                    "and its torch.optim counterpart (trainer route)")
+    ap.add_argument("--weight-decay", type=float, default=0.0)
+    ap.add_argument("--no-clip", action="store_true", help="tables route: no global-norm clip (the reference's Trainer never clips)")
     ap.add_argument("--scale-min", type=float, default=2.0)
     ap.add_argument("--scale-max", type=float, default=4.0)
     ap.add_argument("--text-err", type=float, default=0.1)
