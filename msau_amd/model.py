@@ -142,8 +142,7 @@ class _MSAUFunction(torch.autograd.Function):
     @staticmethod
     def forward(ctx, wrapper, x, sizes, *params):
         plan = wrapper._plan_for(x, training=True, ragged=sizes is not None)
-        if sizes is not None:
-            plan.set_extents(sizes)
+        plan.set_extents(sizes)
         # The saved activations are the plan's own buffers: a second grad-mode forward of the same shape overwrites them.
         # backward() checks that it still belongs to the latest forward instead of returning silently wrong gradients.
         plan.generation += 1
@@ -344,10 +343,14 @@ class MSAUWrapper(nn.Module):
         return self._flat
 
     # ---- plans ----------------------------------------------------------------------------------
+    def _need_gpu(self, inp: Optional[torch.Tensor] = None):
+        """the refusal of CPU inputs: of the tensor `inp`, or (None) of a model that is not on the GPU"""
+        if not (self._flat if inp is None else inp).is_cuda:
+            what = "the model must be on the GPU" if inp is None else "input must be a CUDA/HIP tensor"
+            raise RuntimeError(f"MSAUWrapper runs on an MI355X through libmsau_hip.so; {what} (there is no CPU fallback)")
+
     def _plan_for(self, x: torch.Tensor, training: bool, ragged: bool = False) -> Plan:
-        if not x.is_cuda:
-            raise RuntimeError("MSAUWrapper runs on an MI355X through libmsau_hip.so; input must be a CUDA/HIP tensor "
-                               "(there is no CPU fallback)")
+        self._need_gpu(x)
         B, C, H, W = x.shape
         if C != self.channels:
             raise ValueError(f"expected {self.channels} input channels, got {C}")
@@ -369,6 +372,12 @@ class MSAUWrapper(nn.Module):
             self._plans.move_to_end(key)
         return plan
 
+    def _plan(self, B: int, H: int, W: int, device, training: bool, sizes) -> Plan:
+        """the plan of an eager batch given by its canvas: ragged when it has `sizes`, whose extents go to the device here"""
+        plan = self._plan_for_shape(B, H, W, device, training, ragged=sizes is not None)
+        plan.set_extents(sizes)
+        return plan
+
     # ---- reference API ----------------------------------------------------------------------------
     def forward(self, inp, sizes=None):
         """`sizes` (ragged batch): a CPU integer tensor [B, 2] of every document's (h, w), placed at the origin of the H x W canvas
@@ -384,8 +393,7 @@ class MSAUWrapper(nn.Module):
             aux = outs[1] if len(outs) > 1 else None
         else:
             plan = self._plan_for(x, training=False, ragged=sizes is not None)
-            if sizes is not None:
-                plan.set_extents(sizes)
+            plan.set_extents(sizes)
             lg, ax = plan.forward(self._flat, x)
             logits, aux = lg.clone(), (ax.clone() if ax is not None else None)
         if self.final_act == "softmax":
@@ -403,9 +411,16 @@ class MSAUWrapper(nn.Module):
         B, _, H, W = x.shape
         return Plan.check_sizes(sizes, B, H, W)
 
-    def _check_sizes_for(self, sizes, B: int, H: int, W: int) -> torch.Tensor:
-        """`_check_sizes` for the entry points that have a canvas shape and no input tensor (box lists, id masks)"""
-        return self._check_sizes(torch.empty((B, 0, H, W)), sizes)
+    def _check_sizes_for(self, sizes, B: int, H: int, W: int) -> Optional[torch.Tensor]:
+        """`_check_sizes` for the entry points that have a canvas shape and no input tensor (box lists, id masks); None stays None"""
+        return None if sizes is None else self._check_sizes(torch.empty((B, 0, H, W)), sizes)
+
+    @staticmethod
+    def _check_ids(ids: torch.Tensor, device=None) -> torch.Tensor:
+        """a character-id mask as the kernels take it: int32 [B,H,W], contiguous (moved to `device` when one is given)"""
+        if ids.dim() != 3:
+            raise ValueError("ids must be [B,H,W]")
+        return ids.to(device=device, dtype=torch.int32).contiguous()
 
     @torch.no_grad()
     def predict_nhwc(self, inp: Optional[torch.Tensor] = None, ids: Optional[torch.Tensor] = None, graph: bool = False,
@@ -430,25 +445,18 @@ class MSAUWrapper(nn.Module):
         if self.n_class > 255:
             raise ValueError("the argmax map is uint8: at most 255 classes")
         if ids is not None:
-            if ids.dim() != 3:
-                raise ValueError("ids must be [B,H,W]")
-            ids = ids.to(device=self._flat.device, dtype=torch.int32).contiguous()
+            ref = ids = self._check_ids(ids, self._flat.device)
             B, H, W = ids.shape
-            ref = ids
         else:
-            inp = inp.contiguous().float()
+            ref = inp = inp.contiguous().float()
             B, C, H, W = inp.shape
-            ref = inp
         if sizes is not None:
             sizes = Plan.check_sizes(sizes, B, H, W)
-        if not ref.is_cuda:
-            raise RuntimeError("MSAUWrapper runs on an MI355X through libmsau_hip.so; input must be a CUDA/HIP tensor "
-                               "(there is no CPU fallback)")
+        self._need_gpu(ref)
         ragged = sizes is not None
         plan = self._plan_for(inp, False, ragged) if ids is None else self._plan_for_shape(B, H, W, ref.device, False, ragged)
         if not graph:
-            if ragged:
-                plan.set_extents(sizes)
+            plan.set_extents(sizes)
             return plan.predict(self._flat, x_nchw=inp, ids=ids)
         kind = "ids" if ids is not None else "dense"
         if getattr(self, "_pstream", None) is None:
@@ -456,8 +464,7 @@ class MSAUWrapper(nn.Module):
         cur, gs = torch.cuda.current_stream(), self._pstream
         gs.wait_stream(cur)
         with torch.cuda.stream(gs):
-            if ragged:
-                plan.set_extents(sizes)                               # read by the captured sweep at every replay
+            plan.set_extents(sizes)                                   # read by the captured sweep at every replay
             cache = plan.__dict__.setdefault("_pgraphs", {})
             if kind not in cache:
                 static = ref.clone()
@@ -503,39 +510,24 @@ class MSAUWrapper(nn.Module):
         (the reference's test-split remap, train_chargrid_funsd_msau.py:140).  inp float [B,C,H,W], labels int [B,H,W] (or
         [B,1,H,W]); `sizes` as in `forward`.  Runs the forward-only plan without exporting the logits and adds into `out` when
         given (batches of an epoch accumulate on the device; read the matrix once)."""
-        C = self.n_class
-        if C > 64:
-            raise ValueError(f"confusion_matrix counts at most 64 classes, the model has {C}")
         x = inp.contiguous().float()
         if x.dim() != 4:
             raise ValueError("inp must be [B,C,H,W]")
         B, Cin, H, W = x.shape
         if int(labels.numel()) != B * H * W:
             raise ValueError(f"labels must hold [B,H,W] = {(B, H, W)} values, got shape {tuple(labels.shape)}")
-        if zero_as is not None and not (0 <= int(zero_as) < C):
-            raise ValueError(f"zero_as must be a class in [0, {C}), got {zero_as}")
+        out = self._confusion_args(zero_as, out, x.device)
         if sizes is not None:
             sizes = self._check_sizes(x, sizes)
         if labels.device.type == "cpu" and labels.numel() and \
-                bool((labels < 0).any() or (labels >= C).any()):
-            raise ValueError(f"labels must lie in [0, {C})")
-        if not x.is_cuda:
-            raise RuntimeError("MSAUWrapper runs on an MI355X through libmsau_hip.so; input must be a CUDA/HIP tensor "
-                               "(there is no CPU fallback)")
-        if out is None:
-            out = torch.zeros((C, C), dtype=torch.int64, device=x.device)
-        elif out.dtype != torch.int64 or tuple(out.shape) != (C, C) or out.device != x.device or not out.is_contiguous():
-            raise ValueError(f"out must be a contiguous int64 [{C}, {C}] tensor on {x.device}")
+                bool((labels < 0).any() or (labels >= self.n_class).any()):
+            raise ValueError(f"labels must lie in [0, {self.n_class})")
+        self._need_gpu(x)
         lab = labels.to(device=x.device, dtype=torch.int64).reshape(B, H, W).contiguous()
         plan = self._plan_for(x, training=False, ragged=sizes is not None)
-        if sizes is not None:
-            plan.set_extents(sizes)
+        plan.set_extents(sizes)
         plan.forward(self._flat, x, export=False)
-        lg = plan.logits
-        L.call("msau_eval_confusion", torch.cuda.current_stream().cuda_stream, plan.dtype, lg.data.data_ptr(), lab.data_ptr(),
-               out.data_ptr(), B, H, W, lg.C, lg.Cs, -1 if zero_as is None else int(zero_as),
-               plan.extent_ptr(lg) if sizes is not None else None)
-        return out
+        return self._count_confusion(plan, lab, zero_as, out)
 
     @torch.no_grad()
     def confusion_matrix_boxes(self, grid_boxes, label_boxes, B: int, H: int, W: int, feats=None, sizes=None,
@@ -546,44 +538,57 @@ class MSAUWrapper(nn.Module):
         painted, otherwise it is painted into the forward-only plan's input buffer.  `sizes` (ragged batch): the CPU integer [B, 2]
         of `forward`, every document's boxes in its own coordinates (msau_amd.data.ragged.pack_boxes).  Counts, `zero_as` and `out`
         as in `confusion_matrix`: rows = painted labels in [1, n_class), columns = first maximum of the logits."""
-        from .data import raster
+        dev = self._flat.device
+        out = self._confusion_args(zero_as, out, dev)
+        sizes = self._check_sizes_for(sizes, B, H, W)
+        self._need_gpu()
+        plan = self._plan(B, H, W, dev, False, sizes)
+        feed, lab = self._paint_boxes(plan, grid_boxes, label_boxes, feats)
+        plan.forward(self._flat, None, export=False, **feed)
+        return self._count_confusion(plan, lab, zero_as, out)
+
+    def _confusion_args(self, zero_as, out: Optional[torch.Tensor], dev) -> torch.Tensor:
+        """the checks `confusion_matrix` and `confusion_matrix_boxes` share -> `out`, a new matrix on `dev` when it is None"""
         C = self.n_class
         if C > 64:
             raise ValueError(f"confusion_matrix counts at most 64 classes, the model has {C}")
         if zero_as is not None and not (0 <= int(zero_as) < C):
             raise ValueError(f"zero_as must be a class in [0, {C}), got {zero_as}")
-        if sizes is not None:
-            sizes = self._check_sizes_for(sizes, B, H, W)
-        dev = self._flat.device
-        if dev.type != "cuda":
-            raise RuntimeError("MSAUWrapper runs on an MI355X through libmsau_hip.so; the model must be on the GPU "
-                               "(there is no CPU fallback)")
         if out is None:
-            out = torch.zeros((C, C), dtype=torch.int64, device=dev)
-        elif out.dtype != torch.int64 or tuple(out.shape) != (C, C) or out.device != dev or not out.is_contiguous():
+            return torch.zeros((C, C), dtype=torch.int64, device=dev)
+        if out.dtype != torch.int64 or tuple(out.shape) != (C, C) or out.device != dev or not out.is_contiguous():
             raise ValueError(f"out must be a contiguous int64 [{C}, {C}] tensor on {dev}")
-        plan = self._plan_for_shape(B, H, W, dev, False, ragged=sizes is not None)
-        ext = None
-        if sizes is not None:
-            plan.set_extents(sizes)
-            ext = plan.extents[0]                        # the painters clip to the plan's own level-0 extents
-        if feats is not None and plan._feed_owner(None):
-            ft = feats if isinstance(feats, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(feats, dtype=np.float32)).to(dev)
-            owner, fb, nf, lab = raster.owner_maps(grid_boxes, label_boxes, B, H, W, dev, sizes=ext)
-            plan.forward(self._flat, None, export=False, owner=(owner, fb, nf, ft))
-            plan._feed_owner(None)                       # (Plan.predict of the same plan expects the tensor-fed first conv)
-        else:
-            buf = plan.input_nhwc
-            if feats is None:
-                _, lab = raster.rasterize(grid_boxes, label_boxes, B, H, W, self.channels, self.dtype_name, dev, out=buf, sizes=ext)
-            else:
-                _, lab = raster.rasterize_dense(grid_boxes, label_boxes, feats, B, H, W, self.dtype_name, dev, out=buf, sizes=ext)
-            plan.forward(self._flat, None, export=False, nhwc_ready=True, nhwc_clean=True)
+        return out
+
+    def _count_confusion(self, plan: Plan, lab: torch.Tensor, zero_as, out: torch.Tensor) -> torch.Tensor:
+        """add the counts of the logits `plan` holds against the labels `lab` (int64 [B,H,W] on the device) into `out`"""
         lg = plan.logits
         L.call("msau_eval_confusion", torch.cuda.current_stream().cuda_stream, plan.dtype, lg.data.data_ptr(), lab.data_ptr(),
-               out.data_ptr(), B, H, W, lg.C, lg.Cs, -1 if zero_as is None else int(zero_as),
-               plan.extent_ptr(lg) if sizes is not None else None)
+               out.data_ptr(), plan.B, plan.H, plan.W, lg.C, lg.Cs, -1 if zero_as is None else int(zero_as),
+               plan.extent_ptr(lg) if plan.ragged else None)
         return out
+
+    def _paint_boxes(self, plan: Plan, grid_boxes, label_boxes, feats, out: Optional[torch.Tensor] = None):
+        """A batch of box lists (as `TrainEngine.step_boxes` takes them) on the canvas of `plan` -> (the keywords that make
+        `Plan.forward` read it, labels int64 [B,H,W]).  With a feature table and a box-list instance of the first conv
+        (MSAU_CONV_OWNER, csrc/ownerconv.hip) only the owner map is painted: the embedding grid is piecewise constant, the conv and
+        its weight gradient work from the per-pixel box index and the table.  Otherwise the grid goes into the plan's input buffer
+        -- or into `out`, another buffer of that shape (`TrainEngine.prefetch_boxes`; never the box-list conv then).  On a ragged plan
+        the painters clip to the plan's own level-0 extents: owner map, grid and labels are empty / zero outside the documents as
+        they enter, nothing has to be zeroed afterwards."""
+        from .data import raster
+        B, H, W, dev = plan.B, plan.H, plan.W, self._flat.device
+        ext = plan.extents[0] if plan.ragged else None
+        if feats is not None and out is None and plan._feed_owner(None):
+            ft = feats if isinstance(feats, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(feats, dtype=np.float32)).to(dev)
+            owner, fb, nf, labels = raster.owner_maps(grid_boxes, label_boxes, B, H, W, dev, sizes=ext)
+            return dict(owner=(owner, fb, nf, ft)), labels
+        buf = plan.input_nhwc if out is None else out
+        if feats is None:
+            _, labels = raster.rasterize(grid_boxes, label_boxes, B, H, W, self.channels, self.dtype_name, dev, out=buf, sizes=ext)
+        else:
+            _, labels = raster.rasterize_dense(grid_boxes, label_boxes, feats, B, H, W, self.dtype_name, dev, out=buf, sizes=ext)
+        return dict(nhwc_ready=True, nhwc_clean=True), labels
 
     @torch.no_grad()
     def eval_unet(self, ids: torch.Tensor, labels: torch.Tensor, aux_labels: torch.Tensor, sizes=None, class_weights=None):
@@ -596,21 +601,14 @@ class MSAUWrapper(nn.Module):
         correct) over its pixels with a label in [1, n_class), the prediction being `argmax` of the fp32 logits `forward` returns.
         msau_amd.training.kv_trainer.summarize turns rows into the reference's epoch figures.  No training plan is built or
         touched, parameters and gradients are left alone."""
-        if ids.dim() != 3:
-            raise ValueError("ids must be [B,H,W]")
-        if not ids.is_cuda:
-            raise RuntimeError("MSAUWrapper runs on an MI355X through libmsau_hip.so; input must be a CUDA/HIP tensor "
-                               "(there is no CPU fallback)")
         cw = _device_class_weights(self, class_weights, self.n_class, self._flat.device)
-        ids = ids.to(dtype=torch.int32).contiguous()
+        ids = self._check_ids(ids)
         B, H, W = ids.shape
-        if sizes is not None:
-            sizes = self._check_sizes_for(sizes, B, H, W)
-        plan = self._plan_for_shape(B, H, W, ids.device, False, ragged=sizes is not None)
+        sizes = self._check_sizes_for(sizes, B, H, W)
+        self._need_gpu(ids)
         labels = labels.reshape(B, H, W).contiguous().long()
+        plan = self._plan(B, H, W, ids.device, False, sizes)
         aux_labels = aux_labels.reshape(B, H, W).contiguous().long() if plan.aux is not None else None
-        if sizes is not None:
-            plan.set_extents(sizes)
         plan.forward(self._flat, None, export=False, ids=ids)
         return plan.eval_unet(labels, aux_labels, cw)
 
@@ -791,6 +789,8 @@ class TrainEngine:
         self.sync = GradSync(self.flat_grad, stage_buckets(model._poff, model._total, model.num_blocks), process_group)
         self.world = self.sync.world
         self.use_graph = use_graph
+        self._ar_native = self._ar_started = False       # how the last _fwd_bwd left the gradient exchange (see _allreduce)
+        self._prefetched, self._pf_last = [], 1          # prefetch_boxes: the queue (at most two) and the buffer of the last step
         self._comm = None
         self._init_native_comm(process_group)
         # Graph replays run on a dedicated non-default stream.  Replaying on the legacy NULL stream after the
@@ -950,16 +950,28 @@ class TrainEngine:
                self.eps, self.weight_decay, self._clip(), 1.0 / self.world, self._skip_arr, len(self._skip))
 
     def _allreduce(self):
-        if getattr(self, "_ar_native", False):
+        if self._ar_native:
             return                                       # already in the backward sequence (msau_run_ops_dp)
         if self.sync.active:
-            if getattr(self, "_ar_started", False):
+            if self._ar_started:
                 self.sync.start(0)                       # the end-conv tail: final once every stage is done
             elif os.environ.get("MSAU_DP_BUCKETS", "stage") == "1":
                 self.sync.start_whole()
             else:
                 self.sync.start_all()
             self.sync.finish()
+
+    def _step(self, plan: Plan, labels, x=None, **feed) -> torch.Tensor:
+        """the tail of every eager step: both sweeps (`feed`: the keywords of `_fwd_bwd`), gradient exchange, optimiser -> the loss"""
+        loss = self._fwd_bwd(plan, x, labels, **feed)
+        self._allreduce()
+        self._optim()
+        return loss
+
+    def _eager(self, name: str):
+        """the entry points without a captured-graph form refuse first thing, before they read anything else of the engine"""
+        if self.use_graph:
+            raise RuntimeError(f"{name} is an eager path (use_graph=False)")
 
     def step(self, x: torch.Tensor, labels: torch.Tensor, sizes=None) -> torch.Tensor:
         """One optimisation step.  Returns the (local) loss as a 1-element device tensor (no host sync).
@@ -971,12 +983,8 @@ class TrainEngine:
             sizes = self.model._check_sizes(x, sizes)
         plan = self.model._plan_for(x, training=True, ragged=sizes is not None)
         if not self.use_graph:
-            if sizes is not None:
-                plan.set_extents(sizes)
-            loss = self._fwd_bwd(plan, x, labels)
-            self._allreduce()
-            self._optim()
-            return loss
+            plan.set_extents(sizes)
+            return self._step(plan, labels, x)
         # The captured graphs hold the plan's buffer addresses: they are stored ON the plan (as predict_nhwc does), so
         # that an evicted / rebuilt plan can never be replayed through a stale graph.
         _bury_graphs()
@@ -986,8 +994,7 @@ class TrainEngine:
         gs = self._gstream
         gs.wait_stream(cur)
         with torch.cuda.stream(gs):
-            if sizes is not None:
-                plan.set_extents(sizes)          # (one graph per canvas: the extents buffer is refreshed before every replay)
+            plan.set_extents(sizes)              # (one graph per canvas: the extents buffer is refreshed before every replay)
             if key not in graphs:
                 sx, sl = x.clone(), labels.clone()
                 # warm up outside capture (hipFuncSetAttribute calls, lazy allocations)
@@ -1019,22 +1026,13 @@ class TrainEngine:
         `step(one_hot(ids), labels)`.  Eager only.
         `sizes` (ragged batch, msau_amd.data.ragged.pack_ids): CPU integer [B, 2] of every document's (h, w) at the origin of the
         canvas; ids and labels outside the documents are ignored, loss and gradient are those of `step(one_hot(ids), labels, sizes)`."""
-        if self.use_graph:
-            raise RuntimeError("step_ids is an eager path (use_graph=False)")
-        if ids.dim() != 3:
-            raise ValueError("ids must be [B,H,W]")
-        ids = ids.to(dtype=torch.int32).contiguous()
+        self._eager("step_ids")
+        ids = self.model._check_ids(ids)
         B, H, W = ids.shape
-        if sizes is not None:
-            sizes = self.model._check_sizes_for(sizes, B, H, W)
+        sizes = self.model._check_sizes_for(sizes, B, H, W)
         labels = labels.reshape(B, H, W).contiguous().long()
-        plan = self.model._plan_for_shape(B, H, W, ids.device, True, ragged=sizes is not None)
-        if sizes is not None:
-            plan.set_extents(sizes)
-        loss = self._fwd_bwd(plan, None, labels, ids=ids)
-        self._allreduce()
-        self._optim()
-        return loss
+        plan = self.model._plan(B, H, W, ids.device, True, sizes)
+        return self._step(plan, labels, ids=ids)
 
     def _class_weights(self, class_weights, n_class: int) -> Optional[torch.Tensor]:
         """the class weights on the device, uploaded again only when they change"""
@@ -1052,30 +1050,21 @@ class TrainEngine:
         `stats`: a pair of device tensors (fp32 [B, 2], int32 [B, 2, 2]); the rows of `MSAUWrapper.eval_unet` -- per document the
         losses and (labelled, correct) of this step's forward, the training accuracy of the reference's epoch print -- are then
         written into it by one more launch between the forward and the loss kernel.  None: no such launch."""
-        if self.use_graph:
-            raise RuntimeError("step_unet is an eager path (use_graph=False)")
-        if ids.dim() != 3:
-            raise ValueError("ids must be [B,H,W]")
+        self._eager("step_unet")
         cw = self._class_weights(class_weights, self.model.n_class)
-        ids = ids.to(dtype=torch.int32).contiguous()
+        ids = self.model._check_ids(ids)
         B, H, W = ids.shape
-        if sizes is not None:
-            sizes = self.model._check_sizes_for(sizes, B, H, W)
+        sizes = self.model._check_sizes_for(sizes, B, H, W)
         labels = labels.reshape(B, H, W).contiguous().long()
-        plan = self.model._plan_for_shape(B, H, W, ids.device, True, ragged=sizes is not None)
+        plan = self.model._plan(B, H, W, ids.device, True, sizes)
         aux_labels = aux_labels.reshape(B, H, W).contiguous().long() if plan.aux is not None else None
-        if sizes is not None:
-            plan.set_extents(sizes)
         if stats is None:
             loss_grads = lambda p: p.loss_grads_unet(labels, aux_labels, cw)
         else:
             def loss_grads(p):
                 p.eval_unet(labels, aux_labels, cw, out=stats)
                 return p.loss_grads_unet(labels, aux_labels, cw)
-        loss = self._fwd_bwd(plan, None, None, ids=ids, loss_grads=loss_grads)
-        self._allreduce()
-        self._optim()
-        return loss
+        return self._step(plan, None, ids=ids, loss_grads=loss_grads)
 
     def step_kv(self, tables, class_weights=None, round_to: int = 16, stats=None) -> torch.Tensor:
         """One optimisation step on a group of key-value documents given as their training tables
@@ -1083,8 +1072,7 @@ class TrainEngine:
         canvas and both label canvases (msau_kv_paint_train), then `step_unet` on them with the documents' sizes.  No per-pixel
         array is built on the host and nothing waits for the device -- except for a document whose table is not `ok`, which is
         painted on the host and uploaded (kv_data.STATS counts them).  `stats` as in `step_unet`."""
-        if self.use_graph:
-            raise RuntimeError("step_kv is an eager path (use_graph=False)")
+        self._eager("step_kv")
         from .training import kv_data
         ids, labels, aux_labels, sizes = kv_data.paint_train_device(tables, round_to=round_to, device=self.model._flat.device)
         return self.step_unet(ids, labels, aux_labels, sizes=sizes, class_weights=class_weights, stats=stats)
@@ -1099,8 +1087,7 @@ class TrainEngine:
         dtype) -- what the device painters produce (data_generator_funsd_bert.py:64-93,240).  When `grid` is
         the plan's own buffer (`input_nhwc(B, H, W)`) nothing is copied or converted; otherwise one device copy.  `step(x, l)`
         on the same grid as fp32 NCHW spends a quarter of the 768-channel step (cfg 4) converting 4.2 GB: identical result."""
-        if self.use_graph:
-            raise RuntimeError("step_nhwc is an eager path (use_graph=False)")
+        self._eager("step_nhwc")
         B, H, W, Cs = grid.shape
         plan = self.model._plan_for_shape(B, H, W, grid.device, True)
         buf = plan.input_nhwc
@@ -1109,10 +1096,7 @@ class TrainEngine:
         if grid.data_ptr() != buf.data_ptr():
             buf.copy_(grid)
         labels = labels.reshape(B, H, W).contiguous().long()
-        loss = self._fwd_bwd(plan, None, labels, nhwc_ready=True)
-        self._allreduce()
-        self._optim()
-        return loss
+        return self._step(plan, labels, nhwc_ready=True)
 
     def step_boxes(self, grid_boxes, label_boxes, B: int, H: int, W: int, feats=None, sizes=None) -> torch.Tensor:
         """One optimisation step from BOX LISTS (int32 [n][6] = sample, y0, y1, x0, x1, value; msau_amd/data/raster.py): the
@@ -1123,72 +1107,29 @@ class TrainEngine:
         H x W canvas, every document's boxes in its own coordinates.  Each box is clipped at its own document's edge, the loss is
         the mean of the documents' losses as `step(x, labels, sizes)` defines it, and with `feats` the grid is still never
         painted (the box-list instance of the first conv implements the extents).  Eager only."""
-        from .data import raster
-        if sizes is not None:
-            if self.use_graph:
-                raise RuntimeError("step_boxes: a ragged batch (sizes=...) is an eager path (use_graph=False); there is no "
-                                   "captured-graph form of it")
-            return self._step_boxes_ragged(grid_boxes, label_boxes, B, H, W, feats, self.model._check_sizes_for(sizes, B, H, W))
-        plan = self.model._plan_for_shape(B, H, W, self.model._flat.device, True)
-        if feats is not None and not self.use_graph and plan._feed_owner(None):
-            # the embedding grid is piecewise constant: the first conv and its weight gradient work from the per-pixel box index
-            # and the feature table (MSAU_CONV_OWNER, csrc/ownerconv.hip) -- the 1536-bytes-per-pixel tensor is never painted
-            dev = self.model._flat.device
-            ft = feats if isinstance(feats, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(feats, dtype=np.float32)).to(dev)
-            owner, fb, nf, labels = raster.owner_maps(grid_boxes, label_boxes, B, H, W, dev)
-            loss = self._fwd_bwd(plan, None, labels, owner=(owner, fb, nf, ft))
-            self._allreduce()
-            self._optim()
-            return loss
-        buf = self.input_nhwc(B, H, W)
-        if feats is None:
-            _, labels = raster.rasterize(grid_boxes, label_boxes, B, H, W, self.model.channels, self.model.dtype_name, buf.device, out=buf)
-        else:
-            _, labels = raster.rasterize_dense(grid_boxes, label_boxes, feats, B, H, W, self.model.dtype_name, buf.device, out=buf)
-        return self.step_nhwc(buf, labels)
-
-    def _step_boxes_ragged(self, grid_boxes, label_boxes, B: int, H: int, W: int, feats, sizes) -> torch.Tensor:
-        """`step_boxes` on a ragged plan: the painters clip to the plan's own level-0 extents, so owner map, grid and labels are
-        empty / zero outside the documents -- the plan's invariant holds as they enter, nothing has to be zeroed afterwards"""
-        from .data import raster
-        dev = self.model._flat.device
-        plan = self.model._plan_for_shape(B, H, W, dev, True, ragged=True)
-        plan.set_extents(sizes)
-        ext = plan.extents[0]
-        if feats is not None and plan._feed_owner(None):
-            ft = feats if isinstance(feats, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(feats, dtype=np.float32)).to(dev)
-            owner, fb, nf, labels = raster.owner_maps(grid_boxes, label_boxes, B, H, W, dev, sizes=ext)
-            loss = self._fwd_bwd(plan, None, labels, owner=(owner, fb, nf, ft))
-        else:
-            buf = plan.input_nhwc
-            if feats is None:
-                _, labels = raster.rasterize(grid_boxes, label_boxes, B, H, W, self.model.channels, self.model.dtype_name, dev, out=buf,
-                                             sizes=ext)
-            else:
-                _, labels = raster.rasterize_dense(grid_boxes, label_boxes, feats, B, H, W, self.model.dtype_name, dev, out=buf, sizes=ext)
-            loss = self._fwd_bwd(plan, None, labels, nhwc_ready=True, nhwc_clean=True)
-        self._allreduce()
-        self._optim()
-        return loss
+        self._eager("step_boxes")
+        m = self.model
+        sizes = m._check_sizes_for(sizes, B, H, W)
+        plan = m._plan(B, H, W, m._flat.device, True, sizes)
+        feed, labels = m._paint_boxes(plan, grid_boxes, label_boxes, feats)
+        return self._step(plan, labels, **feed)
 
     def prefetch_boxes(self, grid_boxes, label_boxes, B: int, H: int, W: int, feats=None, sizes=None):
         """Paint the NEXT batch (arguments as `step_boxes`) while the current step runs: the grid goes into the input buffer the
         current step does not read (the plan keeps two), on the plan's side stream -- idle during the forward sweep, which is
         when the painter's store (2.1 GB per batch at 768 channels) is absorbed.  `step_prefetched()` then trains on it.  The
         data-loader counterpart of the reference's generator thread (data_generator_funsd_bert.py:216-240)."""
-        from .data import raster
+        self._eager("prefetch_boxes")
         if sizes is not None:
             raise NotImplementedError("prefetch_boxes paints dense batches only: a ragged batch (sizes=...) goes through "
                                       "step_boxes(..., sizes=sizes)")
-        if self.use_graph:
-            raise RuntimeError("prefetch_boxes is an eager path (use_graph=False)")
         plan = self.model._plan_for_shape(B, H, W, self.model._flat.device, True)
-        q = self.__dict__.setdefault("_prefetched", [])
+        q = self._prefetched
         if len(q) >= 2:
             # the plan keeps TWO input buffers: a third batch would be painted over one that is still queued, unread
             raise RuntimeError("prefetch_boxes: two batches are already queued (the plan has two input buffers); call "
                                "step_prefetched() before painting another one")
-        k = (q[-1][1] + 1) % 2 if q else (getattr(self, "_pf_last", 1) + 1) % 2
+        k = (q[-1][1] + 1) % 2 if q else (self._pf_last + 1) % 2
         buf = plan.input_buffer(k)
         cur = torch.cuda.current_stream()
         if plan._side is None:
@@ -1196,10 +1137,7 @@ class TrainEngine:
         side = plan._side
         side.wait_stream(cur)                    # the buffer's last readers (two steps back) are behind everything enqueued so far
         with torch.cuda.stream(side):
-            if feats is None:
-                _, labels = raster.rasterize(grid_boxes, label_boxes, B, H, W, self.model.channels, self.model.dtype_name, buf.device, out=buf)
-            else:
-                _, labels = raster.rasterize_dense(grid_boxes, label_boxes, feats, B, H, W, self.model.dtype_name, buf.device, out=buf)
+            _, labels = self.model._paint_boxes(plan, grid_boxes, label_boxes, feats, out=buf)
             ev = torch.cuda.Event()
             ev.record(side)
         labels.record_stream(cur)
@@ -1211,10 +1149,7 @@ class TrainEngine:
         self._pf_last = k
         torch.cuda.current_stream().wait_event(ev)
         plan.use_input(k)
-        loss = self._fwd_bwd(plan, None, labels, nhwc_ready=True)
-        self._allreduce()
-        self._optim()
-        return loss
+        return self._step(plan, labels, nhwc_ready=True)
 
     @property
     def grad_norm(self) -> torch.Tensor:

@@ -1097,8 +1097,10 @@ class Plan:
 
     def set_extents(self, sizes) -> None:
         """refresh the device extents of a ragged plan from the CPU sizes [B, 2] (an ordinary copy on the current stream: a captured
-        graph reads the new extents at its next replay)"""
-        assert self.ragged
+        graph reads the new extents at its next replay).  A dense plan has none and takes only None."""
+        if not self.ragged:
+            assert sizes is None, "sizes on a dense plan"
+            return
         host = self.level_extents(self.check_sizes(sizes, self.B, self.H, self.W), len(self.levels))
         if str(self.device).startswith("cuda"):
             host = host.pin_memory()
@@ -1686,13 +1688,25 @@ class Plan:
             return
         L.call("msau_onehot_ids", self._stream(), self.dtype, ids.data_ptr(), a.data.data_ptr(), a.npix, a.C, a.Cs)
 
-    def predict(self, flat_params: torch.Tensor, x_nchw: Optional[torch.Tensor] = None, ids: Optional[torch.Tensor] = None):
-        """Forward-only sweep ending in the inference head -> (probs fp32 [B,H,W,n_class], argmax uint8 [B,H,W]),
-        the NHWC layout `KVModel._extract_value` consumes (kv_model.py:305-313).  The buffers are the plan's own."""
-        assert not self.training and self.head_probs is not None
-        s = self._stream()
-        self.pack(flat_params)
-        if ids is not None:
+    def _feed(self, flat_params: torch.Tensor, x_nchw: Optional[torch.Tensor], ids: Optional[torch.Tensor] = None, owner=None,
+              nhwc_ready: bool = False, nhwc_clean: bool = False):
+        """Point the first conv at this sweep's input (box lists, the painted buffer, an id mask or the NCHW tensor: the keywords
+        of `forward`), un-feeding whatever an earlier sweep of this plan left there, and enqueue the boundary launch it needs."""
+        if owner is not None:
+            # box lists instead of a painted input (`owner` as Plan._feed_owner takes it); the caller checked that an instance exists
+            assert x_nchw is None and ids is None and not nhwc_ready
+            ok = self._feed_owner(owner, flat_params)
+            assert ok, "no MSAU_CONV_OWNER instance for this plan's first conv"
+            return
+        if getattr(self, "_owner_keep", None) is not None:
+            self._feed_owner(None)
+        if nhwc_ready:
+            assert x_nchw is None and ids is None
+            self._feed_ids(None)
+            if self.ragged and not nhwc_clean:
+                a = self.x_in
+                self._zero_outside(a.data, a.data, 1, self.H, self.W, a.data.element_size() * a.Cs)
+        elif ids is not None:
             assert ids.dtype == torch.int32 and ids.is_contiguous() and tuple(ids.shape) == (self.B, self.H, self.W), (ids.shape, ids.dtype)
             if not self._feed_ids(ids):
                 self.load_ids(ids)
@@ -1700,6 +1714,14 @@ class Plan:
             self._feed_ids(None)
             if not self._feed_nchw(x_nchw):
                 self.load_input(x_nchw)
+
+    def predict(self, flat_params: torch.Tensor, x_nchw: Optional[torch.Tensor] = None, ids: Optional[torch.Tensor] = None):
+        """Forward-only sweep ending in the inference head -> (probs fp32 [B,H,W,n_class], argmax uint8 [B,H,W]),
+        the NHWC layout `KVModel._extract_value` consumes (kv_model.py:305-313).  The buffers are the plan's own."""
+        assert not self.training and self.head_probs is not None
+        s = self._stream()
+        self.pack(flat_params)
+        self._feed(flat_params, x_nchw, ids)
         self._run_seq(self._fwd_seq, s)
         if not self.head_fused:
             lg = self.logits
@@ -1748,29 +1770,7 @@ class Plan:
         painters of msau_amd.data.raster with this plan's extents do)."""
         s = self._stream()
         self.pack(flat_params)
-        if owner is not None:
-            # box lists instead of a painted input (`owner` as Plan._feed_owner takes it); the caller checked that an instance exists
-            assert x_nchw is None and ids is None and not nhwc_ready
-            ok = self._feed_owner(owner, flat_params)
-            assert ok, "no MSAU_CONV_OWNER instance for this plan's first conv"
-        elif getattr(self, "_owner_keep", None) is not None:
-            self._feed_owner(None)
-        if owner is not None:
-            pass
-        elif nhwc_ready:
-            assert x_nchw is None and ids is None
-            self._feed_ids(None)
-            if self.ragged and not nhwc_clean:
-                a = self.x_in
-                self._zero_outside(a.data, a.data, 1, self.H, self.W, a.data.element_size() * a.Cs)
-        elif ids is not None:
-            assert ids.dtype == torch.int32 and ids.is_contiguous() and tuple(ids.shape) == (self.B, self.H, self.W), (ids.shape, ids.dtype)
-            if not self._feed_ids(ids):
-                self.load_ids(ids)
-        else:
-            self._feed_ids(None)
-            if not self._feed_nchw(x_nchw):
-                self.load_input(x_nchw)
+        self._feed(flat_params, x_nchw, ids, owner, nhwc_ready, nhwc_clean)
         if self._fwd_side and not self._one_stream(single_stream):
             if self._side is None:
                 self._side = L.concurrent_stream(self.device)

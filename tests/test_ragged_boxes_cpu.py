@@ -161,6 +161,26 @@ def test_sizes_are_checked_on_the_host_before_any_launch():
         m.confusion_matrix_boxes(none, none, 2, 16, 32, sizes=[[3, 3], [1, 1]])
 
 
+def test_eager_entry_points_refuse_a_graph_engine_under_their_own_name_before_anything_else():
+    """every argument below fails at whatever looks at it, and the engine has no attribute but `model` and `use_graph`: the refusal
+    comes first"""
+    m = MSAUWrapper(13, 5, dict(scale_space_num=3, res_depth=1, featRoot=8, num_blocks=2))
+    eng = TrainEngine.__new__(TrainEngine)
+    eng.model, eng.use_graph = m, True
+    cpu = torch.zeros((2, 16, 32))
+    calls = dict(step_ids=lambda: eng.step_ids(None, cpu, sizes=[[17, 3]]),
+                 step_unet=lambda: eng.step_unet(None, cpu, cpu, class_weights=[1.0]),
+                 step_kv=lambda: eng.step_kv(None),
+                 step_nhwc=lambda: eng.step_nhwc(None, cpu),
+                 step_boxes=lambda: eng.step_boxes(None, None, 2, 16, 32),
+                 prefetch_boxes=lambda: eng.prefetch_boxes(None, None, 2, 16, 32))
+    for name, call in calls.items():
+        with pytest.raises(RuntimeError, match=rf"^{name} is an eager path \(use_graph=False\)"):
+            call()
+    with pytest.raises(RuntimeError, match=r"^step_boxes is an eager path \(use_graph=False\)"):
+        eng.step_boxes(None, None, 2, 16, 32, feats=None, sizes=[[17, 3], [1, 1]])
+
+
 @pytest.mark.parametrize("dtype_name,channels", [("fp32", 13), ("bf16", 24), ("bf16", 768)])
 def test_a_ragged_plan_gets_the_box_list_instance_of_its_first_conv(dtype_name, channels):
     """plans build without a device: the first conv of a ragged plan carries MSAU_CONV_EXTENT, and the box-list instance takes it

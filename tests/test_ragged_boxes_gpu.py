@@ -274,6 +274,29 @@ def test_confusion_matrix_boxes(monkeypatch):
     assert torch.equal(m.confusion_matrix_boxes(cb, clb, 3, Hc, Wc).cpu(), m.confusion_matrix(hot_d.to(DEV), clab_d.to(DEV)).cpu())
 
 
+def test_predict_unfeeds_the_box_lists_a_confusion_count_left_in_the_plan(monkeypatch):
+    """`confusion_matrix_boxes` leaves the forward-only plan's first conv on the box lists; `Plan.predict` of the same plan puts it back
+    on the tensor itself and gives the bits of a model that never saw a box list"""
+    monkeypatch.setenv("MSAU_OWNER_CONV", "1")
+    rng = np.random.default_rng(23)
+    C = 24
+    docs = [_box_doc(rng, h, w, 14, C) for h, w in DOCS]
+    gb, lb, feats, sizes, (H, W) = pack_boxes(docs)
+    B = len(docs)
+    assert (B, H, W) == (3, 48, 48)
+    x = pack(_host_docs(docs), round_to=16)[0].to(DEV)
+    m = _model(C).eval()
+    m.confusion_matrix_boxes(gb, lb, B, H, W, feats=feats, sizes=sizes)
+    plan = m._plan_for_shape(B, H, W, DEV, False, ragged=True)
+    assert plan._owner_keep is not None                         # nobody un-fed it
+    probs, amax = (t.clone() for t in m.predict_nhwc(inp=x, sizes=sizes))
+    assert plan._owner_keep is None
+    want_probs, want_amax = (t.clone() for t in _model(C).eval().predict_nhwc(inp=x, sizes=sizes))
+    torch.cuda.synchronize()
+    assert torch.equal(probs, want_probs) and torch.equal(amax, want_amax)
+    assert float(want_probs.abs().max()) > 0
+
+
 # ---- 7. errors ------------------------------------------------------------------------------------------------------------------
 def test_ragged_box_feeds_refuse_what_they_do_not_implement():
     rng = np.random.default_rng(19)
