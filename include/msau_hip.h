@@ -193,7 +193,8 @@ int msau_conv2d(void* stream, int dtype, const msau_conv_desc* d);
  * info[0] = CT (16-row output-channel tiles), info[1] = PT (pixel tiles per wave: tile = 4*PT x 16),
  * info[2] = dynamic LDS bytes, info[3] = workgroups, info[4] = channel chunk, info[5] = chunks,
  * info[6] = 1 if a compile-time-specialised "lean" instance (conv_lean.hip) takes the launch, 2 if the chunked-K instance does,
- *           3 if a row-streaming instance (conv_rows.hip) does,
+ *           3 if a row-streaming instance (conv_rows.hip) does; 0 otherwise: the generic tile kernel, and also a descriptor
+ *           msau_conv2d refuses or gives to the box-list (MSAU_CONV_OWNER) or NCHW (MSAU_CONV_NCHW) instance,
  * info[7] = bit 0: that instance implements MSAU_CONV_HEAD for this descriptor, bit 1: MSAU_CONV_DOUT,
  *           bit 2: MSAU_CONV_LRN, bit 3: MSAU_CONV_POOL, bit 4: MSAU_CONV_IDS, bit 5: MSAU_CONV_OWNER, bit 6: MSAU_CONV_NCHW,
  *           bit 7: MSAU_CONV_EXTENT (the instance that takes the descriptor with the flag added implements it) */

@@ -348,73 +348,7 @@ extern "C" int msau_conv_pack_geometry(int dtype, int C1, int C2, int Cout, int 
     return 0;
 }
 
-static int conv_plan(int dtype, const msau_conv_desc* d, ConvGeom* gout, TileGeom* tout, int* PTout, int64_t* nbout);
-// conv_lean.hip: compile-time-specialised instances for the hot layer shapes
-int msau_conv_lean_applicable(int dtype, const msau_conv_desc* d, int nchunks, int CT);
-int msau_conv_lean_try(hipStream_t s, int dtype, const msau_conv_desc* d, int kchunk, int nchunks, int CT);
-int msau_conv_lean_head_capable(int dtype, const msau_conv_desc* d, int nchunks, int CT);
-int msau_conv_lean_dout_capable(int dtype, const msau_conv_desc* d, int nchunks, int CT);
-int msau_conv_lean_lrn_capable(int dtype, const msau_conv_desc* d, int nchunks, int CT);
-int msau_conv_lean_pool_capable(int dtype, const msau_conv_desc* d, int nchunks, int CT);
-int msau_conv_lean_ids_capable(int dtype, const msau_conv_desc* d, int nchunks, int CT);
-int msau_conv_chunked_try(hipStream_t s, int dtype, const msau_conv_desc* d, int cch, int kchunk, int nchunks, int CT);
-int msau_conv_chunked_capable(int dtype, const msau_conv_desc* d, int cch, int nchunks, int CT);
-int msau_firstconv_takes(int dtype, const msau_conv_desc* d);
-int msau_firstconv_launch(hipStream_t s, int dtype, const msau_conv_desc* d, int real_channels);
-
-// 1 if the instance msau_conv2d runs for `d` (MSAU_CONV_EXTENT set) implements the flag: the box-list instance (MSAU_CONV_OWNER,
-// ownerconv.hip) where it takes the launch, else the generic tile kernel -- no flag that only other instances implement, and none of
-// them takes it (each refuses the flag itself)
-static int conv_takes_extent(int dtype, const msau_conv_desc* d, const ConvGeom& g) {
-    if (d->flags & MSAU_CONV_OWNER) return msau_ownerconv_takes(dtype, d);
-    const int only_others = MSAU_CONV_HEAD | MSAU_CONV_DOUT | MSAU_CONV_LRN | MSAU_CONV_POOL | MSAU_CONV_IDS | MSAU_CONV_NCHW |
-                            MSAU_CONV_WGRAD;
-    if (d->flags & only_others) return 0;
-    if (g.nslices == 1 && (msau_rowconv_takes(dtype, d) || msau_conv_chunked_capable(dtype, d, g.cch, g.nchunks, g.CT) ||
-                           msau_conv_lean_applicable(dtype, d, g.nchunks, g.CT)))
-        return 0;
-    return 1;
-}
-
-extern "C" int msau_conv2d_launch_info(int dtype, const msau_conv_desc* d, int32_t* info) {
-    MSAU_CHECK_ARG(d && info, "conv2d_launch_info: null pointer");
-    ConvGeom g; TileGeom t; int PT; int64_t nb;
-    int rc = conv_plan(dtype, d, &g, &t, &PT, &nb);
-    if (rc) return rc;
-    info[0] = g.CT; info[1] = PT; info[2] = t.total; info[3] = (int32_t)nb; info[4] = g.cch; info[5] = g.nchunks;
-    info[6] = msau_conv_lean_applicable(dtype, d, g.nchunks, g.CT);
-    if (g.nslices == 1 && msau_rowconv_takes(dtype, d)) info[6] = 3;                         // rowconv8_kernel (conv_rows.hip)
-    if (g.nslices == 1 && !(d->flags & (MSAU_CONV_HEAD | MSAU_CONV_DOUT | MSAU_CONV_LRN | MSAU_CONV_POOL | MSAU_CONV_IDS)) &&
-        msau_conv_chunked_capable(dtype, d, g.cch, g.nchunks, g.CT)) info[6] = 2;       // conv_chunked_kernel (conv_lean.hip)
-    info[7] = msau_conv_lean_head_capable(dtype, d, g.nchunks, g.CT) | (msau_conv_lean_dout_capable(dtype, d, g.nchunks, g.CT) << 1) |
-              (((d->flags & MSAU_CONV_DOUT) && g.nslices == 1 && msau_rowconv_takes(dtype, d)) << 1) |
-              (msau_conv_lean_lrn_capable(dtype, d, g.nchunks, g.CT) << 2) | (msau_conv_lean_pool_capable(dtype, d, g.nchunks, g.CT) << 3) |
-              (msau_conv_lean_ids_capable(dtype, d, g.nchunks, g.CT) << 4);
-    {
-        msau_conv_desc p = *d;
-        p.flags |= MSAU_CONV_OWNER;
-        if (msau_ownerconv_takes(dtype, &p)) info[7] |= 32;
-    }
-    {
-        msau_conv_desc p = *d;
-        p.flags |= MSAU_CONV_NCHW;
-        if (msau_firstconv_takes(dtype, &p)) info[7] |= 64;
-    }
-    {                                                    // MSAU_CONV_EXTENT: the generic tile kernel is the one instance with it
-        msau_conv_desc p = *d;
-        p.flags |= MSAU_CONV_EXTENT;
-        if (conv_takes_extent(dtype, &p, g)) info[7] |= 128;
-    }
-    if (g.nslices == 1 && !(info[7] & 4)) {              // would a row-streaming instance take this launch with MSAU_CONV_LRN added?
-        msau_conv_desc p = *d;
-        p.flags |= MSAU_CONV_LRN;
-        if (!p.y2) p.y2 = p.y;
-        if (!(p.lrn_k > 0.f)) p.lrn_k = 1.f;
-        if (msau_rowconv_takes(dtype, &p)) info[7] |= 4;
-    }
-    return 0;
-}
-
+// the tile kernel's geometry for `d`: channel chunks, pixel tiles per wave (tile = 4*PT x 16), LDS, workgroups
 static int conv_plan(int dtype, const msau_conv_desc* d, ConvGeom* gout, TileGeom* tout, int* PTout, int64_t* nbout) {
     ConvGeom g;
     int rc = conv_geom(dtype, d->C1, d->C2, d->Cout, d->KH, d->KW, d->dil, d->stride, d->ups, &g);
@@ -431,88 +365,138 @@ static int conv_plan(int dtype, const msau_conv_desc* d, ConvGeom* gout, TileGeo
     return 0;
 }
 
-extern "C" int msau_conv2d(void* stream, int dtype, const msau_conv_desc* d) {
-    MSAU_CHECK_ARG(d && d->x1 && d->wpack && d->y, "conv2d: null pointer");
-    MSAU_CHECK_ARG(d->B > 0 && d->Hin > 0 && d->Win > 0 && d->Hout > 0 && d->Wout > 0, "conv2d: bad dims");
-    MSAU_CHECK_ARG(d->C1 % 8 == 0 && d->C2 % 8 == 0 && (d->C2 == 0 || d->x2), "conv2d: bad sources");
-    MSAU_CHECK_ARG(!(d->flags & MSAU_CONV_ADD) || d->add, "conv2d: ADD without pointer");
-    MSAU_CHECK_ARG(!(d->flags & MSAU_CONV_MASK_A) || d->mask_a, "conv2d: MASK_A without pointer");
-    MSAU_CHECK_ARG(!(d->flags & MSAU_CONV_MASK_B) || d->mask_b, "conv2d: MASK_B without pointer");
-    if (d->flags & MSAU_CONV_EXTENT) {                                         // ragged batch: the generic tile kernel only
-        MSAU_CHECK_ARG(d->extent, "conv2d: MSAU_CONV_EXTENT without extent pointer");
-        ConvGeom g;
-        int rc = conv_geom(dtype, d->C1, d->C2, d->Cout, d->KH, d->KW, d->dil, d->stride, d->ups, &g);
-        if (rc) return rc;
-        if (!conv_takes_extent(dtype, d, g))
+// ---- routing: which instance runs a descriptor.  conv_route is the one place that knows: msau_conv2d launches what it names,
+// msau_conv2d_launch_info and msau_conv2d_rider_slabs report what it names ("conv2d routing").
+enum { CONV_TILE = 0, CONV_LEAN = 1, CONV_CHUNKED = 2, CONV_ROWS = 3,          // (the numbers of info[6])
+       CONV_OWNER = 4, CONV_FIRST_NCHW = 5, CONV_REFUSED = 6 };
+// flags the tile kernel does not implement, in the order a refusal names them (MSAU_CONV_EXTENT, which it does implement, first:
+// the flag does not combine with any of the others, box lists excepted)
+constexpr int kRefusalOrder[] = {MSAU_CONV_EXTENT, MSAU_CONV_WGRAD, MSAU_CONV_OWNER, MSAU_CONV_NCHW, MSAU_CONV_HEAD, MSAU_CONV_DOUT,
+                                 MSAU_CONV_LRN, MSAU_CONV_IDS, MSAU_CONV_POOL};
+constexpr int kOnlyOthers = MSAU_CONV_WGRAD | MSAU_CONV_OWNER | MSAU_CONV_NCHW | MSAU_CONV_HEAD | MSAU_CONV_DOUT | MSAU_CONV_LRN |
+                            MSAU_CONV_IDS | MSAU_CONV_POOL;
+struct ConvRoute {
+    int family, inst;              // CONV_*, and the instance inside the family (what <family>_case said; the tile kernel's is g.CT, PT)
+    int refused;                   // CONV_REFUSED: the flag no instance implements for this descriptor
+    int geom_rc;                   // CONV_OWNER / CONV_FIRST_NCHW run without the geometry below: its error, if it had one
+    ConvGeom g; TileGeom t; int PT; int64_t nb;      // the tile kernel's geometry = the packed image's, whichever family runs
+};
+
+// Pure host arithmetic.  The order of preference: the two feeds of the first conv (their flag admits nothing else), row-streaming,
+// chunked, lean, tile kernel.  `families`: bit CONV_x clear = leave that family out (msau_conv2d_launch_info's questions).
+static int conv_route(int dtype, const msau_conv_desc* d, ConvRoute* r, int families = ~0) {
+    const int f = d->flags;
+    auto asked = [&](int family) { return (families >> family) & 1; };
+    *r = ConvRoute{};
+    r->family = CONV_REFUSED;
+    const int rc = r->geom_rc = conv_plan(dtype, d, &r->g, &r->t, &r->PT, &r->nb);
+    if (f & MSAU_CONV_OWNER) {                                                 // ownerconv.hip: box lists instead of a painted input tensor
+        if (asked(CONV_OWNER) && msau_ownerconv_takes(dtype, d)) { r->family = CONV_OWNER; r->inst = 1; return 0; }
+    } else if (f & MSAU_CONV_NCHW) {                                           // conv_first.hip: the fp32 NCHW input tensor itself
+        if (asked(CONV_FIRST_NCHW) && msau_firstconv_takes(dtype, d)) { r->family = CONV_FIRST_NCHW; r->inst = 1; return 0; }
+    } else if (!rc) {
+        const ConvGeom& g = r->g;
+        if (g.nslices > 1) r->inst = 0;                                        // more than 128 output channels: slices of the tile kernel
+        else if (asked(CONV_ROWS) && (r->inst = msau_rowconv_case(dtype, d))) r->family = CONV_ROWS;
+        else if (asked(CONV_CHUNKED) && (r->inst = msau_conv_chunked_case(dtype, d, g.cch, g.nchunks, g.CT))) r->family = CONV_CHUNKED;
+        else if (asked(CONV_LEAN) && (r->inst = msau_conv_lean_case(dtype, d, g.nchunks, g.CT))) r->family = CONV_LEAN;
+        if (r->family == CONV_REFUSED && asked(CONV_TILE) && !(f & kOnlyOthers)) r->family = CONV_TILE;
+    }
+    if (rc) return rc;
+    if (r->family == CONV_REFUSED)
+        for (int flag : kRefusalOrder)
+            if (f & flag) { r->refused = flag; break; }
+    return 0;
+}
+
+static int conv_refusal(const msau_conv_desc* d, int flag) {
+    switch (flag) {
+        case MSAU_CONV_EXTENT:
             return msau_set_error(MSAU_ERR_ARG, "conv2d: MSAU_CONV_EXTENT is not implemented for this launch (flags 0x%x; see "
                                   "msau_conv2d_launch_info info[7] & 128): only the generic tile kernel and the box-list instance have it", d->flags);
-    }
-    if (d->flags & MSAU_CONV_WGRAD)                                            // a rider only the row-streaming coupling instance carries
-        MSAU_CHECK_ARG(msau_conv2d_rider_slabs(dtype, d) > 0, "conv2d: MSAU_CONV_WGRAD is not implemented for this launch (msau_conv2d_rider_slabs says 0)");
-    if (d->flags & MSAU_CONV_OWNER) {                                          // ownerconv.hip: box lists instead of a painted input tensor
-        MSAU_CHECK_ARG(msau_ownerconv_takes(dtype, d), "conv2d: MSAU_CONV_OWNER is the 3x3 stride-1 C -> 8 conv, no other flag but RELU_OUT and EXTENT");
-        return msau_ownerconv_fwd(static_cast<hipStream_t>(stream), dtype, d);
-    }
-    if (d->flags & MSAU_CONV_NCHW) {                                           // conv_first.hip: the fp32 NCHW input tensor itself
-        MSAU_CHECK_ARG(msau_firstconv_takes(dtype, d) && d->head_classes > 0 && d->head_classes <= d->C1,
-                       "conv2d: MSAU_CONV_NCHW is the bf16 3x3 64 -> 8 conv (W %% 4 == 0, W <= 288), head_classes = real input channels");
-        return msau_firstconv_launch(static_cast<hipStream_t>(stream), dtype, d, d->head_classes);
-    }
-    ConvGeom g; TileGeom t; int PT; int64_t nb;
-    int rc = conv_plan(dtype, d, &g, &t, &PT, &nb);
-    if (rc) return rc;
-    if (d->flags & MSAU_CONV_HEAD) {
-        MSAU_CHECK_ARG(d->head_probs && d->head_argmax && d->head_classes > 0 && d->head_classes <= 16 &&
-                       d->head_classes <= d->Cout && d->flags == MSAU_CONV_HEAD, "conv2d: bad HEAD arguments");
-        if (!msau_conv_lean_head_capable(dtype, d, g.nchunks, g.CT))
+        case MSAU_CONV_WGRAD:
+            return msau_set_error(MSAU_ERR_ARG, "conv2d: MSAU_CONV_WGRAD is not implemented for this launch (msau_conv2d_rider_slabs says 0)");
+        case MSAU_CONV_OWNER:
+            return msau_set_error(MSAU_ERR_ARG, "conv2d: MSAU_CONV_OWNER is the 3x3 stride-1 C -> 8 conv, no other flag but RELU_OUT and EXTENT");
+        case MSAU_CONV_NCHW:
+            return msau_set_error(MSAU_ERR_ARG, "conv2d: MSAU_CONV_NCHW is the bf16 3x3 64 -> 8 conv (W %% 4 == 0, W <= 288), head_classes = real input channels");
+        case MSAU_CONV_HEAD:
             return msau_set_error(MSAU_ERR_ARG, "conv2d: MSAU_CONV_HEAD is not implemented for this launch (see "
                                   "msau_conv2d_launch_info info[7]); run msau_softmax_argmax_nhwc on y instead");
-    }
-    if (d->flags & MSAU_CONV_DOUT) {
-        const int okf = MSAU_CONV_DOUT | MSAU_CONV_ADD | MSAU_CONV_ACCUM | MSAU_CONV_MASK_B | MSAU_CONV_WGRAD;   // (WGRAD: checked above)
-        MSAU_CHECK_ARG(d->y2 && !(d->flags & ~okf) && !(d->flags2 & ~(MSAU_CONV_ACCUM | MSAU_CONV_MASK_B)) &&
-                       (!(d->flags2 & MSAU_CONV_MASK_B) || d->mask_b2), "conv2d: bad DOUT arguments");
-        if (!msau_conv_lean_dout_capable(dtype, d, g.nchunks, g.CT) && !(g.nslices == 1 && msau_rowconv_takes(dtype, d)))
+        case MSAU_CONV_DOUT:
             return msau_set_error(MSAU_ERR_ARG, "conv2d: MSAU_CONV_DOUT is not implemented for this launch (see "
                                   "msau_conv2d_launch_info info[7]); issue one launch per output instead");
-    }
-    if (d->flags & MSAU_CONV_LRN) {
-        MSAU_CHECK_ARG(d->y2 && !(d->flags & ~(MSAU_CONV_LRN | MSAU_CONV_RELU_IN)) && d->lrn_k > 0.f, "conv2d: bad LRN arguments");
-        if (!msau_conv_lean_lrn_capable(dtype, d, g.nchunks, g.CT) && !(g.nslices == 1 && msau_rowconv_takes(dtype, d)))
+        case MSAU_CONV_LRN:
             return msau_set_error(MSAU_ERR_ARG, "conv2d: MSAU_CONV_LRN is not implemented for this launch (see "
                                   "msau_conv2d_launch_info info[7]); run msau_lrn_fwd on y instead");
-    }
-    if (d->flags & MSAU_CONV_IDS) {
-        if (!msau_conv_lean_ids_capable(dtype, d, g.nchunks, g.CT))
+        case MSAU_CONV_IDS:
             return msau_set_error(MSAU_ERR_ARG, "conv2d: MSAU_CONV_IDS is not implemented for this launch (see msau_conv2d_launch_info "
                                   "info[7] & 16); paint the one-hot input with msau_onehot_ids instead");
-    }
-    if (d->flags & MSAU_CONV_POOL) {
-        MSAU_CHECK_ARG(d->pool_y && !(d->flags & (MSAU_CONV_DOUT | MSAU_CONV_HEAD | MSAU_CONV_LRN)), "conv2d: bad POOL arguments");
-        if (!msau_conv_lean_pool_capable(dtype, d, g.nchunks, g.CT))
+        default:
             return msau_set_error(MSAU_ERR_ARG, "conv2d: MSAU_CONV_POOL is not implemented for this launch (see "
                                   "msau_conv2d_launch_info info[7]); run msau_maxpool2x2_fwd on y instead");
     }
-    if (g.nslices == 1 && msau_rowconv_takes(dtype, d))                       // conv_rows.hip: row-streaming instances (level 0)
-        return msau_rowconv_launch(static_cast<hipStream_t>(stream), dtype, d, g.kchunk, g.rows);
-    if (g.nslices == 1 && !(d->flags & (MSAU_CONV_HEAD | MSAU_CONV_DOUT | MSAU_CONV_LRN | MSAU_CONV_POOL | MSAU_CONV_IDS))) {
-        rc = msau_conv_chunked_try(static_cast<hipStream_t>(stream), dtype, d, g.cch, g.kchunk, g.nchunks, g.CT);
-        if (rc != 0) return rc < 0 ? rc : 0;
+}
+
+// One question of msau_conv2d_launch_info: the family that runs `d` with `flag` added (and its placeholder operands), the flags
+// `ignore` dropped, among `families`; -1 = refused.
+static int conv_offers(int dtype, const msau_conv_desc* d, int flag, int ignore = 0, int families = ~0) {
+    msau_conv_desc p = *d;
+    p.flags = (p.flags & ~ignore) | flag;
+    if (flag == MSAU_CONV_LRN) {
+        if (!p.y2) p.y2 = p.y;
+        if (!(p.lrn_k > 0.f)) p.lrn_k = 1.f;
     }
-    if (g.nslices == 1) {
-        rc = msau_conv_lean_try(static_cast<hipStream_t>(stream), dtype, d, g.kchunk, g.nchunks, g.CT);
-        if (rc != 0) return rc < 0 ? rc : 0;
-    }
-    if (d->flags & MSAU_CONV_DOUT) return msau_set_error(MSAU_ERR_ARG, "conv2d: DOUT launch was not taken by a lean instance");
-    MSAU_CHECK_ARG(g.nslices == 1 || !(d->flags & MSAU_CONV_HEAD), "conv2d: HEAD with more than 128 output channels");
-    hipStream_t s = static_cast<hipStream_t>(stream);
+    ConvRoute r;
+    return conv_route(dtype, &p, &r, families) || r.family == CONV_REFUSED ? -1 : r.family;
+}
+
+extern "C" int msau_conv2d_launch_info(int dtype, const msau_conv_desc* d, int32_t* info) {
+    MSAU_CHECK_ARG(d && info, "conv2d_launch_info: null pointer");
+    ConvRoute r;
+    int rc = conv_route(dtype, d, &r);
+    if (rc || r.geom_rc) return rc ? rc : r.geom_rc;     // (info[0..5] are the geometry, also where the launch does without it)
+    info[0] = r.g.CT; info[1] = r.PT; info[2] = r.t.total; info[3] = (int32_t)r.nb; info[4] = r.g.cch; info[5] = r.g.nchunks;
+    info[6] = r.family <= CONV_ROWS ? r.family : 0;
+    // info[7]: would the launch take the flag?  Bits 4-7 are the router's answer for `d` with the flag added.  Bits 0-3 keep the
+    // answers the plan was built on, which are narrower questions:
+    //  - HEAD, DOUT, LRN, POOL are asked of the lean family alone, whatever fused output or input feed `d` carries already
+    //    (LRN and POOL: whatever input feed; a second fused output refuses them);
+    //  - the row-streaming family is asked about LRN with `d`'s flags as they are, and counts for DOUT only when `d` has the
+    //    flag already (the plan decides about MSAU_CONV_DOUT on a bare prototype, before the small-image row instances exist for it).
+    const int lean = 1 << CONV_LEAN, rows = 1 << CONV_ROWS;
+    const int feeds = MSAU_CONV_IDS | MSAU_CONV_OWNER | MSAU_CONV_NCHW | MSAU_CONV_WGRAD;
+    const int fused = MSAU_CONV_HEAD | MSAU_CONV_DOUT | MSAU_CONV_LRN | MSAU_CONV_POOL;
+    info[7] = (conv_offers(dtype, d, MSAU_CONV_HEAD, feeds | fused, lean) == CONV_LEAN) |
+              ((conv_offers(dtype, d, MSAU_CONV_DOUT, feeds | fused, lean) == CONV_LEAN ||
+                ((d->flags & MSAU_CONV_DOUT) && r.family == CONV_ROWS)) << 1) |
+              ((conv_offers(dtype, d, MSAU_CONV_LRN, feeds, lean) == CONV_LEAN || conv_offers(dtype, d, MSAU_CONV_LRN, 0, rows) == CONV_ROWS) << 2) |
+              ((conv_offers(dtype, d, MSAU_CONV_POOL, feeds, lean) == CONV_LEAN) << 3) |
+              ((conv_offers(dtype, d, MSAU_CONV_IDS) == CONV_LEAN) << 4) |
+              ((conv_offers(dtype, d, MSAU_CONV_OWNER) == CONV_OWNER) << 5) |
+              ((conv_offers(dtype, d, MSAU_CONV_NCHW) == CONV_FIRST_NCHW) << 6) |
+              ((conv_offers(dtype, d, MSAU_CONV_EXTENT) >= 0) << 7);
+    return 0;
+}
+
+// slabs (= workgroups) of an MSAU_CONV_WGRAD launch of this descriptor; 0 if no instance takes the flag
+extern "C" int msau_conv2d_rider_slabs(int dtype, const msau_conv_desc* d) {
+    ConvRoute r;
+    if (!d || !(d->flags & MSAU_CONV_WGRAD) || conv_route(dtype, d, &r) || r.family != CONV_ROWS) return 0;
+    return msau_rowconv_workgroups(d);                   // (the row-streaming coupling instance is the one that carries the rider)
+}
+
+static int tile_launch(hipStream_t s, int dtype, const msau_conv_desc* d, const ConvRoute& r) {
+    const ConvGeom& g = r.g;
+    const TileGeom& t = r.t;
+    const int PT = r.PT;
     // row split: with few pixel tiles (the 21 x 16 and 11 x 8 pixel levels of the reference's constructor defaults: 48-96
     // tiles for 256 CUs) a workgroup takes only `cts` of the CT channel tiles and blockIdx.y the rest -- every workgroup
     // staged all 128 rows of every K chunk (147 KB per chunk at 64 channels x 3x3) for 16 pixels of work per wave: 60 us per
     // launch for a 0.3 MB tensor.  The packed image and the channel order do not change.
     static const int split_wgs = getenv("MSAU_CONV_ROWSPLIT") ? atoi(getenv("MSAU_CONV_ROWSPLIT")) : 768;    // workgroups aimed for; 0 = off
     int cts = g.CT;
-    while (cts > 1 && nb * g.nslices * (g.CT / cts) < split_wgs) cts >>= 1;
+    while (cts > 1 && r.nb * g.nslices * (g.CT / cts) < split_wgs) cts >>= 1;
     const int w_bytes = roundup(cts * 16 * t.WS, 16), lds_total = t.in_bytes + w_bytes + t.tab_bytes;
     for (int sl = 0; sl < g.nslices; ++sl) {
         ConvArgs a;
@@ -533,9 +517,51 @@ extern "C" int msau_conv2d(void* stream, int dtype, const msau_conv_desc* d) {
         a.TIH = t.TIH; a.TIW = t.TIW; a.PS = t.PS; a.WS = t.WS; a.in_bytes = t.in_bytes; a.w_bytes = w_bytes;
         a.tiles_x = cdiv(d->Wout, 16); a.tiles_y = cdiv(d->Hout, 4 * PT);
         a.ct_total = g.CT; a.rows_total = g.rows;
-        rc = dtype == MSAU_F32 ? launch_conv_ct<float>(s, a, cts, PT, (int)nb, g.CT / cts, lds_total)
-                               : launch_conv_ct<bf16_t>(s, a, cts, PT, (int)nb, g.CT / cts, lds_total);
+        int rc = dtype == MSAU_F32 ? launch_conv_ct<float>(s, a, cts, PT, (int)r.nb, g.CT / cts, lds_total)
+                                   : launch_conv_ct<bf16_t>(s, a, cts, PT, (int)r.nb, g.CT / cts, lds_total);
         if (rc) return rc;
     }
     return 0;
+}
+
+extern "C" int msau_conv2d(void* stream, int dtype, const msau_conv_desc* d) {
+    MSAU_CHECK_ARG(d && d->x1 && d->wpack && d->y, "conv2d: null pointer");
+    MSAU_CHECK_ARG(d->B > 0 && d->Hin > 0 && d->Win > 0 && d->Hout > 0 && d->Wout > 0, "conv2d: bad dims");
+    MSAU_CHECK_ARG(d->C1 % 8 == 0 && d->C2 % 8 == 0 && (d->C2 == 0 || d->x2), "conv2d: bad sources");
+    MSAU_CHECK_ARG(!(d->flags & MSAU_CONV_ADD) || d->add, "conv2d: ADD without pointer");
+    MSAU_CHECK_ARG(!(d->flags & MSAU_CONV_MASK_A) || d->mask_a, "conv2d: MASK_A without pointer");
+    MSAU_CHECK_ARG(!(d->flags & MSAU_CONV_MASK_B) || d->mask_b, "conv2d: MASK_B without pointer");
+    MSAU_CHECK_ARG(!(d->flags & MSAU_CONV_EXTENT) || d->extent, "conv2d: MSAU_CONV_EXTENT without extent pointer");
+    ConvRoute r;
+    int rc = conv_route(dtype, d, &r);
+    if (rc) return rc;
+    // refusals come before any launch, in the order the flags are checked: EXTENT, WGRAD, OWNER, NCHW, then per flag its operands
+    // and its refusal (a flag set that passes the operand checks of HEAD, DOUT or LRN holds none of the flags after it)
+    const bool refused = r.family == CONV_REFUSED;
+    if (refused && (r.refused & (MSAU_CONV_EXTENT | MSAU_CONV_WGRAD | MSAU_CONV_OWNER | MSAU_CONV_NCHW))) return conv_refusal(d, r.refused);
+    if (d->flags & MSAU_CONV_HEAD)
+        MSAU_CHECK_ARG(d->head_probs && d->head_argmax && d->head_classes > 0 && d->head_classes <= 16 &&
+                       d->head_classes <= d->Cout && d->flags == MSAU_CONV_HEAD, "conv2d: bad HEAD arguments");
+    if (d->flags & MSAU_CONV_DOUT) {
+        const int okf = MSAU_CONV_DOUT | MSAU_CONV_ADD | MSAU_CONV_ACCUM | MSAU_CONV_MASK_B | MSAU_CONV_WGRAD;
+        MSAU_CHECK_ARG(d->y2 && !(d->flags & ~okf) && !(d->flags2 & ~(MSAU_CONV_ACCUM | MSAU_CONV_MASK_B)) &&
+                       (!(d->flags2 & MSAU_CONV_MASK_B) || d->mask_b2), "conv2d: bad DOUT arguments");
+    }
+    if (d->flags & MSAU_CONV_LRN)
+        MSAU_CHECK_ARG(d->y2 && !(d->flags & ~(MSAU_CONV_LRN | MSAU_CONV_RELU_IN)) && d->lrn_k > 0.f, "conv2d: bad LRN arguments");
+    if (refused && r.refused != MSAU_CONV_POOL) return conv_refusal(d, r.refused);
+    if (d->flags & MSAU_CONV_POOL)
+        MSAU_CHECK_ARG(d->pool_y && !(d->flags & (MSAU_CONV_DOUT | MSAU_CONV_HEAD | MSAU_CONV_LRN)), "conv2d: bad POOL arguments");
+    if (refused) return conv_refusal(d, r.refused);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    switch (r.family) {
+        case CONV_OWNER: return msau_ownerconv_fwd(s, dtype, d);
+        case CONV_FIRST_NCHW:
+            if (!(d->head_classes > 0 && d->head_classes <= d->C1)) return conv_refusal(d, MSAU_CONV_NCHW);
+            return msau_firstconv_launch(s, dtype, d, d->head_classes);
+        case CONV_ROWS: return msau_rowconv_launch(s, d, r.g.kchunk, r.g.rows, r.inst);
+        case CONV_CHUNKED: return msau_conv_chunked_launch(s, dtype, d, r.g.kchunk, r.g.nchunks, r.g.CT, r.inst);
+        case CONV_LEAN: return msau_conv_lean_launch(s, dtype, d, r.g.kchunk, r.g.CT, r.inst);
+        default: return tile_launch(s, dtype, d, r);
+    }
 }

@@ -671,7 +671,7 @@ template <typename T, int CIN8, int CT, int KS, bool DUAL, int DIL = 1, int WGW 
           int STRIDE = 1, int UPS = 1, int EPI = EPI_NONE, int EOP = -1, bool IDS = false>
 int launch_lean_e(hipStream_t s, const LeanArgs& a0) {
     using Cfg = LeanCfg<T, CIN8, CT, KS, DUAL, DIL, WGW, STRIDE>;
-    if (Cfg::LDS + 256 > MSAU_LDS_LIMIT) return 0;          // does not fit: the generic kernel takes the launch
+    MSAU_CHECK_ARG(Cfg::LDS + 256 <= MSAU_LDS_LIMIT, "conv_lean: the instance needs %d B of LDS (msau_conv_lean_case says 0 for it)", Cfg::LDS);
     LeanArgs a = a0;
     a.tiles_x = cdiv(a.d.Wout, 16 * WGW);
     a.ntiles = a.d.B * a.tiles_x * a.tiles_y;
@@ -696,7 +696,7 @@ int launch_lean_e(hipStream_t s, const LeanArgs& a0) {
     }
     hipLaunchKernelGGL((conv_lean_kernel<T, CIN8, CT, KS, DUAL, DIL, WGW, DOUT, SPLIT, STRIDE, UPS, EPI, EOP, IDS>), dim3(grid, SPLIT ? a.ct_total : 1), dim3(256 * WGW), Cfg::LDS, s, a);
     MSAU_CHECK_LAUNCH("conv_lean_kernel");
-    return 1;
+    return 0;
 }
 
 // picks the operand-specialised instance for the 8- / 16-channel layers (the combinations the training step launches:
@@ -715,239 +715,173 @@ int launch_lean(hipStream_t s, const LeanArgs& a) {
     return launch_lean_e<T, CIN8, CT, KS, DUAL, DIL, WGW, DOUT, SPLIT, STRIDE, UPS, EPI, -1>(s, a);
 }
 
-template <typename T, int CIN8, int KS, bool DUAL>
-int lean_ct(hipStream_t s, const LeanArgs& a, int CT) {
-    if constexpr (sizeof(T) == 2 && (CIN8 == 1 || (DUAL && CIN8 == 2)) && KS == 3) {      // 4x4: measured, no gain
-        // 16 x 32 output tile per 512-thread workgroup for the 8/16-channel layers: same work per wave, but a halo
-        // row is 544 B (5-6 lines for 4.25 of payload) instead of 288 B (4 lines for 2.25)
-        if (CT == 1 && a.d.Wout >= 64 && (int64_t)a.d.B * a.tiles_y * cdiv(a.d.Wout, 32) >= 512)
-            return launch_lean<T, CIN8, 1, KS, DUAL, 1, 2>(s, a);
-    }
-    if (CT == 1) return launch_lean<T, CIN8, 1, KS, DUAL>(s, a);
-    if (CT == 2) return launch_lean<T, CIN8, 2, KS, DUAL>(s, a);
-    if constexpr (CIN8 >= 4 && KS != 4) {
-        if (CT == 4) return launch_lean<T, CIN8, 4, KS, DUAL>(s, a);
-    }
-    return 0;
+// ---- the instances.  The number of an instance packs its template arguments; LEAN_TABLE is the one list of those that
+// exist, read by lean_instance() both as the query "does this instance exist and fit the LDS" (msau_conv_lean_case) and as
+// the launch switch (msau_conv_lean_launch): an instance is never named without being launchable, nor launched unnamed.
+constexpr int kLeanIds = 1 << 26;                 // the id-mask input variant (MSAU_CONV_IDS) of an instance
+constexpr int lean_id(int cin8, int ct, int ks, bool dual, int dil = 1, int wgw = 1, bool dout = false, bool split = false,
+                      int stride = 1, int ups = 1, int epi = EPI_NONE) {
+    return cin8 | ct << 5 | ks << 8 | dil << 11 | wgw << 15 | stride << 17 | ups << 19 | epi << 21 | dual << 23 | dout << 24 | split << 25;
 }
+// X(CIN8, CT, KS, DUAL, DIL, WGW, DOUT, SPLIT, STRIDE, UPS, EPI)
+#define LEAN_PLAIN(X, C8, CT, KS, DUAL) X(C8, CT, KS, DUAL, 1, 1, false, false, 1, 1, EPI_NONE)
+#define LEAN_CT12(X, C8, KS, DUAL) LEAN_PLAIN(X, C8, 1, KS, DUAL) LEAN_PLAIN(X, C8, 2, KS, DUAL)
+#define LEAN_CT124(X, C8, KS, DUAL) LEAN_CT12(X, C8, KS, DUAL) LEAN_PLAIN(X, C8, 4, KS, DUAL)
+#define LEAN_DIL(X, C8, CT, DIL) X(C8, CT, 3, false, DIL, 1, false, false, 1, 1, EPI_NONE)
+#define LEAN_DILS(X, DIL) LEAN_DIL(X, 1, 1, DIL) LEAN_DIL(X, 2, 1, DIL) LEAN_DIL(X, 2, 2, DIL) LEAN_DIL(X, 4, 1, DIL) LEAN_DIL(X, 4, 2, DIL) \
+                          LEAN_DIL(X, 4, 4, DIL) LEAN_DIL(X, 8, 2, DIL)
+#define LEAN_STRIDED(X, C8, CT, ST, UP) X(C8, CT, 3, false, 1, 1, false, false, ST, UP, EPI_NONE)
+#define LEAN_DOUT(X, C, KS) X(C, C, KS, false, 1, 1, true, false, 1, 1, EPI_NONE)
+#define LEAN_SPLIT(X, C8, KS, EPI) X(C8, 1, KS, false, 1, 1, false, true, 1, 1, EPI)
+#define LEAN_EPI(X, C8, CT, KS, DUAL, DIL, EPI) X(C8, CT, KS, DUAL, DIL, 1, false, false, 1, 1, EPI)
+#define LEAN_TABLE(X)                                                                                                              \
+    /* k = 1 / 3, stride 1, no dilation: one source of 8 .. 64 channels, two equal sources of 8 .. 32 (1x1: .. 64) */              \
+    LEAN_CT12(X, 1, 1, false) LEAN_CT12(X, 2, 1, false) LEAN_CT124(X, 4, 1, false) LEAN_CT124(X, 8, 1, false)                      \
+    LEAN_CT12(X, 1, 3, false) LEAN_CT12(X, 2, 3, false) LEAN_CT124(X, 4, 3, false) LEAN_CT124(X, 8, 3, false)                      \
+    LEAN_CT12(X, 2, 1, true) LEAN_CT124(X, 4, 1, true) LEAN_CT124(X, 8, 1, true) LEAN_CT124(X, 16, 1, true)                        \
+    LEAN_CT12(X, 2, 3, true) LEAN_CT124(X, 4, 3, true) LEAN_CT124(X, 8, 3, true)                                                   \
+    /* the 4x4 end conv over 8 channels and its data gradient; with the inference head (MSAU_CONV_HEAD) */                         \
+    LEAN_CT12(X, 1, 4, false) LEAN_EPI(X, 1, 1, 4, false, 1, EPI_HEAD)                                                             \
+    /* dilated 3x3 (the level-entry convs of the encoder and their data gradients): single source only */                          \
+    LEAN_DILS(X, 2) LEAN_DILS(X, 4) LEAN_DILS(X, 8)                                                                                \
+    /* transposed conv (ups = 2) and its data gradient (stride = 2), 3x3, single source: (C1 / 8, CT) per level */                 \
+    LEAN_STRIDED(X, 8, 2, 1, 2) LEAN_STRIDED(X, 4, 1, 1, 2) LEAN_STRIDED(X, 2, 1, 1, 2)                                            \
+    LEAN_STRIDED(X, 4, 4, 2, 1) LEAN_STRIDED(X, 2, 2, 2, 1) LEAN_STRIDED(X, 1, 1, 2, 1)                                            \
+    /* two-output data gradient (MSAU_CONV_DOUT): g [C] -> (dx1 [C], dx2 [C]) with C = CT * 8 in {8, 16, 32} */                    \
+    LEAN_DOUT(X, 1, 1) LEAN_DOUT(X, 2, 1) LEAN_DOUT(X, 4, 1) LEAN_DOUT(X, 1, 3) LEAN_DOUT(X, 2, 3) LEAN_DOUT(X, 4, 3)              \
+    /* channel-split instances for small images: the conv's 16-row tiles over blockIdx.y, CT = 1 per workgroup */                  \
+    LEAN_SPLIT(X, 4, 1, EPI_NONE) LEAN_SPLIT(X, 4, 3, EPI_NONE) LEAN_SPLIT(X, 8, 1, EPI_NONE) LEAN_SPLIT(X, 8, 3, EPI_NONE)        \
+    /* fused epilogues (the featRoot-8 / featRoot-16 shapes of the reference's configurations; everything else runs the            \
+       stand-alone LRN / pool launch).  LRN: level-entry convs 8 -> 8, 8 -> 16 (dilation 2), 16 -> 32 (dilation 4 / 2), 16 -> 16 */\
+    LEAN_EPI(X, 1, 1, 3, false, 1, EPI_LRN) LEAN_EPI(X, 1, 1, 3, false, 2, EPI_LRN) LEAN_EPI(X, 2, 2, 3, false, 4, EPI_LRN)        \
+    LEAN_EPI(X, 2, 1, 3, false, 1, EPI_LRN) LEAN_EPI(X, 2, 2, 3, false, 2, EPI_LRN)                                                \
+    /* POOL: coupling 1x1 convs over concat (8+8 -> 8, 16+16 -> 16, 32+32 -> 32) and the split 32 -> 32 3x3 (stage 0, level 2) */  \
+    LEAN_EPI(X, 2, 1, 1, true, 1, EPI_POOL) LEAN_EPI(X, 4, 1, 1, true, 1, EPI_POOL) LEAN_EPI(X, 8, 2, 1, true, 1, EPI_POOL)        \
+    LEAN_SPLIT(X, 4, 3, EPI_POOL)
+// bf16 only: the 16 x 32 output tile per 512-thread workgroup for the 8/16-channel 3x3 layers: same work per wave, but a halo
+// row is 544 B (5-6 lines for 4.25 of payload) instead of 288 B (4 lines for 2.25).  (4x4: measured, no gain)
+#define LEAN_TABLE_BF16(X)                                                                                                         \
+    X(1, 1, 3, false, 1, 2, false, false, 1, 1, EPI_NONE) X(2, 1, 3, true, 1, 2, false, false, 1, 1, EPI_NONE)                     \
+    X(1, 1, 3, false, 1, 2, false, false, 1, 1, EPI_LRN)
+// (the level-3 entry conv, 32 -> 64 channels at dilation 8 with four channel tiles, had an LRN instance in round 4: 15.1 us against
+//  7.8 us for the conv + 1.7 us for the 64-channel LRN launch, 3.086 -> 3.077 ms without it -- removed, profiles/HISTORY_r03_r04.md)
+// (the net's first conv, 64 one-hot channels -> featRoot 8, had one too: 9 us SLOWER per step than the conv + the 8.4 us
+//  stand-alone LRN launch -- removed in round 4, profiles/HISTORY_r03_r04.md)
 
-template <typename T, int KS>
-int lean_cin(hipStream_t s, const LeanArgs& a, int cin8, bool dual, int CT) {
-    if (!dual) {
-        switch (cin8) {
-            case 1: return lean_ct<T, 1, KS, false>(s, a, CT);
-            case 2: return lean_ct<T, 2, KS, false>(s, a, CT);
-            case 4: return lean_ct<T, 4, KS, false>(s, a, CT);
-            case 8: return lean_ct<T, 8, KS, false>(s, a, CT);
-            default: return 0;
+// a == nullptr: 1 if instance `id` exists for T and fits the LDS, else 0.  Otherwise: launch it (0, or an error -- never "not mine")
+template <typename T>
+int lean_instance(int id, hipStream_t s, const LeanArgs* a) {
+    switch (id) {
+#define LEAN_ROW(C8, CT, KS, DUAL, DIL, WGW, DOUT, SPLIT, ST, UP, EPI)                                \
+        case lean_id(C8, CT, KS, DUAL, DIL, WGW, DOUT, SPLIT, ST, UP, EPI):                           \
+            if (!a) return LeanCfg<T, C8, CT, KS, DUAL, DIL, WGW, ST>::LDS + 256 <= MSAU_LDS_LIMIT;   \
+            return launch_lean<T, C8, CT, KS, DUAL, DIL, WGW, DOUT, SPLIT, ST, UP, EPI>(s, *a);
+        LEAN_TABLE(LEAN_ROW)
+        case lean_id(8, 1, 3, false) | kLeanIds:     // id-mask input: the 64 -> 8/16 3x3 first conv
+            if (!a) return LeanCfg<T, 8, 1, 3, false>::LDS + 256 <= MSAU_LDS_LIMIT;
+            return launch_lean_e<T, 8, 1, 3, false, 1, 1, false, false, 1, 1, EPI_NONE, -1, true>(s, *a);
+        default: break;
+    }
+    if constexpr (sizeof(T) == 2) {
+        switch (id) {
+            LEAN_TABLE_BF16(LEAN_ROW)
+#undef LEAN_ROW
+            default: break;
         }
     }
-    switch (cin8) {
-        case 2: return lean_ct<T, 2, KS, true>(s, a, CT);
-        case 4: return lean_ct<T, 4, KS, true>(s, a, CT);
-        case 8: return lean_ct<T, 8, KS, true>(s, a, CT);
-        case 16: if constexpr (KS == 1) return lean_ct<T, 16, KS, true>(s, a, CT); else return 0;
-        default: return 0;
-    }
-}
-
-// dilated 3x3 (the level-entry convs of the encoder and their data gradients): single source only
-template <typename T, int DIL>
-int lean_dil(hipStream_t s, const LeanArgs& a, int cin8, int CT) {
-#define LD_CASE(C8, CTV) if (cin8 == C8 && CT == CTV) return launch_lean<T, C8, CTV, 3, false, DIL>(s, a);
-    LD_CASE(1, 1) LD_CASE(2, 1) LD_CASE(2, 2) LD_CASE(4, 1) LD_CASE(4, 2) LD_CASE(4, 4) LD_CASE(8, 2)
-#undef LD_CASE
-    return 0;
+    return a ? msau_set_error(MSAU_ERR_ARG, "conv_lean: no instance %#x", id) : 0;
 }
 
 }  // namespace
 
-static bool lean_split_wanted(const msau_conv_desc* d, int CT);
-
-// LeanCfg::LDS at run time (same formula), for the applicability queries
-static int lean_lds_bytes(int esz, int cin8, int CT, int KS, int dil, int wgw, int stride, bool dual) {
-    const int ti = 15 * stride + 1 + (KS - 1) * dil, tiw = (16 * wgw - 1) * stride + 1 + (KS - 1) * dil;
-    const int psraw = cin8 * 8 * esz, ps = ((psraw / 16) % 2 == 0) ? psraw + 16 : psraw;
-    const int nch = dual ? 2 : 1, c8h = cin8 / nch, ng = KS * KS * c8h, nksh = (ng + 3) / 4, nks = nch * nksh;
-    const bool wreg = CT * nks <= 8;
-    const int ws = nksh * 32 * esz + 16;
-    const int in_bytes = ((ti * tiw * ps + 15) / 16) * 16;
-    return in_bytes + (wreg ? 0 : nch * CT * 16 * ws);
-}
-
-// transposed conv (ups = 2) and its data gradient (stride = 2), 3x3, single source: (C1/8, CT) per level
-static bool lean_strided_shape(const msau_conv_desc* d, int nchunks, int CT) {
-    if (d->KH != 3 || d->KW != 3 || d->dil != 1 || d->C2 || nchunks != 1 || d->stride * d->ups != 2) return false;
-    if (d->flags & (MSAU_CONV_DOUT | MSAU_CONV_HEAD | MSAU_CONV_RELU_IN)) return false;
-    if (d->pad_t < 0 || d->pad_l < 0 || d->pad_t > 2 || d->pad_l > 2) return false;
-    if ((int64_t)d->B * cdiv(d->Hout, 16) * cdiv(d->Wout, 16) < 64) return false;
-    const int c8 = d->C1 / 8;
-    if (d->ups == 2) return (c8 == 8 && CT == 2) || (c8 == 4 && CT == 1) || (c8 == 2 && CT == 1);
-    return (c8 == 4 && CT == 4) || (c8 == 2 && CT == 2) || (c8 == 1 && CT == 1);
-}
-template <typename T>
-int lean_strided(hipStream_t s, const LeanArgs& a, int c8, int CT, bool ups) {
-#define ST_CASE(C8, CTV, ST, UP) if (c8 == C8 && CT == CTV) return launch_lean<T, C8, CTV, 3, false, 1, 1, false, false, ST, UP>(s, a);
-    if (ups) { ST_CASE(8, 2, 1, 2) ST_CASE(4, 1, 1, 2) ST_CASE(2, 1, 1, 2) }
-    else { ST_CASE(4, 4, 2, 1) ST_CASE(2, 2, 2, 1) ST_CASE(1, 1, 2, 1) }
-#undef ST_CASE
-    return 0;
-}
-
-// Returns 1 if a lean instance handled the launch, 0 if the caller must use the generic kernel,
-// < 0 on error.  `kchunk` / `nchunks` / `CT` come from the generic geometry (same packed image).
-int msau_conv_lean_applicable(int dtype, const msau_conv_desc* d, int nchunks, int CT) {
-    if (d->flags & (MSAU_CONV_ELU | MSAU_CONV_EXTENT)) return 0;   // (ELU epilogues, ragged extents: the generic kernel only)
-    if (d->stride * d->ups == 2) {
-        const int esz = dtype == MSAU_F32 ? 4 : 2;
-        if ((int64_t)d->Hin * d->Win * d->C1 * esz >= (1ll << 31) || (int64_t)d->Wout * d->Cout * esz * 20 >= (1ll << 31)) return 0;
-        if (!lean_strided_shape(d, nchunks, CT)) return 0;
-        return lean_lds_bytes(esz, d->C1 / 8, CT, 3, 1, 1, d->stride, false) + 256 <= MSAU_LDS_LIMIT;
-    }
-    if (d->stride != 1 || d->ups != 1 || d->KH != d->KW || (d->KH != 1 && d->KH != 3 && d->KH != 4)) return 0;
-    if (d->dil != 1) {
-        if (d->KH != 3 || d->C2 || (d->dil != 2 && d->dil != 4 && d->dil != 8)) return 0;
-        const int c8 = d->C1 / 8;
-        const bool ok = (c8 == 1 && CT == 1) || (c8 == 2 && CT <= 2) || (c8 == 4 && (CT == 1 || CT == 2 || CT == 4)) || (c8 == 8 && CT == 2);
-        if (!ok) return 0;
-    }
-    if (nchunks != (d->C2 ? 2 : 1)) return 0;                // one chunk per source (same packed image as conv.hip)
-    if (d->Hin != d->Hout || d->Win != d->Wout) return 0;
-    if (d->pad_t < 0 || d->pad_l < 0 || d->pad_t > (d->KH - 1) * d->dil || d->pad_l > (d->KW - 1) * d->dil) return 0;
-    if (CT > 4 || (CT == 4 && (d->C1 + d->C2) < 32)) return 0;
-    if (d->KH == 4 && ((d->C1 + d->C2) != 8 || d->C2)) return 0;           // only the 8-channel end conv / its data gradient
-    if ((int64_t)d->B * cdiv(d->Hout, 16) * cdiv(d->Wout, 16) < 64) return 0;
-    const bool dual = d->C2 != 0;
-    if (dual && d->C1 != d->C2) return 0;
-    const int cin8 = (d->C1 + d->C2) / 8;
-    const int esz = dtype == MSAU_F32 ? 4 : 2;
-    if ((int64_t)d->Hin * d->Win * (d->C1 > d->C2 ? d->C1 : d->C2) * esz >= (1ll << 31)) return 0;   // 32-bit lane offsets
-    if ((int64_t)d->Wout * d->Cout * esz * 20 >= (1ll << 31)) return 0;
-    if (cin8 != 1 && cin8 != 2 && cin8 != 4 && cin8 != 8 && !(cin8 == 16 && dual && d->KH == 1)) return 0;
-    if (dual && cin8 < 2) return 0;
-    // the instance that would take the launch must fit the LDS (fp32 storage doubles every tile)
-    const bool split = lean_split_wanted(d, CT);
-    if (lean_lds_bytes(esz, cin8, split ? 1 : CT, d->KH, d->dil, 1, 1, dual) + 256 > MSAU_LDS_LIMIT) return 0;
-    return 1;
-}
-
-// two-output data gradient (MSAU_CONV_DOUT): g [C] -> (dx1 [C], dx2 [C]) with C = CT*8 in {8, 16, 32}
-int msau_conv_lean_dout_capable(int dtype, const msau_conv_desc* d, int nchunks, int CT) {
-    if (!msau_conv_lean_applicable(dtype, d, nchunks, CT)) return 0;
-    return d->C2 == 0 && d->dil == 1 && d->stride == 1 && d->ups == 1 && (d->KH == 1 || d->KH == 3) && (CT == 1 || CT == 2 || CT == 4) &&
-           d->Cout == CT * 16 && d->C1 == CT * 8;
-}
-
-// ---- fused epilogues: the instances that exist (the featRoot-8 / featRoot-16 shapes of the reference's configurations);
-// everything else runs the stand-alone LRN / pool launch.  One table for the capability queries and the dispatch.
-//   LRN : level-entry convs  8 -> 8 (3x3), 8 -> 16 (dilation 2), 16 -> 16, 16 -> 32 (dilation 4 / 2), 64 -> 8 (the net's first conv)
-//   POOL: coupling 1x1 convs over concat (8+8 -> 8, 16+16 -> 16, 32+32 -> 32) and the split 32 -> 32 3x3 (stage 0, level 2)
-static bool lean_wide_tile(const msau_conv_desc* d, int tiles_y) {          // the 16 x 32 tile of lean_ct
-    return d->Wout >= 64 && (int64_t)d->B * tiles_y * cdiv(d->Wout, 32) >= 512;
-}
-static int lean_epi_case(int dtype, const msau_conv_desc* d, int CT, int epi) {
-    const int c8 = (d->C1 + d->C2) / 8, k = d->KH;
-    const bool dual = d->C2 != 0, split = lean_split_wanted(d, CT);
-    if (epi == EPI_LRN && !dual && !split && k == 3) {
-        if (c8 == 1 && CT == 1 && d->dil == 1 && d->Cout == 8) return dtype == MSAU_BF16 && lean_wide_tile(d, cdiv(d->Hout, 16)) ? 1 : 2;
-        if (c8 == 1 && CT == 1 && d->dil == 2 && d->Cout == 16) return 3;
-        if (c8 == 2 && CT == 2 && d->dil == 4 && d->Cout == 32) return 4;
-        if (c8 == 2 && CT == 1 && d->dil == 1 && d->Cout == 16) return 5;
-        if (c8 == 2 && CT == 2 && d->dil == 2 && d->Cout == 32) return 6;
-        // (the level-3 entry conv, 32 -> 64 channels at dilation 8 with four channel tiles, had an instance in round 4: 15.1 us against
-        //  7.8 us for the conv + 1.7 us for the 64-channel LRN launch, 3.086 -> 3.077 ms without it -- removed, profiles/HISTORY_r03_r04.md)
-        // (the net's first conv, 64 one-hot channels -> featRoot 8, had an instance too: 9 us SLOWER per step than the conv + the 8.4 us
-        //  stand-alone LRN launch -- removed in round 4, profiles/HISTORY_r03_r04.md)
-    }
-    if (epi == EPI_POOL && d->dil == 1) {
-        if (dual && k == 1 && !split) {
-            if (c8 == 2 && CT == 1) return 10;
-            if (c8 == 4 && CT == 1) return 11;
-            if (c8 == 8 && CT == 2) return 12;
-        }
-        if (!dual && k == 3 && split && c8 == 4) return 13;
-    }
-    return 0;
-}
-template <typename T>
-int lean_epi(hipStream_t s, const LeanArgs& a, int which) {
-    switch (which) {
-        case 1: if constexpr (sizeof(T) == 2) return launch_lean<T, 1, 1, 3, false, 1, 2, false, false, 1, 1, EPI_LRN>(s, a); else return 0;
-        case 2: return launch_lean<T, 1, 1, 3, false, 1, 1, false, false, 1, 1, EPI_LRN>(s, a);
-        case 3: return launch_lean<T, 1, 1, 3, false, 2, 1, false, false, 1, 1, EPI_LRN>(s, a);
-        case 4: return launch_lean<T, 2, 2, 3, false, 4, 1, false, false, 1, 1, EPI_LRN>(s, a);
-        case 5: return launch_lean<T, 2, 1, 3, false, 1, 1, false, false, 1, 1, EPI_LRN>(s, a);
-        case 6: return launch_lean<T, 2, 2, 3, false, 2, 1, false, false, 1, 1, EPI_LRN>(s, a);
-        case 10: return launch_lean<T, 2, 1, 1, true, 1, 1, false, false, 1, 1, EPI_POOL>(s, a);
-        case 11: return launch_lean<T, 4, 1, 1, true, 1, 1, false, false, 1, 1, EPI_POOL>(s, a);
-        case 12: return launch_lean<T, 8, 2, 1, true, 1, 1, false, false, 1, 1, EPI_POOL>(s, a);
-        case 13: return launch_lean<T, 4, 1, 3, false, 1, 1, false, true, 1, 1, EPI_POOL>(s, a);
-        default: return 0;
-    }
-}
-
-// second output LRN(y) (MSAU_CONV_LRN): all Cout channels of a pixel in one workgroup, at most two 16-row tiles
-int msau_conv_lean_lrn_capable(int dtype, const msau_conv_desc* d, int nchunks, int CT) {
-    if (!msau_conv_lean_applicable(dtype, d, nchunks, CT)) return 0;
-    if (d->stride != 1 || d->ups != 1 || (d->flags & (MSAU_CONV_DOUT | MSAU_CONV_HEAD | MSAU_CONV_POOL))) return 0;
-    return lean_epi_case(dtype, d, CT, EPI_LRN) != 0;
-}
-
-// pooled output (MSAU_CONV_POOL): a 16 x 16 tile holds whole 2 x 2 windows
-int msau_conv_lean_pool_capable(int dtype, const msau_conv_desc* d, int nchunks, int CT) {
-    if (!msau_conv_lean_applicable(dtype, d, nchunks, CT)) return 0;
-    if (d->stride != 1 || d->ups != 1 || (d->flags & (MSAU_CONV_DOUT | MSAU_CONV_HEAD | MSAU_CONV_LRN))) return 0;
-    return lean_epi_case(dtype, d, CT, EPI_POOL) != 0;
-}
-
-template <typename T>
-int lean_dout(hipStream_t s, const LeanArgs& a, int KS, int CT) {
-#define DO_CASE(K, C) if (KS == K && CT == C) return launch_lean<T, C, C, K, false, 1, 1, true>(s, a);
-    DO_CASE(1, 1) DO_CASE(1, 2) DO_CASE(1, 4) DO_CASE(3, 1) DO_CASE(3, 2) DO_CASE(3, 4)
-#undef DO_CASE
-    return 0;
-}
-
-// channel-split instances for small images: (CIN8, KS) in {4, 8} x {1, 3}
 static int lean_split_tiles() {
     static const int v = std::getenv("MSAU_SPLIT_TILES") ? atoi(std::getenv("MSAU_SPLIT_TILES")) : 512;      // measured: 0 -> 5.04, 256 -> 4.90, 512 -> 4.83, 1024 -> 4.84 ms/step
     return v;
 }
-static bool lean_split_wanted(const msau_conv_desc* d, int CT) {
-    const int cin8 = d->C1 / 8;
-    return d->C2 == 0 && d->dil == 1 && (d->KH == 1 || d->KH == 3) && (CT == 2 || CT == 4) && (cin8 == 4 || cin8 == 8) &&
-           !(d->flags & (MSAU_CONV_DOUT | MSAU_CONV_HEAD)) &&
-           (int64_t)d->B * cdiv(d->Hout, 16) * cdiv(d->Wout, 16) < lean_split_tiles();
-}
-template <typename T>
-int lean_split(hipStream_t s, const LeanArgs& a, int cin8, int KS) {
-#define SP_CASE(C8, K) if (cin8 == C8 && KS == K) return launch_lean<T, C8, 1, K, false, 1, 1, false, true>(s, a);
-    SP_CASE(4, 1) SP_CASE(4, 3) SP_CASE(8, 1) SP_CASE(8, 3)
-#undef SP_CASE
-    return 0;
+
+// The lean instance msau_conv2d launches for `d` (its number, see lean_id), 0 = none: the tile kernel's launch.  `nchunks` / `CT`
+// come from the generic geometry (same packed image).  Non-zero exactly when msau_conv_lean_launch launches that instance.
+int msau_conv_lean_case(int dtype, const msau_conv_desc* d, int nchunks, int CT) {
+    const int f = d->flags, k = d->KH, esz = dtype == MSAU_F32 ? 4 : 2;
+    const int special = f & (MSAU_CONV_HEAD | MSAU_CONV_DOUT | MSAU_CONV_LRN | MSAU_CONV_POOL | MSAU_CONV_IDS);
+    // (ELU epilogues, ragged extents: the generic kernel only; box lists, the NCHW input, the weight-gradient rider: other families)
+    if ((f & ~(kOperandBits | special)) || (special & (special - 1))) return 0;
+    const int tiles_x = cdiv(d->Wout, 16), tiles_y = cdiv(d->Hout, 16);
+    const int64_t ntiles = (int64_t)d->B * tiles_x * tiles_y;
+    if (ntiles < 64 || ntiles >= (1 << 20) || tiles_x >= 4096 || tiles_y >= 4096) return 0;
+    if (d->pad_t < 0 || d->pad_l < 0 || d->pad_t > (d->KH - 1) * d->dil || d->pad_l > (d->KW - 1) * d->dil) return 0;
+    if ((int64_t)d->Hin * d->Win * (d->C1 > d->C2 ? d->C1 : d->C2) * esz >= (1ll << 31)) return 0;   // 32-bit lane offsets
+    if ((int64_t)d->Wout * d->Cout * esz * 20 >= (1ll << 31)) return 0;
+    const bool dual = d->C2 != 0;
+    const int cin8 = (d->C1 + d->C2) / 8;
+    if (nchunks != (dual ? 2 : 1)) return 0;                 // one chunk per source (same packed image as conv.hip)
+    if (cin8 > 16 || CT > 4 || k > 4 || d->dil > 8) return 0;   // (no such instance; the fields of lean_id)
+    int id = 0;
+    if (d->stride * d->ups == 2) {
+        if (k != 3 || d->KW != 3 || d->dil != 1 || dual || special || (f & MSAU_CONV_RELU_IN)) return 0;
+        id = lean_id(cin8, CT, 3, false, 1, 1, false, false, d->stride, d->ups);
+    } else {
+        if (d->stride != 1 || d->ups != 1 || d->KH != d->KW || d->Hin != d->Hout || d->Win != d->Wout || (dual && d->C1 != d->C2)) return 0;
+        if (k == 4 && cin8 != 1) return 0;                   // only the 8-channel end conv / its data gradient
+        const bool split = !dual && d->dil == 1 && (k == 1 || k == 3) && (CT == 2 || CT == 4) && (cin8 == 4 || cin8 == 8) &&
+                           !(f & (MSAU_CONV_DOUT | MSAU_CONV_HEAD)) && ntiles < lean_split_tiles();
+        // the 16 x 32 tile: bf16, 8 channels or 8 + 8, 3x3, one 16-row tile, enough tiles of that size
+        const bool wide = dtype == MSAU_BF16 && k == 3 && d->dil == 1 && CT == 1 && cin8 == (dual ? 2 : 1) && d->Wout >= 64 &&
+                          (int64_t)d->B * tiles_y * cdiv(d->Wout, 32) >= 512;
+        switch (special) {
+            case MSAU_CONV_IDS:                              // 64 one-hot channels -> one 16-row tile, 3x3, no other source / epilogue operand
+                if (d->C1 != 64 || dual || k != 3 || d->dil != 1 || (f & ~(MSAU_CONV_IDS | MSAU_CONV_RELU_OUT))) return 0;
+                id = lean_id(8, CT, 3, false) | kLeanIds;
+                break;
+            case MSAU_CONV_HEAD:                             // forward-only: the 8-channel 4x4 end conv, one 16-row tile
+                if (k != 4) return 0;
+                id = lean_id(1, CT, 4, false, d->dil, 1, false, false, 1, 1, EPI_HEAD);
+                break;
+            case MSAU_CONV_DOUT:
+                if (dual || d->Cout != CT * 16 || d->C1 != CT * 8) return 0;
+                id = lean_id(CT, CT, k, false, d->dil, 1, true);
+                break;
+            case MSAU_CONV_LRN:                              // second output LRN(y): all Cout channels of a pixel in one workgroup
+                if (split || d->Cout != (cin8 == 1 && d->dil == 1 ? 8 : CT * 16)) return 0;      // (8 -> 8: half a 16-row tile)
+                id = lean_id(cin8, CT, k, dual, d->dil, wide ? 2 : 1, false, false, 1, 1, EPI_LRN);
+                break;
+            case MSAU_CONV_POOL:                             // pooled output: a 16 x 16 tile holds whole 2 x 2 windows
+                id = split ? lean_id(cin8, 1, k, false, 1, 1, false, true, 1, 1, EPI_POOL) : lean_id(cin8, CT, k, dual, d->dil, 1, false, false, 1, 1, EPI_POOL);
+                break;
+            default:
+                id = split ? lean_id(cin8, 1, k, false, 1, 1, false, true) : lean_id(cin8, CT, k, dual, d->dil, wide ? 2 : 1);
+        }
+    }
+    return (dtype == MSAU_F32 ? lean_instance<float>(id, nullptr, nullptr) : lean_instance<bf16_t>(id, nullptr, nullptr)) ? id : 0;
 }
 
-// 1 if the lean instance that takes this launch implements MSAU_CONV_HEAD (the 4x4 end conv, one 16-row tile)
-// id-mask input (MSAU_CONV_IDS): 64 one-hot channels -> one 16-row tile, 3x3, no other source / epilogue operand
-int msau_conv_lean_ids_capable(int dtype, const msau_conv_desc* d, int nchunks, int CT) {
-    msau_conv_desc e = *d;
-    e.flags &= ~MSAU_CONV_IDS;
-    return msau_conv_lean_applicable(dtype, &e, nchunks, CT) && d->C1 == 64 && d->C2 == 0 && CT == 1 && d->KH == 3 && d->dil == 1 &&
-           d->stride == 1 && d->ups == 1 && !(d->flags & ~(MSAU_CONV_IDS | MSAU_CONV_RELU_OUT));
+int msau_conv_lean_launch(hipStream_t s, int dtype, const msau_conv_desc* d, int kchunk, int CT, int id) {
+    const int esz = dtype == MSAU_F32 ? 4 : 2;
+    LeanArgs a;
+    a.d = *d;
+    a.kchunk = kchunk;
+    a.in_px1 = d->C1 * esz; a.in_px2 = d->C2 * esz;
+    a.in_row1 = d->Win * a.in_px1; a.in_row2 = d->Win * a.in_px2;
+    a.out_px = ((d->flags & MSAU_CONV_DOUT) ? d->Cout / 2 : d->Cout) * esz; a.out_row = d->Wout * a.out_px;
+    a.tiles_x = cdiv(d->Wout, 16); a.tiles_y = cdiv(d->Hout, 16);
+    a.ntiles = d->B * a.tiles_x * a.tiles_y;
+    a.mag_tx = (unsigned)((0x100000000ull + a.tiles_x - 1) / a.tiles_x);
+    a.mag_ty = (unsigned)((0x100000000ull + a.tiles_y - 1) / a.tiles_y);
+    a.per_xcd = 0; a.ct_total = CT;
+#ifdef MSAU_STAMPS
+    a.stamps = std::getenv("MSAU_STAMP_PTR") ? reinterpret_cast<unsigned long long*>(strtoull(std::getenv("MSAU_STAMP_PTR"), nullptr, 0)) : nullptr;
+#endif
+    return dtype == MSAU_F32 ? lean_instance<float>(id, s, &a) : lean_instance<bf16_t>(id, s, &a);
 }
 
-int msau_conv_lean_head_capable(int dtype, const msau_conv_desc* d, int nchunks, int CT) {
-    return msau_conv_lean_applicable(dtype, d, nchunks, CT) && d->KH == 4 && CT == 1 && d->dil == 1;
-}
-
-// 1 = handled by conv_chunked_kernel, 0 = not this shape.  (cch / kchunk / nchunks: the generic geometry = the packed image.)
-//   variant 1: many 64-channel chunks -> one 16-row tile, 3x3 (the 768 -> 8 first conv of cfg 4)
-//   variant 2: two 32-channel chunks -> two 16-row tiles, 3x3 dilation 8, bf16 (the data gradient of the level-3 entry conv)
-static int chunked_variant(int dtype, const msau_conv_desc* d, int cch, int nchunks, int CT) {
+// The chunked-K instance msau_conv2d launches for `d`, 0 = none.  (cch / nchunks / CT: the generic geometry = the packed image.)
+//   1: many 64-channel chunks -> one 16-row tile, 3x3 (the 768 -> 8 first conv of cfg 4)
+//   2: two 32-channel chunks -> two 16-row tiles, 3x3 dilation 8, bf16 (the data gradient of the level-3 entry conv)
+int msau_conv_chunked_case(int dtype, const msau_conv_desc* d, int cch, int nchunks, int CT) {
     static const bool off = std::getenv("MSAU_CONV_CHUNKED") && std::getenv("MSAU_CONV_CHUNKED")[0] == '0';
     if (off || nchunks < 2 || d->C2 || d->KH != 3 || d->KW != 3 || d->stride != 1 || d->ups != 1) return 0;
     if (d->Hin != d->Hout || d->Win != d->Wout || d->pad_t < 0 || d->pad_l < 0 || d->pad_t > 2 * d->dil || d->pad_l > 2 * d->dil) return 0;
-    if (d->flags & ~MSAU_CONV_RELU_OUT) return 0;
+    if (d->flags & ~MSAU_CONV_RELU_OUT) return 0;                                      // (no other epilogue: not ELU, EXTENT or a fused output either)
     const int esz = dtype == MSAU_F32 ? 4 : 2;
     if ((int64_t)d->Hin * d->Win * d->C1 * esz >= (1ll << 31)) return 0;              // 32-bit offsets inside an image
     const int64_t ntiles = (int64_t)d->B * cdiv(d->Wout, 16) * cdiv(d->Hout, 16);
@@ -955,10 +889,6 @@ static int chunked_variant(int dtype, const msau_conv_desc* d, int cch, int nchu
     if (cch == 64 && CT == 1 && d->dil == 1) return 1;
     if (cch == 32 && CT == 2 && d->dil == 8 && nchunks == 2 && dtype == MSAU_BF16) return 2;
     return 0;
-}
-int msau_conv_chunked_capable(int dtype, const msau_conv_desc* d, int cch, int nchunks, int CT) {
-    if (d->flags & (MSAU_CONV_ELU | MSAU_CONV_EXTENT)) return 0;
-    return chunked_variant(dtype, d, cch, nchunks, CT) != 0;
 }
 
 template <typename T, int C8CH, int CT, int DIL>
@@ -978,12 +908,10 @@ static int launch_chunked(hipStream_t s, const LeanArgs& a, int nchunks) {
     if (grid > a.ntiles) grid = a.ntiles;
     hipLaunchKernelGGL((conv_chunked_kernel<T, C8CH, CT, DIL>), dim3(grid), dim3(256), lds, s, a, nchunks);
     MSAU_CHECK_LAUNCH("conv_chunked_kernel");
-    return 1;
+    return 0;
 }
 
-int msau_conv_chunked_try(hipStream_t s, int dtype, const msau_conv_desc* d, int cch, int kchunk, int nchunks, int CT) {
-    const int variant = chunked_variant(dtype, d, cch, nchunks, CT);
-    if (!variant) return 0;
+int msau_conv_chunked_launch(hipStream_t s, int dtype, const msau_conv_desc* d, int kchunk, int nchunks, int CT, int which) {
     const int esz = dtype == MSAU_F32 ? 4 : 2;
     LeanArgs a;
     a.d = *d;
@@ -998,58 +926,7 @@ int msau_conv_chunked_try(hipStream_t s, int dtype, const msau_conv_desc* d, int
 #ifdef MSAU_STAMPS
     a.stamps = nullptr;
 #endif
-    if (variant == 2) return launch_chunked<bf16_t, 4, 2, 8>(s, a, nchunks);
-    return dtype == MSAU_F32 ? launch_chunked<float, 8, 1, 1>(s, a, nchunks) : launch_chunked<bf16_t, 8, 1, 1>(s, a, nchunks);
-}
-
-int msau_conv_lean_try(hipStream_t s, int dtype, const msau_conv_desc* d, int kchunk, int nchunks, int CT) {
-    if (!msau_conv_lean_applicable(dtype, d, nchunks, CT)) return 0;
-    const bool dual = d->C2 != 0;
-    const int cin8 = (d->C1 + d->C2) / 8;
-    const int esz = dtype == MSAU_F32 ? 4 : 2;
-    LeanArgs a;
-    a.d = *d;
-    a.kchunk = kchunk;
-    a.in_px1 = d->C1 * esz; a.in_px2 = d->C2 * esz;
-    a.in_row1 = d->Win * a.in_px1; a.in_row2 = d->Win * a.in_px2;
-    const bool dout = d->flags & MSAU_CONV_DOUT;
-    a.out_px = (dout ? d->Cout / 2 : d->Cout) * esz; a.out_row = d->Wout * a.out_px;
-    a.tiles_x = cdiv(d->Wout, 16); a.tiles_y = cdiv(d->Hout, 16);
-    a.ntiles = d->B * a.tiles_x * a.tiles_y;
-    if (a.ntiles >= (1 << 20) || a.tiles_x >= 4096 || a.tiles_y >= 4096) return 0;
-    a.mag_tx = (unsigned)((0x100000000ull + a.tiles_x - 1) / a.tiles_x);
-    a.mag_ty = (unsigned)((0x100000000ull + a.tiles_y - 1) / a.tiles_y);
-    a.ct_total = CT;
-#ifdef MSAU_STAMPS
-    a.stamps = std::getenv("MSAU_STAMP_PTR") ? reinterpret_cast<unsigned long long*>(strtoull(std::getenv("MSAU_STAMP_PTR"), nullptr, 0)) : nullptr;
-#endif
-    if (d->stride * d->ups == 2)
-        return dtype == MSAU_F32 ? lean_strided<float>(s, a, cin8, CT, d->ups == 2) : lean_strided<bf16_t>(s, a, cin8, CT, d->ups == 2);
-    if (d->flags & MSAU_CONV_IDS) {                              // id-mask input: the 64 -> 8/16 3x3 first conv (ids_capable)
-        if (!msau_conv_lean_ids_capable(dtype, d, nchunks, CT)) return 0;
-        return dtype == MSAU_F32 ? launch_lean_e<float, 8, 1, 3, false, 1, 1, false, false, 1, 1, EPI_NONE, -1, true>(s, a)
-                                 : launch_lean_e<bf16_t, 8, 1, 3, false, 1, 1, false, false, 1, 1, EPI_NONE, -1, true>(s, a);
-    }
-    if (d->flags & MSAU_CONV_HEAD) {                             // forward-only: the 8-channel 4x4 end conv (head_capable)
-        if (!msau_conv_lean_head_capable(dtype, d, nchunks, CT)) return 0;
-        return dtype == MSAU_F32 ? launch_lean<float, 1, 1, 4, false, 1, 1, false, false, 1, 1, EPI_HEAD>(s, a)
-                                 : launch_lean<bf16_t, 1, 1, 4, false, 1, 1, false, false, 1, 1, EPI_HEAD>(s, a);
-    }
-    if (d->flags & (MSAU_CONV_LRN | MSAU_CONV_POOL)) {
-        const int which = lean_epi_case(dtype, d, CT, (d->flags & MSAU_CONV_LRN) ? EPI_LRN : EPI_POOL);
-        if (!which) return msau_set_error(MSAU_ERR_ARG, "conv_lean: no instance with this fused epilogue (msau_conv2d_launch_info)");
-        return dtype == MSAU_F32 ? lean_epi<float>(s, a, which) : lean_epi<bf16_t>(s, a, which);
-    }
-    if (lean_split_wanted(d, CT))
-        return dtype == MSAU_F32 ? lean_split<float>(s, a, cin8, d->KH) : lean_split<bf16_t>(s, a, cin8, d->KH);
-    if (dout) {
-        if (!msau_conv_lean_dout_capable(dtype, d, nchunks, CT)) return 0;
-        return dtype == MSAU_F32 ? lean_dout<float>(s, a, d->KH, CT) : lean_dout<bf16_t>(s, a, d->KH, CT);
-    }
-    if (d->dil == 2) return dtype == MSAU_F32 ? lean_dil<float, 2>(s, a, cin8, CT) : lean_dil<bf16_t, 2>(s, a, cin8, CT);
-    if (d->dil == 4) return dtype == MSAU_F32 ? lean_dil<float, 4>(s, a, cin8, CT) : lean_dil<bf16_t, 4>(s, a, cin8, CT);
-    if (d->dil == 8) return dtype == MSAU_F32 ? lean_dil<float, 8>(s, a, cin8, CT) : lean_dil<bf16_t, 8>(s, a, cin8, CT);
-    if (d->KH == 4) return dtype == MSAU_F32 ? lean_ct<float, 1, 4, false>(s, a, CT) : lean_ct<bf16_t, 1, 4, false>(s, a, CT);
-    if (dtype == MSAU_F32) return d->KH == 3 ? lean_cin<float, 3>(s, a, cin8, dual, CT) : lean_cin<float, 1>(s, a, cin8, dual, CT);
-    return d->KH == 3 ? lean_cin<bf16_t, 3>(s, a, cin8, dual, CT) : lean_cin<bf16_t, 1>(s, a, cin8, dual, CT);
+    if (which == 1) return dtype == MSAU_F32 ? launch_chunked<float, 8, 1, 1>(s, a, nchunks) : launch_chunked<bf16_t, 8, 1, 1>(s, a, nchunks);
+    if (which == 2 && dtype == MSAU_BF16) return launch_chunked<bf16_t, 4, 2, 8>(s, a, nchunks);
+    return msau_set_error(MSAU_ERR_ARG, "conv_chunked: no instance %d", which);
 }

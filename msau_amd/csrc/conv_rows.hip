@@ -1705,8 +1705,9 @@ int launch_rowconv8(hipStream_t s, const RowConvArgs& a) {
     MSAU_CHECK_LAUNCH("rowconv8_kernel");
     return 0;
 }
-// instance index of a descriptor, 0 = none
-int rowconv_case(int dtype, const msau_conv_desc* d) {
+}  // namespace
+// the row-streaming instance msau_conv2d launches for `d` (the case numbers of msau_rowconv_launch), 0 = none
+int msau_rowconv_case(int dtype, const msau_conv_desc* d) {
     const RowsEnv& e = rows_env();
     if (!e.on || !e.conv || dtype != MSAU_BF16 || (d->flags & (MSAU_CONV_ELU | MSAU_CONV_EXTENT))) return 0;
     if (d->ups == 2) {                                                     // the 16 -> 8 / 32 -> 16 transposed convs (rowdeconv8 / rowdeconv16)
@@ -1747,9 +1748,6 @@ int rowconv_case(int dtype, const msau_conv_desc* d) {
     }
     return 0;
 }
-}  // namespace
-
-int msau_rowconv_takes(int dtype, const msau_conv_desc* d) { return rowconv_case(dtype, d) != 0; }
 
 namespace {
 // task split of a rowconv8 launch (3x3 / 1x1 / 4x4 instances)
@@ -1769,16 +1767,14 @@ void rowconv_split(const msau_conv_desc* d, RowConvArgs& a) {
 }
 }  // namespace
 
-// slabs (= workgroups) of an MSAU_CONV_WGRAD launch of this descriptor; 0 if no instance takes the flag
-extern "C" int msau_conv2d_rider_slabs(int dtype, const msau_conv_desc* d) {
-    if (!d || !(d->flags & MSAU_CONV_WGRAD) || rowconv_case(dtype, d) != 13) return 0;
+// workgroups of a rowconv8 launch of this descriptor (= the slabs an MSAU_CONV_WGRAD launch writes)
+int msau_rowconv_workgroups(const msau_conv_desc* d) {
     RowConvArgs a;
     rowconv_split(d, a);
     return 8 * (a.tasks_per_xcd / 4);
 }
 
-int msau_rowconv_launch(hipStream_t s, int dtype, const msau_conv_desc* d, int kchunk, int rows) {
-    const int which = rowconv_case(dtype, d);
+int msau_rowconv_launch(hipStream_t s, const msau_conv_desc* d, int kchunk, int rows, int which) {
     if (which == 12 || which == 16) {
         MSAU_CHECK_ARG(kchunk == (which == 12 ? 160 : 288) && rows == 16, "rowdeconv: packed image of another geometry (kchunk %d, rows %d)", kchunk, rows);
         RowDeconvArgs a;

@@ -26,9 +26,22 @@ int msau_ownerconv_wgrad(hipStream_t s, int dtype, const msau_wgrad_desc* d, int
 int msau_ownerconv_slabs(const msau_wgrad_desc* d);
 int msau_rowpair_workgroups(const msau_conv_pair_desc* d);
 int msau_rowpair_launch(hipStream_t s, const msau_conv_pair_desc* d);
-// ... and of msau_conv2d for the single convolutions of the 8-channel level (dispatched from conv.hip)
-int msau_rowconv_takes(int dtype, const msau_conv_desc* d);
-int msau_rowconv_launch(hipStream_t s, int dtype, const msau_conv_desc* d, int kchunk, int rows);
+// The instance families of msau_conv2d besides the tile kernel (conv_route in conv.hip picks one; DESIGN.md, "conv2d routing").
+// <family>_case: the number of the instance that runs the descriptor, 0 = none; pure host arithmetic.  <family>_launch: launches
+// exactly that instance -- a case it has no instance for is an MSAU_ERR_ARG error, never "try the next family".
+// conv_rows.hip: row-streaming instances for the single convolutions of the 8-channel level
+int msau_rowconv_case(int dtype, const msau_conv_desc* d);
+int msau_rowconv_launch(hipStream_t s, const msau_conv_desc* d, int kchunk, int rows, int which);
+int msau_rowconv_workgroups(const msau_conv_desc* d);
+// conv_lean.hip: the chunked-K instances and the compile-time-specialised instances for the hot layer shapes
+// (cch / kchunk / nchunks / CT: the generic geometry = the packed image)
+int msau_conv_chunked_case(int dtype, const msau_conv_desc* d, int cch, int nchunks, int CT);
+int msau_conv_chunked_launch(hipStream_t s, int dtype, const msau_conv_desc* d, int kchunk, int nchunks, int CT, int which);
+int msau_conv_lean_case(int dtype, const msau_conv_desc* d, int nchunks, int CT);
+int msau_conv_lean_launch(hipStream_t s, int dtype, const msau_conv_desc* d, int kchunk, int CT, int which);
+// conv_first.hip: the first conv fed with the fp32 NCHW input tensor (MSAU_CONV_NCHW); one instance
+int msau_firstconv_takes(int dtype, const msau_conv_desc* d);
+int msau_firstconv_launch(hipStream_t s, int dtype, const msau_conv_desc* d, int real_channels);
 // ... and of msau_conv2d_wgrad for the 8 -> 8 3x3 weight gradients (dispatched from conv_wgrad.hip)
 int msau_rowwgrad_takes(int dtype, const msau_wgrad_desc* d, int cch, int nchunks, int kextc);
 int msau_rowwgrad_launch(hipStream_t s, const msau_wgrad_desc* d);

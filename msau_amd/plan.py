@@ -46,6 +46,13 @@ def _ru(a: int, b: int) -> int:
     return -(-a // b) * b
 
 
+def _launch_info(dtype: int, d) -> "C.Array":
+    """msau_conv2d_launch_info of a conv descriptor: info[0..7] (include/msau_hip.h)"""
+    info = (L.i32 * 8)()
+    L.call("msau_conv2d_launch_info", dtype, C.byref(d), info)
+    return info
+
+
 def _ptr(t: Optional[torch.Tensor]) -> Optional[int]:
     return None if t is None else t.data_ptr()
 
@@ -222,8 +229,7 @@ class ConvOp(Op):
             proto.dil, proto.stride, proto.ups = self.dil, 1, 1
             proto.pad_t = (self.k - 1) * self.dil - self.pad_t
             proto.pad_l = (self.k - 1) * self.dil - self.pad_l
-            info = (L.i32 * 8)()
-            L.call("msau_conv2d_launch_info", P.dtype, C.byref(proto), info)
+            info = _launch_info(P.dtype, proto)
             if info[7] & 2:
                 gd = self._geom(out.Cs, 0, x1.Cs + x2.Cs, self.dil, 1, 1)
                 self.dd_off = P.alloc_pack(gd.bytes)
@@ -279,15 +285,13 @@ class ConvOp(Op):
             # softmax + argmax in the end conv's epilogue when the instance taking the launch implements it,
             # otherwise Plan.predict runs the stand-alone kernel on the stored logits (same arithmetic)
             d.head_probs, d.head_argmax, d.head_classes = _ptr(P.head_probs), _ptr(P.head_argmax), out.C
-            info = (L.i32 * 8)()
-            L.call("msau_conv2d_launch_info", P.dtype, C.byref(d), info)
+            info = _launch_info(P.dtype, d)
             P.head_fused = bool(info[7] & 1) and d.flags == 0 and out.C <= 16
             if P.head_fused:
                 d.flags = L.CONV_HEAD
         lrn = getattr(self, "lrn", None)
         if lrn is not None and conv and d.flags & ~L.CONV_RELU_IN == 0 and lrn.a.C == lrn.a.Cs:
-            info = (L.i32 * 8)()
-            L.call("msau_conv2d_launch_info", P.dtype, C.byref(d), info)
+            info = _launch_info(P.dtype, d)
             if info[7] & 4:                  # LocalResponseNorm(size=C) in this conv's epilogue: layers.py:145,161-162
                 d.flags |= L.CONV_LRN
                 d.y2 = _ptr(lrn.y.data)
@@ -295,8 +299,7 @@ class ConvOp(Op):
                 lrn.fused_into = self
         pool = getattr(self, "pool", None)
         if pool is not None and conv and not (d.flags & (L.CONV_LRN | L.CONV_HEAD)):
-            info = (L.i32 * 8)()
-            L.call("msau_conv2d_launch_info", P.dtype, C.byref(d), info)
+            info = _launch_info(P.dtype, d)
             if info[7] & 8:                  # zero pad + MaxPool2d(2,2) in this conv's epilogue: model/model.py:158-160
                 d.flags |= L.CONV_POOL
                 d.pool_y, d.pool_idx = _ptr(pool.y.data), _ptr(pool.idx)
@@ -459,8 +462,7 @@ class ConvOp(Op):
             taps * cin_real * self.out.C
 
         def conv_meta(d):
-            info = (L.i32 * 8)()
-            L.call("msau_conv2d_launch_info", P.dtype, C.byref(d), info)
+            info = _launch_info(P.dtype, d)
             nin = d.B * d.Hin * d.Win * (d.C1 + d.C2)
             nout = d.B * d.Hout * d.Wout * d.Cout
             extra = sum(1 for f in (L.CONV_ADD, L.CONV_ACCUM, L.CONV_MASK_A, L.CONV_MASK_B, L.CONV_LRN) if d.flags & f)
@@ -1532,8 +1534,7 @@ class Plan:
             ok = c is not None and os.environ.get("MSAU_FIRST_NCHW", "1") != "0" and not (c.pair is not None and c.pair.active) \
                 and not (c.fdesc.flags & ~L.CONV_RELU_OUT)
             if ok:
-                info = (L.i32 * 8)()
-                L.call("msau_conv2d_launch_info", self.dtype, C.byref(c.fdesc), info)
+                info = _launch_info(self.dtype, c.fdesc)
                 ok = bool(info[7] & 64)
             self._nchw_conv = c if ok else None
             self._nchw_on = False
@@ -1579,8 +1580,7 @@ class Plan:
             if ok:
                 probe = L.ConvDesc.from_buffer_copy(c.fdesc)
                 probe.flags |= L.CONV_IDS
-                info = (L.i32 * 8)()
-                L.call("msau_conv2d_launch_info", self.dtype, C.byref(probe), info)
+                info = _launch_info(self.dtype, probe)
                 ok = bool(info[7] & 16)
             if ok and self.training and c.wdesc is not None:        # the id-mask weight gradient is the bf16 64 -> 8 instance
                 ok = self.dtype == L.BF16 and c.wgeom.lean and c.wdesc.C1 == 64 and c.wdesc.Cout == 8 and c.wgeom.nchunks == 1
@@ -1617,13 +1617,12 @@ class Plan:
             ok = c is not None and os.environ.get("MSAU_OWNER_CONV", "1") != "0" and not (c.pair is not None and c.pair.active) \
                 and not (c.fdesc.flags & ~(L.CONV_RELU_OUT | L.CONV_EXTENT))
             if ok:
-                info = (L.i32 * 8)()
-                L.call("msau_conv2d_launch_info", self.dtype, C.byref(c.fdesc), info)
+                info = _launch_info(self.dtype, c.fdesc)
                 ok = bool(info[7] & 32)
                 if ok and self.ragged:
                     probe = L.ConvDesc.from_buffer_copy(c.fdesc)
                     probe.flags |= L.CONV_OWNER
-                    L.call("msau_conv2d_launch_info", self.dtype, C.byref(probe), info)
+                    info = _launch_info(self.dtype, probe)
                     ok = bool(info[7] & 128)
             if ok and self.training and c.wdesc is not None:
                 ok = c.wdesc.flags == 0 and c.uentry is not None and c.kind == "conv"
