@@ -787,6 +787,22 @@ int msau_kv_regions_limits(int32_t* out);
 int msau_kv_regions(void* stream, const uint8_t* argmax, const uint16_t* line_ids, const uint16_t* char_pos, const int32_t* boxes,
                     const int32_t* box_off, const int32_t* extent, int B, int H, int W, int n_class, int32_t* header,
                     int32_t* regions, int cap_regions, int32_t* pairs, int cap_pairs, int32_t* overflow);
+/*   msau_kv_regions_large  : the same table for documents of any size (h * w < 2^31): the same phases with the labels in a
+ *                            workspace in device memory, one workgroup per (listed document, class), each on its own h * w int32
+ *                            of it.  To be called after msau_kv_regions, on the same stream, with the same arguments and output
+ *                            buffers, for the documents that launch flagged 1 (the caller knows them from their sizes).
+ *                              docs    int32 [n_docs] in HOST memory: the documents to redo, each in [0, B), none twice
+ *                              ws_off  int64 [n_docs] in HOST memory, increasing: document docs[i] owns workspace[ws_off[i] ..
+ *                                      ws_off[i + 1]) (the last one up to workspace_ints) and needs (n_class - 2) * h * w of it
+ *                              workspace int32 [workspace_ints] in device memory; holds nothing between calls
+ *                            For each listed document: its overflow word is REPLACED by this launch's own flags (1: h * w or
+ *                            the extent out of range, or its workspace share too small; 2 .. 16 as above), its header rows are
+ *                            zeroed and written, its list slices written.  No other document is touched.  The limits per class
+ *                            (msau_kv_regions_limits) and the capacities hold as above. */
+int msau_kv_regions_large(void* stream, const uint8_t* argmax, const uint16_t* line_ids, const uint16_t* char_pos, const int32_t* boxes,
+                          const int32_t* box_off, const int32_t* extent, int B, int H, int W, int n_class, const int32_t* docs,
+                          int n_docs, const int64_t* ws_off, int32_t* workspace, int64_t workspace_ints, int32_t* header,
+                          int32_t* regions, int cap_regions, int32_t* pairs, int cap_pairs, int32_t* overflow);
 
 /* ------------------------------------------------------------------------------------------
  * Mask painter for key-value inference (inference/kv_model.py:83-148 `_generate_masks_from_label`, the per-pixel part):

@@ -223,6 +223,8 @@ _SIGNATURES = {
     "msau_eval_confusion": (C.c_int, [vp, C.c_int, vp, vp, vp] + [C.c_int] * 6 + [vp]),
     "msau_kv_regions_limits": (C.c_int, [C.POINTER(i32)]),
     "msau_kv_regions": (C.c_int, [vp] * 7 + [C.c_int] * 4 + [vp, vp, C.c_int, vp, C.c_int, vp]),
+    "msau_kv_regions_large": (C.c_int, [vp] * 7 + [C.c_int] * 4 + [C.POINTER(i32), C.c_int, C.POINTER(i64), vp, i64]
+                              + [vp, vp, C.c_int, vp, C.c_int, vp]),
     "msau_kv_paint": (C.c_int, [vp] * 6 + [C.c_int] * 3 + [vp, vp, vp]),
     "msau_kv_paint_train": (C.c_int, [vp] * 7 + [C.c_int] * 3 + [vp, vp, vp]),
     "msau_label_hist": (C.c_int, [vp, vp, vp, vp] + [C.c_int] * 5),

@@ -7,6 +7,8 @@
 //           non-zero character position over the pixels of k inside line v's box
 // One workgroup per (document, class); the whole document lives in LDS:
 //   labels   int32 [RG_MAXPIX]      union-find forest, parent <= child, so a root is its component's smallest linear index
+//                                   (the large form, for documents of more pixels: h * w int32 of a workspace in device memory,
+//                                   indexed alike; everything else as here)
 //   pairs    4 x uint32 [RG_HASH]   open-addressing hash keyed (k << 16) | v, sorted in place (bitonic) before it is written
 //   comps    6 x int32 [RG_MAXK]    first pixel, box, count
 // Every loop is a counted loop whose bound follows from the document's pixel count (or from the sizes of the LDS tables); a
@@ -39,7 +41,8 @@ RG_DEV int rg_amax(int* p, int v) { return atomicMax(p, v); }
 RG_DEV int rg_aadd(int* p, int v) { return atomicAdd(p, v); }
 RG_DEV int rg_aor(int* p, int v) { return atomicOr(p, v); }
 RG_DEV unsigned rg_acas(unsigned* p, unsigned cmp, unsigned v) { return atomicCAS(p, cmp, v); }
-RG_DEV int rg_ld(const int* p) { return *(const volatile int*)p; }
+// a label another wave may change in the same phase: never from a register or (large form) from the L1, always a value written
+RG_DEV int rg_ld(const int* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 #define RG_SYNC() __syncthreads()
 #endif
 // a uniform exit: every lane reads the flags, THEN a barrier, so that no lane of the next phase can change them under a reader
@@ -52,6 +55,8 @@ RG_DEV int rg_ld(const int* p) { return *(const volatile int*)p; }
 #define RG_REGION_INTS 8
 #define RG_PAIR_INTS 4
 #define RG_MAXLINES 65535
+#define RG_LARGE_MAXPIX (0x7FFFFFFF - 2 * RG_THREADS)   // the large form: p + RG_THREADS and lane * chunk + i stay in an int
+#define RG_LARGE_DOCS 32                                // documents per launch of the large form (their list is a kernel argument)
 #define RG_EMPTY 0xFFFFFFFFu
 #define RG_BG (-1)
 enum { RG_OVF_PIXELS = 1, RG_OVF_LABEL = 2, RG_OVF_REGIONS = 4, RG_OVF_PAIRS = 8, RG_OVF_LINES = 16 };
@@ -70,17 +75,19 @@ struct RgCtx {                      // one (document, class)
 };
 
 struct RgLds {
-    int* L;                                          // [RG_MAXPIX]
+    int* L;                                          // [RG_MAXPIX] in LDS, or [h * w] of the workspace (large form)
     unsigned* hk; int* hn; int* hmn; int* hmx;       // [RG_HASH]
     int* cfirst; int* cy0; int* cy1; int* cx0; int* cx1; int* ccnt;   // [RG_MAXK]
     int* scan;                                       // [RG_THREADS]
     int* part;                                       // [32]
     int* misc;                                       // [RG_MISC]
 };
-#define RG_LDS_INTS (RG_MAXPIX + 4 * RG_HASH + 6 * RG_MAXK + RG_THREADS + 32 + RG_MISC)
+#define RG_TABLE_INTS (4 * RG_HASH + 6 * RG_MAXK + RG_THREADS + 32 + RG_MISC)
+#define RG_LDS_INTS (RG_MAXPIX + RG_TABLE_INTS)
 
-RG_DEV void rg_carve(RgLds& s, int* base) {
-    s.L = base; base += RG_MAXPIX;
+// L: the labels; base: RG_TABLE_INTS for the tables
+RG_DEV void rg_carve(RgLds& s, int* L, int* base) {
+    s.L = L;
     s.hk = (unsigned*)base; base += RG_HASH;
     s.hn = base; base += RG_HASH;
     s.hmn = base; base += RG_HASH;
@@ -118,7 +125,7 @@ RG_DEV int rg_find(const RgLds& s, int a, int npix) {
 
 // lock-free union: hang the larger root under the smaller one; a + b decreases with every retry
 RG_DEV void rg_union(const RgLds& s, int a, int b, int npix) {
-    for (int it = 0; it < 2 * npix + 2; ++it) {
+    for (unsigned it = 0; it < 2u * (unsigned)npix + 2u; ++it) {             // (unsigned: npix may be close to 2^31)
         a = rg_find(s, a, npix);
         b = rg_find(s, b, npix);
         if (a == b) return;
@@ -354,11 +361,55 @@ RG_DEV int rg_body(const RgCtx& c, const RgLds& s) {
     return 0;
 }
 
-// the checks that need no LDS: a document the LDS form does not hold, an extent outside the canvas, a line list too long
-RG_DEV int rg_precheck(int h, int w, int H, int W, int n_lines) {
-    if (h < 1 || w < 1 || h > H || w > W || (int64_t)h * w > RG_MAXPIX) return RG_OVF_PIXELS;
+// the checks that need no LDS: a document this form does not hold, an extent outside the canvas, a line list too long
+RG_DEV int rg_precheck(int h, int w, int H, int W, int n_lines, int64_t max_pixels) {
+    if (h < 1 || w < 1 || h > H || w > W || (int64_t)h * w > max_pixels) return RG_OVF_PIXELS;
     if (n_lines < 0 || n_lines > RG_MAXLINES) return RG_OVF_LINES;
     return 0;
+}
+
+// the (document b, class cc) of a launch
+RG_DEV void rg_ctx(RgCtx& c, int b, int cc, const uint8_t* argmax, const uint16_t* line_ids, const uint16_t* char_pos, const int32_t* boxes,
+                   const int32_t* box_off, const int32_t* extent, int H, int W, int n_class, int32_t* header, int32_t* regions,
+                   int cap_regions, int32_t* pairs, int cap_pairs) {
+    const size_t plane = (size_t)b * H * W;
+    c.cls = argmax + plane; c.line = line_ids + plane; c.chr = char_pos + plane;
+    c.boxes = boxes + 4 * (size_t)box_off[b]; c.n_lines = box_off[b + 1] - box_off[b];
+    c.h = extent ? extent[2 * b] : H; c.w = extent ? extent[2 * b + 1] : W; c.W = W; c.c = cc;
+    c.hdr = header + 4 * (size_t)b * n_class;
+    c.regions = regions + (size_t)b * cap_regions * RG_REGION_INTS; c.cap_regions = cap_regions;
+    c.pairs = pairs + (size_t)b * cap_pairs * RG_PAIR_INTS; c.cap_pairs = cap_pairs;
+}
+
+// ---- the large form ------------------------------------------------------------------------------------------------
+// The documents of one launch and their shares of the workspace.  Class cc of document doc[i] labels in
+// workspace[off[i] + (cc - 2) * h * w ..); a share that is too small for that is the document's RG_OVF_PIXELS.
+struct RgLargeDocs { int64_t off[RG_LARGE_DOCS]; int64_t share[RG_LARGE_DOCS]; int32_t doc[RG_LARGE_DOCS]; };
+
+// what the host can say about the list; `ext` = the extents when the host can read them (ext_known), NULL with ext_known for a
+// dense batch.  -> NULL or the complaint
+static inline const char* rg_large_args(int B, int H, int W, int n_class, const int32_t* docs, int n_docs, const int64_t* ws_off,
+                                        int64_t workspace_ints, const int32_t* ext, int ext_known) {
+    if (!docs || !ws_off) return "null document list";
+    if (n_docs < 1 || n_docs > B) return "n_docs must be in [1, B]";
+    if (workspace_ints < 0) return "negative workspace size";
+    for (int i = 0; i < n_docs; ++i) {
+        if (docs[i] < 0 || docs[i] >= B) return "a listed document is outside [0, B)";
+        for (int j = 0; j < i; ++j) if (docs[j] == docs[i]) return "a document is listed twice";
+        const int64_t end = i + 1 < n_docs ? ws_off[i + 1] : workspace_ints;
+        if (ws_off[i] < 0 || end < ws_off[i] || end > workspace_ints) return "workspace offsets must increase within the workspace";
+        if (ext_known) {
+            const int64_t h = ext ? ext[2 * docs[i]] : H, w = ext ? ext[2 * docs[i] + 1] : W;
+            if (h >= 1 && w >= 1 && h <= H && w <= W && (n_class - 2) * h * w > end - ws_off[i])
+                return "a workspace share is smaller than (n_class - 2) * h * w";
+        }
+    }
+    return 0;
+}
+
+RG_DEV int64_t rg_large_pixels(int64_t share, int n_class) {
+    const int64_t fit = share / (n_class - 2);
+    return fit < RG_LARGE_MAXPIX ? fit : RG_LARGE_MAXPIX;
 }
 
 #ifdef MSAU_REGIONS_CPU
@@ -373,19 +424,43 @@ extern "C" int msau_kv_regions_cpu(const uint8_t* argmax, const uint16_t* line_i
     for (int b = 0; b < B; ++b)
         for (int cc = 2; cc < n_class; ++cc) {
             RgCtx c;
-            const size_t plane = (size_t)b * H * W;
-            c.cls = argmax + plane; c.line = line_ids + plane; c.chr = char_pos + plane;
-            c.boxes = boxes + 4 * (size_t)box_off[b]; c.n_lines = box_off[b + 1] - box_off[b];
-            c.h = extent ? extent[2 * b] : H; c.w = extent ? extent[2 * b + 1] : W; c.W = W; c.c = cc;
-            c.hdr = header + 4 * (size_t)b * n_class;
-            c.regions = regions + (size_t)b * cap_regions * RG_REGION_INTS; c.cap_regions = cap_regions;
-            c.pairs = pairs + (size_t)b * cap_pairs * RG_PAIR_INTS; c.cap_pairs = cap_pairs;
+            rg_ctx(c, b, cc, argmax, line_ids, char_pos, boxes, box_off, extent, H, W, n_class, header, regions, cap_regions, pairs, cap_pairs);
             RgLds s;
-            rg_carve(s, lds);
-            int f = rg_precheck(c.h, c.w, H, W, c.n_lines);
+            rg_carve(s, lds, lds + RG_MAXPIX);
+            int f = rg_precheck(c.h, c.w, H, W, c.n_lines, RG_MAXPIX);
             if (!f) f = rg_body(c, s);
             overflow[b] |= f;
         }
+    free(lds);
+    return 0;
+}
+// the large launch, lane by lane on the host: same arguments as msau_kv_regions_large without the stream; 2 = refused arguments
+extern "C" int msau_kv_regions_large_cpu(const uint8_t* argmax, const uint16_t* line_ids, const uint16_t* char_pos, const int32_t* boxes,
+                                         const int32_t* box_off, const int32_t* extent, int B, int H, int W, int n_class,
+                                         const int32_t* docs, int n_docs, const int64_t* ws_off, int32_t* workspace, int64_t workspace_ints,
+                                         int32_t* header, int32_t* regions, int cap_regions, int32_t* pairs, int cap_pairs, int32_t* overflow) {
+    if (!(argmax && line_ids && char_pos && boxes && box_off && workspace && header && regions && pairs && overflow)) return 2;
+    if (!(B > 0 && H > 0 && W > 0 && (int64_t)H * W < (1ll << 31) && n_class >= 1 && n_class <= 255 && cap_regions >= 1 && cap_pairs >= 1)) return 2;
+    if (rg_large_args(B, H, W, n_class, docs, n_docs, ws_off, workspace_ints, extent, 1)) return 2;
+    int* lds = (int*)malloc(sizeof(int) * RG_TABLE_INTS);
+    if (!lds) return 1;
+    for (int i = 0; i < n_docs; ++i) {
+        const int b = docs[i];
+        memset(header + 4 * (size_t)b * n_class, 0, sizeof(int32_t) * 4 * n_class);
+        overflow[b] = 0;
+        const int64_t share = (i + 1 < n_docs ? ws_off[i + 1] : workspace_ints) - ws_off[i];
+        for (int cc = 2; cc < n_class; ++cc) {
+            RgCtx c;
+            rg_ctx(c, b, cc, argmax, line_ids, char_pos, boxes, box_off, extent, H, W, n_class, header, regions, cap_regions, pairs, cap_pairs);
+            RgLds s;
+            int f = rg_precheck(c.h, c.w, H, W, c.n_lines, rg_large_pixels(share, n_class));
+            if (!f) {
+                rg_carve(s, workspace + ws_off[i] + (int64_t)(cc - 2) * c.h * c.w, lds);
+                f = rg_body(c, s);
+            }
+            overflow[b] |= f;
+        }
+    }
     free(lds);
     return 0;
 }
@@ -402,18 +477,39 @@ kv_regions_kernel(const uint8_t* argmax, const uint16_t* line_ids, const uint16_
     extern __shared__ int rg_lds[];
     const int b = blockIdx.y;
     RgCtx c;
-    const size_t plane = (size_t)b * H * W;
-    c.cls = argmax + plane; c.line = line_ids + plane; c.chr = char_pos + plane;
-    c.boxes = boxes + 4 * (size_t)box_off[b]; c.n_lines = box_off[b + 1] - box_off[b];
-    c.h = extent ? extent[2 * b] : H; c.w = extent ? extent[2 * b + 1] : W; c.W = W; c.c = 2 + (int)blockIdx.x;
-    c.hdr = header + 4 * (size_t)b * n_class;
-    c.regions = regions + (size_t)b * cap_regions * RG_REGION_INTS; c.cap_regions = cap_regions;
-    c.pairs = pairs + (size_t)b * cap_pairs * RG_PAIR_INTS; c.cap_pairs = cap_pairs;
+    rg_ctx(c, b, 2 + (int)blockIdx.x, argmax, line_ids, char_pos, boxes, box_off, extent, H, W, n_class, header, regions, cap_regions, pairs, cap_pairs);
     RgLds s;
-    rg_carve(s, rg_lds);
-    int f = rg_precheck(c.h, c.w, H, W, c.n_lines);           // uniform over the workgroup, like every exit of rg_body
+    rg_carve(s, rg_lds, rg_lds + RG_MAXPIX);
+    int f = rg_precheck(c.h, c.w, H, W, c.n_lines, RG_MAXPIX);     // uniform over the workgroup, like every exit of rg_body
     if (!f) f = rg_body(c, s);
     if (f && threadIdx.x == 0) atomicOr(overflow + b, f);
+}
+
+// The large form: the labels of (document ld.doc[blockIdx.y], class 2 + blockIdx.x) in that pair's own h * w int32 of the
+// workspace, the tables in LDS, the phases of rg_body as they are.  Only this workgroup touches its share, and only between its
+// own barriers: see DESIGN.md 5b for why plain accesses and rg_ld's L2 loads see what they must.
+__global__ void __launch_bounds__(RG_THREADS)
+kv_regions_large_kernel(const uint8_t* argmax, const uint16_t* line_ids, const uint16_t* char_pos, const int32_t* boxes, const int32_t* box_off,
+                        const int32_t* extent, int H, int W, int n_class, RgLargeDocs ld, int32_t* workspace, int32_t* header,
+                        int32_t* regions, int cap_regions, int32_t* pairs, int cap_pairs, int32_t* overflow) {
+    __shared__ int rg_tables[RG_TABLE_INTS];
+    const int i = blockIdx.y, b = ld.doc[i];
+    RgCtx c;
+    rg_ctx(c, b, 2 + (int)blockIdx.x, argmax, line_ids, char_pos, boxes, box_off, extent, H, W, n_class, header, regions, cap_regions, pairs, cap_pairs);
+    RgLds s;
+    int f = rg_precheck(c.h, c.w, H, W, c.n_lines, rg_large_pixels(ld.share[i], n_class));
+    if (!f) {
+        rg_carve(s, workspace + ld.off[i] + (int64_t)blockIdx.x * c.h * c.w, rg_tables);
+        f = rg_body(c, s);
+    }
+    if (f && threadIdx.x == 0) atomicOr(overflow + b, f);
+}
+
+// the listed documents' header rows and overflow words, as msau_kv_regions leaves them before its launch
+__global__ void kv_regions_large_reset_kernel(RgLargeDocs ld, int n_class, int32_t* header, int32_t* overflow) {
+    const int b = ld.doc[blockIdx.x];
+    for (int i = threadIdx.x; i < 4 * n_class; i += blockDim.x) header[4 * (size_t)b * n_class + i] = 0;
+    if (threadIdx.x == 0) overflow[b] = 0;
 }
 
 extern "C" int msau_kv_regions_limits(int32_t* out) {
@@ -444,6 +540,38 @@ extern "C" int msau_kv_regions(void* stream, const uint8_t* argmax, const uint16
     hipLaunchKernelGGL(kv_regions_kernel, dim3(n_class - 2, B), dim3(RG_THREADS), sizeof(int) * RG_LDS_INTS, s, argmax, line_ids, char_pos, boxes,
                        box_off, extent, H, W, n_class, header, regions, cap_regions, pairs, cap_pairs, overflow);
     MSAU_CHECK_LAUNCH("kv_regions");
+    return 0;
+}
+
+extern "C" int msau_kv_regions_large(void* stream, const uint8_t* argmax, const uint16_t* line_ids, const uint16_t* char_pos, const int32_t* boxes,
+                                     const int32_t* box_off, const int32_t* extent, int B, int H, int W, int n_class, const int32_t* docs,
+                                     int n_docs, const int64_t* ws_off, int32_t* workspace, int64_t workspace_ints, int32_t* header,
+                                     int32_t* regions, int cap_regions, int32_t* pairs, int cap_pairs, int32_t* overflow) {
+    MSAU_CHECK_ARG(argmax && line_ids && char_pos && boxes && box_off && workspace && header && regions && pairs && overflow,
+                   "kv_regions_large: null pointer");
+    MSAU_CHECK_ARG(B > 0 && B <= 65535 && H > 0 && W > 0 && (int64_t)H * W < (1ll << 31), "kv_regions_large: bad shape B = %d, H = %d, W = %d", B, H, W);
+    MSAU_CHECK_ARG(n_class >= 1 && n_class <= 255, "kv_regions_large: n_class = %d, must be in [1, 255]", n_class);
+    MSAU_CHECK_ARG(cap_regions >= 1 && cap_pairs >= 1 && cap_regions < (1 << 24) && cap_pairs < (1 << 24), "kv_regions_large: bad capacities");
+    const char* bad = rg_large_args(B, H, W, n_class, docs, n_docs, ws_off, workspace_ints, nullptr, extent == nullptr);
+    MSAU_CHECK_ARG(!bad, "kv_regions_large: %s", bad);
+    static_assert(sizeof(int) * RG_TABLE_INTS <= 64 * 1024, "kv_regions_large: the tables are a static LDS array");
+    static_assert(sizeof(RgLargeDocs) <= 1024, "kv_regions_large: the document list is a kernel argument");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    for (int k = 0; k < n_docs; k += RG_LARGE_DOCS) {
+        const int n = n_docs - k < RG_LARGE_DOCS ? n_docs - k : RG_LARGE_DOCS;
+        RgLargeDocs ld = {};
+        for (int i = 0; i < n; ++i) {
+            ld.doc[i] = docs[k + i];
+            ld.off[i] = ws_off[k + i];
+            ld.share[i] = (k + i + 1 < n_docs ? ws_off[k + i + 1] : workspace_ints) - ws_off[k + i];
+        }
+        hipLaunchKernelGGL(kv_regions_large_reset_kernel, dim3(n), dim3(256), 0, s, ld, n_class, header, overflow);
+        MSAU_CHECK_LAUNCH("kv_regions_large (reset)");
+        if (n_class < 3) continue;
+        hipLaunchKernelGGL(kv_regions_large_kernel, dim3(n_class - 2, n), dim3(RG_THREADS), 0, s, argmax, line_ids, char_pos, boxes, box_off,
+                           extent, H, W, n_class, ld, workspace, header, regions, cap_regions, pairs, cap_pairs, overflow);
+        MSAU_CHECK_LAUNCH("kv_regions_large");
+    }
     return 0;
 }
 #endif

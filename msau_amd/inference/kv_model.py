@@ -19,6 +19,9 @@ character-position masks and the line boxes go up with the ids, a kernel behind 
 `device_masks=True` (with `device_post=True`) paints the three masks on the device as well: a document goes up as its glyph
 table (msau_amd.inference.glyphs: 32 bytes per line, 8 per character), one launch (csrc/paint.hip) writes the canvases the
 forward and the region kernel read, and the host builds a per-pixel array only for a document that falls back.  Same results.
+
+`large_documents=True` (with `device_post=True`, with or without `device_masks`) sends a page of more pixels than the region
+kernel holds in LDS through that kernel's large form (labels in device memory) and not through the host fallback.  Same results.
 """
 from __future__ import annotations
 
@@ -265,11 +268,11 @@ class KVModel:
                 eval_results[value_id]["num_label"] += 1
         return correct_answers
 
-    def _run_regions(self, docs_masks):
+    def _run_regions(self, docs_masks, large=False):
         """`device_post`: the masks of a group of documents -> per document its region table.  One forward (dense at one
         document, ragged otherwise) with the region kernel behind it; a document whose overflow flag is set (more pixels, regions
         or pairs than the kernel's tables hold) gets its table from `regions_host` on its crop of the class map, copied back for
-        that document alone -- the same table, never an approximation."""
+        that document alone -- the same table, never an approximation.  `large`: more pixels are no overflow (`regions_device`)."""
         if not torch.cuda.is_available():
             raise RuntimeError("KVModel.predict runs the network through libmsau_hip.so on an MI355X; no GPU is "
                                "visible and there is no CPU fallback")
@@ -286,7 +289,7 @@ class KVModel:
             line_ids, _ = pack_masks([m[1] for m in docs_masks])
             char_pos, _ = pack_masks([m[2] for m in docs_masks])
         tables, flags, amax = self.net.predict_regions(ids=ids.cuda(), sizes=sizes, line_ids=line_ids, char_pos=char_pos,
-                                                       boxes=boxes)
+                                                       boxes=boxes, large=large)
         for b, m in enumerate(docs_masks):
             if flags[b] != 0:
                 h, w = m[0].shape
@@ -305,7 +308,7 @@ class KVModel:
             return self._generate_masks_from_label(json_path), table
         return (None, None, None, table.lines, table.scale, table.bg_pad, table.text_bbox), table
 
-    def _run_regions_painted(self, docs, json_paths):
+    def _run_regions_painted(self, docs, json_paths, large=False):
         """`_run_regions` with the masks painted on the device: docs = [(masks, glyph table)] of `_doc_for_paint`.  One upload of
         the group's tables and one launch paint the canvases; a document without a table has its host masks copied into them.  A
         document whose overflow flag is set has its masks painted on the host then, for `regions_host`."""
@@ -322,7 +325,7 @@ class KVModel:
             if not t.ok:
                 G.upload_host_masks((ids, line_ids, char_pos), b, m[:3])
         tables, flags, amax = self.net.predict_regions(ids=ids, sizes=None if single else torch.from_numpy(sizes),
-                                                       line_ids=line_ids, char_pos=char_pos, boxes=boxes)
+                                                       line_ids=line_ids, char_pos=char_pos, boxes=boxes, large=large)
         for b, (m, t) in enumerate(docs):
             if flags[b] != 0:
                 host = m[:3] if m[0] is not None else self._generate_masks_from_label(json_paths[b])[:3]
@@ -353,44 +356,50 @@ class KVModel:
         return kv_results
 
     @staticmethod
-    def _check_flags(device_post, device_masks):
+    def _check_flags(device_post, device_masks, large_documents=False):
         if device_masks and not device_post:
             raise ValueError("device_masks=True needs device_post=True: the host post-processing reads the masks on the host")
+        if large_documents and not device_post:
+            raise ValueError("large_documents=True needs device_post=True: it chooses the form of the region kernel")
 
-    def predict(self, data, debug_info=None, label_path=None, eval_results=None, device_post=False, device_masks=False):
+    def predict(self, data, debug_info=None, label_path=None, eval_results=None, device_post=False, device_masks=False,
+                large_documents=False):
         """data = (layout JSON path, page image or None) -> ({field: text}, debug image).
         The debug rendering of the reference (OpenCV + PIL drawing) is not part of this build: the second result is
         always None; everything that feeds `kv_results` and `eval_results` is computed as in kv_model.py:264-347.
         device_post=True: the field regions are extracted on the device (module docstring); the results are the same.
-        device_masks=True (needs device_post): the masks are painted on the device from the glyph table; the results are the same."""
-        self._check_flags(device_post, device_masks)
+        device_masks=True (needs device_post): the masks are painted on the device from the glyph table; the results are the same.
+        large_documents=True (needs device_post): a page beyond the region kernel's LDS form stays on the device; the same results."""
+        self._check_flags(device_post, device_masks, large_documents)
         json_path, _debug_im = data
         masks, table = self._doc_for_paint(json_path) if device_masks else (self._generate_masks_from_label(json_path), None)
         input_im, _line_mask, _char_mask, _label_lines, scale, bg_pad, (min_x, min_y, _max_x, _max_y) = masks
         correct_answers = self._read_answers(label_path, scale, (min_x - bg_pad, min_y - bg_pad), eval_results)
         if device_masks:
-            regions = self._run_regions_painted([(masks, table)], [json_path])[0]
+            regions = self._run_regions_painted([(masks, table)], [json_path], large_documents)[0]
             return self._finish_regions(masks, regions, correct_answers, eval_results), None
         if device_post:
-            return self._finish_regions(masks, self._run_regions([masks])[0], correct_answers, eval_results), None
+            return self._finish_regions(masks, self._run_regions([masks], large_documents)[0], correct_answers, eval_results), None
         a_pred, a_cls = self._run_net(input_im)
         return self._finish(masks, a_pred, a_cls, correct_answers, eval_results), None
 
-    def predict_batch(self, json_paths, label_paths=None, eval_results=None, device_post=False, device_masks=False):
+    def predict_batch(self, json_paths, label_paths=None, eval_results=None, device_post=False, device_masks=False,
+                      large_documents=False):
         """`predict` for a group of layout JSONs with one network forward: the documents' id masks share a ragged canvas
         (each is computed as it would be alone).  -> [kv_results] in the order of `json_paths`.  The ground truth of the whole
         group is read before the forward, so a label file that cannot be read is reported before any result is returned
         (`run_test` prints each such message next to its own document, as at batch 1).  device_post=True, device_masks=True: as
-        in `predict`; the group's glyph tables go up in one copy and one launch paints its canvases."""
-        results, notes = self._predict_group(json_paths, label_paths, eval_results, device_post, device_masks)
+        in `predict`; the group's glyph tables go up in one copy and one launch paints its canvases.  large_documents=True: as in
+        `predict`, for the pages of the group that need it."""
+        results, notes = self._predict_group(json_paths, label_paths, eval_results, device_post, device_masks, large_documents)
         for doc_notes in notes:
             for n in doc_notes:
                 print(*n)
         return results
 
-    def _predict_group(self, json_paths, label_paths, eval_results, device_post=False, device_masks=False):
+    def _predict_group(self, json_paths, label_paths, eval_results, device_post=False, device_masks=False, large_documents=False):
         """predict_batch -> ([kv_results], per document the list of its unprinted messages)"""
-        self._check_flags(device_post, device_masks)
+        self._check_flags(device_post, device_masks, large_documents)
         docs, notes, painted = [], [], []
         for k, json_path in enumerate(json_paths):
             if device_masks:
@@ -404,24 +413,27 @@ class KVModel:
             docs.append((masks, self._read_answers(label_path, scale, (min_x - bg_pad, min_y - bg_pad), eval_results,
                                                    notes[-1])))
         if device_post:
-            tables = self._run_regions_painted(painted, json_paths) if device_masks else self._run_regions([masks for masks, _ in docs])
+            tables = (self._run_regions_painted(painted, json_paths, large_documents) if device_masks
+                      else self._run_regions([masks for masks, _ in docs], large_documents))
             return [self._finish_regions(masks, table, correct_answers, eval_results)
                     for (masks, correct_answers), table in zip(docs, tables)], notes
         outs = self._run_net_batch([masks[0] for masks, _ in docs])
         return [self._finish(masks, a_pred, a_cls, correct_answers, eval_results)
                 for (masks, correct_answers), (a_pred, a_cls) in zip(docs, outs)], notes
 
-    def run_test(self, list_inf, out_dir, label_dir=None, img_dir=None, batch_size=1, device_post=False, device_masks=False):
+    def run_test(self, list_inf, out_dir, label_dir=None, img_dir=None, batch_size=1, device_post=False, device_masks=False,
+                 large_documents=False):
         """predict every layout JSON of `list_inf`; with `label_dir`, print per-class counts and precision / recall /
         F1 over region boxes (kv_model.py:350-387).  Unlike the reference a missing page image does not skip the
         document, because no debug image is drawn.  batch_size > 1: consecutive groups of `batch_size` documents go through
         the network as one ragged forward (as in `predict_batch`); results, printing and `eval_results` keep the order of
         `list_inf`, and the last group may be shorter.  The counts are kept as `self.eval_results`.  device_post=True: the
         field regions of every document are extracted on the device (module docstring); results and printing are the same.
-        device_masks=True (needs device_post): the masks are painted on the device as well; results and printing are the same."""
+        device_masks=True (needs device_post): the masks are painted on the device as well; results and printing are the same.
+        large_documents=True (needs device_post): pages beyond the region kernel's LDS form stay on the device; the same again."""
         if batch_size < 1:
             raise ValueError(f"batch_size must be >= 1, got {batch_size}")
-        self._check_flags(device_post, device_masks)
+        self._check_flags(device_post, device_masks, large_documents)
         eval_results = [{"num_pred": 0, "num_correct": 0, "num_label": 0} for _ in range(self.n_class)]
         self.eval_results = eval_results
         kv_results = []
@@ -432,10 +444,11 @@ class KVModel:
             if batch_size == 1:
                 results = [self.predict((group[0], None), debug_info=("", None),
                                         label_path=label_paths[0] if label_paths is not None else None,
-                                        eval_results=eval_results, device_post=device_post, device_masks=device_masks)[0]]
+                                        eval_results=eval_results, device_post=device_post, device_masks=device_masks,
+                                        large_documents=large_documents)[0]]
                 notes = [[]]                                     # (printed by predict)
             else:
-                results, notes = self._predict_group(group, label_paths, eval_results, device_post, device_masks)
+                results, notes = self._predict_group(group, label_paths, eval_results, device_post, device_masks, large_documents)
             for basename, result, doc_notes in zip(names, results, notes):
                 for n in doc_notes:
                     print(*n)

@@ -33,7 +33,8 @@ DEFAULT_CAP_REGIONS = 8192
 DEFAULT_CAP_PAIRS = 4096
 
 # what the device path has copied and how often the host had to step in (tools/infer_bench.py reads and resets these)
-STATS = {"calls": 0, "documents": 0, "d2h_bytes": 0, "fallbacks": 0}
+# "large_documents": documents whose table the large form of the kernel wrote (`regions_device(large=True)`)
+STATS = {"calls": 0, "documents": 0, "d2h_bytes": 0, "fallbacks": 0, "large_documents": 0}
 
 # multi-line fields: KVModel.multiple_lines_fields (kv_model.py:155)
 MULTIPLE_LINES_FIELDS = (5, 11)
@@ -193,16 +194,32 @@ def table_from_records(header_doc: np.ndarray, regions_doc: np.ndarray, pairs_do
 
 
 _buffers: dict = {}
+_workspaces: dict = {}
+
+
+def _workspace(dev, n_ints: int):
+    """the large form's labels: int32 on `dev`, kept and grown; it holds nothing between calls"""
+    import torch
+    ws = _workspaces.get(dev)
+    if ws is None or ws.numel() < n_ints:
+        _workspaces.pop(dev, None)
+        ws = _workspaces[dev] = torch.empty(max(n_ints, 1), dtype=torch.int32, device=dev)
+    return ws
 
 
 def regions_device(argmax, line_ids, char_pos, boxes: Sequence, n_class: int, sizes=None,
-                   cap_regions: Optional[int] = None, cap_pairs: Optional[int] = None) -> Tuple[List[Optional[dict]], List[int]]:
+                   cap_regions: Optional[int] = None, cap_pairs: Optional[int] = None,
+                   large: bool = False) -> Tuple[List[Optional[dict]], List[int]]:
     """The region tables of a batch, by the kernel, on the current stream (so: behind the forward that wrote `argmax`).
 
     argmax uint8 [B, H, W] on the device (the plan's `head_argmax`, not copied); line_ids / char_pos [B, H, W] on the device,
     uint16 values in int16 (or uint16) storage, zero outside the documents (msau_amd.data.ragged.pack_masks); boxes: per document
     the [x1, y1, x2, y2] of its lines; sizes: CPU integer [B, 2] of (h, w) for a ragged batch, None for a dense one.
     cap_regions / cap_pairs: how many records a document may produce (defaults DEFAULT_CAP_*).
+    large=True: the documents of more than `device_limits()["max_pixels"]` pixels (known here from their sizes, nothing is read
+    back for it) get their tables from a second launch behind the first, the large form of the kernel, which keeps their labels
+    in a workspace in device memory; without it such a document is flagged OVF_PIXELS.  The per-class limits and the capacities
+    hold for them as for the others.
     -> ([table or None per document], [overflow flags per document]); a document with a non-zero flag (OVF_*) has no table:
     run `regions_host` on its class map.  Reads back the header (16 bytes per class) and the used prefix of the two lists."""
     import torch
@@ -249,6 +266,19 @@ def regions_device(argmax, line_ids, char_pos, boxes: Sequence, n_class: int, si
     L.call("msau_kv_regions", torch.cuda.current_stream().cuda_stream, argmax.data_ptr(), line_ids.data_ptr(), char_pos.data_ptr(),
            base + 4 * (3 * B + 1), base, base + 4 * (B + 1) if sizes is not None else None, B, H, W, n_class,
            head_d.data_ptr(), reg_d.data_ptr(), cap_regions, pair_d.data_ptr(), cap_pairs, head_d.data_ptr() + 16 * B * n_class)
+    if large and n_class > 2:
+        pixels = [int(h) * int(w) for h, w in sz] if sizes is not None else [H * W] * B
+        big = [b for b in range(B) if pixels[b] > lim["max_pixels"]]
+        if big:
+            share = [(n_class - 2) * pixels[b] for b in big]
+            ws = _workspace(dev, sum(share))
+            docs_a = (C.c_int32 * len(big))(*big)
+            off_a = (C.c_int64 * len(big))(*np.concatenate([[0], np.cumsum(share)[:-1]]).tolist())
+            L.call("msau_kv_regions_large", torch.cuda.current_stream().cuda_stream, argmax.data_ptr(), line_ids.data_ptr(),
+                   char_pos.data_ptr(), base + 4 * (3 * B + 1), base, base + 4 * (B + 1) if sizes is not None else None, B, H, W,
+                   n_class, docs_a, len(big), off_a, ws.data_ptr(), sum(share), head_d.data_ptr(), reg_d.data_ptr(), cap_regions,
+                   pair_d.data_ptr(), cap_pairs, head_d.data_ptr() + 16 * B * n_class)
+            STATS["large_documents"] += len(big)
     head = head_d.cpu().numpy()
     header, flags = head[:B * n_class * 4].reshape(B, n_class, 4), head[B * n_class * 4:].tolist()
     ok = [b for b in range(B) if flags[b] == 0]

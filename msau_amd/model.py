@@ -485,20 +485,21 @@ class MSAUWrapper(nn.Module):
     @torch.no_grad()
     def predict_regions(self, inp: Optional[torch.Tensor] = None, ids: Optional[torch.Tensor] = None, sizes=None, *,
                         line_ids: torch.Tensor, char_pos: torch.Tensor, boxes, cap_regions: Optional[int] = None,
-                        cap_pairs: Optional[int] = None):
+                        cap_pairs: Optional[int] = None, large: bool = False):
         """`predict_nhwc` followed, on the same stream, by the region kernel (csrc/regions.hip) on the class map the head wrote:
         nothing per pixel comes back to the host.  inp / ids / sizes as in `predict_nhwc`; line_ids / char_pos: 16-bit integer
         [B, H, W] tensors on the canvas of the input, zero outside the documents (msau_amd.data.ragged.pack_masks), moved to the
         device here if they are not there; boxes: per document the [x1, y1, x2, y2] of its text lines in grid coordinates.
         -> (tables, flags, argmax): per document its region table (msau_amd.inference.regions) or None, per document the
         overflow flags (0 = the table is complete; otherwise run `regions_host` on that document's crop of `argmax`), and the
-        plan's uint8 [B, H, W] class map on the device.  Eager only: there is no captured-graph form of the region stage."""
+        plan's uint8 [B, H, W] class map on the device.  large=True: documents beyond the LDS form's pixel limit get their table
+        from the large form of the kernel (`regions_device`).  Eager only: there is no captured-graph form of the region stage."""
         from .inference.regions import regions_device
         _probs, amax = self.predict_nhwc(inp=inp, ids=ids, sizes=sizes)
         dev = amax.device
         tables, flags = regions_device(amax, line_ids.to(dev), char_pos.to(dev), boxes, self.n_class,
                                        sizes=None if sizes is None else torch.as_tensor(sizes).tolist(),
-                                       cap_regions=cap_regions, cap_pairs=cap_pairs)
+                                       cap_regions=cap_regions, cap_pairs=cap_pairs, large=large)
         return tables, flags, amax
 
     @torch.no_grad()

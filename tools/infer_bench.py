@@ -7,7 +7,9 @@ With --post B: ms per document of KVModel's post-processing on the host against 
 csrc/regions.hip) and against device_post=True, device_masks=True (the masks painted on the device as well, csrc/paint.hip),
 interleaved in one process: (a) predict_batch end to end on the golden layouts with the golden (seeded, random-weight) net,
 (b) the region stage alone on the reference's clean class maps, both arms starting from class maps on the
-device.  Reads tests/golden/kv only.
+device.  With --post B --large: pages of more pixels than the region kernel holds in LDS (generated here, 260 x 190 at the
+model's scale, 57 824 pixels with the painter's margin) through device_post=True without and with large_documents=True (host fallback against the large form of the
+kernel), interleaved, with the fallback counts of each arm.  Reads tests/golden/kv only.
 Not the headline metric (bench.py is); numbers are quoted in DESIGN.md."""
 import argparse
 import json
@@ -203,6 +205,87 @@ def run_post(B, dtype, repeats, n_docs=48):
     return out
 
 
+def large_layout(seed, height=260, width=190):
+    """a page of text lines 3 units high (so the grid scale is 1): an A4 scan with 40 px lines at KVModel's scale, 278 x 208 =
+    57 824 pixels with the painter's margin; a line every 5 rows, one to three fields of 4 to 30 characters on each"""
+    import numpy as np
+    rng = np.random.default_rng(seed)
+    alphabet = "abcXYZ :-./#0123456789"
+    lines = [{"box": [0, 0, 12, 3], "text": "abc", "type": 0, "value": 0},
+             {"box": [width - 12, height - 3, width, height], "text": "xyz", "type": 0, "value": 0}]     # the page's corners
+    for y in range(5, height - 8, 5):
+        x = int(rng.integers(0, 30))
+        for _ in range(int(rng.integers(1, 4))):
+            n = int(rng.integers(4, 31))
+            x2 = x + 2 * n + int(rng.integers(0, 3))
+            if x2 > width:
+                break
+            lines.append({"box": [x, y, x2, y + 3], "text": "".join(alphabet[i] for i in rng.integers(0, len(alphabet), size=n)),
+                          "type": 0, "value": 0})
+            x = x2 + int(rng.integers(3, 20))
+    return {"lines": lines}
+
+
+def run_large(B, dtype, repeats, n_docs=16, bias_class=3, bias=6.0):
+    """The seeded golden net with the end conv's bias of one field class raised: as it is, its class map has thousands of regions
+    per class on such a page and every document overflows the per-class tables in both arms."""
+    import tempfile
+    import numpy as np
+    from msau_amd.inference import KVModel
+    from msau_amd.inference import glyphs as G
+    from msau_amd.inference import regions as R
+    from oracle import msau_oracle as O
+    KV = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests", "golden", "kv")
+    meta = json.load(open(os.path.join(KV, "kv.json")))
+    n_class, cfg = meta["n_class"], meta["net"]["cfg"]
+    km = KVModel()
+    with tempfile.TemporaryDirectory() as tmp:
+        sd = O.init_params(cfg, meta["net"]["seed"])
+        sd[f"msau_net.end_convs.{cfg.get('num_blocks', 3) - 1}.custom_conv.bias"][bias_class] += bias
+        wpath = os.path.join(tmp, "w.pt")
+        torch.save(sd, wpath)
+        km.load(model_weight=wpath, charset=os.path.join(KV, "charset.txt"), n_class=n_class, dtype=dtype,
+                model_kwargs=dict(featRoot=cfg["featRoot"], scale_space_num=cfg["scale_space_num"], res_depth=cfg["res_depth"],
+                                  filter_size=cfg["filter_size"], pool_size=cfg["pool_size"], final_act="softmax"))
+        files = []
+        for i in range(n_docs):
+            files.append(os.path.join(tmp, f"page{i}.json"))
+            with open(files[-1], "w") as fh:
+                json.dump(large_layout(100 + i), fh)
+        groups = [files[k:k + B] for k in range(0, n_docs, B)]
+        pixels = [int(km._generate_masks_from_label(f)[0].size) for f in files]
+        out = {"batch": B, "dtype": dtype, "n_docs": n_docs, "repeats": repeats, "n_class": n_class,
+               "pixels_per_doc": [min(pixels), max(pixels)], "max_pixels_lds_form": R.device_limits()["max_pixels"]}
+        arms = {}
+        for masks in (False, True):
+            for large in (False, True):
+                arms[("masks_" if masks else "") + ("large" if large else "fallback")] = \
+                    (lambda masks=masks, large=large: [km.predict_batch(gr, device_post=True, device_masks=masks, large_documents=large)
+                                                       for gr in groups])
+        first = {name: fn() for name, fn in arms.items()}                   # (the warm-up)
+        out["same_results"] = all(r == first["fallback"] for r in first.values())
+        out["fields_found"] = sum(1 for grp in first["fallback"] for r in grp for v in r.values() if v)
+        ms = {name: [] for name in arms}
+        stats = {name: {k: 0 for k in R.STATS} for name in arms}
+        for _ in range(repeats):
+            for name, fn in arms.items():
+                before = dict(R.STATS)
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                fn()
+                torch.cuda.synchronize()
+                ms[name].append(round((time.perf_counter() - t0) / n_docs * 1e3, 4))
+                for k in R.STATS:
+                    stats[name][k] += R.STATS[k] - before[k]
+        for name in arms:
+            docs = max(stats[name]["documents"], 1)
+            out[name] = {"ms_per_doc": ms[name], "fallbacks": stats[name]["fallbacks"], "large_documents": stats[name]["large_documents"],
+                         "documents": stats[name]["documents"], "d2h_bytes_per_doc": round(stats[name]["d2h_bytes"] / docs)}
+        out["large_faster_in_every_repeat"] = all(a < b for a, b in zip(ms["large"], ms["fallback"]))
+        out["masks_large_faster_in_every_repeat"] = all(a < b for a, b in zip(ms["masks_large"], ms["masks_fallback"]))
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--iters", type=int, default=30)
@@ -212,7 +295,14 @@ def main():
     ap.add_argument("--post", type=int, default=0, help="only the post-processing comparison (host against device_post=True and device_masks=True), "
                                                         "in batches of this size")
     ap.add_argument("--repeats", type=int, default=5, help="interleaved repeats per arm of --post")
+    ap.add_argument("--large", action="store_true", help="with --post: pages beyond the region kernel's LDS form, host fallback against "
+                                                         "large_documents=True")
+    ap.add_argument("--dtypes", default="bf16,fp32", help="with --post --large: the dtypes to run")
     a = ap.parse_args()
+    if a.post and a.large:
+        for dtype in a.dtypes.split(","):
+            print(json.dumps(run_large(a.post, dtype, a.repeats, min(a.docs, 16))), flush=True)
+        return
     if a.post:
         for dtype in ("bf16", "fp32"):
             print(json.dumps(run_post(a.post, dtype, a.repeats, a.docs)), flush=True)
