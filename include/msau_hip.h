@@ -446,6 +446,10 @@ int msau_selfattn_bwd_ext(void* stream, int dtype, const void* f, const void* g,
                           const float* stats, void* df, void* dg, void* dh, float* ws, int B, int N, int Ds, int Cs,
                           const int32_t* extent, int W);
 
+/* Which kernel family msau_selfattn_fwd / _bwd (and _ext) run for (dtype, N, Ds, Cs): 0 = a compile-time VALU instance, 1 = the
+ * run-time "any width" kernels, 2 = the bf16 MFMA sweeps; -1 for an unknown dtype.  The dispatchers themselves call it. */
+int msau_selfattn_route(int dtype, int N, int Ds, int Cs);
+
 /* Ragged batch: dst[b][p][y][x][:] = (y < h_b && x < w_b) ? src[b][p][y][x][:] : 0 for a tensor of `planes` planes of H x W pixels of
  * `pixel_bytes` bytes each per sample (NHWC activation: planes 1, pixel_bytes Cs * esz; int64 labels: 1, 8; NCHW fp32: C, 4).
  * extent [B][2] int32 (h, w).  src == dst is allowed (in place).  pixel_bytes must be a multiple of 4. */

@@ -181,6 +181,7 @@ _SIGNATURES = {
     "msau_maxpool2x2_bwd_ext": (C.c_int, [vp, C.c_int, vp, vp, vp, vp] + [C.c_int] * 5 + [vp]),
     "msau_selfattn_fwd_ext": (C.c_int, [vp, C.c_int, vp, vp, vp, vp, vp, vp] + [C.c_int] * 4 + [vp, C.c_int]),
     "msau_selfattn_bwd_ext": (C.c_int, [vp, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp, vp] + [C.c_int] * 4 + [vp, C.c_int]),
+    "msau_selfattn_route": (C.c_int, [C.c_int] * 4),
     "msau_extent_copy": (C.c_int, [vp, vp, vp] + [C.c_int] * 5 + [vp]),
     "msau_label_counts": (C.c_int, [vp, vp, vp, C.c_int, i64]),
     "msau_label_counts_split": (C.c_int, [vp, vp, vp, C.c_int, i64, C.c_int]),

@@ -417,26 +417,29 @@ int attn_any_bwd(hipStream_t s, const void* f, const void* g, const void* h, con
                   : attn_any_bwd_e<T, false>(s, f, g, h, dy, stats, df, dg, dh, ws, B, N, Ds, Cs, nullptr, 0);
 }
 
-#define ATTN_DISPATCH(FN, ...)                                                                      \
-    do {                                                                                            \
-        if (Ds == 8 && Cs == 8) return FN<T, 8, 8>(__VA_ARGS__);                                    \
-        if (Ds == 8 && Cs == 16) return FN<T, 8, 16>(__VA_ARGS__);                                  \
-        if (Ds == 8 && Cs == 32) return FN<T, 8, 32>(__VA_ARGS__);                                  \
-        if (Ds == 8 && Cs == 64) return FN<T, 8, 64>(__VA_ARGS__);                                  \
-        if (Ds == 16 && Cs == 128) return FN<T, 16, 128>(__VA_ARGS__);                              \
-    } while (0)
+// the (Ds, Cs) pairs with a compile-time instance: one list for the dispatch and for msau_selfattn_route
+#define ATTN_INSTANCES(X) X(8, 8) X(8, 16) X(8, 32) X(8, 64) X(16, 128)
 
+enum { ROUTE_VALU = 0, ROUTE_ANY = 1, ROUTE_MFMA = 2 };
+
+// `route`: msau_selfattn_route's answer for this call (the MFMA route never comes here)
 template <typename T>
-int attn_fwd_d(hipStream_t s, const void* f, const void* g, const void* h, const void* x, void* y, float* stats,
+int attn_fwd_d(int route, hipStream_t s, const void* f, const void* g, const void* h, const void* x, void* y, float* stats,
                int B, int N, int Ds, int Cs, const int32_t* extent, int W) {
-    ATTN_DISPATCH(attn_fwd_t, s, f, g, h, x, y, stats, B, N, extent, W);
-    return attn_any_fwd<T>(s, f, g, h, x, y, stats, B, N, Ds, Cs, extent, W);
+    if (route == ROUTE_ANY) return attn_any_fwd<T>(s, f, g, h, x, y, stats, B, N, Ds, Cs, extent, W);
+#define ATTN_FWD_CASE(DS, CS) if (Ds == DS && Cs == CS) return attn_fwd_t<T, DS, CS>(s, f, g, h, x, y, stats, B, N, extent, W);
+    ATTN_INSTANCES(ATTN_FWD_CASE)
+#undef ATTN_FWD_CASE
+    return msau_set_error(MSAU_ERR_ARG, "selfattn_fwd: no instance for (Ds,Cs)=(%d,%d)", Ds, Cs);
 }
 template <typename T>
-int attn_bwd_d(hipStream_t s, const void* f, const void* g, const void* h, const void* dy, const float* stats,
+int attn_bwd_d(int route, hipStream_t s, const void* f, const void* g, const void* h, const void* dy, const float* stats,
                void* df, void* dg, void* dh, float* ws, int B, int N, int Ds, int Cs, const int32_t* extent, int W) {
-    ATTN_DISPATCH(attn_bwd_t, s, f, g, h, dy, stats, df, dg, dh, ws, B, N, extent, W);
-    return attn_any_bwd<T>(s, f, g, h, dy, stats, df, dg, dh, ws, B, N, Ds, Cs, extent, W);
+    if (route == ROUTE_ANY) return attn_any_bwd<T>(s, f, g, h, dy, stats, df, dg, dh, ws, B, N, Ds, Cs, extent, W);
+#define ATTN_BWD_CASE(DS, CS) if (Ds == DS && Cs == CS) return attn_bwd_t<T, DS, CS>(s, f, g, h, dy, stats, df, dg, dh, ws, B, N, extent, W);
+    ATTN_INSTANCES(ATTN_BWD_CASE)
+#undef ATTN_BWD_CASE
+    return msau_set_error(MSAU_ERR_ARG, "selfattn_bwd: no instance for (Ds,Cs)=(%d,%d)", Ds, Cs);
 }
 
 }  // namespace
@@ -447,6 +450,18 @@ int msau_attn_mfma_fwd(hipStream_t s, const void* f, const void* g, const void* 
                        int B, int N, int Ds, int Cs, const int32_t* extent, int W);
 int msau_attn_mfma_bwd(hipStream_t s, const void* f, const void* g, const void* h, const void* dy, const float* stats,
                        void* df, void* dg, void* dh, float* ws, int B, int N, int Ds, int Cs, const int32_t* extent, int W);
+
+// The one place that picks the kernel family of a call (the dispatchers below ask it): bf16 with an MFMA instance whose statistics
+// kernel fits one sample's f in LDS -> the matrix cores; a (Ds, Cs) pair with a compile-time instance -> the VALU instances; else
+// the run-time "any width" kernels.
+extern "C" int msau_selfattn_route(int dtype, int N, int Ds, int Cs) {
+    if (dtype != MSAU_F32 && dtype != MSAU_BF16) return -1;
+    if (dtype == MSAU_BF16 && msau_attn_mfma_supported(Ds, Cs, N)) return ROUTE_MFMA;
+#define ATTN_ROUTE_CASE(DS, CS) if (Ds == DS && Cs == CS) return ROUTE_VALU;
+    ATTN_INSTANCES(ATTN_ROUTE_CASE)
+#undef ATTN_ROUTE_CASE
+    return ROUTE_ANY;
+}
 
 extern "C" int msau_selfattn_fwd(void* stream, int dtype, const void* f, const void* g, const void* h, const void* x, void* y,
                                  float* stats, int B, int N, int Ds, int Cs) {
@@ -463,10 +478,11 @@ extern "C" int msau_selfattn_fwd_ext(void* stream, int dtype, const void* f, con
     MSAU_CHECK_ARG(f && g && h && x && y && stats && B > 0 && N > 0, "selfattn_fwd: bad args");
     MSAU_CHECK_ARG(!extent || (W > 0 && N % W == 0), "selfattn_fwd: extent needs the grid width W (N = %d, W = %d)", N, W);
     hipStream_t s = static_cast<hipStream_t>(stream);
-    if (dtype == MSAU_F32) return attn_fwd_d<float>(s, f, g, h, x, y, stats, B, N, Ds, Cs, extent, W);
-    if (dtype == MSAU_BF16 && msau_attn_mfma_supported(Ds, Cs, N)) return msau_attn_mfma_fwd(s, f, g, h, x, y, stats, B, N, Ds, Cs, extent, W);
-    if (dtype == MSAU_BF16) return attn_fwd_d<bf16_t>(s, f, g, h, x, y, stats, B, N, Ds, Cs, extent, W);
-    return msau_set_error(MSAU_ERR_ARG, "selfattn_fwd: bad dtype");
+    const int route = msau_selfattn_route(dtype, N, Ds, Cs);
+    if (route < 0) return msau_set_error(MSAU_ERR_ARG, "selfattn_fwd: bad dtype");
+    if (route == ROUTE_MFMA) return msau_attn_mfma_fwd(s, f, g, h, x, y, stats, B, N, Ds, Cs, extent, W);
+    if (dtype == MSAU_F32) return attn_fwd_d<float>(route, s, f, g, h, x, y, stats, B, N, Ds, Cs, extent, W);
+    return attn_fwd_d<bf16_t>(route, s, f, g, h, x, y, stats, B, N, Ds, Cs, extent, W);
 }
 
 extern "C" int msau_selfattn_bwd_ext(void* stream, int dtype, const void* f, const void* g, const void* h, const void* dy,
@@ -475,9 +491,9 @@ extern "C" int msau_selfattn_bwd_ext(void* stream, int dtype, const void* f, con
     MSAU_CHECK_ARG(f && g && h && dy && stats && df && dg && dh && ws && B > 0 && N > 0, "selfattn_bwd: bad args");
     MSAU_CHECK_ARG(!extent || (W > 0 && N % W == 0), "selfattn_bwd: extent needs the grid width W (N = %d, W = %d)", N, W);
     hipStream_t s = static_cast<hipStream_t>(stream);
-    if (dtype == MSAU_F32) return attn_bwd_d<float>(s, f, g, h, dy, stats, df, dg, dh, ws, B, N, Ds, Cs, extent, W);
-    if (dtype == MSAU_BF16 && msau_attn_mfma_supported(Ds, Cs, N))
-        return msau_attn_mfma_bwd(s, f, g, h, dy, stats, df, dg, dh, ws, B, N, Ds, Cs, extent, W);
-    if (dtype == MSAU_BF16) return attn_bwd_d<bf16_t>(s, f, g, h, dy, stats, df, dg, dh, ws, B, N, Ds, Cs, extent, W);
-    return msau_set_error(MSAU_ERR_ARG, "selfattn_bwd: bad dtype");
+    const int route = msau_selfattn_route(dtype, N, Ds, Cs);
+    if (route < 0) return msau_set_error(MSAU_ERR_ARG, "selfattn_bwd: bad dtype");
+    if (route == ROUTE_MFMA) return msau_attn_mfma_bwd(s, f, g, h, dy, stats, df, dg, dh, ws, B, N, Ds, Cs, extent, W);
+    if (dtype == MSAU_F32) return attn_bwd_d<float>(route, s, f, g, h, dy, stats, df, dg, dh, ws, B, N, Ds, Cs, extent, W);
+    return attn_bwd_d<bf16_t>(route, s, f, g, h, dy, stats, df, dg, dh, ws, B, N, Ds, Cs, extent, W);
 }

@@ -296,8 +296,12 @@ __device__ __forceinline__ void attn_sweep_body(const bf16_t* __restrict__ f, co
     issue(0);
 
     // one 32-row step, phase by phase (K steps side by side): row offset of step k = k * SW * 32 (+ `extra` rows, run time)
-    auto run_steps = [&](auto KC, int extra) {
+    // TAIL (own-i sweeps without extents, the sweep's last step): only `left` < 32 rows of the step exist.  A compile-time flag, not
+    // a test of `left` inside the step: with a branch between a score MFMA and the arithmetic on its result the compiler padded
+    // the read hazard on the fall-through path only, and the taken path read the registers before the MFMA had written them.
+    auto run_steps = [&](auto KC, auto TAILC, int extra, int left) {
         constexpr int K = decltype(KC)::value;
+        constexpr bool TAIL = decltype(TAILC)::value;
         const unsigned char* pvs = a_vs + extra * RB;
         const unsigned char* pts = a_ts + extra * TS;
         const unsigned char* ptt = a_trt + extra * TS;
@@ -342,6 +346,13 @@ __device__ __forceinline__ void attn_sweep_body(const bf16_t* __restrict__ f, co
                 }
 #pragma unroll
                 for (int r = 0; r < 4; ++r) S[k][t][r] = __builtin_amdgcn_exp2f(__builtin_fmaf(S[k][t][r], LOG2E, -ll[r]));
+                if constexpr (TAIL) {
+                    // a swept row j >= N is staged as zeros: its score is 0 and exp2(0 - lse2) overflows for a row i whose scores
+                    // are all below -89 -- inf * 0 in the second product.  P = 0 there, as the own-j modes and the EXT instances
+                    // have it through lse2 = 3e38.
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) S[k][t][r] = (t * 16 + lg * 4 + r < left) ? S[k][t][r] : 0.f;
+                }
                 if constexpr (!ACC_C) {
                     f32x4 dl;
                     if constexpr (OWN_I) dl = f32x4{odl, odl, odl, odl};
@@ -387,11 +398,19 @@ __device__ __forceinline__ void attn_sweep_body(const bf16_t* __restrict__ f, co
         if (r0 + CHUNK < N) issue(r0 + CHUNK);
 
         const int nstep = min(CHUNK, ((N - r0 + 31) / 32) * 32) / 32;
-        if (nstep == NSTEP) {
+        // (own-i sweeps without extents: the step that holds rows beyond N runs last and masked -- a chunk that has one takes the
+        // step loop even when it has all its steps)
+        constexpr bool MASK_TAIL = OWN_I && !EXT;
+        const int nfull = MASK_TAIL ? min(nstep, (N - r0) / 32) : nstep;             // steps whose 32 rows all exist
+        if (nfull == NSTEP) {
 #pragma unroll
-            for (int u = 0; u < KW / KU; ++u) run_steps(std::integral_constant<int, KU>{}, u * KU * SW * 32);
+            for (int u = 0; u < KW / KU; ++u) run_steps(std::integral_constant<int, KU>{}, std::false_type{}, u * KU * SW * 32, 32);
         } else {
-            for (int st = part_id; st < nstep; st += SW) run_steps(std::integral_constant<int, 1>{}, (st - part_id) * 32);
+            for (int st = part_id; st < nfull; st += SW) run_steps(std::integral_constant<int, 1>{}, std::false_type{}, (st - part_id) * 32, 32);
+            if constexpr (MASK_TAIL) {
+                if (nfull < nstep && nfull % SW == part_id)
+                    run_steps(std::integral_constant<int, 1>{}, std::true_type{}, (nfull - part_id) * 32, N - r0 - nfull * 32);
+            }
         }
         if (r0 < 6 * CHUNK) { asm volatile("" :: "v"(acc[0][0])); ASTAMP(2 + 2 * (r0 / CHUNK)); }
     }

@@ -465,3 +465,30 @@ def test_lrn_and_attention_at_256_channels(dtype):
     y, _, dx, _ = run_graph(build, {}, x, gy, dtype)
     bf = dtype == L.BF16
     assert err(y, yr.detach(), bf) < TOL[dtype] and err(dx, xr.grad, bf) < TOL[dtype]
+
+    # the attention half: the (32, 256) core through AttnCoreOp -- the run-time "any width" kernels -- every stored element
+    # against the float64 reference on the operands the op read
+    from tests import attention_util as AU
+    p = {f"{m}.{n}": v for m, co in (("f", 32), ("g", 32), ("h", 256))
+         for n, v in (("weight", 0.02 * torch.randn(co, 256, 1, 1)), ("bias", 0.1 * torch.randn(co)))}
+    held = {}
+
+    def build_attn(plan):
+        xi = plan.x_in
+        f = Act(plan, "f", xi.H, xi.W, 32); g = Act(plan, "g", xi.H, xi.W, 32); h = Act(plan, "h", xi.H, xi.W, 256)
+        ConvOp(plan, "f", xi, None, "f.weight", "f.bias", f, 1)
+        ConvOp(plan, "g", xi, None, "g.weight", "g.bias", g, 1)
+        hop = ConvOp(plan, "h", xi, None, "h.weight", "h.bias", h, 1)
+        ya = Act(plan, "y", xi.H, xi.W, 256)
+        held["op"] = AttnCoreOp(plan, "a", f, g, h, xi, ya)
+        hop.bwd_add = ya
+        plan.logits = ya
+    run_graph(build_attn, p, x, gy, dtype)
+    op = held["op"]
+    B, N = 2, op.N
+    assert L.load().msau_selfattn_route(dtype, N, 32, 256) == 1
+    flat = lambda t, C: t[..., :C].reshape(B, N, C).float()
+    ins = [flat(op.f.data, 32), flat(op.g.data, 32), flat(op.h.data, 256), flat(op.x.data, 256), flat(op.y.grad, 256)]
+    got = {"m": op.stats[..., 0], "Z": op.stats[..., 1], "y": flat(op.y.data, 256), "dh": flat(op.h.grad, 256),
+           "delta": op.ws.view(B, N), "dg": flat(op.g.grad, 32), "df": flat(op.f.grad, 32)}
+    AU.check(got, AU.attn_ref(*ins), "bf16_valu" if bf else "f32", "AttnCoreOp (32,256)")
