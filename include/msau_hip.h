@@ -304,8 +304,11 @@ void msau_reload_env(void);
  * Weight / bias gradient of the same convolution (autograd of torch.nn.Conv2d reached from
  * train_chargrid_funsd_msau.py:57 `loss.backward()`), and with stride=2 of the transposed conv
  * (roles of input and output-gradient swapped, see msau_amd/plan.py).
- *   slab[s][co][k]  partial sums over the pixel tiles workgroup s visited (deterministic, no atomics)
- *   k = [chunk][tap][channel] as in the forward pack, plus one extra column holding sum(g) = dbias.
+ *   slab[s][chunk][co][k]  partial sums over the pixel tiles workgroup s visited (deterministic, no atomics)
+ *   The input channels are cut into nchunks chunks of cch (msau_wgrad_geometry; a chunk never straddles x1 | x2), and every
+ *   chunk has its own [Cout][kext] block: k = tap * cch + channel-in-chunk for k < taps * cch, column taps * cch holds
+ *   sum(g) = dbias (the "ones" column, the same value in every chunk), the columns up to kext = taps * cch + 8 rounded up to
+ *   16 are padding (zero, or never written).  One slab is nchunks * Cout * kext floats.
  * msau_wgrad_reduce() sums the slabs and scatters into the flat fp32 gradient buffer.
  * ------------------------------------------------------------------------------------------ */
 typedef struct {
@@ -319,13 +322,13 @@ typedef struct {
     const void* x1;
     const void* x2;
     const void* g;              /* [B][Hout][Wout][Cout] gradient w.r.t. the conv's pre-activation  */
-    float* slabs;               /* [nslabs][Cout][kext] fp32                                        */
+    float* slabs;               /* [nslabs][nchunks][Cout][kext] fp32                               */
     int32_t nslabs;             /* number of workgroups per chunk to launch (<= tiles)              */
 } msau_wgrad_desc;
 
 typedef struct {
     int32_t cch, nchunks;
-    int32_t kext;               /* columns per row of a slab: nchunks*taps*cch + 8, rounded to 16   */
+    int32_t kext;               /* columns per row of ONE chunk: taps*cch + 8, rounded to 16        */
     int32_t max_slabs;          /* number of pixel tiles (upper bound for nslabs)                   */
     int64_t slab_bytes;         /* bytes of ONE slab                                                */
     int32_t lean;               /* 1: a compile-time-specialised instance (wgrad_lean.hip) takes it; 2: the row-streaming
@@ -335,6 +338,18 @@ typedef struct {
 
 int msau_wgrad_geometry(int dtype, const msau_wgrad_desc* d, msau_wgrad_geom* out);
 int msau_conv2d_wgrad(void* stream, int dtype, const msau_wgrad_desc* d);
+/* Which kernel msau_conv2d_wgrad launches for the descriptor (host only: no launch, no device, the pointers are not read;
+ * d->nslabs >= 1 as for the launch).  msau_conv2d_wgrad, msau_wgrad_geometry (its `lean`) and msau_conv2d_wgrad_groupable
+ * take their decision from it.  Returns 0, or the error the launch would return (info[0] = 0).
+ *   info[0] family: 0 refused, 1 the generic tile kernel, 2 a lean instance, 3 a dilated / stride-2 lean instance, 4 the
+ *           64 -> 8 role-swapped instance, 5 the same fed with ids (MSAU_CONV_IDS), 6 the row-streaming instance, 7 the
+ *           box-list weight gradient (MSAU_CONV_OWNER)
+ *   info[1], info[2]  generic kernel: CTN (16-channel row tiles per slice as instantiated: 3 -> 4, 5..8 -> 8) and NKW (rounds of
+ *           4 k-tiles per wave: 1, 2, 3, 5, 10); else 0
+ *   info[3] 1: the generic kernel's compact form (dil >= 16: one 16 x 16 input block per tap)
+ *   info[4] launches = output-channel slices (generic kernel: 128 channels each in bf16, 64 in fp32, 32 in fp32 compact; else 1)
+ *   info[5], info[6], info[7]  cch, nchunks, kext of the msau_wgrad_geom struct; set whenever the geometry exists */
+int msau_wgrad_route(int dtype, const msau_wgrad_desc* d, int32_t info[8]);
 /* Up to 4 weight gradients of one shape (everything but the tensors equal: msau_conv2d_wgrad_groupable(a, b) != 0) in ONE
  * grid -- the level-2/3 launches have 64-107 workgroups each and otherwise queue behind each other.  Same slabs, same bits
  * as n separate launches. */

@@ -164,6 +164,7 @@ _SIGNATURES = {
     "msau_reload_env": (None, []),
     "msau_wgrad_geometry": (C.c_int, [C.c_int, C.POINTER(WgradDesc), C.POINTER(WgradGeom)]),
     "msau_conv2d_wgrad": (C.c_int, [vp, C.c_int, C.POINTER(WgradDesc)]),
+    "msau_wgrad_route": (C.c_int, [C.c_int, C.POINTER(WgradDesc), C.POINTER(i32)]),
     "msau_conv2d_wgrad_groupable": (C.c_int, [C.c_int, C.POINTER(WgradDesc), C.POINTER(WgradDesc)]),
     "msau_conv2d_wgrad_group": (C.c_int, [vp, C.c_int, C.POINTER(C.POINTER(WgradDesc)), C.c_int]),
     "msau_pack_params": (C.c_int, [vp, vp, vp, vp, C.c_int, C.c_int]),

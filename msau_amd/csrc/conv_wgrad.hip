@@ -287,20 +287,63 @@ int launch_wgrad_ct(hipStream_t s, const WArgs& a, int CTN, int NKW, dim3 grid, 
 }  // namespace
 
 // wgrad_lean.hip: compile-time-specialised instances
-int msau_wgrad_lean_applicable(int dtype, const msau_wgrad_desc* d, int cch);
+int msau_wgrad_lean_instance(int dtype, const msau_wgrad_desc* d, int cch);
 int msau_wgrad_lean_try(hipStream_t s, int dtype, const msau_wgrad_desc* d, int cch, int nchunks, int kextc);
 int msau_wgrad_lean_group(hipStream_t s, int dtype, const msau_wgrad_desc* const* ds, int n, int cch, int nchunks, int kextc);
-int msau_wgrad_lean_groupable(int dtype, const msau_wgrad_desc* d, int cch);
+
+namespace {
+
+// the one routing decision (include/msau_hip.h, msau_wgrad_route): family, and for the generic kernel its instance and slices
+enum { WF_NONE = 0, WF_TILE = 1, WF_LEAN = 2, WF_SPECIAL = 3, WF_IN64 = 4, WF_IN64_IDS = 5, WF_ROWS = 6, WF_OWNER = 7 };
+struct WRoute { int family, CTN, NKW, slices; };
+
+int wgrad_route(int dtype, const msau_wgrad_desc* d, WGeom* g, WRoute* r) {
+    *r = WRoute{WF_NONE, 0, 0, 0};
+    int rc = wgrad_geom(dtype, d, g);
+    if (rc) return rc;
+    r->slices = 1;
+    if (d->flags & MSAU_CONV_OWNER) { r->family = WF_OWNER; return 0; }       // ownerconv.hip: per-box sums of g instead of a painted input tensor
+    if (msau_rowwgrad_takes(dtype, d, g->cch, g->nchunks, g->kextc)) { r->family = WF_ROWS; return 0; }      // conv_rows.hip: every row of x and g read once
+    const int inst = d->Cout <= g->slice ? msau_wgrad_lean_instance(dtype, d, g->cch) : 0;
+    if (d->flags & MSAU_CONV_IDS) {
+        r->slices = 0;
+        MSAU_CHECK_ARG(inst == WF_IN64, "wgrad: MSAU_CONV_IDS is implemented by the bf16 64 -> 8 3x3 instance only");
+        MSAU_CHECK_ARG(g->nchunks == 1 && !d->C2, "wgrad: MSAU_CONV_IDS needs one 64-channel one-hot source");
+        r->family = WF_IN64_IDS; r->slices = 1;
+        return 0;
+    }
+    if (inst) { r->family = inst; return 0; }
+    r->slices = 0;
+    const int CTN = g->CTN == 3 ? 4 : (g->CTN > 4 ? 8 : g->CTN);              // CTN as instantiated (3 -> 4)
+    MSAU_CHECK_ARG(!(CTN == 8 && g->NKW > 5), "wgrad: Cout %d with K %d unsupported", d->Cout, g->kextc);
+    r->family = WF_TILE; r->CTN = CTN; r->NKW = g->NKW; r->slices = cdiv(d->Cout, g->slice);
+    return 0;
+}
+
+}  // namespace
+
+extern "C" int msau_wgrad_route(int dtype, const msau_wgrad_desc* d, int32_t info[8]) {
+    MSAU_CHECK_ARG(d && info, "wgrad_route: null pointer");
+    for (int i = 0; i < 8; ++i) info[i] = 0;
+    WGeom g = {};                                                              // (filled whenever the geometry exists, refused or not)
+    WRoute r;
+    const int rc = wgrad_route(dtype, d, &g, &r);
+    info[5] = g.cch; info[6] = g.nchunks; info[7] = g.kextc;
+    if (rc) return rc;
+    info[0] = r.family; info[1] = r.CTN; info[2] = r.NKW; info[3] = r.family == WF_TILE && g.compact; info[4] = r.slices;
+    return 0;
+}
 
 extern "C" int msau_wgrad_geometry(int dtype, const msau_wgrad_desc* d, msau_wgrad_geom* out) {
     WGeom g;
+    WRoute r;
     int rc = wgrad_geom(dtype, d, &g);
     if (rc) return rc;
     out->cch = g.cch; out->nchunks = g.nchunks; out->kext = g.kextc;
     out->max_slabs = d->B * cdiv(d->Hout, 16) * cdiv(d->Wout, 16);
     out->slab_bytes = (int64_t)g.nchunks * d->Cout * g.kextc * 4;
-    out->lean = msau_wgrad_lean_applicable(dtype, d, g.cch);
-    if (d->nslabs >= 1 && msau_rowwgrad_takes(dtype, d, g.cch, g.nchunks, g.kextc)) out->lean = 2;     // row-streaming instance
+    wgrad_route(dtype, d, &g, &r);                                             // (a descriptor no kernel takes: lean 0)
+    out->lean = r.family == WF_ROWS ? 2 : r.family >= WF_LEAN && r.family <= WF_IN64_IDS;
     out->reserved = 0;
     return 0;
 }
@@ -309,24 +352,20 @@ extern "C" int msau_conv2d_wgrad(void* stream, int dtype, const msau_wgrad_desc*
     MSAU_CHECK_ARG(d && d->x1 && d->g && d->slabs, "wgrad: null pointer");
     MSAU_CHECK_ARG(d->C2 == 0 || d->x2, "wgrad: x2 missing");
     WGeom g;
-    int rc = wgrad_geom(dtype, d, &g);
+    WRoute r;
+    int rc = wgrad_route(dtype, d, &g, &r);
     if (rc) return rc;
-    if (d->flags & MSAU_CONV_OWNER)                                            // ownerconv.hip: per-box sums of g instead of a painted input tensor
-        return msau_ownerconv_wgrad(static_cast<hipStream_t>(stream), dtype, d, g.cch, g.nchunks, g.kextc);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (r.family == WF_OWNER) return msau_ownerconv_wgrad(s, dtype, d, g.cch, g.nchunks, g.kextc);
     const int tiles_x = cdiv(d->Wout, 16), tiles_y = cdiv(d->Hout, 16), ntiles = d->B * tiles_x * tiles_y;
     MSAU_CHECK_ARG(d->nslabs >= 1 && d->nslabs <= ntiles, "wgrad: nslabs %d not in [1,%d]", d->nslabs, ntiles);
-    if (msau_rowwgrad_takes(dtype, d, g.cch, g.nchunks, g.kextc))              // conv_rows.hip: every row of x and g read once
-        return msau_rowwgrad_launch(static_cast<hipStream_t>(stream), d);
-    if (d->Cout <= g.slice) {
-        rc = msau_wgrad_lean_try(static_cast<hipStream_t>(stream), dtype, d, g.cch, g.nchunks, g.kextc);
-        if (rc != 0) return rc < 0 ? rc : 0;
+    if (r.family == WF_ROWS) return msau_rowwgrad_launch(s, d);
+    if (r.family != WF_TILE) {
+        rc = msau_wgrad_lean_try(s, dtype, d, g.cch, g.nchunks, g.kextc);
+        if (rc == 0) return msau_set_error(MSAU_ERR_ARG, "wgrad: the route names family %d, wgrad_lean.hip has no instance", r.family);
+        return rc < 0 ? rc : 0;
     }
-    MSAU_CHECK_ARG(!(d->flags & MSAU_CONV_IDS), "wgrad: MSAU_CONV_IDS is implemented by the bf16 64 -> 8 3x3 instance only");
-    // CTN as instantiated (3 -> 4)
-    int CTN = g.CTN == 3 ? 4 : (g.CTN > 4 ? 8 : g.CTN);
-    MSAU_CHECK_ARG(!(CTN == 8 && g.NKW > 5), "wgrad: Cout %d with K %d unsupported", d->Cout, g.kextc);
     dim3 grid(d->nslabs, g.nchunks);
-    hipStream_t s = static_cast<hipStream_t>(stream);
     // wide outputs: one launch per slice; every slice writes its rows of the same slabs
     for (int co0 = 0; co0 < d->Cout; co0 += g.slice) {
         WArgs a;
@@ -337,7 +376,7 @@ extern "C" int msau_conv2d_wgrad(void* stream, int dtype, const msau_wgrad_desc*
         a.TIH = g.TIH; a.TIW = g.TIW; a.PSx = g.PSx; a.PSg = g.PSg;
         a.x_bytes = g.x_bytes; a.g_bytes = g.g_bytes; a.tab_bytes = g.tab_bytes;
         a.tiles_x = tiles_x; a.tiles_y = tiles_y; a.ntiles = ntiles;
-        rc = dtype == MSAU_F32 ? launch_wgrad_ct<float>(s, a, CTN, g.NKW, grid, g.total) : launch_wgrad_ct<bf16_t>(s, a, CTN, g.NKW, grid, g.total);
+        rc = dtype == MSAU_F32 ? launch_wgrad_ct<float>(s, a, r.CTN, r.NKW, grid, g.total) : launch_wgrad_ct<bf16_t>(s, a, r.CTN, r.NKW, grid, g.total);
         if (rc) return rc;
     }
     return 0;
@@ -349,9 +388,9 @@ extern "C" int msau_owner_slabs(const msau_wgrad_desc* d) { return d ? msau_owne
 extern "C" int msau_conv2d_wgrad_groupable(int dtype, const msau_wgrad_desc* a, const msau_wgrad_desc* b) {
     if (!a || !b) return 0;
     WGeom g;
-    if (wgrad_geom(dtype, a, &g)) return 0;
-    if (msau_rowwgrad_takes(dtype, a, g.cch, g.nchunks, g.kextc)) return 0;        // the row kernel runs one layer per launch
-    if (a->Cout > g.slice || !msau_wgrad_lean_groupable(dtype, a, g.cch)) return 0;
+    WRoute r;
+    if (wgrad_route(dtype, a, &g, &r)) return 0;
+    if (r.family != WF_LEAN && r.family != WF_SPECIAL) return 0;      // (the row kernel and the 64 -> 8 one run one layer per launch)
     return a->B == b->B && a->Hin == b->Hin && a->Win == b->Win && a->Hout == b->Hout && a->Wout == b->Wout && a->C1 == b->C1 &&
            a->C2 == b->C2 && a->Cout == b->Cout && a->KH == b->KH && a->KW == b->KW && a->dil == b->dil && a->pad_t == b->pad_t &&
            a->pad_l == b->pad_l && a->stride == b->stride && a->nslabs == b->nslabs;

@@ -480,7 +480,7 @@ __global__ __launch_bounds__(256) void wgrad_in64_kernel(const WLeanArgs a) {
                 *reinterpret_cast<V8*>(lds_g + m * PSG) = gr[it];
                 // bias: every output pixel belongs to exactly one tile's rows / columns [2 - pad, 17 - pad]
                 const int i = m / TG, j = m - i * TG;
-                if (chunk == 0 && i >= 2 - d.pad_t && i <= 17 - d.pad_t && j >= 2 - d.pad_l && j <= 17 - d.pad_l) {
+                if (i >= 2 - d.pad_t && i <= 17 - d.pad_t && j >= 2 - d.pad_l && j <= 17 - d.pad_l) {
 #pragma unroll
                     for (int e = 0; e < 8; ++e) bsum[it][e] += (float)gr[it][e];
                 }
@@ -556,7 +556,7 @@ __global__ __launch_bounds__(256) void wgrad_in64_kernel(const WLeanArgs a) {
     if (tid < 8 && tid < d.Cout) {
         float s = 0.f;
         for (int t = 0; t < 512; ++t) s += bred[t * 8 + tid];        // fixed order
-        for (int k = 576; k < a.kextc; ++k) slab[(size_t)tid * a.kextc + k] = k == 576 && chunk == 0 ? s : 0.f;
+        for (int k = 576; k < a.kextc; ++k) slab[(size_t)tid * a.kextc + k] = k == 576 ? s : 0.f;      // (every chunk carries it, as in wgrad_kernel)
     }
 }
 
@@ -684,7 +684,10 @@ int msau_wgrad_lean_try(hipStream_t s, int dtype, const msau_wgrad_desc* d, int 
     return msau_wgrad_lean_group(s, dtype, &d, 1, cch, nchunks, kextc);
 }
 
-// launches that may share a grid: the same lean instance (not the 64 -> 8 one)
-int msau_wgrad_lean_groupable(int dtype, const msau_wgrad_desc* d, int cch) {
-    return msau_wgrad_lean_applicable(dtype, d, cch) && !wlean_in64(dtype, d, cch);
+// the instance msau_wgrad_lean_group launches for one descriptor (host only; msau_wgrad_route in conv_wgrad.hip): 0 none,
+// 2 a lean shape, 3 a dilated / stride-2 one, 4 the 64 -> 8 kernel
+int msau_wgrad_lean_instance(int dtype, const msau_wgrad_desc* d, int cch) {
+    if (!msau_wgrad_lean_applicable(dtype, d, cch)) return 0;
+    if (d->stride != 1 || d->dil != 1) return 3;
+    return wlean_in64(dtype, d, cch) ? 4 : 2;
 }
