@@ -844,7 +844,8 @@ int msau_kv_paint(void* stream, const int32_t* lines, const void* glyphs, const 
                   const int32_t* sizes, int B, int H, int W, int32_t* ids, uint16_t* line_ids, uint16_t* char_pos);
 
 /* ------------------------------------------------------------------------------------------
- * Key-value training (data_generator/data_generator_text.py:160-250 without its warps, model/training/cost.py:35-65 `UNetLoss`).
+ * Key-value training (data_generator/data_generator_text.py:160-250, its affine and rotation warps (:303-344) as
+ * msau_kv_warp_train below, model/training/cost.py:35-65 `UNetLoss`).
  *   msau_kv_paint_train : the painter of a training batch from the documents' training tables (msau_amd/training/kv_data.py): lines,
  *                   glyphs, offsets and sizes as msau_kv_paint takes them, line_labels int32 [n][2] = (label, aux label) per line, sharing
  *                   the lines' offsets.  ids int32 as msau_kv_paint writes them; labels / aux_labels int64 [B][H][W]: the record of
@@ -895,6 +896,35 @@ int64_t msau_unet_eval_ws_bytes(int B, int K);
 int msau_unet_eval(void* stream, int dtype, const void* logits, const void* aux, const int64_t* labels, const int64_t* aux_labels,
                    const int32_t* extent, const float* class_w, int K, float* doc_loss, int32_t* doc_counts, void* ws, int B, int H,
                    int W, int C, int Cs);
+
+/* ------------------------------------------------------------------------------------------
+ * Key-value training, the generator's affine / rotation augmentation (data_generator/data_generator_text.py:303-344,
+ * utils/image_util.py:38-55; msau_amd/training/kv_warp.py states what is computed, csrc/warp.hip how).
+ *   msau_kv_warp_train : the canvases msau_kv_paint_train leaves (ids int32, labels / aux_labels int64 [B][H][W], src_sizes int32
+ *                   [B][2] = (h, w) <= (H, W)) resampled as scipy's cubic spline resamples the generator's one-hot planes x 255
+ *                   (order 3, mode "constant", cval 0), thresholded at > 64.  warps double [B][6] = m00, m01, m10, m11, off0, off1:
+ *                   output pixel (oy, ox) of document b reads the source at off + M (oy, ox), (row, col) order, float64;
+ *                   dst_sizes int32 [B][2] = (ho, wo) <= (Ho, Wo).  All device memory.
+ *                     grid [B][Ho][Wo][Cs] in `dtype` (the plan's input): channel c < n_token is 1 iff the warped plane
+ *                       [ids == c] exceeds the threshold -- multi-hot or zero-hot -- every other element 0: the channels from
+ *                       n_token on, pixels whose source lies outside [0, h-1] x [0, w-1], outside (ho, wo) and in the padding
+ *                     labels_out / aux_out int64 [B][Ho][Wo]: 1 if the warped plane [labels == 1] is set, else the smallest set
+ *                       plane in [2, n_class), else 0; -1 outside (ho, wo)
+ *                     flags int32 [B]: 0, or why the document has to be warped on the host instead (bit 0: more than 4 planes of
+ *                       a pixel are set, or a pixel's 12 x 12 centre window holds more than 48 distinct values; bit 1: its matrix or
+ *                       offset is not finite, nothing of it was resampled)
+ *                   Every element of the four outputs is written exactly once, nothing is cleared first, no atomics: equal inputs
+ *                   give equal bits.  Coordinates in float64 (no fused multiply-add), weights and sums in fp32 over a window of
+ *                   32 x 32 source pixels: a plane's grey level is within 1e-4 + fp32 rounding of the float64 value, so the
+ *                   outputs equal the float64 statement except where a plane comes that close to 64.5.  ws: int32
+ *                   [msau_kv_warp_train_ws_ints(B, Ho, Wo)], one word per 16 x 16 tile.  Two launches (the tiles; the flags).
+ *                   B <= 65535, B*H*W < 2^31, B*Ho*Wo < 2^31, n_token <= Cs, Cs % 8 == 0, n_token and n_class <= 32767, grid 16-byte aligned.
+ * ------------------------------------------------------------------------------------------ */
+int64_t msau_kv_warp_train_ws_ints(int B, int Ho, int Wo);
+int msau_kv_warp_train(void* stream, int dtype, const int32_t* ids, const int64_t* labels, const int64_t* aux_labels,
+                       const int32_t* src_sizes, const double* warps, const int32_t* dst_sizes, int B, int H, int W, int Ho, int Wo,
+                       int n_token, int Cs, int n_class, void* grid, int64_t* labels_out, int64_t* aux_out, int32_t* flags,
+                       int32_t* ws);
 
 #ifdef __cplusplus
 }

@@ -1056,8 +1056,13 @@ class TrainEngine:
         ids = self.model._check_ids(ids)
         B, H, W = ids.shape
         sizes = self.model._check_sizes_for(sizes, B, H, W)
-        labels = labels.reshape(B, H, W).contiguous().long()
         plan = self.model._plan(B, H, W, ids.device, True, sizes)
+        return self._step_unet(plan, labels, aux_labels, cw, stats, ids=ids)
+
+    def _step_unet(self, plan: Plan, labels, aux_labels, cw, stats, **feed) -> torch.Tensor:
+        """the tail `step_unet` and `step_unet_nhwc` share: the label maps as the loss kernel takes them, UNetLoss, `_step`"""
+        B, H, W = plan.B, plan.H, plan.W
+        labels = labels.reshape(B, H, W).contiguous().long()
         aux_labels = aux_labels.reshape(B, H, W).contiguous().long() if plan.aux is not None else None
         if stats is None:
             loss_grads = lambda p: p.loss_grads_unet(labels, aux_labels, cw)
@@ -1065,18 +1070,61 @@ class TrainEngine:
             def loss_grads(p):
                 p.eval_unet(labels, aux_labels, cw, out=stats)
                 return p.loss_grads_unet(labels, aux_labels, cw)
-        return self._step(plan, None, ids=ids, loss_grads=loss_grads)
+        return self._step(plan, None, loss_grads=loss_grads, **feed)
+
+    def step_unet_nhwc(self, grid: torch.Tensor, labels: torch.Tensor, aux_labels: torch.Tensor, sizes=None, class_weights=None,
+                       stats=None) -> torch.Tensor:
+        """`step_unet` for an input that is ALREADY on the device in the kernels' layout ([B][H][W][Cs], storage dtype, as
+        `step_nhwc` takes it): a one-hot, multi-hot or zero-hot grid, e.g. what the warp kernel leaves (msau_kv_warp_train).  When
+        `grid` is the plan's own input buffer nothing is copied; otherwise one device copy.  `labels`,
+        `aux_labels`, `sizes`, `class_weights` and `stats` as in `step_unet`; with `sizes` the buffer is zeroed outside the documents
+        before the sweep.  On the one-hot grid of an id canvas the step is bit-identical to `step_unet` on the ids.  Eager only."""
+        self._eager("step_unet_nhwc")
+        cw = self._class_weights(class_weights, self.model.n_class)
+        B, H, W, _ = grid.shape
+        sizes = self.model._check_sizes_for(sizes, B, H, W)
+        plan = self.model._plan(B, H, W, grid.device, True, sizes)
+        buf = plan.input_nhwc
+        if tuple(grid.shape) != tuple(buf.shape) or grid.dtype != buf.dtype:
+            raise ValueError(f"step_unet_nhwc wants {tuple(buf.shape)} {buf.dtype} (channels padded to a multiple of 8), got "
+                             f"{tuple(grid.shape)} {grid.dtype}")
+        if grid.data_ptr() != buf.data_ptr():
+            buf.copy_(grid)
+        return self._step_unet(plan, labels, aux_labels, cw, stats, nhwc_ready=True)
 
     def step_kv(self, tables, class_weights=None, round_to: int = 16, stats=None) -> torch.Tensor:
         """One optimisation step on a group of key-value documents given as their training tables
         (msau_amd.training.kv_data.train_table / KVTrainBatches): one upload of the packed tables, one launch that paints the id
         canvas and both label canvases (msau_kv_paint_train), then `step_unet` on them with the documents' sizes.  No per-pixel
         array is built on the host and nothing waits for the device -- except for a document whose table is not `ok`, which is
-        painted on the host and uploaded (kv_data.STATS counts them).  `stats` as in `step_unet`."""
+        painted on the host and uploaded (kv_data.STATS counts them).  `stats` as in `step_unet`.
+        When a table carries a `warp` (the generator's affine or rotation augmentation: kv_warp.py, `KVTrainBatches(kwargs_dat=...)`)
+        the painted canvases are resampled on the device: paint -> msau_kv_warp_train, which writes the multi-hot input straight
+        into the plan's input buffer and the two warped label maps -> the tail of `step_unet_nhwc`, on the warped sizes and their
+        canvas (rounded up to `round_to`).  Tables without a warp in such a group take the identity.  The launch leaves one flag
+        per document, which the host reads before the sweep (the one wait of this path); a flagged document is warped by
+        `kv_warp.warp_host` and uploaded (kv_data.STATS["host_warped"]).  A group without warps takes the path above, launch for
+        launch."""
         self._eager("step_kv")
         from .training import kv_data
-        ids, labels, aux_labels, sizes = kv_data.paint_train_device(tables, round_to=round_to, device=self.model._flat.device)
-        return self.step_unet(ids, labels, aux_labels, sizes=sizes, class_weights=class_weights, stats=stats)
+        dev = self.model._flat.device
+        ids, labels, aux_labels, sizes = kv_data.paint_train_device(tables, round_to=round_to, device=dev)
+        if all(t.warp is None for t in tables):
+            return self.step_unet(ids, labels, aux_labels, sizes=sizes, class_weights=class_weights, stats=stats)
+        from .training import kv_warp
+        m = self.model
+        cw = self._class_weights(class_weights, m.n_class)
+        warps = [kv_warp.identity_warp(t.shape) if t.warp is None else t.warp for t in tables]
+        wsizes, (Ho, Wo) = kv_warp.warped_canvas(warps, round_to=round_to)
+        B = len(tables)
+        plan = m._plan(B, Ho, Wo, dev, True, m._check_sizes_for(torch.from_numpy(wsizes), B, Ho, Wo))
+        grid = plan.input_nhwc
+        wl, wa, flags = kv_warp.warp_train_device(ids, labels, aux_labels, sizes, warps, grid, m.channels, m.n_class, plan.dtype)
+        for b in torch.nonzero(flags.cpu()).reshape(-1).tolist():
+            kv_warp.upload_host_warp(b, tables[b], warps[b], grid, wl, wa, m.channels, m.n_class)
+            kv_data.STATS["host_warped"] += 1
+        # (the kernel and the host warp leave zeros outside the warped extents: nothing to clear)
+        return self._step_unet(plan, wl, wa, cw, stats, nhwc_ready=True, nhwc_clean=True)
 
     def input_nhwc(self, B: int, H: int, W: int) -> torch.Tensor:
         """The training plan's own input buffer for this shape, [B][H][W][Cs] in the storage dtype: the zero-copy target of

@@ -12,7 +12,9 @@ The random text scale, the aspect jitter, the random pad and the OCR errors are 
 generator's expressions in the generator's order, so a table under `random.Random(s)` is the generator's batch under
 `random.seed(s)`.  `paint_train_host` is the statement of what the kernel computes (a gather), `paint_train_painter` the plain
 loop of the generator: the fallback for a document whose table is not `ok` (STATS counts them) and what the gather is tested
-against.  The generator's affine, elastic and rotation warps are not here."""
+against.  The generator's affine and rotation warps are a table's optional `warp` (msau_amd/training/kv_warp.py): `KVTrainBatches`
+draws them when `kwargs_dat` asks for them and `TrainEngine.step_kv` resamples the painted canvases on the device
+(csrc/warp.hip, `msau_kv_warp_train`).  The elastic warp is not here."""
 from __future__ import annotations
 
 import json
@@ -23,11 +25,13 @@ from typing import List, Optional, Sequence, Tuple
 import numpy as np
 
 from ..inference import glyphs as G
+from .kv_warp import Warp, affine_warp, mod90_angle, rotate_warp
 
 LABEL_INTS = 2
 
 # what the device painter was given (tools/kv_train_loop.py reads and resets these)
-STATS = {"calls": 0, "documents": 0, "host_painted": 0, "h2d_bytes": 0}
+# "host_warped": documents of a warped group that the warp kernel flagged and `kv_warp.warp_host` warped instead
+STATS = {"calls": 0, "documents": 0, "host_painted": 0, "h2d_bytes": 0, "host_warped": 0}
 
 
 @dataclass
@@ -43,6 +47,7 @@ class TrainTable:
     line_rec: Optional[np.ndarray]      # int32 [n_lines, 8] as glyphs.GlyphTable; None when the table cannot represent the document
     glyph_rec: Optional[np.ndarray]     # int16 [n_glyphs, 4]
     reason: str = ""                    # why not, when it cannot
+    warp: Optional[Warp] = None         # the generator's affine or rotation augmentation of the painted document, if any
 
     @property
     def ok(self) -> bool:
@@ -233,13 +238,34 @@ def load_charset(charset_path: str):
 
 class KVTrainBatches:
     """Iterator of table groups (lists of `batch_size` TrainTables) over epochs, without end: the generator's `_fillQueue` without its
-    threads and warps.  ONE `random.Random(seed)` gives the order (a shuffle per epoch) and the jitter of every table.  The defaults
-    are the generator's `scale_min`, `scale_max` and `text_err_train`."""
+    threads.  ONE `random.Random(seed)` gives the order (a shuffle per epoch) and the jitter of every table.  The defaults are the
+    generator's `scale_min`, `scale_max` and `text_err_train`.
+
+    `kwargs_dat` takes the generator's augmentation keys: `affine_tr` with `affine_value` (default 0.025), `rotate_tr` and
+    `rotateMod90_tr`.  A table then carries a `warp` (kv_warp.py), drawn AFTER the table's own draws: for the affine map one
+    `getrandbits(32)` that seeds the `RandomState` of its six draws (the generator's own `RandomState(None)` cannot be seeded), for a
+    rotation the generator's `uniform(-20, 20)`.  `rotateMod90_tr` maps that angle as the generator does, which -- as written there
+    -- always yields -45 degrees (kv_warp.mod90_angle); the oddity is kept.  With every flag off not one extra draw is taken.
+    Refused with NotImplementedError: `affine_tr` together with a rotation (the generator re-interpolates the grey-level planes of the
+    first warp, which the id canvases cannot express), `elastic_tr` (the generator's version needs `scipy.misc.imresize`, which no
+    current scipy has) and the `*_val` flags (validation is not augmented here)."""
 
     def __init__(self, paths: Sequence[str], charset_path: str, n_class: int, batch_size: int, scale_min: float = 2.0,
-                 scale_max: float = 4.0, text_err: float = 0.1, shuffle: bool = True, seed: int = 0):
+                 scale_max: float = 4.0, text_err: float = 0.1, shuffle: bool = True, seed: int = 0, kwargs_dat: Optional[dict] = None):
         if len(paths) == 0 or batch_size < 1:
             raise ValueError("KVTrainBatches: needs at least one document and batch_size >= 1")
+        kw = dict(kwargs_dat or {})
+        self.affine, self.affine_value = bool(kw.get("affine_tr", False)), float(kw.get("affine_value", 0.025))
+        self.rotate, self.rotate_mod90 = bool(kw.get("rotate_tr", False)), bool(kw.get("rotateMod90_tr", False))
+        if self.affine and (self.rotate or self.rotate_mod90):
+            raise NotImplementedError("KVTrainBatches: affine_tr together with rotate_tr / rotateMod90_tr -- the generator rotates the "
+                                      "grey-level planes the affine warp interpolated, which cannot be computed from the id canvases")
+        if kw.get("elastic_tr", False):
+            raise NotImplementedError("KVTrainBatches: elastic_tr -- the generator's elastic_transform needs scipy.misc.imresize, which "
+                                      "no current scipy has")
+        on = [k for k in ("affine_val", "elastic_val", "rotate_val", "rotateMod90_val") if kw.get(k, False)]
+        if on:
+            raise NotImplementedError(f"KVTrainBatches: {', '.join(on)} -- validation tables are not augmented")
         self.paths, self.n_class, self.batch_size = list(paths), int(n_class), int(batch_size)
         self.scale_min, self.scale_max, self.text_err, self.shuffle = scale_min, scale_max, text_err, shuffle
         self.tok_to_id, self.blank_idx, self.n_token = load_charset(charset_path)
@@ -262,8 +288,17 @@ class KVTrainBatches:
                 if self.shuffle:
                     self.rng.shuffle(self._order)
                 self._order.reverse()                     # (popped from the end: the shuffled order, first to last)
-            group.append(self.table(self._order.pop()))
+            group.append(self._augment(self.table(self._order.pop())))
         return group
+
+    def _augment(self, t: TrainTable) -> TrainTable:
+        """the table with the warp `kwargs_dat` asks for, drawn from the iterator's generator; no flag on: the table, no draw"""
+        if self.affine:
+            t.warp = affine_warp(t.shape, self.affine_value, np.random.RandomState(self.rng.getrandbits(32)))
+        elif self.rotate or self.rotate_mod90:
+            angle = self.rng.uniform(-20, 20)
+            t.warp = rotate_warp(t.shape, mod90_angle(angle) if self.rotate_mod90 else angle)
+        return t
 
     def validation(self, scale: float = 3.0) -> List[List[TrainTable]]:
         """the deterministic tables of all documents in groups of `batch_size` (the last may be smaller): scale_min == scale_max ==

@@ -11,6 +11,9 @@
 Prints for each route the documents per second of the WHOLE step (host work included), the bytes uploaded per document and
 the loss trajectory, and one JSON line.  The two routes see the same jitter settings but not the same draws, and the optimisers
 differ (the engine clips the gradient norm), so the trajectories are to be read side by side, not compared digit for digit.
+--warp affine|rotate turns on the generator's augmentation (kwargs_dat affine_tr / rotate_tr): the tables route resamples the painted
+canvases on the device (msau_kv_warp_train), the trainer route warps the one-hot planes x 255 with scipy.ndimage on the host, plane
+by plane, as the generator does -- the comparison that `--warp` is about.
 Not the headline metric (bench.py is); numbers are quoted in DESIGN.md 5e and profiles/kv_train.md.
 
 --eval times VALIDATION instead (forward only, loss and accuracy per document), again two routes over the same deterministic tables
@@ -48,8 +51,23 @@ def model(n_token, n_class, dtype):
 
 
 def batches(args, batch_size):
+    kwargs_dat = {"affine": {"affine_tr": True}, "rotate": {"rotate_tr": True}}.get(args.warp, {})
     return KVTrainBatches(args.layouts, args.charset, args.n_class, batch_size, args.scale_min, args.scale_max, args.text_err,
-                          shuffle=True, seed=args.seed)
+                          shuffle=True, seed=args.seed, kwargs_dat=kwargs_dat)
+
+
+def scipy_warp(t, maps):
+    """the generator's host route for a table's warp: the one-hot maps [h, w, c] x 255 as uint8, every plane through scipy's cubic
+    spline, thresholded at > 64; the targets made one-hot again (1 first, then the smallest set class, else 0)"""
+    from scipy import ndimage
+    from msau_amd.training.kv_warp import _label_of
+    out = []
+    for k, m in enumerate(maps):
+        planes = m * np.uint8(255)
+        res = np.stack([ndimage.affine_transform(planes[:, :, d], t.warp.matrix, offset=t.warp.offset, output_shape=t.warp.out_shape)
+                        for d in range(planes.shape[2])], axis=2) > 64
+        out.append(res.astype("B") if k == 0 else np.eye(m.shape[2], dtype="B")[_label_of(res)])
+    return out
 
 
 def run_tables(args):
@@ -61,7 +79,7 @@ def run_tables(args):
     for _ in range(args.warmup):
         eng.step_kv(next(it), class_weights=cw, round_to=args.round_to)
     torch.cuda.synchronize()
-    kv_data.STATS.update(calls=0, documents=0, host_painted=0, h2d_bytes=0)
+    kv_data.STATS.update(calls=0, documents=0, host_painted=0, h2d_bytes=0, host_warped=0)
     losses = []
     t0 = time.perf_counter()
     for _ in range(args.steps):
@@ -72,7 +90,7 @@ def run_tables(args):
     return dict(route="tables", batch_size=args.batch_size, optimizer=args.optimizer, clip=not args.no_clip, weight_decay=args.weight_decay,
                 optim_launches=[key for key, _ in eng.optim_launches()], docs_per_s=docs / dt,
                 h2d_bytes_per_doc=kv_data.STATS["h2d_bytes"] / docs,
-                host_painted=kv_data.STATS["host_painted"], loss=[round(float(l[0]), 5) for l in torch.stack(losses).cpu()])
+                host_painted=kv_data.STATS["host_painted"], host_warped=kv_data.STATS["host_warped"], warp=args.warp, loss=[round(float(l[0]), 5) for l in torch.stack(losses).cpu()])
 
 
 def run_trainer(args):
@@ -87,7 +105,10 @@ def run_trainer(args):
     def step():
         (t,) = next(it)
         ids, lab, aux = kv_data.paint_train_host(t) if t.ok else kv_data.paint_train_painter(t)
-        maps = [np.ascontiguousarray(e[m].transpose(2, 0, 1))[None] for e, m in ((eye_in, ids), (eye_out, lab), (eye_out, aux))]
+        maps = [e[m] for e, m in ((eye_in, ids), (eye_out, lab), (eye_out, aux))]
+        if t.warp is not None:
+            maps = scipy_warp(t, maps)
+        maps = [np.ascontiguousarray(m.transpose(2, 0, 1))[None] for m in maps]
         bx, bt, ba = (torch.from_numpy(m) for m in maps)
         nbytes = bx.numel() * 4 + (bt.numel() + ba.numel()) * 8                 # as Trainer._batch uploads them: float, long, long
         bx, bt, ba = bx.float().cuda(), bt.long().cuda(), ba.long().cuda()
@@ -110,7 +131,7 @@ def run_trainer(args):
         nbytes += n
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
-    return dict(route="trainer", batch_size=1, docs_per_s=docs / dt, h2d_bytes_per_doc=nbytes / docs,
+    return dict(route="trainer", batch_size=1, warp=args.warp, docs_per_s=docs / dt, h2d_bytes_per_doc=nbytes / docs,
                 loss=[round(float(l), 5) for l in torch.stack(losses).cpu()][::max(1, args.batch_size)])
 
 
@@ -210,6 +231,8 @@ def main():
     ap.add_argument("--text-err", type=float, default=0.1)
     ap.add_argument("--class-weights", default="", help="comma-separated, n_class values (tables route)")
     ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--warp", default="", choices=["", "affine", "rotate"], help="the generator's augmentation: on the device in the tables "
+                    "route, scipy.ndimage on the host in the trainer route")
     ap.add_argument("--round-to", type=int, default=32, help="canvas sizes are rounded up to a multiple (fewer distinct plans)")
     ap.add_argument("--routes", default="tables,trainer")
     ap.add_argument("--eval", action="store_true", help="time validation (eval_kv against the Trainer's route) instead of training")
