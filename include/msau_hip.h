@@ -770,6 +770,20 @@ int msau_softmax_channels_nchw(void* stream, const float* logits, float* pred, i
  *                              values (as float: torch's argmax of the fp32 export, ties included), a 0 becomes zero_as
  *                              when zero_as >= 0; then counts[label * C + pred] += 1.  counts int64 [C][C] accumulates
  *                              across calls (zero it first); integer sums, independent of arrival order
+ *   msau_box_vote            : entity-level predictions: every box of a list gets the class most of its pixels vote for.
+ *                              logits as for msau_eval_confusion (1 <= C <= 64, C <= Cs, Cs % 8 == 0); boxes int32 [n][6] =
+ *                              sample, y0, y1, x0, x1, value.  Box i is clipped as msau_raster_owner (extent NULL) or
+ *                              msau_raster_owner_ext (extent int32 [B][2]) clip it; a sample outside [0, B) is an empty box.
+ *                              A pixel's class is the first maximum of its C stored values (NaN counts as the maximum),
+ *                              0 -> zero_as when zero_as >= 0.  owner NULL: the whole clipped rectangle votes; otherwise
+ *                              owner int32 [B][H][W] is the map msau_raster_owner[_ext] wrote for this same list and only
+ *                              the pixels with owner == i vote (every pixel votes for one box).
+ *                              hist int32 [n][C] (may be NULL): votes per class, zeros included; votes int32 [n][2] = (votes
+ *                              of the winner, voting pixels); pred int32 [n] = the smallest class among the most voted, -1
+ *                              (and votes 0, 0) when no pixel votes.  counts int64 [C][C] (may be NULL) accumulates across
+ *                              calls: counts[value * C + pred] += 1 for the boxes with 1 <= value < C and pred >= 0.
+ *                              Every element of pred / votes / hist is written exactly once; all integers, independent of
+ *                              arrival order.  n == 0 launches nothing; H * W < 2^31
  * ------------------------------------------------------------------------------------------ */
 int msau_softmax_argmax_nhwc(void* stream, int dtype, const void* logits, float* probs, uint8_t* argmax,
                              int64_t npix, int C, int Cs);
@@ -778,6 +792,9 @@ int msau_onehot_ids_ext(void* stream, int dtype, const int32_t* ids, void* grid_
                         const int32_t* extent);
 int msau_eval_confusion(void* stream, int dtype, const void* logits, const int64_t* labels, int64_t* counts, int B, int H, int W,
                         int C, int Cs, int zero_as, const int32_t* extent);
+int msau_box_vote(void* stream, int dtype, const void* logits, const int32_t* boxes, int n, const int32_t* owner, int32_t* pred,
+                  int32_t* votes, int32_t* hist, int64_t* counts, int B, int H, int W, int C, int Cs, int zero_as,
+                  const int32_t* extent);
 
 /* ------------------------------------------------------------------------------------------
  * Region extraction for key-value inference (the per-pixel part of inference/kv_model.py:150-261), one workgroup per

@@ -223,6 +223,7 @@ _SIGNATURES = {
     "msau_onehot_ids": (C.c_int, [vp, C.c_int, vp, vp, i64, C.c_int, C.c_int]),
     "msau_onehot_ids_ext": (C.c_int, [vp, C.c_int, vp, vp] + [C.c_int] * 5 + [vp]),
     "msau_eval_confusion": (C.c_int, [vp, C.c_int, vp, vp, vp] + [C.c_int] * 6 + [vp]),
+    "msau_box_vote": (C.c_int, [vp, C.c_int, vp, vp, C.c_int, vp, vp, vp, vp, vp] + [C.c_int] * 6 + [vp]),
     "msau_kv_regions_limits": (C.c_int, [C.POINTER(i32)]),
     "msau_kv_regions": (C.c_int, [vp] * 7 + [C.c_int] * 4 + [vp, vp, C.c_int, vp, C.c_int, vp]),
     "msau_kv_regions_large": (C.c_int, [vp] * 7 + [C.c_int] * 4 + [C.POINTER(i32), C.c_int, C.POINTER(i64), vp, i64]

@@ -33,6 +33,28 @@ def document_boxes(doc: dict, sample: int = 0) -> Tuple[np.ndarray, np.ndarray, 
     return (np.asarray(chars, np.int32).reshape(-1, 6), np.asarray(labs, np.int32).reshape(-1, 6), geo["H"], geo["W"])
 
 
+def document_word_boxes(doc: dict, sample: int = 0) -> np.ndarray:
+    """-> one box [6] per WORD of `doc["cells_word"]` in the chargrid geometry (the canvas of `document_boxes`): the union of the
+    word's character boxes (`word_char_boxes`; a word without characters: its own (x, x + w)), value = the label of its text line
+    + 1 (`doc["word_to_textline"]`).  The list `box_predictions` votes over for a word-level metric; the entity-level list is
+    the label boxes `document_boxes` / `document_line_boxes` return."""
+    words = doc["cells_word"]
+    geo = chargrid_geometry(words)
+    span = {}
+    for wi, _j, y0, y1, x0, x1 in word_char_boxes(words, geo):
+        a = span.get(wi)
+        span[wi] = (y0, y1, x0, x1) if a is None else (min(a[0], y0), max(a[1], y1), min(a[2], x0), max(a[3], x1))
+    out = []
+    for wi, c in enumerate(words):
+        if wi not in span:
+            x = int((c.x - geo["min_x"]) / geo["min_scale"])
+            y = int((c.y - geo["min_y"]) / geo["min_h"])
+            span[wi] = (y, y + max(int(c.h / geo["min_h"]), 1), x, x + max(int(c.w / geo["min_scale"]), 1))
+        y0, y1, x0, x1 = span[wi]
+        out.append((sample, y0, y1, x0, x1, int(doc["labels"][doc["word_to_textline"][wi]]) + 1))
+    return np.asarray(out, np.int32).reshape(-1, 6)
+
+
 def _dev_boxes(boxes, dev):
     """box list -> (device int32 [n][6] tensor or None, n); numpy arrays are uploaded, device tensors taken as they are"""
     if isinstance(boxes, torch.Tensor):
@@ -66,12 +88,14 @@ def _owner(s, bt, n, owner, B, H, W, ext):
 
 
 def rasterize(char_boxes, label_boxes, B: int, H: int, W: int, C: int,
-              dtype: str = "bf16", device="cuda", out: torch.Tensor = None, sizes=None) -> Tuple[torch.Tensor, torch.Tensor]:
+              dtype: str = "bf16", device="cuda", out: torch.Tensor = None, sizes=None, label_owner: bool = False):
     """-> (grid [B,H,W,Cs] one-hot in `dtype` storage, labels int64 [B,H,W]) on `device`.  `out`: paint the grid into this
     buffer (a plan's own input buffer: TrainEngine.input_nhwc) instead of a new tensor.  Box lists may be numpy arrays
     (uploaded here) or int32 device tensors (nothing crosses PCIe, no host synchronisation).
     `sizes` (ragged batch): CPU integer [B, 2] of every document's (h, w) at the origin of the H x W canvas, or the int32 [B, 2]
-    tensor already on the device; every box is then clipped to its own document and grid and labels are 0 outside the documents."""
+    tensor already on the device; every box is then clipped to its own document and grid and labels are 0 outside the documents.
+    label_owner=True: a third result (owner int32 [B,H,W] of the LABEL boxes, those boxes on the device or None, their number):
+    the map the labels were painted from, for `msau_box_vote`."""
     dt = L.BF16 if dtype in ("bf16", "bfloat16") else L.F32
     Cs = -(-C // 8) * 8
     dev = torch.device(device)
@@ -98,14 +122,17 @@ def rasterize(char_boxes, label_boxes, B: int, H: int, W: int, C: int,
     for t in keep + [owner]:
         if t is not None:
             t.record_stream(torch.cuda.current_stream(dev))
+    if label_owner:
+        return grid, labels, (owner, bt, n)                 # the loop's last list is the label list
     return grid, labels
 
 
-def owner_maps(feat_boxes, label_boxes, B: int, H: int, W: int, device="cuda", sizes=None):
+def owner_maps(feat_boxes, label_boxes, B: int, H: int, W: int, device="cuda", sizes=None, label_owner: bool = False):
     """-> (owner int32 [B,H,W]: index of the feature box that owns each pixel, -1 = none; the feature boxes as a device
     tensor [n,6] (or None) and n; labels int64 [B,H,W]).  What the dense painters start from -- and all that the net's first
     conv needs when it is fed with box lists (MSAU_CONV_OWNER, csrc/ownerconv.hip): the grid itself is never painted.
-    `sizes` (ragged batch, as `rasterize`): owner is -1 and labels are 0 everywhere outside the documents."""
+    `sizes` (ragged batch, as `rasterize`): owner is -1 and labels are 0 everywhere outside the documents.
+    label_owner=True: a fifth result (owner map of the LABEL boxes, those boxes on the device or None, their number)."""
     dev = torch.device(device)
     if dev.index is None and dev.type == "cuda":
         dev = torch.device("cuda", torch.cuda.current_device())
@@ -122,6 +149,8 @@ def owner_maps(feat_boxes, label_boxes, B: int, H: int, W: int, device="cuda", s
     for t in (fb, lb, lown, ext):
         if t is not None:
             t.record_stream(torch.cuda.current_stream(dev))
+    if label_owner:
+        return owner, fb, nf, labels, (lown, lb, nl)
     return owner, fb, nf, labels
 
 
@@ -135,10 +164,10 @@ def document_line_boxes(doc: dict, sample: int = 0, feat_base: int = 0):
 
 
 def rasterize_dense(feat_boxes, label_boxes, feats, B: int, H: int, W: int,
-                    dtype: str = "bf16", device="cuda", out: torch.Tensor = None, sizes=None) -> Tuple[torch.Tensor, torch.Tensor]:
+                    dtype: str = "bf16", device="cuda", out: torch.Tensor = None, sizes=None, label_owner: bool = False):
     """-> (grid [B,H,W,Cs] with feats[value] painted over each box in `dtype` storage, labels int64 [B,H,W]); only the
     box list and the [n_lines, C] feature table cross PCIe (at 768 channels the dense fp32 grid is 264 MB per tile).  `out`,
-    device-tensor arguments, `sizes`: as `rasterize`."""
+    device-tensor arguments, `sizes`, `label_owner`: as `rasterize`."""
     dt = L.BF16 if dtype in ("bf16", "bfloat16") else L.F32
     dev = torch.device(device)
     if dev.index is None and dev.type == "cuda":
@@ -169,4 +198,6 @@ def rasterize_dense(feat_boxes, label_boxes, feats, B: int, H: int, W: int,
     for t in keep + [owner]:
         if t is not None:
             t.record_stream(torch.cuda.current_stream(dev))
+    if label_owner:
+        return grid, labels, (owner, bt, n)                 # the loop's last list is the label list
     return grid, labels

@@ -548,15 +548,16 @@ class MSAUWrapper(nn.Module):
         plan.forward(self._flat, None, export=False, **feed)
         return self._count_confusion(plan, lab, zero_as, out)
 
-    def _confusion_args(self, zero_as, out: Optional[torch.Tensor], dev) -> torch.Tensor:
-        """the checks `confusion_matrix` and `confusion_matrix_boxes` share -> `out`, a new matrix on `dev` when it is None"""
+    def _confusion_args(self, zero_as, out: Optional[torch.Tensor], dev, new: bool = True) -> Optional[torch.Tensor]:
+        """the checks `confusion_matrix`, `confusion_matrix_boxes` and the box votes share -> `out`, a new matrix on `dev` when it is
+        None (new=False: None stays None, the box votes count into a matrix only when they are given one)"""
         C = self.n_class
         if C > 64:
             raise ValueError(f"confusion_matrix counts at most 64 classes, the model has {C}")
         if zero_as is not None and not (0 <= int(zero_as) < C):
             raise ValueError(f"zero_as must be a class in [0, {C}), got {zero_as}")
         if out is None:
-            return torch.zeros((C, C), dtype=torch.int64, device=dev)
+            return torch.zeros((C, C), dtype=torch.int64, device=dev) if new else None
         if out.dtype != torch.int64 or tuple(out.shape) != (C, C) or out.device != dev or not out.is_contiguous():
             raise ValueError(f"out must be a contiguous int64 [{C}, {C}] tensor on {dev}")
         return out
@@ -569,27 +570,98 @@ class MSAUWrapper(nn.Module):
                plan.extent_ptr(lg) if plan.ragged else None)
         return out
 
-    def _paint_boxes(self, plan: Plan, grid_boxes, label_boxes, feats, out: Optional[torch.Tensor] = None):
+    @torch.no_grad()
+    def box_predictions(self, inp: torch.Tensor, boxes, sizes=None, zero_as: Optional[int] = None, owned: bool = False,
+                        out: Optional[torch.Tensor] = None, hist: bool = False):
+        """Entity-level predictions on the device: every box of `boxes` (int32 [n][6] = sample, y0, y1, x0, x1, value; a numpy array
+        or a device tensor; an entity list such as the label boxes of msau_amd.data.raster.document_boxes, or its
+        document_word_boxes) gets the class most of its pixels vote for.  A pixel's class is the first maximum of the logits,
+        exactly `argmax(0)` of the fp32 NCHW logits `forward` returns, with `zero_as` as in `confusion_matrix`; boxes are clipped to
+        the canvas, or with `sizes` (as in `forward`; boxes in their own document's coordinates) to their document.  owned=False:
+        the whole clipped box votes; owned=True: only the pixels the box owns after the list is painted in order (a later box
+        takes the pixels it shares with an earlier one), so every pixel votes for one box.
+        -> (pred int32 [n]: the smallest class among the most voted, -1 for a box without a voting pixel; votes int32 [n, 2] =
+        (votes of the winner, voting pixels); the per-class votes int32 [n, n_class] with hist=True, else None), on the device.
+        `out`: an int64 [n_class, n_class] matrix on the device that gets out[value, pred] += 1 for every box with a value in
+        [1, n_class) and a prediction (batches of an epoch accumulate; msau_amd.training.metrics.classification_report takes it).
+        Runs the forward-only plan without exporting the logits; nothing waits for the device."""
+        x = inp.contiguous().float()
+        if x.dim() != 4:
+            raise ValueError("inp must be [B,C,H,W]")
+        out = self._confusion_args(zero_as, out, x.device, new=False)
+        if sizes is not None:
+            sizes = self._check_sizes(x, sizes)
+        self._need_gpu(x)
+        from .data import raster
+        bt, n = raster._dev_boxes(boxes, x.device)
+        plan = self._plan_for(x, training=False, ragged=sizes is not None)
+        plan.set_extents(sizes)
+        plan.forward(self._flat, x, export=False)
+        owner = None
+        if owned and n:
+            owner = torch.empty((plan.B, plan.H, plan.W), dtype=torch.int32, device=x.device)
+            raster._owner(torch.cuda.current_stream(x.device).cuda_stream, bt, n, owner, plan.B, plan.H, plan.W,
+                          plan.extents[0] if plan.ragged else None)
+        return self._vote_boxes(plan, bt, n, owner, zero_as, out, hist)
+
+    @torch.no_grad()
+    def box_predictions_boxes(self, grid_boxes, label_boxes, B: int, H: int, W: int, feats=None, sizes=None,
+                              zero_as: Optional[int] = None, owned: bool = False, out: Optional[torch.Tensor] = None,
+                              hist: bool = False):
+        """`box_predictions` for a batch that comes as BOX LISTS, fed as `confusion_matrix_boxes` feeds it: the voted boxes are the
+        label boxes.  owned=True votes with the owner map the label painter has made of them anyway (nothing is painted twice)."""
+        dev = self._flat.device
+        out = self._confusion_args(zero_as, out, dev, new=False)
+        sizes = self._check_sizes_for(sizes, B, H, W)
+        self._need_gpu()
+        plan = self._plan(B, H, W, dev, False, sizes)
+        feed, _lab, (owner, bt, n) = self._paint_boxes(plan, grid_boxes, label_boxes, feats, label_owner=True)
+        plan.forward(self._flat, None, export=False, **feed)
+        return self._vote_boxes(plan, bt, n, owner if owned and n else None, zero_as, out, hist)
+
+    def _vote_boxes(self, plan: Plan, bt: Optional[torch.Tensor], n: int, owner: Optional[torch.Tensor], zero_as,
+                    out: Optional[torch.Tensor], hist: bool):
+        """msau_box_vote on the logits `plan` holds: the n boxes of the device list `bt` (None when n == 0), `owner` their owner map
+        or None -> (pred, votes, hist or None) on the device; counts go into `out` when it is given"""
+        lg, dev = plan.logits, self._flat.device
+        stream = torch.cuda.current_stream(dev)
+        pred = torch.empty((n,), dtype=torch.int32, device=dev)
+        votes = torch.empty((n, 2), dtype=torch.int32, device=dev)
+        hs = torch.empty((n, lg.C), dtype=torch.int32, device=dev) if hist else None
+        L.call("msau_box_vote", stream.cuda_stream, plan.dtype, lg.data.data_ptr(), bt.data_ptr() if n else None, n,
+               owner.data_ptr() if owner is not None else None, pred.data_ptr(), votes.data_ptr(),
+               hs.data_ptr() if hs is not None else None, out.data_ptr() if out is not None else None, plan.B, plan.H, plan.W,
+               lg.C, lg.Cs, -1 if zero_as is None else int(zero_as), plan.extent_ptr(lg) if plan.ragged else None)
+        # an uploaded box list and the owner map must outlive the launch that reads them (see msau_amd/data/raster.py)
+        for t in (bt, owner):
+            if t is not None:
+                t.record_stream(stream)
+        return pred, votes, hs
+
+    def _paint_boxes(self, plan: Plan, grid_boxes, label_boxes, feats, out: Optional[torch.Tensor] = None, label_owner: bool = False):
         """A batch of box lists (as `TrainEngine.step_boxes` takes them) on the canvas of `plan` -> (the keywords that make
         `Plan.forward` read it, labels int64 [B,H,W]).  With a feature table and a box-list instance of the first conv
         (MSAU_CONV_OWNER, csrc/ownerconv.hip) only the owner map is painted: the embedding grid is piecewise constant, the conv and
         its weight gradient work from the per-pixel box index and the table.  Otherwise the grid goes into the plan's input buffer
         -- or into `out`, another buffer of that shape (`TrainEngine.prefetch_boxes`; never the box-list conv then).  On a ragged plan
         the painters clip to the plan's own level-0 extents: owner map, grid and labels are empty / zero outside the documents as
-        they enter, nothing has to be zeroed afterwards."""
+        they enter, nothing has to be zeroed afterwards.  label_owner=True: a third result, the label painter's (owner map, label
+        boxes on the device or None, their number) for `_vote_boxes`."""
         from .data import raster
         B, H, W, dev = plan.B, plan.H, plan.W, self._flat.device
         ext = plan.extents[0] if plan.ragged else None
         if feats is not None and out is None and plan._feed_owner(None):
             ft = feats if isinstance(feats, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(feats, dtype=np.float32)).to(dev)
-            owner, fb, nf, labels = raster.owner_maps(grid_boxes, label_boxes, B, H, W, dev, sizes=ext)
-            return dict(owner=(owner, fb, nf, ft)), labels
+            owner, fb, nf, labels, *lown = raster.owner_maps(grid_boxes, label_boxes, B, H, W, dev, sizes=ext, label_owner=label_owner)
+            return (dict(owner=(owner, fb, nf, ft)), labels, *lown)
         buf = plan.input_nhwc if out is None else out
         if feats is None:
-            _, labels = raster.rasterize(grid_boxes, label_boxes, B, H, W, self.channels, self.dtype_name, dev, out=buf, sizes=ext)
+            _, labels, *lown = raster.rasterize(grid_boxes, label_boxes, B, H, W, self.channels, self.dtype_name, dev, out=buf, sizes=ext,
+                                                label_owner=label_owner)
         else:
-            _, labels = raster.rasterize_dense(grid_boxes, label_boxes, feats, B, H, W, self.dtype_name, dev, out=buf, sizes=ext)
-        return dict(nhwc_ready=True, nhwc_clean=True), labels
+            _, labels, *lown = raster.rasterize_dense(grid_boxes, label_boxes, feats, B, H, W, self.dtype_name, dev, out=buf, sizes=ext,
+                                                      label_owner=label_owner)
+        return (dict(nhwc_ready=True, nhwc_clean=True), labels, *lown)
 
     @torch.no_grad()
     def eval_unet(self, ids: torch.Tensor, labels: torch.Tensor, aux_labels: torch.Tensor, sizes=None, class_weights=None):

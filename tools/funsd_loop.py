@@ -26,6 +26,15 @@ document's plan cached; reports, as one JSON object:
                                          extent flag costs on the generic kernels
                            ms per step and bytes uploaded per step of each arm, every repeat; only this comparison runs
 
+  entities                 with --eval B --entities: entity-level predictions of the same documents (one text-line-like entity box
+                           per ~150 pixels) in ragged batches of B, two ways on identical batches, interleaved, --repeats times:
+                           "device"  MSAUWrapper.box_predictions: forward-only plan + msau_box_vote, the int64 matrix read once per
+                                     epoch; timed with device events around the epoch (the read included)
+                           "host"    forward, copy of the exported logits to the host, msau_amd.data.entities.box_vote_host; timed
+                                     with the wall clock around the epoch (it ends in host work)
+                           docs/s of every repeat, bytes copied to the host per document, and whether both routes gave the same
+                           predictions for every box; a timed window is --epochs passes over the documents; only this comparison runs
+
     python tools/funsd_loop.py [--docs 120] [--epochs 3] [--channels 64] [--dtype bf16] [--graph] [--ragged 16] [--eval 16]
     python tools/funsd_loop.py --ragged 16 --boxes --channels 768 --dtype bf16 [--repeats 5]
 """
@@ -303,6 +312,77 @@ def run_eval(args, B):
     return res
 
 
+def run_entities(args, B):
+    """entity-level predictions: the device route (forward-only plan + vote) against the host route (forward, export, numpy)"""
+    import numpy as np
+    import torch
+    from msau_amd.data.entities import box_vote_host
+    from msau_amd.data.ragged import batches, pack
+    dev = torch.device("cuda", 0)
+    m = make_model(args).eval()
+    docs = make_docs(args)
+    C = m.n_class
+    rng = np.random.default_rng(1)
+    steps = []
+    for idx in batches(docs, B, round_to=16):
+        x, _lab, sizes = pack([docs[i] for i in idx], round_to=16)
+        boxes = []
+        for b, (h, w) in enumerate(sizes.tolist()):
+            for _ in range(max(4, h * w // 150)):
+                y0, x0 = int(rng.integers(0, h)), int(rng.integers(-2, w - 4))
+                boxes.append((b, y0, y0 + int(rng.integers(1, 4)), x0, x0 + int(rng.integers(6, 40)), int(rng.integers(1, C))))
+        steps.append((x.to(dev), np.asarray(boxes, np.int32), sizes))
+    m.max_cached_plans = len(steps) + 2
+    n_boxes = sum(len(bx) for _, bx, _ in steps)
+
+    def device(keep=None):
+        em = torch.zeros((C, C), dtype=torch.int64, device=dev)
+        for x, bx, sizes in steps:
+            pred, _votes, _hist = m.box_predictions(x, bx, sizes=sizes, out=em)
+            if keep is not None:
+                keep.append(pred)
+        return em.cpu().numpy()
+
+    def host(keep=None):
+        em = np.zeros((C, C), np.int64)
+        with torch.no_grad():
+            for x, bx, sizes in steps:
+                _, logits, _ = m(x, sizes)
+                pred, _votes, _hist, counts = box_vote_host(logits.permute(0, 2, 3, 1).cpu().numpy(), bx, C, extent=sizes.numpy())
+                em += counts
+                if keep is not None:
+                    keep.append(pred)
+        return em
+
+    kd, kh = [], []
+    em_d, em_h = device(kd), host(kh)                          # plans built, first launches done; the comparison of the routes
+    torch.cuda.synchronize()
+    same = bool(np.array_equal(em_d, em_h)) and all(np.array_equal(a.cpu().numpy(), b) for a, b in zip(kd, kh))
+    res = {"device": {"docs_per_s": []}, "host": {"docs_per_s": []}}
+    passes = max(args.epochs, 1)                               # epochs per timed window (--epochs 20: windows of 0.2 s and more)
+    for _ in range(max(args.repeats, 5)):
+        torch.cuda.synchronize()
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(passes):
+            device()
+        e1.record()
+        torch.cuda.synchronize()
+        res["device"]["docs_per_s"].append(round(passes * len(docs) / (1e-3 * e0.elapsed_time(e1)), 1))
+        t0 = time.perf_counter()
+        for _ in range(passes):
+            host()
+        res["host"]["docs_per_s"].append(round(passes * len(docs) / (time.perf_counter() - t0), 1))
+    res["device"].update(clock="device events", bytes_to_host_per_doc=round(C * C * 8 / len(docs), 1))
+    res["host"].update(clock="wall clock", bytes_to_host_per_doc=round(sum(x.shape[0] * C * x.shape[2] * x.shape[3] * 4 for x, _, _ in steps) / len(docs), 1))
+    med = lambda v: sorted(v)[len(v) // 2]
+    res.update(batch=B, docs=len(docs), forwards=len(steps), boxes=n_boxes, epochs_per_window=passes, dtype=args.dtype, channels=args.channels, same_predictions=same,
+               entity_acc=round(float(np.trace(em_d)) / max(int(em_d.sum()), 1), 6),
+               speedup_median=round(med(res["device"]["docs_per_s"]) / med(res["host"]["docs_per_s"]), 3),
+               device_faster_in_every_repeat=all(d > h for d, h in zip(res["device"]["docs_per_s"], res["host"]["docs_per_s"])))
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--docs", type=int, default=120)
@@ -315,8 +395,14 @@ def main():
     ap.add_argument("--eval", type=int, default=0, help="also compare the per-document evaluation loop with ragged batches of this size")
     ap.add_argument("--eval-only", action="store_true", help="only the evaluation comparison (e.g. under rocprofv3)")
     ap.add_argument("--boxes", action="store_true", help="with --ragged: ragged batches from box lists against the host-painted canvas (only this runs)")
-    ap.add_argument("--repeats", type=int, default=5, help="--boxes: interleaved repeats (at least 5)")
+    ap.add_argument("--repeats", type=int, default=5, help="--boxes / --entities: interleaved repeats (at least 5)")
+    ap.add_argument("--entities", action="store_true", help="with --eval: entity-level predictions, device route against host route (only this runs)")
     args = ap.parse_args()
+    if args.entities:
+        if not args.eval:
+            ap.error("--entities compares evaluation routes: give --eval B")
+        print(json.dumps({"entities": run_entities(args, args.eval)}))
+        return
     if args.boxes:
         if not args.ragged:
             ap.error("--boxes compares ragged batches: give --ragged B")

@@ -10,6 +10,8 @@ every 10 epochs under ckpt/<dataset>_<method>_h<hidden>_o<out>/<epoch>.pth.tar.
 --batch-size N trains ragged batches (msau_amd.data.ragged: each document computes what it would alone, the loss is the mean of
 the documents' losses); --eval-batch-size N evaluates in ragged batches.  The evaluation counts a confusion matrix on the device
 (MSAUWrapper.confusion_matrix) and prints sklearn's classification report for the test split, as the reference does.
+--entity-level adds the entity-level figures: every annotated entity box gets the class most of its pixels predict
+(MSAUWrapper.box_predictions, counted on the device as well) and a second accuracy / report is printed over entities.
 
 Two step implementations, selected with --loop:
   engine     (default) msau_amd.TrainEngine: fused masked-CE + clip + Adam, no per-step host sync
@@ -27,7 +29,7 @@ import torch
 from msau_amd import MSAUWrapper as MSAU
 from msau_amd import TrainEngine
 from msau_amd.data import FUNSDCharGridDataLoaderBoxMaskBoxLabel
-from msau_amd.data import ragged
+from msau_amd.data import ragged, raster
 from msau_amd.training import metrics, save_checkpoint
 
 
@@ -64,26 +66,46 @@ def canvases(docs, batch_size, round_to=16):
 def evaluate(dataset, model, args, name="Validation", testing=False, max_num_examples=None, labels_map=None, batch_size=None):
     """accuracy over the labelled pixels (reference :121-163) from a confusion matrix that the device accumulates
     (MSAUWrapper.confusion_matrix): no logits leave the device and the host reads the matrix once.  batch_size (default
-    --eval-batch-size) > 1 runs the documents in ragged batches.  The test split also prints the classification report."""
+    --eval-batch-size) > 1 runs the documents in ragged batches.  The test split also prints the classification report.
+    With args.entity_level every document brings its entity boxes ("boxes", int32 [m, 6]); a second matrix counts (entity label,
+    class most of the entity's pixels predict) on the device (MSAUWrapper.box_predictions, a forward of its own; whole boxes vote,
+    same `zero_as`), and the entity accuracy and report are printed after the per-pixel ones and returned as "entity_acc" /
+    "entity_matrix"."""
     model.eval()
     device = model.flat_parameters.device
     bs = batch_size if batch_size is not None else getattr(args, "eval_batch_size", 1)
     docs = dataset[:eval_count(len(dataset), max_num_examples)]
     zero_as = labels_map["other"] if testing and labels_map is not None and "other" in labels_map else None   # reference :140
     cm = torch.zeros((model.n_class, model.n_class), dtype=torch.int64, device=device)
+    entities = getattr(args, "entity_level", False)           # documents then carry "boxes": their entity boxes [m, 6]
+    em = torch.zeros_like(cm) if entities else None
     with torch.no_grad():
         if bs == 1:
             for data in docs:
-                model.confusion_matrix(data["mask"].float().to(device), data["label"].long(), zero_as=zero_as, out=cm)
+                x = data["mask"].float().to(device)
+                model.confusion_matrix(x, data["label"].long(), zero_as=zero_as, out=cm)
+                if entities:
+                    model.box_predictions(x, data["boxes"], zero_as=zero_as, out=em)
         else:
             for idx in ragged.batches(docs, bs):
                 x, lab, sizes = ragged.pack([docs[i] for i in idx])
-                model.confusion_matrix(x.to(device), lab, sizes=sizes, zero_as=zero_as, out=cm)
+                x = x.to(device)
+                model.confusion_matrix(x, lab, sizes=sizes, zero_as=zero_as, out=cm)
+                if entities:
+                    none = np.zeros((0, 6), np.int32)
+                    _, boxes, _, _, _ = ragged.pack_boxes([(none, docs[i]["boxes"]) + tuple(docs[i]["mask"].shape[2:]) for i in idx])
+                    model.box_predictions(x, boxes, sizes=sizes, zero_as=zero_as, out=em)
     cm = cm.cpu().numpy()
     result = metrics.scores(cm)
     print(name, " accuracy:", result["acc"])
+    names = list(labels_map.keys()) if labels_map is not None else None
     if testing:
-        print(metrics.classification_report(cm, list(labels_map.keys()) if labels_map is not None else None))
+        print(metrics.classification_report(cm, names))
+    if entities:
+        em = em.cpu().numpy()
+        result = dict(result, entity_acc=metrics.scores(em)["acc"], entity_matrix=em)
+        print(name, " entity accuracy:", result["entity_acc"])
+        print(metrics.classification_report(em, names))
     return result
 
 
@@ -136,7 +158,7 @@ def train(dataset, model, args, val_dataset=None, test_dataset=None, labels_map=
                 best_val = {"acc": vr["acc"], "epoch": epoch, "loss": avg_loss}
         if test_dataset:
             tr = evaluate(test_dataset, model, args, testing=True, name="Test", labels_map=labels_map)
-            print("Test result: ", dict(tr, epoch=epoch))
+            print("Test result: ", dict({k: v for k, v in tr.items() if k != "entity_matrix"}, epoch=epoch))
         print("Best val result: ", best_val)
         if epoch % 10 == 0:
             torch.save(model.state_dict(), ckpt_filename(args.ckptdir, args, epoch))
@@ -161,6 +183,8 @@ def parse_args(argv=None):
     ap.add_argument("--batch-size", type=int, default=1,
                     help="documents per training step; > 1 trains ragged batches of documents of similar size")
     ap.add_argument("--eval-batch-size", type=int, default=1, help="documents per evaluation forward (ragged batches when > 1)")
+    ap.add_argument("--entity-level", action="store_true",
+                    help="also report accuracy / precision / recall over the annotated entity boxes (each box votes with its pixels)")
     args = ap.parse_args(argv)
     if args.batch_size < 1 or args.eval_batch_size < 1:
         ap.error("--batch-size and --eval-batch-size must be >= 1")
@@ -188,9 +212,14 @@ def main(argv=None):
     indices = list(range(len(data_loader)))
     random.shuffle(indices)
     cut = int(len(indices) * args.train_ratio)
-    train_instances = [data_loader[i] for i in indices[:cut]]
-    val_instances = [data_loader[i] for i in indices[cut:]]
-    test_instances = [data_loader_test[i] for i in range(len(data_loader_test))]
+
+    def instance(loader, i):
+        """the loader's item; with --entity-level also the document's entity boxes (the boxes its label mask is painted from)"""
+        return dict(loader[i], boxes=raster.document_boxes(loader.inp_list[i])[1]) if args.entity_level else loader[i]
+
+    train_instances = [instance(data_loader, i) for i in indices[:cut]]
+    val_instances = [instance(data_loader, i) for i in indices[cut:]]
+    test_instances = [instance(data_loader_test, i) for i in range(len(data_loader_test))]
     print("Num training instances: ", len(train_instances), "; Num validation instances: ", len(val_instances),
           "; Num testing instances: ", len(test_instances))
     # batch 1 with a different H x W per document (data_generator_funsd_bert.py:216-222): every shape has its own static
