@@ -55,7 +55,7 @@ struct BvArgs {
     int n, B, H, W, C, Cs, zero_as;
 };
 
-// strictly greater: the first maximum wins; a NaN counts as the maximum, as in torch.argmax (first_max of elementwise.hip)
+// strictly greater: the first maximum wins; a NaN counts as the maximum, as in torch.argmax (first_max of loss.hip)
 BV_DEV void bv_first_max(float v, int c, float& bv, int& best) {
     if (v > bv || (v != v && bv == bv)) { bv = v; best = c; }
 }

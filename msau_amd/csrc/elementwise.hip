@@ -1,19 +1,11 @@
-// HBM-bound kernels of the MSAU train path: boundary layout conversion, cross-channel LRN,
-// 2x2 max pool, masked cross entropy, clip+Adam.  All vectorised 16 B per lane along the
-// channel (NHWC) dimension; accumulation in fp32.
+// HBM-bound kernels of the MSAU train path: boundary layout conversion, cross-channel LRN, 2x2 max pool, extent copy,
+// per-channel sums, clip+Adam, one-hot ids, and the stream, spin and fork-visibility utilities.  Vectorised 16 B per lane
+// along the channel (NHWC) dimension where a tensor is touched; accumulation in fp32.  The losses, the evaluation counts and
+// the softmax heads are loss.hip.
 #include "msau_common.h"
 #include <cstdlib>
 
 namespace {
-
-constexpr int kThreads = 256;
-
-inline int grid_for(int64_t work, int cap = 256 * 16) {
-    int64_t b = cdiv64(work, kThreads);
-    if (b > cap) b = cap;
-    if (b < 1) b = 1;
-    return (int)b;
-}
 
 // =============================================================================================
 // layout: NCHW fp32 (reference API, train_chargrid_funsd_msau.py:50-53) <-> NHWC T
@@ -421,606 +413,6 @@ __global__ __launch_bounds__(256) void pool_bwd_kernel(const T* __restrict__ dy,
 }
 
 // =============================================================================================
-// masked cross entropy (model/model.py:446-459), batch rule of SURVEY 8(e)
-// =============================================================================================
-// One 1024-thread workgroup per sample, 16-byte loads (two labels), eight in flight per thread, no atomics and no
-// memset: counts[b] is written, not accumulated.  (The first version spread a sample over 64 workgroups and let every
-// wave atomicAdd into counts[b]: 4096 same-address atomics took 51 us for 11 MB of labels.)
-__global__ __launch_bounds__(1024) void label_count_kernel(const int64_t* __restrict__ labels, int32_t* __restrict__ counts, int64_t hw) {
-    __shared__ int red[16];
-    const int b = blockIdx.x;
-    const int64_t* base = labels + (int64_t)b * hw;
-    int local = 0;
-    typedef long long ll2 __attribute__((ext_vector_type(2)));
-    const int64_t npair = hw >> 1;                                   // base is 16-byte aligned when hw is even or b == 0
-    const bool aligned = ((reinterpret_cast<uintptr_t>(base) & 15) == 0);
-    if (aligned) {
-        const ll2* p2 = reinterpret_cast<const ll2*>(base);
-        int64_t i = threadIdx.x;
-        for (; i + 7 * 1024 < npair; i += 8 * 1024) {
-            ll2 v[8];
-#pragma unroll
-            for (int u = 0; u < 8; ++u) v[u] = p2[i + u * 1024];
-#pragma unroll
-            for (int u = 0; u < 8; ++u) local += (v[u][0] > 0) + (v[u][1] > 0);
-        }
-        for (; i < npair; i += 1024) { ll2 v = p2[i]; local += (v[0] > 0) + (v[1] > 0); }
-        if ((hw & 1) && threadIdx.x == 0) local += base[hw - 1] > 0;
-    } else {
-        for (int64_t i = threadIdx.x; i < hw; i += 1024) local += base[i] > 0;
-    }
-    for (int o = 32; o > 0; o >>= 1) local += __shfl_down(local, o, 64);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = local;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        int t = 0;
-        for (int i = 0; i < 16; ++i) t += red[i];
-        counts[b] = t;
-    }
-}
-
-// The same count with a sample spread over K workgroups (grid K x B): partial[b * K + k] is written, the consumer
-// (msau_masked_ce_multi with counts_k = K) adds the K integers up -- exact in any order, no atomics, no follow-up launch.  One
-// workgroup per sample left 240 of 256 CUs idle: 15 us for the bench's 11 MB of labels, on the main queue between the sweeps.
-__global__ __launch_bounds__(256) void label_count_split_kernel(const int64_t* __restrict__ labels, int32_t* __restrict__ partial,
-                                                                int64_t hw, int K) {
-    __shared__ int red[4];
-    const int b = blockIdx.y, k = blockIdx.x;
-    const int64_t chunk = (hw + K - 1) / K;
-    const int64_t lo = (int64_t)k * chunk, hi = lo + chunk < hw ? lo + chunk : hw;
-    const int64_t* base = labels + (int64_t)b * hw;
-    int local = 0;
-    int64_t i = lo + threadIdx.x;
-    for (; i + 7 * 256 < hi; i += 8 * 256) {
-        int64_t v[8];
-#pragma unroll
-        for (int u = 0; u < 8; ++u) v[u] = base[i + u * 256];
-#pragma unroll
-        for (int u = 0; u < 8; ++u) local += v[u] > 0;
-    }
-    for (; i < hi; i += 256) local += base[i] > 0;
-    for (int o = 32; o > 0; o >>= 1) local += __shfl_down(local, o, 64);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = local;
-    __syncthreads();
-    if (threadIdx.x == 0) partial[b * K + k] = red[0] + red[1] + red[2] + red[3];
-}
-
-// the block's sum of class weights (second reduction of the weighted CE), same order as the loss partials
-__device__ __forceinline__ void ce_weight_sum(float local_w, float* red, float* out) {
-    __syncthreads();
-    for (int o = 32; o > 0; o >>= 1) local_w += __shfl_down(local_w, o, 64);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = local_w;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        float s = 0.f;
-        for (int i = 0; i < kThreads / 64; ++i) s += red[i];
-        out[blockIdx.x] = s;
-    }
-}
-
-template <typename T, bool ALL>
-__global__ void masked_ce_kernel(const T* __restrict__ logits, const int64_t* __restrict__ labels,
-                                 const int32_t* __restrict__ counts, T* __restrict__ dlogits, float* __restrict__ partials,
-                                 int B, int64_t hw, int C, int Cs, float scale, const float* __restrict__ cw = nullptr) {
-    // cw (ALL only): per-class weights of torch.nn.CrossEntropyLoss(weight) (model/training/cost.py:24-31): every pixel's term and
-    // gradient are multiplied by cw[label]; the sum of those weights -- the loss's denominator -- goes to the second half of partials
-    __shared__ float red[kThreads / 64];
-    float local = 0.f, local_w = 0.f;
-    const int64_t total = (int64_t)B * hw;
-    for (int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; p < total; p += (int64_t)gridDim.x * blockDim.x) {
-        const int b = (int)(p / hw);
-        const int64_t lab = labels[p];
-        const bool on = ALL ? (lab >= 0 && lab < C) : (lab > 0 && lab < C);
-        float w = on ? (ALL ? scale : scale / (float)max(counts[b], 1)) : 0.f;
-        if (ALL && cw && on) { const float c = cw[(int)lab]; w *= c; local_w += c; }
-        float x[16];
-        float mx = -INFINITY;
-        for (int c0 = 0; c0 < Cs && c0 < 16; c0 += 8) {
-            typename Vec8<T>::type v = load8<T>(logits + p * Cs + c0);
-#pragma unroll
-            for (int j = 0; j < 8; ++j) { x[c0 + j] = (float)v[j]; if (c0 + j < C) mx = fmaxf(mx, x[c0 + j]); }
-        }
-        float se = 0.f;
-        for (int c = 0; c < C; ++c) se += __expf(x[c] - mx);
-        const float lse = mx + __logf(se);
-        if (on) local += w * (lse - x[(int)lab]);
-        for (int c0 = 0; c0 < Cs; c0 += 8) {
-            typename Vec8<T>::type o;
-#pragma unroll
-            for (int j = 0; j < 8; ++j) {
-                int c = c0 + j;
-                float g = 0.f;
-                if (on && c < C) g = w * (__expf(x[c] - lse) - (c == (int)lab ? 1.f : 0.f));
-                o[j] = (T)g;
-            }
-            store8<T>(dlogits + p * Cs + c0, o);
-        }
-    }
-    for (int o = 32; o > 0; o >>= 1) local += __shfl_down(local, o, 64);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = local;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        float s = 0.f;
-        for (int i = 0; i < kThreads / 64; ++i) s += red[i];
-        partials[blockIdx.x] = s;
-    }
-    if (ALL && cw) ce_weight_sum(local_w, red, partials + gridDim.x);
-}
-
-// Any class count (Cs > 16: e.g. the 17-class key-value head): the logits of a pixel are read three times from the
-// cache instead of being held in registers.  Same arithmetic and summation order as masked_ce_kernel.
-template <typename T, bool ALL>
-__global__ void masked_ce_wide_kernel(const T* __restrict__ logits, const int64_t* __restrict__ labels,
-                                      const int32_t* __restrict__ counts, T* __restrict__ dlogits, float* __restrict__ partials,
-                                      int B, int64_t hw, int C, int Cs, float scale, const float* __restrict__ cw = nullptr) {
-    // cw (ALL only): per-class weights of torch.nn.CrossEntropyLoss(weight) (model/training/cost.py:24-31): every pixel's term and
-    // gradient are multiplied by cw[label]; the sum of those weights -- the loss's denominator -- goes to the second half of partials
-    __shared__ float red[kThreads / 64];
-    float local = 0.f, local_w = 0.f;
-    const int64_t total = (int64_t)B * hw;
-    for (int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; p < total; p += (int64_t)gridDim.x * blockDim.x) {
-        const int b = (int)(p / hw);
-        const int64_t lab = labels[p];
-        const bool on = ALL ? (lab >= 0 && lab < C) : (lab != 0 && lab > 0 && lab < C);
-        float w = on ? (ALL ? scale : scale / (float)max(counts[b], 1)) : 0.f;
-        if (ALL && cw && on) { const float c = cw[(int)lab]; w *= c; local_w += c; }
-        const T* l = logits + p * Cs;
-        float mx = -INFINITY;
-        for (int c = 0; c < C; ++c) mx = fmaxf(mx, (float)l[c]);
-        float se = 0.f;
-        for (int c = 0; c < C; ++c) se += __expf((float)l[c] - mx);
-        const float lse = mx + __logf(se);
-        if (on) local += w * (lse - (float)l[lab]);
-        for (int c = 0; c < Cs; ++c) {
-            float g = 0.f;
-            if (on && c < C) g = w * (__expf((float)l[c] - lse) - (c == (int)lab ? 1.f : 0.f));
-            dlogits[p * Cs + c] = (T)g;
-        }
-    }
-    for (int o = 32; o > 0; o >>= 1) local += __shfl_down(local, o, 64);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = local;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        float s = 0.f;
-        for (int i = 0; i < kThreads / 64; ++i) s += red[i];
-        partials[blockIdx.x] = s;
-    }
-    if (ALL && cw) ce_weight_sum(local_w, red, partials + gridDim.x);
-}
-
-constexpr int kCeMaxB = 1024;
-// Final + auxiliary masked CE in ONE launch (model/model.py:455-458: CE(out) + CE(aux) over the same labelled pixels):
-// the label and the per-sample weight are read once, both gradients are written, block partial sums go to ws and the
-// one-wave follow-up kernel adds them up in index order -> loss[0], reproducibly.  (A "last block sums" ticket
-// instead of the second launch was tried: thousands of same-address atomics cost 200 us.)
-template <typename T, int NL, int CS8>
-__global__ void masked_ce_multi_kernel(const T* __restrict__ l0, const T* __restrict__ l1, const int64_t* __restrict__ labels,
-                                       const int32_t* __restrict__ counts, T* __restrict__ d0, T* __restrict__ d1,
-                                       float* __restrict__ ws, float* __restrict__ loss, int B, int hw, int C, float scale, int K) {
-    constexpr int Cs = CS8 * 8;
-    __shared__ float red[kThreads / 64];
-    __shared__ int cnt[kCeMaxB];                                       // per-sample counts: the K partial counts added up (B <= kCeMaxB)
-    const bool in_lds = B <= kCeMaxB;
-    if (in_lds) {
-        for (int b = threadIdx.x; b < B; b += blockDim.x) {
-            int t = 0;
-            for (int k = 0; k < K; ++k) t += counts[b * K + k];
-            cnt[b] = t;
-        }
-        __syncthreads();
-    }
-    float local = 0.f;
-    const int64_t total = (int64_t)B * hw;
-    for (int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; p < total; p += (int64_t)gridDim.x * blockDim.x) {
-        const int b = (int)((unsigned)p / (unsigned)hw);               // total < 2^31 (checked by the host)
-        const int lab = (int)labels[p];
-        const bool on = lab != 0 && lab < C && lab > 0;
-        const float w = on ? scale / (float)max(in_lds ? cnt[b] : counts[b], 1) : 0.f;
-#pragma unroll
-        for (int t = 0; t < NL; ++t) {
-            const T* lg = t ? l1 : l0;
-            T* dg = t ? d1 : d0;
-            float x[Cs];                                               // every index below is a compile-time constant:
-            float mx = -INFINITY, xl = 0.f;                            // the array stays in registers
-#pragma unroll
-            for (int c0 = 0; c0 < Cs; c0 += 8) {
-                typename Vec8<T>::type v = load8<T>(lg + p * Cs + c0);
-#pragma unroll
-                for (int j = 0; j < 8; ++j) {
-                    x[c0 + j] = (float)v[j];
-                    if (c0 + j < C) mx = fmaxf(mx, x[c0 + j]);
-                    xl = (c0 + j == lab) ? x[c0 + j] : xl;
-                }
-            }
-            float se = 0.f;
-#pragma unroll
-            for (int c = 0; c < Cs; ++c) se += c < C ? __expf(x[c] - mx) : 0.f;
-            const float lse = mx + __logf(se);
-            if (on) local += w * (lse - xl);
-#pragma unroll
-            for (int c0 = 0; c0 < Cs; c0 += 8) {
-                typename Vec8<T>::type o;
-#pragma unroll
-                for (int j = 0; j < 8; ++j) {
-                    const int c = c0 + j;
-                    float g = 0.f;
-                    if (on && c < C) g = w * (__expf(x[c] - lse) - (c == lab ? 1.f : 0.f));
-                    o[j] = (T)g;
-                }
-                store8<T>(dg + p * Cs + c0, o);
-            }
-        }
-    }
-    for (int o = 32; o > 0; o >>= 1) local += __shfl_down(local, o, 64);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = local;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        float s = 0.f;
-        for (int i = 0; i < kThreads / 64; ++i) s += red[i];
-        ws[blockIdx.x] = s;
-    }
-}
-
-// 256 threads, fixed association order (thread t adds elements t, t+256, ...; lanes, then waves, combine in index
-// order) -> reproducible.  SET overwrites out[0], otherwise out[0] += sum.
-template <bool SET>
-__global__ __launch_bounds__(256) void ordered_sum_kernel_t(const float* __restrict__ partials, int n, float* __restrict__ out) {
-    __shared__ float red[4];
-    float s = 0.f;
-    for (int i = threadIdx.x; i < n; i += 256) s += partials[i];
-    for (int o = 32; o > 0; o >>= 1) s += __shfl_down(s, o, 64);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        const float t = (red[0] + red[1]) + (red[2] + red[3]);
-        if (SET) out[0] = t; else out[0] += t;
-    }
-}
-
-// =============================================================================================
-// UNetLoss for a (ragged) batch of documents (model/training/cost.py:35-65): plain CE over every pixel of a document, class 0
-// counted, 0.5 * final + 0.5 * auxiliary, optional class weights; every head has its own label map
-// =============================================================================================
-constexpr int kHistMaxC = 256;
-// Class histogram of the labelled pixels of a document: grid K x B, a document's pixels shared out over its K workgroups, one LDS
-// histogram per wavefront (LDS atomics only), partial[(b * K + k) * C + c] is WRITTEN.  The consumer adds the K rows: exact in any order.
-__global__ __launch_bounds__(256) void label_hist_kernel(const int64_t* __restrict__ labels, const int32_t* __restrict__ extent,
-                                                         int32_t* __restrict__ partial, int H, int W, int C, int K) {
-    __shared__ int hist[4][kHistMaxC];
-    const int b = blockIdx.y, k = blockIdx.x, wv = threadIdx.x >> 6;
-    for (int i = threadIdx.x; i < 4 * kHistMaxC; i += 256) (&hist[0][0])[i] = 0;
-    __syncthreads();
-    const int hw = H * W;                                            // B * H * W < 2^31 (checked by the host)
-    const int eh = extent ? min(max(extent[2 * b], 0), H) : H, ew = extent ? min(max(extent[2 * b + 1], 0), W) : W;
-    const int chunk = (hw + K - 1) / K;
-    const int lo = k * chunk, hi = min(lo + chunk, hw);
-    const int64_t* base = labels + (int64_t)b * hw;
-    for (int i = lo + (int)threadIdx.x; i < hi; i += 256) {
-        const int64_t lab = base[i];
-        if (lab >= 0 && lab < C && pos_in_extent(i, W, eh, ew)) atomicAdd(&hist[wv][(int)lab], 1);
-    }
-    __syncthreads();
-    for (int c = threadIdx.x; c < C; c += 256)
-        partial[((int64_t)b * K + k) * C + c] = (hist[0][c] + hist[1][c]) + (hist[2][c] + hist[3][c]);
-}
-
-// inv[t * B + b] = 1 / (B * D_b(head t)), 0 for a document without weight: D_b is the extent's area, or with class weights
-// sum_c cw[c] * hist_t[b][c], the classes added in index order (hist_t = hist + t * B * K * C, its K rows added first)
-__device__ __forceinline__ void unet_ce_denominators(float* inv, const int32_t* __restrict__ extent, const float* __restrict__ cw,
-                                                     const int32_t* __restrict__ hist, int NL, int B, int H, int W, int C, int K) {
-    for (int i = threadIdx.x; i < NL * B; i += blockDim.x) {
-        const int t = i / B, b = i - t * B;
-        float d;
-        if (cw) {
-            const int32_t* h = hist + ((int64_t)t * B + b) * K * C;
-            d = 0.f;
-            for (int c = 0; c < C; ++c) {
-                int n = 0;
-                for (int k = 0; k < K; ++k) n += h[k * C + c];
-                d += cw[c] * (float)n;
-            }
-        } else {
-            const int eh = extent ? min(max(extent[2 * b], 0), H) : H, ew = extent ? min(max(extent[2 * b + 1], 0), W) : W;
-            d = (float)eh * (float)ew;
-        }
-        inv[i] = d > 0.f ? 1.f / ((float)B * d) : 0.f;
-    }
-    __syncthreads();
-}
-
-// the block's two sums -> ws[blockIdx.x] (final), ws[gridDim.x + blockIdx.x] (auxiliary)
-__device__ __forceinline__ void unet_ce_block_sums(float l0, float l1, float* red, float* __restrict__ ws) {
-    for (int o = 32; o > 0; o >>= 1) { l0 += __shfl_down(l0, o, 64); l1 += __shfl_down(l1, o, 64); }
-    if ((threadIdx.x & 63) == 0) { red[threadIdx.x >> 6] = l0; red[kThreads / 64 + (threadIdx.x >> 6)] = l1; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        float s0 = 0.f, s1 = 0.f;
-        for (int i = 0; i < kThreads / 64; ++i) { s0 += red[i]; s1 += red[kThreads / 64 + i]; }
-        ws[blockIdx.x] = s0;
-        ws[gridDim.x + blockIdx.x] = s1;
-    }
-}
-
-// A pixel's softmax statistics, shared by the training kernels (unet_ce_*) and the forward-only ones (unet_eval_*).
-// Register form: the pixel's Cs = 8 * CS8 stored values -> x[] (every index a compile-time constant), xl = x[lab] (0 when lab is
-// not a channel), returns the log-sum-exp over the C real classes.
-template <typename T, int CS8>
-__device__ __forceinline__ float unet_pixel_lse(const T* __restrict__ px, int C, int lab, float (&x)[CS8 * 8], float& xl) {
-    constexpr int Cs = CS8 * 8;
-    float mx = -INFINITY;
-    xl = 0.f;
-#pragma unroll
-    for (int c0 = 0; c0 < Cs; c0 += 8) {
-        typename Vec8<T>::type v = load8<T>(px + c0);
-#pragma unroll
-        for (int jj = 0; jj < 8; ++jj) {
-            x[c0 + jj] = (float)v[jj];
-            if (c0 + jj < C) mx = fmaxf(mx, x[c0 + jj]);
-            xl = (c0 + jj == lab) ? x[c0 + jj] : xl;
-        }
-    }
-    float se = 0.f;
-#pragma unroll
-    for (int c = 0; c < Cs; ++c) se += c < C ? __expf(x[c] - mx) : 0.f;
-    return mx + __logf(se);
-}
-
-// Cache-read form (any class count): the pixel's C values are read twice, nothing is kept.
-template <typename T>
-__device__ __forceinline__ float unet_pixel_lse_wide(const T* __restrict__ l, int C) {
-    float mx = -INFINITY;
-    for (int c = 0; c < C; ++c) mx = fmaxf(mx, (float)l[c]);
-    float se = 0.f;
-    for (int c = 0; c < C; ++c) se += __expf((float)l[c] - mx);
-    return mx + __logf(se);
-}
-
-// Both heads in one launch, the logits of a pixel in registers (Cs = 8 * CS8 <= 32: every index is a compile-time constant).
-// A thread's weight of head t at pixel p of document b: hw_t * cw[lab] / (B * D_b(t)) inside the extent with lab in [0, C), else 0;
-// the loss partials carry the weight WITHOUT hw_t (loss3[1], loss3[2] are the heads' own losses).
-template <typename T, int NL, int CS8>
-__global__ void unet_ce_kernel(const T* __restrict__ l0, const T* __restrict__ l1, const int64_t* __restrict__ lab0,
-                               const int64_t* __restrict__ lab1, const int32_t* __restrict__ extent, const float* __restrict__ cw,
-                               const int32_t* __restrict__ hist, int K, T* __restrict__ d0, T* __restrict__ d1,
-                               float* __restrict__ ws, int B, int H, int W, int C) {
-    constexpr int Cs = CS8 * 8;
-    __shared__ float red[2 * kThreads / 64];
-    __shared__ float inv[2 * kCeMaxB];
-    unet_ce_denominators(inv, extent, cw, hist, NL, B, H, W, C, K);
-    const float hwt = NL == 2 ? 0.5f : 1.f;
-    const int hw = H * W;
-    float local[2] = {0.f, 0.f};
-    const int64_t total = (int64_t)B * hw;
-    for (int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; p < total; p += (int64_t)gridDim.x * blockDim.x) {
-        const int b = (int)((unsigned)p / (unsigned)hw);               // total < 2^31 (checked by the host)
-        const int j = (int)p - b * hw;
-        const bool in = extent ? pos_in_extent(j, W, extent[2 * b], extent[2 * b + 1]) : true;
-#pragma unroll
-        for (int t = 0; t < NL; ++t) {
-            const T* lg = t ? l1 : l0;
-            T* dg = t ? d1 : d0;
-            const int64_t lab64 = (t ? lab1 : lab0)[p];
-            const bool on = in && lab64 >= 0 && lab64 < C;
-            const int lab = on ? (int)lab64 : -1;
-            const float w = on ? inv[t * B + b] * (cw ? cw[lab] : 1.f) : 0.f;
-            float x[Cs];
-            float xl;
-            const float lse = unet_pixel_lse<T, CS8>(lg + p * Cs, C, lab, x, xl);
-            if (on && w != 0.f) local[t] += w * (lse - xl);
-            const float wg = hwt * w;
-#pragma unroll
-            for (int c0 = 0; c0 < Cs; c0 += 8) {
-                typename Vec8<T>::type o;
-#pragma unroll
-                for (int jj = 0; jj < 8; ++jj) {
-                    const int c = c0 + jj;
-                    float g = 0.f;
-                    if (on && w != 0.f && c < C) g = wg * (__expf(x[c] - lse) - (c == lab ? 1.f : 0.f));
-                    o[jj] = (T)g;
-                }
-                store8<T>(dg + p * Cs + c0, o);
-            }
-        }
-    }
-    unet_ce_block_sums(local[0], local[1], red, ws);
-}
-
-// Any class count (Cs > 32): the logits of a pixel are read three times from the cache.  Same arithmetic and summation order.
-template <typename T>
-__global__ void unet_ce_wide_kernel(const T* __restrict__ l0, const T* __restrict__ l1, const int64_t* __restrict__ lab0,
-                                    const int64_t* __restrict__ lab1, const int32_t* __restrict__ extent, const float* __restrict__ cw,
-                                    const int32_t* __restrict__ hist, int K, T* __restrict__ d0, T* __restrict__ d1,
-                                    float* __restrict__ ws, int B, int H, int W, int C, int Cs) {
-    __shared__ float red[2 * kThreads / 64];
-    __shared__ float inv[2 * kCeMaxB];
-    const int NL = l1 ? 2 : 1;
-    unet_ce_denominators(inv, extent, cw, hist, NL, B, H, W, C, K);
-    const float hwt = NL == 2 ? 0.5f : 1.f;
-    const int hw = H * W;
-    float local[2] = {0.f, 0.f};
-    const int64_t total = (int64_t)B * hw;
-    for (int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; p < total; p += (int64_t)gridDim.x * blockDim.x) {
-        const int b = (int)((unsigned)p / (unsigned)hw);
-        const int j = (int)p - b * hw;
-        const bool in = extent ? pos_in_extent(j, W, extent[2 * b], extent[2 * b + 1]) : true;
-        for (int t = 0; t < NL; ++t) {
-            const T* l = (t ? l1 : l0) + p * Cs;
-            T* dg = (t ? d1 : d0) + p * Cs;
-            const int64_t lab64 = (t ? lab1 : lab0)[p];
-            const bool on = in && lab64 >= 0 && lab64 < C;
-            const int lab = on ? (int)lab64 : -1;
-            const float w = on ? inv[t * B + b] * (cw ? cw[lab] : 1.f) : 0.f;
-            const float lse = unet_pixel_lse_wide(l, C);
-            const bool act = on && w != 0.f;
-            if (act) local[t] += w * (lse - (float)l[lab]);
-            const float wg = hwt * w;
-            for (int c = 0; c < Cs; ++c) {
-                float g = 0.f;
-                if (act && c < C) g = wg * (__expf((float)l[c] - lse) - (c == lab ? 1.f : 0.f));
-                dg[c] = (T)g;
-            }
-        }
-    }
-    unet_ce_block_sums(local[0], local[1], red, ws);
-}
-
-// the follow-up: the block partials of each head added in ordered_sum_kernel_t's order -> loss3 = (total, final, auxiliary), written
-__global__ __launch_bounds__(256) void unet_ce_finish_kernel(const float* __restrict__ ws, int n, int two, float* __restrict__ loss3) {
-    __shared__ float red[8];
-    float s0 = 0.f, s1 = 0.f;
-    for (int i = threadIdx.x; i < n; i += 256) { s0 += ws[i]; s1 += ws[n + i]; }
-    for (int o = 32; o > 0; o >>= 1) { s0 += __shfl_down(s0, o, 64); s1 += __shfl_down(s1, o, 64); }
-    if ((threadIdx.x & 63) == 0) { red[threadIdx.x >> 6] = s0; red[4 + (threadIdx.x >> 6)] = s1; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        const float f = (red[0] + red[1]) + (red[2] + red[3]);
-        const float a = two ? (red[4] + red[5]) + (red[6] + red[7]) : 0.f;
-        loss3[0] = two ? 0.5f * f + 0.5f * a : f;
-        loss3[1] = f;
-        loss3[2] = a;
-    }
-}
-
-// =============================================================================================
-// UNetLoss and the reference's accuracy, forward only and per document (validation: model/training/trainer.py's epoch print,
-// cost.py:44-48 `non_zero_mask`).  Grid K x B as label_hist_kernel: workgroup k of document b takes rows [k * rpk, (k + 1) * rpk) of
-// the document's extent, rpk = ceil(h_b / K), and WRITES one partial row; nothing outside the extent is read.
-// =============================================================================================
-struct UnetEvalRow { float num[2], den[2]; int32_t cnt[2][2]; };    // per head: sum cw * nll, sum cw; (labelled, correct)
-
-// strictly greater: the first maximum wins; a NaN counts as the maximum, as in torch.argmax
-__device__ __forceinline__ void first_max(float v, int c, float& bv, int& best) {
-    if (v > bv || (v != v && bv == bv)) { bv = v; best = c; }
-}
-
-// one pixel of one head into the thread's sums.  lse / xl: the pixel's log-sum-exp and its logit at the label; pred: its first maximum
-__device__ __forceinline__ void unet_eval_add(int lab, bool on, float lse, float xl, int pred, const float* __restrict__ cw,
-                                              float& num, float& den, int& labelled, int& correct) {
-    if (!on) return;
-    const float w = cw ? cw[lab] : 1.f;
-    den += w;
-    if (w != 0.f) num += w * (lse - xl);
-    if (lab >= 1) { labelled += 1; correct += pred == lab; }
-}
-
-// the workgroup's sums -> its row: lanes, then the four waves in index order (reproducible)
-__device__ __forceinline__ void unet_eval_block_row(float (&num)[2], float (&den)[2], int (&cnt)[2][2], UnetEvalRow* __restrict__ row) {
-    __shared__ float redf[4][4];
-    __shared__ int redi[4][4];
-    float f[4] = {num[0], num[1], den[0], den[1]};
-    int n[4] = {cnt[0][0], cnt[0][1], cnt[1][0], cnt[1][1]};
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-        for (int o = 32; o > 0; o >>= 1) { f[i] += __shfl_down(f[i], o, 64); n[i] += __shfl_down(n[i], o, 64); }
-    if ((threadIdx.x & 63) == 0) {
-#pragma unroll
-        for (int i = 0; i < 4; ++i) { redf[threadIdx.x >> 6][i] = f[i]; redi[threadIdx.x >> 6][i] = n[i]; }
-    }
-    __syncthreads();
-    if (threadIdx.x < 4) {
-        const int i = threadIdx.x;
-        const float fs = (redf[0][i] + redf[1][i]) + (redf[2][i] + redf[3][i]);
-        const int ns = (redi[0][i] + redi[1][i]) + (redi[2][i] + redi[3][i]);
-        (i < 2 ? row->num : row->den)[i & 1] = fs;
-        row->cnt[i >> 1][i & 1] = ns;
-    }
-}
-
-// the slab of workgroup k: pixel i of it -> canvas offset of the pixel inside document b, false past the slab's end
-struct UnetEvalSlab {
-    int r0, n, ew;
-    __device__ __forceinline__ UnetEvalSlab(const int32_t* __restrict__ extent, int b, int k, int K, int H, int W) {
-        const int eh = extent ? min(max(extent[2 * b], 0), H) : H;
-        ew = extent ? min(max(extent[2 * b + 1], 0), W) : W;
-        const int rpk = (eh + K - 1) / K;
-        r0 = min(k * rpk, eh);
-        n = (min(r0 + rpk, eh) - r0) * ew;                            // <= H * W < 2^31 (checked by the host)
-    }
-    __device__ __forceinline__ int offset(int i, int W) const { const int y = i / ew; return (r0 + y) * W + (i - y * ew); }
-};
-
-template <typename T, int NL, int CS8>
-__global__ __launch_bounds__(256) void unet_eval_kernel(const T* __restrict__ l0, const T* __restrict__ l1,
-                                                        const int64_t* __restrict__ lab0, const int64_t* __restrict__ lab1,
-                                                        const int32_t* __restrict__ extent, const float* __restrict__ cw,
-                                                        UnetEvalRow* __restrict__ rows, int H, int W, int C) {
-    constexpr int Cs = CS8 * 8;
-    const int b = blockIdx.y, k = blockIdx.x, K = gridDim.x;
-    const UnetEvalSlab slab(extent, b, k, K, H, W);
-    const int64_t base = (int64_t)b * H * W;
-    float num[2] = {0.f, 0.f}, den[2] = {0.f, 0.f};
-    int cnt[2][2] = {{0, 0}, {0, 0}};
-    for (int i = threadIdx.x; i < slab.n; i += 256) {
-        const int64_t p = base + slab.offset(i, W);
-#pragma unroll
-        for (int t = 0; t < NL; ++t) {
-            const int64_t lab64 = (t ? lab1 : lab0)[p];
-            const bool on = lab64 >= 0 && lab64 < C;
-            const int lab = on ? (int)lab64 : -1;
-            float x[Cs];
-            float xl;
-            const float lse = unet_pixel_lse<T, CS8>((t ? l1 : l0) + p * Cs, C, lab, x, xl);
-            int pred = 0;
-            float bv = -INFINITY;
-#pragma unroll
-            for (int c = 0; c < Cs; ++c)
-                if (c < C) first_max(x[c], c, bv, pred);
-            unet_eval_add(lab, on, lse, xl, pred, cw, num[t], den[t], cnt[t][0], cnt[t][1]);
-        }
-    }
-    unet_eval_block_row(num, den, cnt, rows + (int64_t)b * K + k);
-}
-
-// Any class count (Cs > 32): the logits of a pixel are read from the cache.  Same arithmetic and summation order.
-template <typename T>
-__global__ __launch_bounds__(256) void unet_eval_wide_kernel(const T* __restrict__ l0, const T* __restrict__ l1,
-                                                             const int64_t* __restrict__ lab0, const int64_t* __restrict__ lab1,
-                                                             const int32_t* __restrict__ extent, const float* __restrict__ cw,
-                                                             UnetEvalRow* __restrict__ rows, int H, int W, int C, int Cs) {
-    const int b = blockIdx.y, k = blockIdx.x, K = gridDim.x;
-    const int NL = l1 ? 2 : 1;
-    const UnetEvalSlab slab(extent, b, k, K, H, W);
-    const int64_t base = (int64_t)b * H * W;
-    float num[2] = {0.f, 0.f}, den[2] = {0.f, 0.f};
-    int cnt[2][2] = {{0, 0}, {0, 0}};
-    for (int i = threadIdx.x; i < slab.n; i += 256) {
-        const int64_t p = base + slab.offset(i, W);
-        for (int t = 0; t < NL; ++t) {
-            const T* l = (t ? l1 : l0) + p * Cs;
-            const int64_t lab64 = (t ? lab1 : lab0)[p];
-            const bool on = lab64 >= 0 && lab64 < C;
-            const int lab = on ? (int)lab64 : -1;
-            const float lse = unet_pixel_lse_wide(l, C);
-            int pred = 0;
-            float bv = -INFINITY;
-            for (int c = 0; c < C; ++c) first_max((float)l[c], c, bv, pred);
-            unet_eval_add(lab, on, lse, on ? (float)l[lab] : 0.f, pred, cw, num[t], den[t], cnt[t][0], cnt[t][1]);
-        }
-    }
-    unet_eval_block_row(num, den, cnt, rows + (int64_t)b * K + k);
-}
-
-// the follow-up: one thread per (document, head) adds the document's K rows in index order and divides; every output is written
-__global__ __launch_bounds__(256) void unet_eval_finish_kernel(const UnetEvalRow* __restrict__ rows, int B, int K,
-                                                               float* __restrict__ doc_loss, int32_t* __restrict__ doc_counts) {
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i >= 2 * B) return;
-    const int b = i >> 1, t = i & 1;
-    float n = 0.f, d = 0.f;
-    int labelled = 0, correct = 0;
-    for (int k = 0; k < K; ++k) {
-        const UnetEvalRow& r = rows[(int64_t)b * K + k];
-        n += r.num[t];
-        d += r.den[t];
-        labelled += r.cnt[t][0];
-        correct += r.cnt[t][1];
-    }
-    doc_loss[i] = d > 0.f ? n / d : 0.f;
-    doc_counts[2 * i] = labelled;
-    doc_counts[2 * i + 1] = correct;
-}
-
-// =============================================================================================
 // per-channel sums (bias gradient of the transposed conv)
 // =============================================================================================
 template <typename T>
@@ -1128,44 +520,6 @@ __global__ void adam_kernel(float* __restrict__ p, const float* __restrict__ g, 
     }
 }
 
-__global__ void softmax_nchw_kernel(const float* __restrict__ logits, float* __restrict__ pred, int B, int C, int64_t hw) {
-    const int64_t total = (int64_t)B * hw;
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
-        int64_t b = i / hw, p = i % hw;
-        const float* src = logits + b * C * hw + p;
-        float mx = -INFINITY;
-        for (int c = 0; c < C; ++c) mx = fmaxf(mx, src[c * hw]);
-        float se = 0.f;
-        for (int c = 0; c < C; ++c) se += __expf(src[c * hw] - mx);
-        float inv = 1.f / se;
-        for (int c = 0; c < C; ++c) pred[b * C * hw + c * hw + p] = __expf(src[c * hw] - mx) * inv;
-    }
-}
-
-// softmax + first-maximum index over the C real channels of NHWC logits, any C <= 255.  Operation for operation
-// msau_head_softmax() of msau_common.h (max, sum and product in channel order, __expf), which the conv epilogue
-// (MSAU_CONV_HEAD) uses for C <= 16: the two produce identical bits.
-template <typename T>
-__global__ void softmax_argmax_nhwc_kernel(const T* __restrict__ logits, float* __restrict__ probs,
-                                           uint8_t* __restrict__ amax, int64_t npix, int C, int Cs) {
-    for (int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; p < npix; p += (int64_t)gridDim.x * blockDim.x) {
-        const T* l = logits + p * Cs;
-        float mx = -INFINITY;
-        for (int c = 0; c < C; ++c) mx = fmaxf(mx, (float)l[c]);
-        float se = 0.f;
-        for (int c = 0; c < C; ++c) se += __expf((float)l[c] - mx);
-        const float inv = 1.f / se;
-        int best = 0;
-        float bp = -1.f;
-        for (int c = 0; c < C; ++c) {
-            const float pr = __expf((float)l[c] - mx) * inv;
-            probs[p * C + c] = pr;
-            if (pr > bp) { bp = pr; best = c; }
-        }
-        amax[p] = (uint8_t)best;
-    }
-}
-
 template <typename T>
 __global__ void onehot_ids_kernel(const int32_t* __restrict__ ids, T* __restrict__ grid, int64_t npix, int C, int Cs) {
     const int cgs = Cs >> 3;
@@ -1202,59 +556,7 @@ __global__ void onehot_ids_ext_kernel(const int32_t* __restrict__ ids, T* __rest
     }
 }
 
-// Evaluation counts (the per-epoch accuracy / classification report of train_chargrid_funsd_msau.py): for every pixel whose
-// label is in [1, C) (and, with `extent`, that lies inside its sample's extent) pred = the first maximum of the C stored logits
-// (torch's argmax of the fp32 export, ties included), 0 -> zero_as when zero_as >= 0, and counts[label * C + pred] += 1.
-// A workgroup histograms into LDS (uint32 bins) and adds each non-empty bin to the int64 matrix with one global atomic:
-// integer sums, so the result does not depend on arrival order.
-constexpr int kConfusionMaxC = 64;
-
-template <typename T>
-__global__ __launch_bounds__(256) void eval_confusion_kernel(const T* __restrict__ logits, const int64_t* __restrict__ labels,
-                                                             unsigned long long* __restrict__ counts, int64_t npix, int H, int W,
-                                                             int C, int Cs, int zero_as, const int32_t* __restrict__ extent) {
-    __shared__ uint32_t hist[kConfusionMaxC * kConfusionMaxC];
-    const int bins = C * C;
-    for (int i = threadIdx.x; i < bins; i += blockDim.x) hist[i] = 0u;
-    __syncthreads();
-    const int64_t hw = (int64_t)H * W;
-    for (int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; p < npix; p += (int64_t)gridDim.x * blockDim.x) {
-        const int64_t lab = labels[p];
-        if (lab < 1 || lab >= C) continue;
-        if (extent) {
-            const int b = (int)(p / hw);
-            const int64_t r = p - (int64_t)b * hw;
-            const int y = (int)(r / W), x = (int)(r - (int64_t)y * W);
-            if (y >= extent[2 * b] || x >= extent[2 * b + 1]) continue;
-        }
-        const T* l = logits + p * Cs;
-        int best = 0;
-        float bv = -INFINITY;
-        for (int c0 = 0; c0 < C; c0 += 8) {
-            const typename Vec8<T>::type v8 = load8<T>(l + c0);
-#pragma unroll
-            for (int j = 0; j < 8; ++j) {
-                if (c0 + j < C) first_max((float)v8[j], c0 + j, bv, best);
-            }
-        }
-        if (best == 0 && zero_as >= 0) best = zero_as;
-        atomicAdd(&hist[(int)lab * C + best], 1u);
-    }
-    __syncthreads();
-    for (int i = threadIdx.x; i < bins; i += blockDim.x) {
-        const uint32_t n = hist[i];
-        if (n) atomicAdd(counts + i, (unsigned long long)n);
-    }
-}
-
 }  // namespace
-
-#define DISPATCH_T(dtype, CALL_F32, CALL_BF16)                          \
-    do {                                                                \
-        if ((dtype) == MSAU_F32) { CALL_F32; }                          \
-        else if ((dtype) == MSAU_BF16) { CALL_BF16; }                   \
-        else return msau_set_error(MSAU_ERR_ARG, "bad dtype %d", (int)(dtype)); \
-    } while (0)
 
 extern "C" int msau_nchw_to_nhwc(void* stream, int dtype, const float* src, void* dst, int B, int C, int Cs, int H, int W) {
     MSAU_CHECK_ARG(src && dst && B > 0 && C > 0 && Cs >= C && Cs % 8 == 0 && H > 0 && W > 0, "nchw_to_nhwc: bad args");
@@ -1404,197 +706,6 @@ extern "C" int msau_extent_copy(void* stream, const void* src, void* dst, int B,
     return 0;
 }
 
-extern "C" int msau_label_counts(void* stream, const int64_t* labels, int32_t* counts, int B, int64_t hw) {
-    MSAU_CHECK_ARG(labels && counts && B > 0 && hw > 0, "label_counts: bad args");
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    hipLaunchKernelGGL(label_count_kernel, dim3(B), dim3(1024), 0, s, labels, counts, hw);
-    MSAU_CHECK_LAUNCH("label_count");
-    return 0;
-}
-
-extern "C" int msau_label_counts_split(void* stream, const int64_t* labels, int32_t* partial, int B, int64_t hw, int K) {
-    MSAU_CHECK_ARG(labels && partial && B > 0 && B <= 65535 && hw > 0 && K >= 1 && K <= 64, "label_counts_split: bad args");
-    hipLaunchKernelGGL(label_count_split_kernel, dim3(K, B), dim3(256), 0, static_cast<hipStream_t>(stream), labels, partial, hw, K);
-    MSAU_CHECK_LAUNCH("label_count_split");
-    return 0;
-}
-
-static int ce_blocks(int64_t npix) { return grid_for(npix, 1024); }
-extern "C" int64_t msau_ce_ws_floats(int64_t npix_total) { return 2 * ce_blocks(npix_total); }      // (second half: msau_softmax_ce_weighted's weight sums)
-
-extern "C" int msau_masked_ce(void* stream, int dtype, const void* logits, const int64_t* labels, const int32_t* counts,
-                              void* dlogits, float* loss_accum, float* ws, int B, int64_t hw, int C, int Cs, float scale) {
-    MSAU_CHECK_ARG(logits && labels && counts && dlogits && loss_accum && ws, "masked_ce: null pointer");
-    MSAU_CHECK_ARG(B > 0 && hw > 0 && C > 0 && C <= Cs && Cs % 8 == 0 && Cs <= 256, "masked_ce: bad dims (n_class <= 256)");
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    int nb = ce_blocks((int64_t)B * hw);
-    if (Cs > 16) {
-        DISPATCH_T(dtype,
-                   hipLaunchKernelGGL((masked_ce_wide_kernel<float, false>), dim3(nb), dim3(kThreads), 0, s, static_cast<const float*>(logits), labels, counts, static_cast<float*>(dlogits), ws, B, hw, C, Cs, scale),
-                   hipLaunchKernelGGL((masked_ce_wide_kernel<bf16_t, false>), dim3(nb), dim3(kThreads), 0, s, static_cast<const bf16_t*>(logits), labels, counts, static_cast<bf16_t*>(dlogits), ws, B, hw, C, Cs, scale));
-        MSAU_CHECK_LAUNCH("masked_ce_wide");
-        hipLaunchKernelGGL(ordered_sum_kernel_t<false>, dim3(1), dim3(256), 0, s, ws, nb, loss_accum);
-        MSAU_CHECK_LAUNCH("ordered_sum");
-        return 0;
-    }
-    DISPATCH_T(dtype,
-               hipLaunchKernelGGL((masked_ce_kernel<float, false>), dim3(nb), dim3(kThreads), 0, s, static_cast<const float*>(logits), labels, counts, static_cast<float*>(dlogits), ws, B, hw, C, Cs, scale),
-               hipLaunchKernelGGL((masked_ce_kernel<bf16_t, false>), dim3(nb), dim3(kThreads), 0, s, static_cast<const bf16_t*>(logits), labels, counts, static_cast<bf16_t*>(dlogits), ws, B, hw, C, Cs, scale));
-    MSAU_CHECK_LAUNCH("masked_ce");
-    hipLaunchKernelGGL(ordered_sum_kernel_t<false>, dim3(1), dim3(256), 0, s, ws, nb, loss_accum);
-    MSAU_CHECK_LAUNCH("ordered_sum");
-    return 0;
-}
-
-static int ce_multi_blocks(int64_t npix) { return grid_for(npix, 2048); }
-extern "C" int64_t msau_ce_multi_ws_floats(int64_t npix_total) { return ce_multi_blocks(npix_total) + 1; }
-
-extern "C" int msau_masked_ce_multi(void* stream, int dtype, const void* logits, const void* aux, const int64_t* labels,
-                                    const int32_t* counts, void* dlogits, void* daux, float* loss, float* ws,
-                                    int B, int64_t hw, int C, int Cs, float scale, int counts_k) {
-    MSAU_CHECK_ARG(logits && labels && counts && dlogits && loss && ws && (!aux || daux), "masked_ce_multi: null pointer");
-    MSAU_CHECK_ARG(counts_k == 1 || (counts_k > 1 && counts_k <= 64 && B <= kCeMaxB), "masked_ce_multi: counts_k > 1 needs B <= 1024");
-    MSAU_CHECK_ARG(B > 0 && hw > 0 && C > 0 && C <= Cs && Cs % 8 == 0 && Cs <= 16 && (int64_t)B * hw < (1ll << 31),
-                   "masked_ce_multi: bad dims (n_class <= 16, B*H*W < 2^31)");
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    const int nb = ce_multi_blocks((int64_t)B * hw);
-#define CE_MULTI(T, NL, C8) hipLaunchKernelGGL((masked_ce_multi_kernel<T, NL, C8>), dim3(nb), dim3(kThreads), 0, s, static_cast<const T*>(logits), \
-        static_cast<const T*>(aux), labels, counts, static_cast<T*>(dlogits), static_cast<T*>(daux), ws, loss, B, (int)hw, C, scale, counts_k)
-    if (aux && Cs == 8) { DISPATCH_T(dtype, CE_MULTI(float, 2, 1), CE_MULTI(bf16_t, 2, 1)); }
-    else if (aux) { DISPATCH_T(dtype, CE_MULTI(float, 2, 2), CE_MULTI(bf16_t, 2, 2)); }
-    else if (Cs == 8) { DISPATCH_T(dtype, CE_MULTI(float, 1, 1), CE_MULTI(bf16_t, 1, 1)); }
-    else { DISPATCH_T(dtype, CE_MULTI(float, 1, 2), CE_MULTI(bf16_t, 1, 2)); }
-#undef CE_MULTI
-    MSAU_CHECK_LAUNCH("masked_ce_multi");
-    hipLaunchKernelGGL(ordered_sum_kernel_t<true>, dim3(1), dim3(256), 0, s, ws, nb, loss);
-    MSAU_CHECK_LAUNCH("ordered_sum_set");
-    return 0;
-}
-
-extern "C" int msau_label_hist(void* stream, const int64_t* labels, const int32_t* extent, int32_t* partial, int B, int H, int W,
-                               int C, int K) {
-    MSAU_CHECK_ARG(labels && partial, "label_hist: null pointer");
-    MSAU_CHECK_ARG(B > 0 && B <= 65535 && H > 0 && W > 0 && (int64_t)B * H * W < (1ll << 31) && C > 0 && C <= kHistMaxC && K >= 1 && K <= 64,
-                   "label_hist: bad args (B*H*W < 2^31, n_class <= %d, 1 <= K <= 64)", kHistMaxC);
-    hipLaunchKernelGGL(label_hist_kernel, dim3(K, B), dim3(256), 0, static_cast<hipStream_t>(stream), labels, extent, partial, H, W, C, K);
-    MSAU_CHECK_LAUNCH("label_hist");
-    return 0;
-}
-
-static int unet_ce_blocks(int64_t npix) { return grid_for(npix, 2048); }
-extern "C" int64_t msau_unet_ce_ws_floats(int64_t npix_total) { return 2 * unet_ce_blocks(npix_total); }
-
-extern "C" int msau_unet_ce(void* stream, int dtype, const void* logits, const void* aux, const int64_t* labels,
-                            const int64_t* aux_labels, const int32_t* extent, const float* class_w, const int32_t* hist_partial, int K,
-                            void* dlogits, void* daux, float* loss3, float* ws, int B, int H, int W, int C, int Cs) {
-    MSAU_CHECK_ARG(logits && labels && dlogits && loss3 && ws && (!aux || (daux && aux_labels)), "unet_ce: null pointer");
-    MSAU_CHECK_ARG(!class_w || (hist_partial && K >= 1 && K <= 64), "unet_ce: class weights need the label histograms (1 <= K <= 64)");
-    MSAU_CHECK_ARG(B > 0 && B <= kCeMaxB && H > 0 && W > 0 && (int64_t)B * H * W < (1ll << 31) && C > 0 && C <= Cs && Cs % 8 == 0 && Cs <= 256,
-                   "unet_ce: bad dims (B <= %d, B*H*W < 2^31, n_class <= 256)", kCeMaxB);
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    const int nb = unet_ce_blocks((int64_t)B * H * W);
-#define UNET_CE(T, NL, C8) hipLaunchKernelGGL((unet_ce_kernel<T, NL, C8>), dim3(nb), dim3(kThreads), 0, s, static_cast<const T*>(logits), \
-        static_cast<const T*>(aux), labels, aux_labels, extent, class_w, hist_partial, K, static_cast<T*>(dlogits), static_cast<T*>(daux), \
-        ws, B, H, W, C)
-#define UNET_CE_NL(C8) do { if (aux) { DISPATCH_T(dtype, UNET_CE(float, 2, C8), UNET_CE(bf16_t, 2, C8)); } \
-                            else { DISPATCH_T(dtype, UNET_CE(float, 1, C8), UNET_CE(bf16_t, 1, C8)); } } while (0)
-#define UNET_CE_WIDE(T) hipLaunchKernelGGL((unet_ce_wide_kernel<T>), dim3(nb), dim3(kThreads), 0, s, static_cast<const T*>(logits), \
-        static_cast<const T*>(aux), labels, aux_labels, extent, class_w, hist_partial, K, static_cast<T*>(dlogits), static_cast<T*>(daux), \
-        ws, B, H, W, C, Cs)
-    if (Cs == 8) UNET_CE_NL(1);
-    else if (Cs == 16) UNET_CE_NL(2);
-    else if (Cs == 24) UNET_CE_NL(3);
-    else if (Cs == 32) UNET_CE_NL(4);
-    else { DISPATCH_T(dtype, UNET_CE_WIDE(float), UNET_CE_WIDE(bf16_t)); }
-#undef UNET_CE_WIDE
-#undef UNET_CE_NL
-#undef UNET_CE
-    MSAU_CHECK_LAUNCH("unet_ce");
-    hipLaunchKernelGGL(unet_ce_finish_kernel, dim3(1), dim3(256), 0, s, ws, nb, aux ? 1 : 0, loss3);
-    MSAU_CHECK_LAUNCH("unet_ce_finish");
-    return 0;
-}
-
-extern "C" int64_t msau_unet_eval_ws_bytes(int B, int K) {
-    return B > 0 && K > 0 ? (int64_t)B * K * (int64_t)sizeof(UnetEvalRow) : 0;
-}
-
-extern "C" int msau_unet_eval(void* stream, int dtype, const void* logits, const void* aux, const int64_t* labels,
-                              const int64_t* aux_labels, const int32_t* extent, const float* class_w, int K, float* doc_loss,
-                              int32_t* doc_counts, void* ws, int B, int H, int W, int C, int Cs) {
-    MSAU_CHECK_ARG(logits && labels && doc_loss && doc_counts && ws && (!aux || aux_labels), "unet_eval: null pointer");
-    MSAU_CHECK_ARG(K >= 1 && K <= 256, "unet_eval: K = %d workgroups per document (1 <= K <= 256)", K);
-    MSAU_CHECK_ARG(B > 0 && B <= kCeMaxB && H > 0 && W > 0 && (int64_t)B * H * W < (1ll << 31) && C > 0 && C <= Cs && Cs % 8 == 0 && Cs <= 256,
-                   "unet_eval: bad dims (B <= %d, B*H*W < 2^31, n_class <= 256)", kCeMaxB);
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    UnetEvalRow* rows = static_cast<UnetEvalRow*>(ws);
-    const dim3 grid(K, B);
-#define UNET_EVAL(T, NL, C8) hipLaunchKernelGGL((unet_eval_kernel<T, NL, C8>), grid, dim3(256), 0, s, static_cast<const T*>(logits), \
-        static_cast<const T*>(aux), labels, aux_labels, extent, class_w, rows, H, W, C)
-#define UNET_EVAL_NL(C8) do { if (aux) { DISPATCH_T(dtype, UNET_EVAL(float, 2, C8), UNET_EVAL(bf16_t, 2, C8)); } \
-                              else { DISPATCH_T(dtype, UNET_EVAL(float, 1, C8), UNET_EVAL(bf16_t, 1, C8)); } } while (0)
-#define UNET_EVAL_WIDE(T) hipLaunchKernelGGL((unet_eval_wide_kernel<T>), grid, dim3(256), 0, s, static_cast<const T*>(logits), \
-        static_cast<const T*>(aux), labels, aux_labels, extent, class_w, rows, H, W, C, Cs)
-    if (Cs == 8) UNET_EVAL_NL(1);
-    else if (Cs == 16) UNET_EVAL_NL(2);
-    else if (Cs == 24) UNET_EVAL_NL(3);
-    else if (Cs == 32) UNET_EVAL_NL(4);
-    else { DISPATCH_T(dtype, UNET_EVAL_WIDE(float), UNET_EVAL_WIDE(bf16_t)); }
-#undef UNET_EVAL_WIDE
-#undef UNET_EVAL_NL
-#undef UNET_EVAL
-    MSAU_CHECK_LAUNCH("unet_eval");
-    hipLaunchKernelGGL(unet_eval_finish_kernel, dim3((2 * B + 255) / 256), dim3(256), 0, s, rows, B, K, doc_loss, doc_counts);
-    MSAU_CHECK_LAUNCH("unet_eval_finish");
-    return 0;
-}
-
-extern "C" int msau_softmax_ce(void* stream, int dtype, const void* logits, const int64_t* labels, void* dlogits,
-                               float* loss_accum, float* ws, int B, int64_t hw, int C, int Cs, float scale) {
-    MSAU_CHECK_ARG(logits && labels && dlogits && loss_accum && ws, "softmax_ce: null pointer");
-    MSAU_CHECK_ARG(B > 0 && hw > 0 && C > 0 && C <= Cs && Cs % 8 == 0 && Cs <= 256, "softmax_ce: bad dims (n_class <= 256)");
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    int nb = ce_blocks((int64_t)B * hw);
-    if (Cs > 16) {
-        DISPATCH_T(dtype,
-                   hipLaunchKernelGGL((masked_ce_wide_kernel<float, true>), dim3(nb), dim3(kThreads), 0, s, static_cast<const float*>(logits), labels, nullptr, static_cast<float*>(dlogits), ws, B, hw, C, Cs, scale),
-                   hipLaunchKernelGGL((masked_ce_wide_kernel<bf16_t, true>), dim3(nb), dim3(kThreads), 0, s, static_cast<const bf16_t*>(logits), labels, nullptr, static_cast<bf16_t*>(dlogits), ws, B, hw, C, Cs, scale));
-        MSAU_CHECK_LAUNCH("softmax_ce_wide");
-        hipLaunchKernelGGL(ordered_sum_kernel_t<false>, dim3(1), dim3(256), 0, s, ws, nb, loss_accum);
-        MSAU_CHECK_LAUNCH("ordered_sum");
-        return 0;
-    }
-    DISPATCH_T(dtype,
-               hipLaunchKernelGGL((masked_ce_kernel<float, true>), dim3(nb), dim3(kThreads), 0, s, static_cast<const float*>(logits), labels, nullptr, static_cast<float*>(dlogits), ws, B, hw, C, Cs, scale),
-               hipLaunchKernelGGL((masked_ce_kernel<bf16_t, true>), dim3(nb), dim3(kThreads), 0, s, static_cast<const bf16_t*>(logits), labels, nullptr, static_cast<bf16_t*>(dlogits), ws, B, hw, C, Cs, scale));
-    MSAU_CHECK_LAUNCH("softmax_ce");
-    hipLaunchKernelGGL(ordered_sum_kernel_t<false>, dim3(1), dim3(256), 0, s, ws, nb, loss_accum);
-    MSAU_CHECK_LAUNCH("ordered_sum");
-    return 0;
-}
-
-extern "C" int msau_softmax_ce_weighted(void* stream, int dtype, const void* logits, const int64_t* labels, const float* class_w,
-                                        void* dlogits, float* sums, float* ws, int B, int64_t hw, int C, int Cs) {
-    MSAU_CHECK_ARG(logits && labels && class_w && dlogits && sums && ws, "softmax_ce_weighted: null pointer");
-    MSAU_CHECK_ARG(B > 0 && hw > 0 && C > 0 && C <= Cs && Cs % 8 == 0 && Cs <= 256, "softmax_ce_weighted: bad dims (n_class <= 256)");
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    const int nb = ce_blocks((int64_t)B * hw);
-    if (Cs > 16) {
-        DISPATCH_T(dtype,
-                   hipLaunchKernelGGL((masked_ce_wide_kernel<float, true>), dim3(nb), dim3(kThreads), 0, s, static_cast<const float*>(logits), labels, nullptr, static_cast<float*>(dlogits), ws, B, hw, C, Cs, 1.f, class_w),
-                   hipLaunchKernelGGL((masked_ce_wide_kernel<bf16_t, true>), dim3(nb), dim3(kThreads), 0, s, static_cast<const bf16_t*>(logits), labels, nullptr, static_cast<bf16_t*>(dlogits), ws, B, hw, C, Cs, 1.f, class_w));
-    } else {
-        DISPATCH_T(dtype,
-                   hipLaunchKernelGGL((masked_ce_kernel<float, true>), dim3(nb), dim3(kThreads), 0, s, static_cast<const float*>(logits), labels, nullptr, static_cast<float*>(dlogits), ws, B, hw, C, Cs, 1.f, class_w),
-                   hipLaunchKernelGGL((masked_ce_kernel<bf16_t, true>), dim3(nb), dim3(kThreads), 0, s, static_cast<const bf16_t*>(logits), labels, nullptr, static_cast<bf16_t*>(dlogits), ws, B, hw, C, Cs, 1.f, class_w));
-    }
-    MSAU_CHECK_LAUNCH("softmax_ce_weighted");
-    hipLaunchKernelGGL(ordered_sum_kernel_t<false>, dim3(1), dim3(256), 0, s, ws, nb, sums);
-    hipLaunchKernelGGL(ordered_sum_kernel_t<false>, dim3(1), dim3(256), 0, s, ws + nb, nb, sums + 1);
-    MSAU_CHECK_LAUNCH("ordered_sum");
-    return 0;
-}
-
 extern "C" int msau_channel_sum(void* stream, int dtype, const void* g, int64_t npix, int Cs, float* partials, int nblk) {
     MSAU_CHECK_ARG(g && partials && npix > 0 && Cs % 8 == 0 && Cs <= 256 && nblk > 0, "channel_sum: bad args");
     MSAU_CHECK_ARG(kThreads % (Cs / 8) == 0, "channel_sum: Cs/8 must divide %d", kThreads);
@@ -1717,25 +828,6 @@ extern "C" int msau_fill_zero(void* stream, void* p, int64_t bytes) {
     return 0;
 }
 
-extern "C" int msau_softmax_channels_nchw(void* stream, const float* logits, float* pred, int B, int C, int64_t hw) {
-    MSAU_CHECK_ARG(logits && pred && B > 0 && C > 0 && hw > 0, "softmax: bad args");
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    hipLaunchKernelGGL(softmax_nchw_kernel, dim3(grid_for((int64_t)B * hw)), dim3(kThreads), 0, s, logits, pred, B, C, hw);
-    MSAU_CHECK_LAUNCH("softmax_nchw");
-    return 0;
-}
-
-extern "C" int msau_softmax_argmax_nhwc(void* stream, int dtype, const void* logits, float* probs, uint8_t* argmax,
-                                        int64_t npix, int C, int Cs) {
-    MSAU_CHECK_ARG(logits && probs && argmax && npix > 0 && C > 0 && C <= 255 && C <= Cs, "softmax_argmax: bad args");
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    DISPATCH_T(dtype,
-               hipLaunchKernelGGL(softmax_argmax_nhwc_kernel<float>, dim3(grid_for(npix)), dim3(kThreads), 0, s, static_cast<const float*>(logits), probs, argmax, npix, C, Cs),
-               hipLaunchKernelGGL(softmax_argmax_nhwc_kernel<bf16_t>, dim3(grid_for(npix)), dim3(kThreads), 0, s, static_cast<const bf16_t*>(logits), probs, argmax, npix, C, Cs));
-    MSAU_CHECK_LAUNCH("softmax_argmax_nhwc");
-    return 0;
-}
-
 extern "C" int msau_onehot_ids(void* stream, int dtype, const int32_t* ids, void* grid, int64_t npix, int C, int Cs) {
     MSAU_CHECK_ARG(ids && grid && npix > 0 && C > 0 && Cs % 8 == 0 && C <= Cs, "onehot_ids: bad args");
     hipStream_t s = static_cast<hipStream_t>(stream);
@@ -1755,24 +847,5 @@ extern "C" int msau_onehot_ids_ext(void* stream, int dtype, const int32_t* ids, 
                hipLaunchKernelGGL(onehot_ids_ext_kernel<float>, dim3(grid_for(npix * (Cs / 8))), dim3(kThreads), 0, s, ids, static_cast<float*>(grid), npix, H, W, C, Cs, extent),
                hipLaunchKernelGGL(onehot_ids_ext_kernel<bf16_t>, dim3(grid_for(npix * (Cs / 8))), dim3(kThreads), 0, s, ids, static_cast<bf16_t*>(grid), npix, H, W, C, Cs, extent));
     MSAU_CHECK_LAUNCH("onehot_ids_ext");
-    return 0;
-}
-
-extern "C" int msau_eval_confusion(void* stream, int dtype, const void* logits, const int64_t* labels, int64_t* counts, int B, int H,
-                                   int W, int C, int Cs, int zero_as, const int32_t* extent) {
-    MSAU_CHECK_ARG(logits && labels && counts && B > 0 && H > 0 && W > 0, "eval_confusion: bad args");
-    MSAU_CHECK_ARG(C >= 1 && C <= kConfusionMaxC && C <= Cs && Cs % 8 == 0, "eval_confusion: C = %d (Cs = %d) must satisfy 1 <= C <= %d, C <= Cs, Cs %% 8 == 0",
-                   C, Cs, kConfusionMaxC);
-    MSAU_CHECK_ARG(zero_as < C, "eval_confusion: zero_as = %d is not a class of %d", zero_as, C);
-    const int64_t npix = (int64_t)B * H * W;
-    MSAU_CHECK_ARG(npix < (1ll << 40), "eval_confusion: too many pixels");
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    // at least 4 pixels per lane and at most 512 workgroups: the LDS histogram's clear and flush stay small beside the pixels
-    const dim3 grid(grid_for(cdiv64(npix, 4), 512));
-    unsigned long long* out = reinterpret_cast<unsigned long long*>(counts);
-    DISPATCH_T(dtype,
-               hipLaunchKernelGGL(eval_confusion_kernel<float>, grid, dim3(kThreads), 0, s, static_cast<const float*>(logits), labels, out, npix, H, W, C, Cs, zero_as, extent),
-               hipLaunchKernelGGL(eval_confusion_kernel<bf16_t>, grid, dim3(kThreads), 0, s, static_cast<const bf16_t*>(logits), labels, out, npix, H, W, C, Cs, zero_as, extent));
-    MSAU_CHECK_LAUNCH("eval_confusion");
     return 0;
 }

@@ -62,6 +62,23 @@ static inline int64_t cdiv64(int64_t a, int64_t b) { return (a + b - 1) / b; }
 static inline int cdiv(int a, int b) { return (a + b - 1) / b; }
 static inline int roundup(int a, int b) { return cdiv(a, b) * b; }
 
+// ---- the grid-stride kernels of elementwise.hip and loss.hip: workgroup size, capped grid, storage-type dispatch ----
+constexpr int kThreads = 256;
+
+static inline int grid_for(int64_t work, int cap = 256 * 16) {
+    int64_t b = cdiv64(work, kThreads);
+    if (b > cap) b = cap;
+    if (b < 1) b = 1;
+    return (int)b;
+}
+
+#define DISPATCH_T(dtype, CALL_F32, CALL_BF16)                          \
+    do {                                                                \
+        if ((dtype) == MSAU_F32) { CALL_F32; }                          \
+        else if ((dtype) == MSAU_BF16) { CALL_BF16; }                   \
+        else return msau_set_error(MSAU_ERR_ARG, "bad dtype %d", (int)(dtype)); \
+    } while (0)
+
 // ---- LDS strides of the MFMA-operand images (conv_lean / conv_pair / conv_chunked) ---------------------------------
 // A fragment read is one ds_read_b128 per lane, lane = (lr = lane & 15: pixel / weight row, lg = lane >> 4: 8-channel k-group).
 // The LDS serves a ds_read_b128 in four groups of 16 lanes that are NOT lr = 0..15 of one lg: they are

@@ -5,7 +5,6 @@
 
 namespace {
 
-constexpr int kThreads = 256;
 constexpr int kMaxBlocks = 512;          // the update's grid-stride grid (as adam_kernel's)
 constexpr int kMaxSqBlocks = 128;        // partial sums of squares: two per lane of the wave that adds them up again
 

@@ -316,10 +316,10 @@ def test_golden_recipe_reproduces_committed_fixtures(tmp_path):
 def test_isa_of_the_built_kernels_has_no_cross_half_packed_fp32_adds(tmp_path):
     """Round 2 traced run-to-run deviations of the level-0 LRN backward (beside the side stream) to its chains of
     v_pk_add_f32 with op_sel -- packed fp32 instructions that take an operand from the OTHER half of a register pair -- and
-    builds elementwise.hip without packed-fp32 instructions (msau_amd/build.py; the listing of the
+    builds elementwise.hip (and loss.hip, once part of it) without packed-fp32 instructions (msau_amd/build.py; the listing of the
     deviating build: profiles/r03_lrn_bwd_c8_packed_isa.s).  This test reads the ISA of the library as built and keeps the
     pattern from coming back unnoticed:
-      * elementwise.o has NO packed-fp32 instruction at all (the flag is in force);
+      * elementwise.o and loss.o have NO packed-fp32 instruction at all (the flag is in force);
       * the translation units of the bf16 train path that run on the main stream beside the weight gradients (conv, conv_lean,
         conv_pair, conv_rows, wgrad_lean, conv_wgrad, attention_mfma, pack, raster, ownerconv, boxconv) have NO packed-fp32
         instruction with op_sel / op_sel_hi;
@@ -346,6 +346,7 @@ def test_isa_of_the_built_kernels_has_no_cross_half_packed_fp32_adds(tmp_path):
         lines = [ln for ln in dis.splitlines() if pk.search(ln)]
         counts[name] = (len(lines), sum(1 for ln in lines if "op_sel" in ln))
     assert counts["elementwise"] == (0, 0), counts["elementwise"]
+    assert counts["loss"] == (0, 0), counts["loss"]
     clean = ("conv", "conv_lean", "conv_pair", "conv_rows", "wgrad_lean", "conv_wgrad", "attention_mfma", "pointwise", "pack", "raster", "ownerconv", "boxconv")
     assert all(counts[n][1] == 0 for n in clean), {n: counts[n] for n in clean}
     assert counts["conv_lean"][0] > 0                 # the check does see packed instructions where they are

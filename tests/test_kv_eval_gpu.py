@@ -107,6 +107,35 @@ def test_kernel_equals_host_statement(C, dtype):
                         assert float(loss[:, 1].abs().max()) == 0.0 and int(counts[:, 1].abs().max()) == 0, (what, K)
 
 
+@pytest.mark.parametrize("dtype", ["fp32", "bf16"])
+def test_register_form_equals_cache_form(dtype):
+    """the same 17 real logits stored at Cs = 24 (a pixel in registers) and zero-padded to Cs = 40 (a pixel read from the cache): the
+    two forms share one statement of a pixel's log-sum-exp (loss.hip) -- the same loss bits and the same counts"""
+    C = 17
+    dt = L.F32 if dtype == "fp32" else L.BF16
+    for ragged in (True, False):
+        logits, labs, ext, cw = _inputs(C, dtype, ragged)
+        lab_d = [x.to(DEV) for x in labs]
+        ext_d = torch.tensor(ext, dtype=torch.int32, device=DEV) if ragged else None
+        got = {}
+        for Cs in (24, 40):
+            lg_d = []
+            for x in logits:
+                p = torch.zeros(B, H, W, Cs, dtype=x.dtype)
+                p[..., :C] = x[..., :C]
+                lg_d.append(p.to(DEV))
+            for with_aux in (True, False):
+                for weighted in (False, True):
+                    for K in (1, 4, 7):
+                        got[(Cs, with_aux, weighted, K)] = _run_eval(dt, lg_d, lab_d, ext_d, cw.to(DEV) if weighted else None, with_aux, K, C, Cs)
+        for (Cs, *what), (loss, counts) in got.items():
+            if Cs != 24:
+                continue
+            wide_loss, wide_counts = got[(40, *what)]
+            assert torch.equal(loss, wide_loss) and torch.equal(counts, wide_counts), (ragged, what, loss.tolist(), wide_loss.tolist())
+            assert bool(torch.isfinite(loss).all()) and float(loss[0, 0]) > 0 and int(counts[0, 0, 0]) > 0, (ragged, what)
+
+
 def test_kernel_refuses_bad_arguments():
     x = torch.zeros(64, device=DEV)
     lab = torch.zeros(8, dtype=torch.int64, device=DEV)

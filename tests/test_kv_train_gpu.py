@@ -230,6 +230,52 @@ def test_unet_ce_wide_form_matches_register_form():
     assert abs(float(loss3[0]) - 0.5 * (float(loss3[1]) + float(loss3[2]))) <= 1e-6 * float(loss3[0])
 
 
+@pytest.mark.parametrize("dtype", ["fp32", "bf16"])
+def test_unet_ce_register_form_equals_cache_form(dtype):
+    """the same 17 real logits stored at Cs = 24 (a pixel in registers) and zero-padded to Cs = 40 (a pixel read from the cache): the
+    two forms share one statement of the log-sum-exp and of the gradient (loss.hip) -- the same three loss bits, the same gradient
+    bits in the real channels, zeros in the padded ones; ragged and dense, with and without class weights and the second head"""
+    B, H, W, C, K = 3, 37, 29, 17, 4
+    td, dt = (torch.float32, L.F32) if dtype == "fp32" else (torch.bfloat16, L.BF16)
+    g = torch.Generator().manual_seed(17)
+    real = [(torch.randn(B, H, W, C, generator=g) * 2).to(td) for _ in range(2)]
+    lab_d = [_labels(B, H, W, C, 40 + t, True).to(DEV) for t in range(2)]
+    cw = torch.rand(C, generator=g) + 0.5
+    cw[2] = 0.0
+    cw = cw.to(DEV)
+    ws = torch.zeros(int(L.load().msau_unet_ce_ws_floats(B * H * W)), device=DEV)
+    got = {}
+    for Cs in (24, 40):
+        lg_d = []
+        for x in real:
+            p = torch.zeros(B, H, W, Cs, dtype=td)
+            p[..., :C] = x
+            lg_d.append(p.to(DEV))
+        for ragged in (False, True):
+            ext = torch.tensor(EXTENTS, dtype=torch.int32, device=DEV) if ragged else None
+            hist = torch.zeros((2, B, K, C), dtype=torch.int32, device=DEV)
+            for t in range(2):
+                L.call("msau_label_hist", _stream(), lab_d[t].data_ptr(), ext.data_ptr() if ragged else None, hist[t].data_ptr(), B, H, W, C, K)
+            for with_aux in (True, False):
+                for weighted in (False, True):
+                    loss3 = torch.full((3,), 123.0, device=DEV)
+                    d = [torch.full_like(x, 9.0) for x in lg_d]
+                    L.call("msau_unet_ce", _stream(), dt, lg_d[0].data_ptr(), lg_d[1].data_ptr() if with_aux else None, lab_d[0].data_ptr(),
+                           lab_d[1].data_ptr() if with_aux else None, ext.data_ptr() if ragged else None,
+                           cw.data_ptr() if weighted else None, hist.data_ptr() if weighted else None, K, d[0].data_ptr(),
+                           d[1].data_ptr() if with_aux else None, loss3.data_ptr(), ws.data_ptr(), B, H, W, C, Cs)
+                    torch.cuda.synchronize()
+                    got[(Cs, ragged, with_aux, weighted)] = (loss3.cpu(), [x.cpu() for x in d[:2 if with_aux else 1]])
+    for (Cs, *what), (loss3, d) in got.items():
+        if Cs != 24:
+            continue
+        wide_loss3, wide_d = got[(40, *what)]
+        assert torch.equal(loss3, wide_loss3) and bool(torch.isfinite(loss3).all()) and float(loss3[0]) > 0, (what, loss3, wide_loss3)
+        for a, b in zip(d, wide_d):
+            assert torch.equal(a[..., :C], b[..., :C]) and float(a[..., :C].float().abs().max()) > 0, what
+            assert float(a[..., C:].float().abs().max()) == 0.0 and float(b[..., C:].float().abs().max()) == 0.0, what
+
+
 # ---- 9 - 15: the step -----------------------------------------------------------------------------------------------------------------
 def _model(dtype="fp32", **extra):
     return MSAUWrapper(CH, NCLS, dict(KW, dtype=dtype, **extra)).to(DEV)

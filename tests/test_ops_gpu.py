@@ -410,6 +410,48 @@ def test_masked_ce_more_than_16_classes(dtype):
     assert float(d[..., C:].float().abs().max()) == 0.0
 
 
+@pytest.mark.parametrize("dtype", ["fp32", "bf16"])
+def test_masked_ce_register_form_equals_cache_form(dtype):
+    """the same 13 real logits stored at Cs = 16 (a pixel in registers) and zero-padded to Cs = 24 (a pixel read from the cache):
+    both forms state a pixel's log-sum-exp and gradient once (loss.hip), so the masked, the plain and the weighted CE give the same
+    loss bits and the same gradient bits in the real channels, and zeros in the padded ones"""
+    torch.manual_seed(13)
+    B, H, W, C = 3, 37, 29, 13
+    td = torch.float32 if dtype == "fp32" else torch.bfloat16
+    dt = L.F32 if dtype == "fp32" else L.BF16
+    real = (torch.randn(B, H, W, C) * 2).to(td)
+    labels = torch.randint(-1, C + 1, (B, H, W), dtype=torch.int64)       # 0, -1 and C occur: not labelled
+    labels[1] = 0                                                         # a sample without labelled pixels
+    labels = labels.cuda()
+    cw = torch.rand(C) + 0.5
+    cw[2] = 0.0
+    cw = cw.cuda()
+    s = torch.cuda.current_stream().cuda_stream
+    counts = torch.zeros(B, dtype=torch.int32, device="cuda")
+    L.call("msau_label_counts", s, labels.data_ptr(), counts.data_ptr(), B, H * W)
+    ws = torch.zeros(int(L.load().msau_ce_ws_floats(B * H * W)), device="cuda")
+    got = {}
+    for Cs in (16, 24):
+        lg = torch.zeros(B, H, W, Cs, dtype=td)
+        lg[..., :C] = real
+        lg = lg.cuda()
+        d = [torch.full_like(lg, 9.0) for _ in range(3)]
+        loss, plain, sums = torch.zeros(1, device="cuda"), torch.zeros(1, device="cuda"), torch.zeros(2, device="cuda")
+        L.call("msau_masked_ce", s, dt, lg.data_ptr(), labels.data_ptr(), counts.data_ptr(), d[0].data_ptr(), loss.data_ptr(), ws.data_ptr(),
+               B, H * W, C, Cs, 1.0 / B)
+        L.call("msau_softmax_ce", s, dt, lg.data_ptr(), labels.data_ptr(), d[1].data_ptr(), plain.data_ptr(), ws.data_ptr(),
+               B, H * W, C, Cs, 1.0 / (B * H * W))
+        L.call("msau_softmax_ce_weighted", s, dt, lg.data_ptr(), labels.data_ptr(), cw.data_ptr(), d[2].data_ptr(), sums.data_ptr(),
+               ws.data_ptr(), B, H * W, C, Cs)
+        torch.cuda.synchronize()
+        got[Cs] = ([loss.cpu(), plain.cpu(), sums.cpu()], [x.cpu() for x in d])
+    for a, b in zip(got[16][0], got[24][0]):
+        assert torch.equal(a, b) and bool(torch.isfinite(a).all()) and float(a.abs().min()) > 0, (a, b)
+    for a, b in zip(got[16][1], got[24][1]):
+        assert torch.equal(a[..., :C], b[..., :C]) and float(a[..., :C].float().abs().max()) > 0
+        assert float(a[..., C:].float().abs().max()) == 0.0 and float(b[..., C:].float().abs().max()) == 0.0
+
+
 @pytest.mark.parametrize("dtype", DT)
 @pytest.mark.parametrize("k,cin,cout", [(1, 192, 64), (3, 192, 64), (1, 136, 8)])
 def test_data_gradient_wider_than_128_channels(dtype, k, cin, cout):
