@@ -210,15 +210,15 @@ int msau_conv2d_launch_info(int dtype, const msau_conv_desc* d, int32_t* info8);
  *   mid = t                          ([B][H][W][C], zero outside the image: the second conv's SAME padding)
  *   y   = epilogue(W2 * mid + b2)    flags2 = MSAU_CONV_{MASK_A, ADD, ACCUM, RELU_OUT, MASK_B, POOL} exactly as msau_conv2d
  * w1 / w2 are the packed images msau_pack_params writes for a single-source 3x3 conv C -> C (forward or flipped
- * data-gradient image).  msau_conv_pair_applicable: 1 if an instance exists for the shape (C, enough tiles, LDS).
+ * data-gradient image).  msau_conv_pair_applicable: 1 if an instance takes the descriptor (shape, flags, the riders' operands).
  * ------------------------------------------------------------------------------------------ */
 enum { MSAU_PAIR_RELU_IN = 1, MSAU_PAIR_RELU_MID = 2, MSAU_PAIR_MASK_MID = 4,
        MSAU_PAIR_LRN_BWD = 16,  /* backward flag set only: x0 (whose gradient this launch produces) is the output of
                                    LocalResponseNorm(size = C) applied to lrn_a (layers.py:145,161-162), and nothing else
                                    contributes to its gradient: the launch runs the LRN backward on the storage-rounded result in
                                    its epilogue and writes lrn_da (gradient w.r.t. lrn_a) INSTEAD of y -- the msau_lrn_bwd launch,
-                                   its read of dy and the write of dy disappear.  Row-streaming 8-channel instance only
-                                   (msau_conv_pair_applicable says so); lrn_alpha_over_n / lrn_beta / lrn_k as in msau_conv_desc */
+                                   its read of dy and the write of dy disappear.  The row-streaming backward instances have it, at 8 and
+                                   (unless MSAU_LRN_BWD16=0) at 16 channels (msau_conv_pair_applicable says so); lrn_alpha_over_n / lrn_beta / lrn_k as in msau_conv_desc */
        MSAU_PAIR_WGRAD1 = 32,   /* backward flag set only: the weight gradient of the block's FIRST conv in the same launch -- its g
                                    operand is the intermediate gradient this launch produces, so that tensor is neither written
                                    (`mid` is left untouched) nor re-read; wg1_x = the block's forward input x0 (ReLU applied on load),
@@ -287,17 +287,20 @@ typedef struct {
 int msau_conv_pair_applicable(int dtype, const msau_conv_pair_desc* d);
 int msau_conv_pair(void* stream, int dtype, const msau_conv_pair_desc* d);
 /* bytes of ONE mask plane (bits_mid or bits_a) for this descriptor's shape.  The planes are private between the forward and
- * the backward launch of one residual block and their layout follows the instance that takes the shape: a byte per
- * (pixel, 8-channel group) for the tile kernels (conv_pair.hip), 32 bytes of lane ballots per (row, 30-column strip) for the
- * row-streaming 8-channel bf16 kernel (conv_rows.hip).  Allocate with this, never from the layout comment above. */
+ * the backward launch of one residual block and their layout follows the instance that takes the descriptor once it has planes
+ * (it need not have them yet): a byte per (pixel, 8-channel group) for the tile kernels (conv_pair.hip) and for a shape no
+ * instance takes, 32 bytes of lane ballots per (row, strip) for the row-streaming bf16 kernels (conv_rows.hip; strips of 30
+ * columns at 8 channels, of 14 at 16).  Allocate with this, never from the layout comment above. */
 int64_t msau_conv_pair_bits_bytes(int dtype, const msau_conv_pair_desc* d);
 /* number of slabs an MSAU_PAIR_WGRAD1 launch of this descriptor writes (= its workgroups); 0 if no instance takes the flag */
 int msau_conv_pair_wgrad_slabs(int dtype, const msau_conv_pair_desc* d);
 /* which instance takes the descriptor: 0 none, 1 a tile kernel (conv_pair.hip), 2 a row-streaming kernel (conv_rows.hip) */
 int msau_conv_pair_instance(int dtype, const msau_conv_pair_desc* d);
-/* The library reads its MSAU_* environment switches once.  msau_reload_env() makes the row-streaming kernel's switches
- * (MSAU_PAIR_ROWS, MSAU_CONV_ROWS, MSAU_WGRAD_ROWS, MSAU_ROWS_SH, MSAU_ROWS_WAVES, MSAU_ROWS_MIN_TASKS, MSAU_ROWS_MAXC) be read again on the next call: for tests and A/B
- * tools that change them inside one process. */
+/* The library reads its MSAU_* environment switches once.  msau_reload_env() makes the switches of the row-streaming kernels
+ * (conv_rows.hip: MSAU_PAIR_ROWS, MSAU_CONV_ROWS, MSAU_WGRAD_ROWS, MSAU_WGRAD_ROWS4, MSAU_DOUT_ROWS, MSAU_DECONV_ROWS, MSAU_ROWS_SH,
+ * MSAU_ROWS_SH16, MSAU_ROWS_WAVES, MSAU_ROWS_MIN_TASKS, MSAU_ROWS_MAXC, MSAU_PAIR_WGRAD, MSAU_PAIR_COUPLE, MSAU_COUPLE_WGRAD,
+ * MSAU_LRN_BWD16) be read again on the next call: for tests and A/B tools that change them inside one process.  Every other
+ * switch of the library, those of conv_pair.hip among them, is read once per process. */
 void msau_reload_env(void);
 
 /* ------------------------------------------------------------------------------------------

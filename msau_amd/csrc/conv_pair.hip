@@ -34,6 +34,7 @@ struct PairArgs {
     unsigned long long* stamps;                  // diagnostic build only: 16 words per workgroup (s_memrealtime at phase ends)
 #endif
 };
+constexpr int kPairOH = 14;                       // output rows of a tile; its columns: 16 TW - 2 (PairCfg)
 #ifdef MSAU_STAMPS
 #define PSTAMP(i) do { if (a.stamps && threadIdx.x == 0) a.stamps[(size_t)blockIdx.x * 16 + (i)] = __builtin_amdgcn_s_memrealtime(); } while (0)
 #else
@@ -669,12 +670,8 @@ template <typename T, int C8, int TW, bool BWD, bool POOL = false, bool BITS = f
 int launch_pair(hipStream_t s, const PairArgs& a0) {
     using Cfg = PairCfg<T, C8, TW, BWD, RPW>;
     static_assert(Cfg::LDS + Cfg::LDS_PAD + 256 <= MSAU_LDS_LIMIT, "conv_pair instance does not fit the LDS");
+    static_assert(Cfg::OH == kPairOH && Cfg::OW == 16 * TW - 2, "the tile counts of pair_tile_case");
     PairArgs a = a0;
-    a.tiles_x = cdiv(a.d.W, Cfg::OW);
-    a.tiles_y = cdiv(a.d.H, Cfg::OH);
-    a.ntiles = a.d.B * a.tiles_x * a.tiles_y;
-    a.mag_tx = (unsigned)((0x100000000ull + a.tiles_x - 1) / a.tiles_x);
-    a.mag_ty = (unsigned)((0x100000000ull + a.tiles_y - 1) / a.tiles_y);
     static bool attr_set = false;
     if (!attr_set && Cfg::LDS + Cfg::LDS_PAD > 60 * 1024) {
         hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_pair_kernel<T, C8, TW, BWD, POOL, BITS, RPW, CPL, DCP>),
@@ -722,31 +719,44 @@ int pair_tw(int dtype, const msau_conv_pair_desc* d) {
     return d->W >= 120 ? 2 : 1;
 }
 
-// the two flag combinations the kernel is compiled for: the residual block's forward, and its data gradient
 #ifndef MSAU_PAIR_RPW32
 #define MSAU_PAIR_RPW32 2                      // rows per wave of the 32-channel bf16 instances (PairCfg)
 #endif
-constexpr int kFwd1 = MSAU_PAIR_RELU_IN | MSAU_PAIR_RELU_MID, kFwd2 = MSAU_CONV_ADD | MSAU_CONV_RELU_OUT;
-constexpr int kBwd1 = MSAU_PAIR_MASK_MID, kBwd2 = MSAU_CONV_MASK_A | MSAU_CONV_ADD;
 
-}  // namespace
+// ---- the instances.  The number of an instance packs its template arguments; PAIR_TABLE is the one list of those that exist, read
+// by pair_instance() both as the query "does this instance exist for T" (pair_tile_case) and as the launch switch (pair_tile_launch),
+// like LEAN_TABLE in conv_lean.hip.  That an instance fits the LDS is launch_pair's static_assert.
+constexpr int pair_id(int c8, int tw, bool bwd, bool pool, bool bits, int rpw, int cpl, bool dcp) {
+    return c8 | tw << 3 | rpw << 5 | cpl << 8 | bwd << 10 | pool << 11 | bits << 12 | dcp << 13;
+}
+// X(F32, C8, TW, BWD, POOL, BITS, RPW, CPL, DCP); F32: also in fp32 (LDS).  PAIR_BITS: the ReLU masks as tensors and as bit planes;
+// PAIR_GROUP: forward, forward with the pooled output, backward
+#define PAIR_BITS(X, F32, C8, TW, BWD, POOL, RPW, CPL, DCP) X(F32, C8, TW, BWD, POOL, false, RPW, CPL, DCP) X(F32, C8, TW, BWD, POOL, true, RPW, CPL, DCP)
+#define PAIR_GROUP(X, F32, C8, TW, RPW) PAIR_BITS(X, F32, C8, TW, false, false, RPW, 0, false) PAIR_BITS(X, F32, C8, TW, false, true, RPW, 0, false) \
+                                        PAIR_BITS(X, F32, C8, TW, true, false, RPW, 0, false)
+#define PAIR_TABLE(X)                                                                                                                  \
+    PAIR_GROUP(X, true, 1, 1, 4) PAIR_GROUP(X, true, 1, 2, 4) PAIR_GROUP(X, true, 2, 1, 4) PAIR_GROUP(X, false, 2, 2, 4)               \
+    /* 32 channels: also with the coupling conv in the forward (CPL 1; 2: and its pooled output) and its data gradients as the         \
+       backward's prologue (DCP) */                                                                                                    \
+    PAIR_GROUP(X, false, 4, 1, MSAU_PAIR_RPW32) PAIR_BITS(X, false, 4, 1, false, false, MSAU_PAIR_RPW32, 1, false)                     \
+    PAIR_BITS(X, false, 4, 1, false, false, MSAU_PAIR_RPW32, 2, false) PAIR_BITS(X, false, 4, 1, true, false, MSAU_PAIR_RPW32, 0, true)
 
-extern "C" int msau_conv_pair_applicable(int dtype, const msau_conv_pair_desc* d) {
-    if (!d || (dtype != MSAU_F32 && dtype != MSAU_BF16)) return 0;
-    static const int maxc = std::getenv("MSAU_PAIR_MAXC") ? atoi(std::getenv("MSAU_PAIR_MAXC")) : 32;   // measured: C = 32 (84x64 images) gains nothing, 4.03 vs 4.00 ms/step
-    // ... at batch 16; a launch of a few hundred pixels is launch-bound whatever it computes: there the 32-channel block fuses too
-    const bool tiny = (int64_t)d->B * d->H * d->W <= 16384;
-    if ((d->C != 8 && d->C != 16 && d->C != 32) || (d->C > maxc && !(tiny && d->C == 32))) return 0;
-    if (dtype == MSAU_F32 && d->C == 32) return 0;                 // two fp32 tiles + two weight sets exceed the LDS
-    if (d->B <= 0 || d->H <= 0 || d->W <= 0) return 0;
-    const int f1 = d->flags1 & ~(MSAU_PAIR_TILES | MSAU_PAIR_LRN_BWD | MSAU_PAIR_WGRAD1 | MSAU_PAIR_COUPLE | MSAU_PAIR_DCOUPLE);
-    const bool fwd = f1 == kFwd1 && (d->flags2 & ~MSAU_CONV_POOL) == kFwd2, bwd = f1 == kBwd1 && d->flags2 == kBwd2;
-    if (fwd && (d->flags2 & MSAU_CONV_POOL) && !d->pool_y) return 0;
-    if (!fwd && !bwd) return 0;
-    if (d->add != d->x) return 0;                                  // the ADD operand is read back from the input tile
-    if ((d->flags1 & MSAU_PAIR_DCOUPLE) && !bwd) return 0;
-    if ((d->flags1 & MSAU_PAIR_COUPLE) && !fwd) return 0;
-    if (msau_rowpair_takes(dtype, d)) return 1;                    // 8 channels, bf16: the row-streaming kernel (conv_rows.hip)
+// a == nullptr: 1 if instance `id` exists for T, else 0.  Otherwise: launch it (0, or an error -- never "not mine")
+template <typename T>
+int pair_instance(int id, hipStream_t s, const PairArgs* a) {
+    switch (id) {
+#define PAIR_ROW(F32, C8, TW, BWD, POOL, BITS, RPW, CPL, DCP)                                                             \
+        case pair_id(C8, TW, BWD, POOL, BITS, RPW, CPL, DCP):                                                             \
+            if constexpr (F32 || sizeof(T) == 2) return a ? launch_pair<T, C8, TW, BWD, POOL, BITS, RPW, CPL, DCP>(s, *a) : 1; \
+            break;
+        PAIR_TABLE(PAIR_ROW)
+#undef PAIR_ROW
+    }
+    return a ? msau_set_error(MSAU_ERR_ARG, "conv_pair: no instance %#x", id) : 0;
+}
+
+// The tile instance that runs `d` (see pair_id) and its tile counts into `r`, 0 = none.  `d` is behind pair_route's own checks.
+int pair_tile_case(int dtype, const msau_conv_pair_desc* d, PairRoute* r) {
     if (d->flags1 & (MSAU_PAIR_LRN_BWD | MSAU_PAIR_WGRAD1)) return 0;              // riders of the row-streaming instances only
     if (d->flags1 & MSAU_PAIR_DCOUPLE) {                                           // the coupling conv's data gradients as the backward's prologue
         static const bool dcp32 = !(std::getenv("MSAU_PAIR_DCOUPLE32") && std::getenv("MSAU_PAIR_DCOUPLE32")[0] == '0');
@@ -754,82 +764,90 @@ extern "C" int msau_conv_pair_applicable(int dtype, const msau_conv_pair_desc* d
         msau_conv_pack_geom g;                                                     // the image the prologue indexes: [64 rows][kchunk 32]
         if (msau_conv_pack_geometry(dtype, 32, 0, 64, 1, 1, 1, 1, 1, &g) != 0 || g.nchunks != 1 || g.kchunk != 32 || g.rows != 64) return 0;
     }
-    if (d->flags1 & MSAU_PAIR_COUPLE) {                                            // ... the coupling conv: also the 32-channel bf16 forward tile pair
+    if (d->flags1 & MSAU_PAIR_COUPLE) {                                            // ... the coupling conv (the table: 32 channels, bf16, no pooled y)
         static const bool cpl32 = !(std::getenv("MSAU_PAIR_COUPLE32") && std::getenv("MSAU_PAIR_COUPLE32")[0] == '0');
-        if (!(cpl32 && fwd && dtype == MSAU_BF16 && d->C == 32 && !(d->flags2 & MSAU_CONV_POOL) && d->cpl_prev && d->cpl_w && d->cpl_b && d->cpl_y))
-            return 0;
+        if (!(cpl32 && d->cpl_prev && d->cpl_w && d->cpl_b && d->cpl_y)) return 0;
     }
-    const int esz = dtype == MSAU_F32 ? 4 : 2;
-    if ((int64_t)d->H * d->W * d->C * esz >= (1ll << 31)) return 0;             // 32-bit lane offsets inside an image
-    const int tw = pair_tw(dtype, d);
-    const int64_t tiles = (int64_t)d->B * cdiv(d->H, 14) * cdiv(d->W, 16 * tw - 2);
+    if ((int64_t)d->H * d->W * d->C * (dtype == MSAU_F32 ? 4 : 2) >= (1ll << 31)) return 0;      // 32-bit lane offsets inside an image
+    const int tw = pair_tw(dtype, d), tiles_x = cdiv(d->W, 16 * tw - 2), tiles_y = cdiv(d->H, kPairOH);
+    const int64_t tiles = (int64_t)d->B * tiles_y * tiles_x;
     static const int min_tiles = std::getenv("MSAU_PAIR_MIN_TILES") ? atoi(std::getenv("MSAU_PAIR_MIN_TILES")) : 1;
     // (round 2 sent launches below 64 tiles to the one-conv kernels; at those sizes the step is launch-bound -- the batch-1
     //  document loop of the reference, tools/funsd_loop.py -- and one launch instead of two is what counts)
-    if (tiles < min_tiles || tiles >= (1 << 20)) return 0;
-    if (cdiv(d->H, 14) >= 4096 || cdiv(d->W, 16 * tw - 2) >= 4096) return 0;   // the tile decode (__umulhi) is exact below 2^12 tiles per axis
-    return 1;
+    if (tiles < min_tiles || tiles >= (1 << 20) || tiles_y >= 4096 || tiles_x >= 4096) return 0;       // the tile decode (__umulhi) is exact below 2^12 tiles per axis
+    const int id = pair_id(d->C / 8, tw, r->dir == PAIR_BWD, d->flags2 & MSAU_CONV_POOL, d->bits_mid && d->bits_a, d->C == 32 ? MSAU_PAIR_RPW32 : 4,
+                           d->flags1 & MSAU_PAIR_COUPLE ? (d->cpl_pool_y ? 2 : 1) : 0, d->flags1 & MSAU_PAIR_DCOUPLE);
+    if (!(dtype == MSAU_F32 ? pair_instance<float>(id, nullptr, nullptr) : pair_instance<bf16_t>(id, nullptr, nullptr))) return 0;
+    r->tw = tw, r->tiles_x = tiles_x, r->tiles_y = tiles_y;
+    return id;
 }
 
-// which instance msau_conv_pair launches for this descriptor: 0 none, 1 a tile kernel (conv_pair.hip), 2 a row-streaming kernel
-// (conv_rows.hip) -- for profiling / roofline labels, like msau_conv2d_launch_info
-extern "C" int msau_conv_pair_instance(int dtype, const msau_conv_pair_desc* d) {
-    if (!msau_conv_pair_applicable(dtype, d)) return 0;
-    return msau_rowpair_takes(dtype, d) ? 2 : 1;
-}
-
-extern "C" int msau_conv_pair_wgrad_slabs(int dtype, const msau_conv_pair_desc* d) {
-    if (!d || !(d->flags1 & MSAU_PAIR_WGRAD1) || !msau_conv_pair_applicable(dtype, d) || !msau_rowpair_takes(dtype, d)) return 0;
-    return msau_rowpair_workgroups(d);
-}
-
-// bytes of ONE ReLU-mask plane (bits_mid / bits_a) for this descriptor: the tile kernels keep a byte per (pixel, 8-channel
-// group), the row-streaming kernel 32 bytes of lane ballots per (row, 30-column strip)
-extern "C" int64_t msau_conv_pair_bits_bytes(int dtype, const msau_conv_pair_desc* d) {
-    if (!d || d->C <= 0 || d->B <= 0 || d->H <= 0 || d->W <= 0) return 0;
-    msau_conv_pair_desc probe = *d;                                // "would it take this shape once it has planes?"
-    uint8_t one = 0;
-    probe.bits_mid = probe.bits_a = &one;
-    if (msau_rowpair_takes(dtype, &probe)) return msau_rowpair_plane_bytes(d);
-    return (int64_t)d->B * d->H * d->W * (d->C / 8);
-}
-
-extern "C" int msau_conv_pair(void* stream, int dtype, const msau_conv_pair_desc* d) {
-    MSAU_CHECK_ARG(d && d->x && d->w1 && d->w2 && d->mid && (d->y || (d->flags1 & MSAU_PAIR_LRN_BWD)), "conv_pair: null pointer");
-    MSAU_CHECK_ARG(msau_conv_pair_applicable(dtype, d), "conv_pair: unsupported shape or flags (C %d, %dx%d, B %d, flags 0x%x / 0x%x; "
-                   "MSAU_CONV_ADD must name the input tensor)", d->C, d->H, d->W, d->B, d->flags1, d->flags2);
-    const bool bwd = (d->flags1 & ~(MSAU_PAIR_TILES | MSAU_PAIR_LRN_BWD | MSAU_PAIR_WGRAD1 | MSAU_PAIR_DCOUPLE)) == kBwd1;
-    MSAU_CHECK_ARG(!bwd || (d->mask_mid && d->mask_a) || (d->bits_mid && d->bits_a), "conv_pair: backward without mask_mid / mask_a (tensors or bit planes)");
-    MSAU_CHECK_ARG(!d->bits_mid == !d->bits_a, "conv_pair: bits_mid and bits_a come together");
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    if (msau_rowpair_takes(dtype, d)) return msau_rowpair_launch(s, d);
-    const int esz = dtype == MSAU_F32 ? 4 : 2;
+int pair_tile_launch(hipStream_t s, int dtype, const msau_conv_pair_desc* d, const PairRoute& r) {
     PairArgs a;
     a.d = *d;
 #ifdef MSAU_STAMPS
     a.stamps = std::getenv("MSAU_STAMP_PTR") ? reinterpret_cast<unsigned long long*>(strtoull(std::getenv("MSAU_STAMP_PTR"), nullptr, 0)) : nullptr;
 #endif
     a.kchunk = roundup(9 * d->C, 32);
-    a.px = d->C * esz;
-    a.row = d->W * a.px;
-    const int c8 = d->C / 8, tw = pair_tw(dtype, d);
-    const bool pool = !bwd && (d->flags2 & MSAU_CONV_POOL);
-    const bool bits = d->bits_mid && d->bits_a;
-#define PAIR_CASE(T, C8V, TWV, RPWV) if (c8 == C8V && tw == TWV) { \
-        if (bwd) return bits ? launch_pair<T, C8V, TWV, true, false, true, RPWV>(s, a) : launch_pair<T, C8V, TWV, true, false, false, RPWV>(s, a); \
-        if (pool) return bits ? launch_pair<T, C8V, TWV, false, true, true, RPWV>(s, a) : launch_pair<T, C8V, TWV, false, true, false, RPWV>(s, a); \
-        return bits ? launch_pair<T, C8V, TWV, false, false, true, RPWV>(s, a) : launch_pair<T, C8V, TWV, false, false, false, RPWV>(s, a); }
-    if (dtype == MSAU_BF16 && (d->flags1 & MSAU_PAIR_DCOUPLE))                     // (applicable: backward, 32 channels)
-        return bits ? launch_pair<bf16_t, 4, 1, true, false, true, MSAU_PAIR_RPW32, 0, true>(s, a) : launch_pair<bf16_t, 4, 1, true, false, false, MSAU_PAIR_RPW32, 0, true>(s, a);
-    if (dtype == MSAU_BF16 && (d->flags1 & MSAU_PAIR_COUPLE)) {                    // (applicable: forward, 32 channels, no pooled y)
-        if (d->cpl_pool_y) return bits ? launch_pair<bf16_t, 4, 1, false, false, true, MSAU_PAIR_RPW32, 2>(s, a) : launch_pair<bf16_t, 4, 1, false, false, false, MSAU_PAIR_RPW32, 2>(s, a);
-        return bits ? launch_pair<bf16_t, 4, 1, false, false, true, MSAU_PAIR_RPW32, 1>(s, a) : launch_pair<bf16_t, 4, 1, false, false, false, MSAU_PAIR_RPW32, 1>(s, a);
+    a.px = d->C * (dtype == MSAU_F32 ? 4 : 2); a.row = d->W * a.px;
+    a.tiles_x = r.tiles_x; a.tiles_y = r.tiles_y; a.ntiles = d->B * a.tiles_x * a.tiles_y;
+    a.mag_tx = (unsigned)((0x100000000ull + a.tiles_x - 1) / a.tiles_x);
+    a.mag_ty = (unsigned)((0x100000000ull + a.tiles_y - 1) / a.tiles_y);
+    return dtype == MSAU_F32 ? pair_instance<float>(r.inst, s, &a) : pair_instance<bf16_t>(r.inst, s, &a);
+}
+
+// The one place that knows which instance runs a descriptor and with what geometry: pure host arithmetic ("conv_pair
+// routing").  msau_conv_pair launches what it names, the four queries report it.  The row-streaming instances come first.
+PairRoute pair_route(int dtype, const msau_conv_pair_desc* d) {
+    PairRoute route{}, *r = &route;
+    if (!d || d->C <= 0 || d->B <= 0 || d->H <= 0 || d->W <= 0) return route;
+    r->plane_bytes = (int64_t)d->B * d->H * d->W * (d->C / 8);    // the tile kernels' planes: a byte per (pixel, 8-channel group)
+    static const int maxc = std::getenv("MSAU_PAIR_MAXC") ? atoi(std::getenv("MSAU_PAIR_MAXC")) : 32;   // measured: C = 32 (84x64 images) gains nothing, 4.03 vs 4.00 ms/step
+    // ... at batch 16; a launch of a few hundred pixels is launch-bound whatever it computes: there the 32-channel block fuses too
+    const bool tiny = (int64_t)d->B * d->H * d->W <= 16384;
+    if ((d->C != 8 && d->C != 16 && d->C != 32) || (d->C > maxc && !(tiny && d->C == 32))) return route;
+    if (dtype != MSAU_BF16 && (dtype != MSAU_F32 || d->C == 32)) return route;      // (two fp32 tiles + two weight sets of 32 channels exceed the LDS)
+    r->dir = msau_pair_direction(d);
+    // the pooled output needs its tensor; the ADD operand is read back from the input tile
+    if (!r->dir || ((d->flags2 & MSAU_CONV_POOL) && !d->pool_y) || d->add != d->x) return route;
+    if ((r->inst = msau_rowpair_case(dtype, d)) != 0) {
+        r->family = PAIR_ROWS;
+        msau_rowpair_split(d, r);
+        if (d->flags1 & MSAU_PAIR_WGRAD1) r->slabs = r->workgroups;           // one slab per workgroup
+    } else if ((r->inst = pair_tile_case(dtype, d, r)) != 0) {
+        r->family = PAIR_TILE;
     }
-    if (dtype == MSAU_BF16) {
-        PAIR_CASE(bf16_t, 1, 1, 4) PAIR_CASE(bf16_t, 1, 2, 4) PAIR_CASE(bf16_t, 2, 1, 4) PAIR_CASE(bf16_t, 2, 2, 4) PAIR_CASE(bf16_t, 4, 1, MSAU_PAIR_RPW32)
-    } else {
-        PAIR_CASE(float, 1, 1, 4) PAIR_CASE(float, 1, 2, 4) PAIR_CASE(float, 2, 1, 4)
-    }
-#undef PAIR_CASE
-    return msau_set_error(MSAU_ERR_ARG, "conv_pair: no instance for C %d tile width %d", d->C, tw);
+    return route;
+}
+
+}  // namespace
+
+// which instance msau_conv_pair launches for this descriptor: 0 none, 1 a tile kernel (conv_pair.hip), 2 a row-streaming kernel
+// (conv_rows.hip) -- for profiling / roofline labels, like msau_conv2d_launch_info
+extern "C" int msau_conv_pair_instance(int dtype, const msau_conv_pair_desc* d) { return pair_route(dtype, d).family; }
+extern "C" int msau_conv_pair_applicable(int dtype, const msau_conv_pair_desc* d) { return pair_route(dtype, d).family != PAIR_NONE; }
+extern "C" int msau_conv_pair_wgrad_slabs(int dtype, const msau_conv_pair_desc* d) { return pair_route(dtype, d).slabs; }
+
+// bytes of ONE ReLU-mask plane (bits_mid / bits_a) in the layout of the instance that takes the shape ONCE IT HAS PLANES (the
+// row-streaming instances take a backward only with them): a byte per (pixel, 8-channel group), or 32 bytes of ballots per (row, strip)
+extern "C" int64_t msau_conv_pair_bits_bytes(int dtype, const msau_conv_pair_desc* d) {
+    if (!d) return 0;
+    msau_conv_pair_desc probe = *d;
+    uint8_t one = 0;
+    probe.bits_mid = probe.bits_a = &one;
+    return pair_route(dtype, &probe).plane_bytes;
+}
+
+extern "C" int msau_conv_pair(void* stream, int dtype, const msau_conv_pair_desc* d) {
+    MSAU_CHECK_ARG(d && d->x && d->w1 && d->w2 && d->mid && (d->y || (d->flags1 & MSAU_PAIR_LRN_BWD)), "conv_pair: null pointer");
+    const PairRoute r = pair_route(dtype, d);
+    MSAU_CHECK_ARG(r.family != PAIR_NONE, "conv_pair: unsupported shape or flags (C %d, %dx%d, B %d, flags 0x%x / 0x%x; "
+                   "MSAU_CONV_ADD must name the input tensor)", d->C, d->H, d->W, d->B, d->flags1, d->flags2);
+    MSAU_CHECK_ARG(r.dir != PAIR_BWD || (d->mask_mid && d->mask_a) || (d->bits_mid && d->bits_a), "conv_pair: backward without mask_mid / mask_a (tensors or bit planes)");
+    MSAU_CHECK_ARG(!d->bits_mid == !d->bits_a, "conv_pair: bits_mid and bits_a come together");
+    if (d->flags1 & MSAU_PAIR_WGRAD1)        // (the task split follows MSAU_ROWS_* switches: a plan built under other settings must not be launched)
+        MSAU_CHECK_ARG(r.slabs == d->wg1_nslabs, "conv_pair: MSAU_PAIR_WGRAD1 launch has %d workgroups, the caller allocated %d slabs "
+                       "(msau_conv_pair_wgrad_slabs under other MSAU_ROWS_* settings?)", r.slabs, d->wg1_nslabs);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    return r.family == PAIR_ROWS ? msau_rowpair_launch(s, d, &r) : pair_tile_launch(s, dtype, d, r);
 }

@@ -1560,9 +1560,6 @@ __global__ __launch_bounds__(64 * WG_WAVES) void rowwgrad8_kernel(const RowWgrad
     for (int i = threadIdx.x; i < 8 * KEXT; i += 64 * WG_WAVES) out[i] = slab[i];
 }
 
-constexpr int kFwd1 = MSAU_PAIR_RELU_IN | MSAU_PAIR_RELU_MID, kFwd2 = MSAU_CONV_ADD | MSAU_CONV_RELU_OUT;
-constexpr int kBwd1 = MSAU_PAIR_MASK_MID, kBwd2 = MSAU_CONV_MASK_A | MSAU_CONV_ADD;
-
 // environment switches of this file, read once; msau_reload_env() makes the next call read them again (tests, A/B tools)
 struct RowsEnv { int on, sh, sh16, waves, min_tasks, maxc, conv, wgrad, wgrad4, dout, pairwg, couple, deconv, cplwg, lrnb16; };
 RowsEnv g_env;
@@ -1603,98 +1600,103 @@ int segment_rows(int B, int H, int nstrips, int warm, bool c16 = false) {
     return sh < H ? sh : H;
 }
 
-}  // namespace
+// ---- the residual pair (msau_conv_pair descriptors).  The number of an instance packs its template arguments; ROWPAIR_TABLE is the
+// one list of the instances that exist, read by rowpair_instance() both as the query "does this instance exist" (msau_rowpair_case)
+// and as the launch switch (msau_rowpair_launch): an instance is never named without being launchable, nor launched unnamed.
+constexpr int rowpair_id(bool c16, bool bwd, bool bits, bool lrnb, bool wg1, int cpl, bool pool) {
+    return 1 | c16 << 1 | bwd << 2 | bits << 3 | lrnb << 4 | wg1 << 5 | cpl << 6 | pool << 8;
+}
+// X(C16, BWD, BITS, LRNB, WG1, CPL, POOL)
+#define ROWPAIR_FWD(X, C16, CPL, POOL) X(C16, false, false, false, false, CPL, POOL) X(C16, false, true, false, false, CPL, POOL)
+#define ROWPAIR_BWD(X, C16, LRNB, WG1) X(C16, true, true, LRNB, WG1, 0, false)
+#define ROWPAIR_TABLE(X)                                                                                                           \
+    /* 8 channels.  Forward without / with ballot planes: plain, the coupling conv (CPL 1), also its pooled output (CPL 2) */      \
+    ROWPAIR_FWD(X, false, 0, false) ROWPAIR_FWD(X, false, 1, false) ROWPAIR_FWD(X, false, 2, false)                                \
+    /* backward (planes only): plain, the LRN backward, the first conv's weight gradient, both */                                  \
+    ROWPAIR_BWD(X, false, false, false) ROWPAIR_BWD(X, false, true, false) ROWPAIR_BWD(X, false, false, true)                      \
+    ROWPAIR_BWD(X, false, true, true)                                                                                              \
+    /* 16 channels: the forwards of 8 channels and the pooled output of y (MSAU_CONV_POOL); backward plain, the LRN backward */    \
+    ROWPAIR_FWD(X, true, 0, false) ROWPAIR_FWD(X, true, 1, false) ROWPAIR_FWD(X, true, 2, false) ROWPAIR_FWD(X, true, 0, true)     \
+    ROWPAIR_BWD(X, true, false, false) ROWPAIR_BWD(X, true, true, false)
 
-// which msau_conv_pair descriptors the row-streaming kernels take: 8 or 16 channels, bf16, the residual block's forward flag
-// set (with or without ballot planes; at 16 channels also with MSAU_CONV_POOL) or its data-gradient flag set WITH ballot planes
-int msau_rowpair_takes(int dtype, const msau_conv_pair_desc* d) {
-    const RowsEnv& e = rows_env();
-    if (!e.on || dtype != MSAU_BF16 || (d->C != 8 && d->C != 16) || d->C > e.maxc || (d->flags1 & MSAU_PAIR_TILES)) return 0;
-    const int pool_ok = d->C == 16 ? MSAU_CONV_POOL : 0;
-    const bool lrnb = d->flags1 & MSAU_PAIR_LRN_BWD, wg1 = d->flags1 & MSAU_PAIR_WGRAD1, cpl = d->flags1 & MSAU_PAIR_COUPLE;
-    const bool fwd = (d->flags1 & ~MSAU_PAIR_COUPLE) == kFwd1 && (d->flags2 & ~pool_ok) == kFwd2,
-               bwd = (d->flags1 & ~(MSAU_PAIR_LRN_BWD | MSAU_PAIR_WGRAD1)) == kBwd1 && d->flags2 == kBwd2;
-    if (!fwd && !bwd) return 0;
-    if (lrnb && !(bwd && (d->C == 8 || (d->C == 16 && e.lrnb16)) && d->lrn_a && d->lrn_da && d->lrn_k > 0.f)) return 0;
-    if (wg1 && !(bwd && d->C == 8 && d->wg1_x && d->wg1_slabs && e.pairwg)) return 0;
-    if (cpl) {
-        // the coupling conv rides on the forward launch: its packed image must be the one the kernels index (1x1 over
-        // concat(C, C) -> C: one chunk per source, 16 rows of 32)
-        if (!fwd || !e.couple || (d->flags2 & MSAU_CONV_POOL) || !d->cpl_prev || !d->cpl_w || !d->cpl_y) return 0;
-        msau_conv_pack_geom g;
-        if (msau_conv_pack_geometry(dtype, d->C, d->C, d->C, 1, 1, 1, 1, 1, &g) != 0 || g.cch != d->C || g.nchunks != 2 || g.kchunk != 32 || g.rows != 16) return 0;
-        if (d->cpl_pool_y && ((d->H | d->W) < 2)) return 0;
+template <bool C16, bool BWD, bool BITS, bool LRNB, bool WG1, int CPL, bool POOL>
+int launch_rowpair(hipStream_t s, const RowArgs& a) {
+    const dim3 grid(8 * (a.tasks_per_xcd / 4)), block(256);
+    if constexpr (C16) hipLaunchKernelGGL((rowpair_c16_kernel<BWD, BITS, POOL, CPL, LRNB>), grid, block, 0, s, a);
+    else hipLaunchKernelGGL((rowpair_c8_kernel<BWD, BITS, LRNB, WG1, CPL>), grid, block, 0, s, a);
+    MSAU_CHECK_LAUNCH("rowpair_kernel");
+    return 0;
+}
+
+// a == nullptr: 1 if instance `id` exists, else 0.  Otherwise: launch it (0, or an error -- never "not mine")
+int rowpair_instance(int id, hipStream_t s, const RowArgs* a) {
+    switch (id) {
+#define ROWPAIR_ROW(C16, BWD, BITS, LRNB, WG1, CPL, POOL) \
+        case rowpair_id(C16, BWD, BITS, LRNB, WG1, CPL, POOL): return a ? launch_rowpair<C16, BWD, BITS, LRNB, WG1, CPL, POOL>(s, *a) : 1;
+        ROWPAIR_TABLE(ROWPAIR_ROW)
+#undef ROWPAIR_ROW
     }
-    if (fwd && (d->flags2 & MSAU_CONV_POOL) && !d->pool_y) return 0;
-    if (bwd && !(d->bits_mid && d->bits_a)) return 0;
-    if (d->add != d->x) return 0;
-    if ((int64_t)d->H * d->W * d->C * 2 >= (1ll << 31)) return 0;
-    const int nstrips = cdiv(d->W, d->C == 8 ? OW : OW16);
-    if ((int64_t)d->H * nstrips * 32 >= (1ll << 31)) return 0;
-    if ((int64_t)d->B * nstrips * cdiv(d->H, 8) < e.min_tasks) return 0;    // too little work to fill the device: the tile kernels
-    return 1;
+    return a ? msau_set_error(MSAU_ERR_ARG, "rowpair: no instance %#x", id) : 0;
 }
 
-extern "C" void msau_reload_env(void) { g_env_ok = false; }
+int rowpair_strips(const msau_conv_pair_desc* d) { return cdiv(d->W, d->C == 8 ? OW : OW16); }
 
-int64_t msau_rowpair_plane_bytes(const msau_conv_pair_desc* d) {
-    return (int64_t)d->B * d->H * cdiv(d->W, d->C == 8 ? OW : OW16) * 32;
-}
-
-// workgroups (= slabs of an MSAU_PAIR_WGRAD1 launch) of the descriptor's launch
-int msau_rowpair_workgroups(const msau_conv_pair_desc* d) {
-    const bool c8 = d->C == 8;
-    const int nstrips = cdiv(d->W, c8 ? OW : OW16);
-    const int SH = segment_rows(d->B, d->H, nstrips, c8 ? 2 + SKEW : 2, !c8);
-    const int ntasks = d->B * nstrips * cdiv(d->H, SH);
-    return 8 * (roundup(cdiv(ntasks, 8), 4) / 4);
-}
-
-int msau_rowpair_launch(hipStream_t s, const msau_conv_pair_desc* d) {
-    RowArgs a;
-    a.d = *d;
-    const bool c8 = d->C == 8;
-    const bool bwd = (d->flags1 & ~(MSAU_PAIR_LRN_BWD | MSAU_PAIR_WGRAD1)) == kBwd1, bits = d->bits_mid && d->bits_a, pool = !bwd && (d->flags2 & MSAU_CONV_POOL);
-    const int cpl = !bwd && (d->flags1 & MSAU_PAIR_COUPLE) ? (d->cpl_pool_y ? 2 : 1) : 0;
-    a.nstrips = cdiv(d->W, c8 ? OW : OW16);
+// The task split of instance `id` on `d`, computed here and nowhere else: strips, segment height, segments, tasks, image and plane sizes.
+void rowpair_split(const msau_conv_pair_desc* d, int id, RowArgs& a) {
+    const bool c8 = d->C == 8, pooled = (id >> 8 & 1) || (id >> 6 & 3) == 2;   // POOL, or CPL == 2 (rowpair_id)
+    a.nstrips = rowpair_strips(d);
     a.SH = segment_rows(d->B, d->H, a.nstrips, c8 ? 2 + SKEW : 2, !c8);
-    if ((pool || cpl == 2) && (a.SH & 1) && a.SH < d->H) ++a.SH;            // 2x2 windows do not straddle segments
+    if (pooled && (a.SH & 1) && a.SH < d->H) ++a.SH;                        // 2x2 windows (of y, or of the coupling conv's z) do not straddle segments
     a.nseg = cdiv(d->H, a.SH);
     a.ntasks = d->B * a.nstrips * a.nseg;
     a.tasks_per_xcd = roundup(cdiv(a.ntasks, 8), 4);
     a.row_bytes = d->W * d->C * 2;
     a.img_bytes = (unsigned)d->H * (unsigned)a.row_bytes;
     a.plane_img = (unsigned)d->H * (unsigned)a.nstrips * 32u;
-    const dim3 grid(8 * (a.tasks_per_xcd / 4)), block(256);
-    if (d->flags1 & MSAU_PAIR_WGRAD1)        // (the task split follows MSAU_ROWS_* switches: a plan built under other settings must not be launched)
-        MSAU_CHECK_ARG((int)grid.x == d->wg1_nslabs, "conv_pair: MSAU_PAIR_WGRAD1 launch has %d workgroups, the caller allocated %d slabs "
-                       "(msau_conv_pair_wgrad_slabs under other MSAU_ROWS_* settings?)", (int)grid.x, d->wg1_nslabs);
-    if (c8) {
-        const bool lrnb = d->flags1 & MSAU_PAIR_LRN_BWD, wg1 = d->flags1 & MSAU_PAIR_WGRAD1;
-        if (bwd && lrnb && wg1) hipLaunchKernelGGL((rowpair_c8_kernel<true, true, true, true>), grid, block, 0, s, a);
-        else if (bwd && wg1) hipLaunchKernelGGL((rowpair_c8_kernel<true, true, false, true>), grid, block, 0, s, a);
-        else if (bwd && lrnb) hipLaunchKernelGGL((rowpair_c8_kernel<true, true, true>), grid, block, 0, s, a);
-        else if (bwd) hipLaunchKernelGGL((rowpair_c8_kernel<true, true>), grid, block, 0, s, a);
-        else if (cpl == 2 && bits) hipLaunchKernelGGL((rowpair_c8_kernel<false, true, false, false, 2>), grid, block, 0, s, a);
-        else if (cpl == 2) hipLaunchKernelGGL((rowpair_c8_kernel<false, false, false, false, 2>), grid, block, 0, s, a);
-        else if (cpl && bits) hipLaunchKernelGGL((rowpair_c8_kernel<false, true, false, false, 1>), grid, block, 0, s, a);
-        else if (cpl) hipLaunchKernelGGL((rowpair_c8_kernel<false, false, false, false, 1>), grid, block, 0, s, a);
-        else if (bits) hipLaunchKernelGGL((rowpair_c8_kernel<false, true>), grid, block, 0, s, a);
-        else hipLaunchKernelGGL((rowpair_c8_kernel<false, false>), grid, block, 0, s, a);
-    } else {
-        if (bwd && (d->flags1 & MSAU_PAIR_LRN_BWD)) hipLaunchKernelGGL((rowpair_c16_kernel<true, true, false, 0, true>), grid, block, 0, s, a);
-        else if (bwd) hipLaunchKernelGGL((rowpair_c16_kernel<true, true, false>), grid, block, 0, s, a);
-        else if (cpl == 2 && bits) hipLaunchKernelGGL((rowpair_c16_kernel<false, true, false, 2>), grid, block, 0, s, a);
-        else if (cpl == 2) hipLaunchKernelGGL((rowpair_c16_kernel<false, false, false, 2>), grid, block, 0, s, a);
-        else if (cpl && bits) hipLaunchKernelGGL((rowpair_c16_kernel<false, true, false, 1>), grid, block, 0, s, a);
-        else if (cpl) hipLaunchKernelGGL((rowpair_c16_kernel<false, false, false, 1>), grid, block, 0, s, a);
-        else if (bits && pool) hipLaunchKernelGGL((rowpair_c16_kernel<false, true, true>), grid, block, 0, s, a);
-        else if (bits) hipLaunchKernelGGL((rowpair_c16_kernel<false, true, false>), grid, block, 0, s, a);
-        else if (pool) hipLaunchKernelGGL((rowpair_c16_kernel<false, false, true>), grid, block, 0, s, a);
-        else hipLaunchKernelGGL((rowpair_c16_kernel<false, false, false>), grid, block, 0, s, a);
+}
+
+}  // namespace
+
+// The row-streaming instance msau_conv_pair launches for `d` (see rowpair_id), 0 = none: 8 or 16 channels, bf16, the residual block's
+// forward with or without ballot planes, or its data gradient WITH them.  What has no entry in ROWPAIR_TABLE is refused there:
+// MSAU_CONV_POOL at 8 channels or beside MSAU_PAIR_COUPLE, MSAU_PAIR_WGRAD1 at 16 channels, a backward without planes.
+int msau_rowpair_case(int dtype, const msau_conv_pair_desc* d) {
+    const RowsEnv& e = rows_env();
+    if (!e.on || dtype != MSAU_BF16 || (d->C != 8 && d->C != 16) || d->C > e.maxc || (d->flags1 & (MSAU_PAIR_TILES | MSAU_PAIR_DCOUPLE))) return 0;
+    const bool c16 = d->C == 16, bwd = msau_pair_direction(d) == PAIR_BWD, bits = d->bits_mid && d->bits_a;
+    const bool lrnb = d->flags1 & MSAU_PAIR_LRN_BWD, wg1 = d->flags1 & MSAU_PAIR_WGRAD1, cpl = d->flags1 & MSAU_PAIR_COUPLE;
+    if (lrnb && !((!c16 || e.lrnb16) && d->lrn_a && d->lrn_da && d->lrn_k > 0.f)) return 0;
+    if (wg1 && !(d->wg1_x && d->wg1_slabs && e.pairwg)) return 0;
+    if (cpl) {
+        // its packed image must be the one the kernels index (1x1 over concat(C, C) -> C: one chunk per source, 16 rows of 32)
+        if (!e.couple || !d->cpl_prev || !d->cpl_w || !d->cpl_y) return 0;
+        msau_conv_pack_geom g;
+        if (msau_conv_pack_geometry(dtype, d->C, d->C, d->C, 1, 1, 1, 1, 1, &g) != 0 || g.cch != d->C || g.nchunks != 2 || g.kchunk != 32 || g.rows != 16) return 0;
+        if (d->cpl_pool_y && ((d->H | d->W) < 2)) return 0;
     }
-    MSAU_CHECK_LAUNCH("rowpair_kernel");
-    return 0;
+    const int nstrips = rowpair_strips(d);
+    if ((int64_t)d->H * d->W * d->C * 2 >= (1ll << 31) || (int64_t)d->H * nstrips * 32 >= (1ll << 31)) return 0;
+    if ((int64_t)d->B * nstrips * cdiv(d->H, 8) < e.min_tasks) return 0;    // too little work to fill the device: the tile kernels
+    const int id = rowpair_id(c16, bwd, bits, lrnb, wg1, cpl ? (d->cpl_pool_y ? 2 : 1) : 0, d->flags2 & MSAU_CONV_POOL);
+    return rowpair_instance(id, nullptr, nullptr) ? id : 0;
+}
+
+extern "C" void msau_reload_env(void) { g_env_ok = false; }
+
+// the task split and the bytes of one ballot plane of the route's instance
+void msau_rowpair_split(const msau_conv_pair_desc* d, PairRoute* r) {
+    RowArgs a;
+    rowpair_split(d, r->inst, a);
+    r->nstrips = a.nstrips, r->SH = a.SH, r->nseg = a.nseg, r->ntasks = a.ntasks;
+    r->workgroups = 8 * (a.tasks_per_xcd / 4);
+    r->plane_bytes = (int64_t)d->B * a.plane_img;
+}
+
+int msau_rowpair_launch(hipStream_t s, const msau_conv_pair_desc* d, const PairRoute* r) {
+    RowArgs a;
+    a.d = *d;
+    rowpair_split(d, r->inst, a);
+    return rowpair_instance(r->inst, s, &a);
 }
 
 // ---- single convolutions (msau_conv2d descriptors)

@@ -16,16 +16,40 @@ typedef float f32x8 __attribute__((ext_vector_type(8)));
 
 int msau_set_error(int code, const char* fmt, ...);
 
-// conv_rows.hip: the row-streaming form of msau_conv_pair for the 8-channel bf16 layers (dispatched from conv_pair.hip)
-int msau_rowpair_takes(int dtype, const msau_conv_pair_desc* d);
-int64_t msau_rowpair_plane_bytes(const msau_conv_pair_desc* d);
+// ---- msau_conv_pair (pair_route in conv_pair.hip picks the family and the instance; DESIGN.md, "conv_pair routing")
+// The two flag combinations the kernels are compiled for: the residual block's forward, and its data gradient ...
+constexpr int kFwd1 = MSAU_PAIR_RELU_IN | MSAU_PAIR_RELU_MID, kFwd2 = MSAU_CONV_ADD | MSAU_CONV_RELU_OUT;
+constexpr int kBwd1 = MSAU_PAIR_MASK_MID, kBwd2 = MSAU_CONV_MASK_A | MSAU_CONV_ADD;
+// ... and the rider flags of flags1, which do not change the direction: a rider belongs to one direction (MSAU_PAIR_TILES to both)
+constexpr int kPairFwdRiders = MSAU_PAIR_COUPLE, kPairBwdRiders = MSAU_PAIR_LRN_BWD | MSAU_PAIR_WGRAD1 | MSAU_PAIR_DCOUPLE;
+constexpr int kPairRiders = MSAU_PAIR_TILES | kPairFwdRiders | kPairBwdRiders;
+enum { PAIR_NONE = 0, PAIR_TILE = 1, PAIR_ROWS = 2 };      // the families (= the answers of msau_conv_pair_instance)
+enum { PAIR_FWD = 1, PAIR_BWD = 2 };
+// the direction of a descriptor, 0 = neither flag set or a rider of the other direction; MSAU_CONV_POOL rides on the forward
+static inline int msau_pair_direction(const msau_conv_pair_desc* d) {
+    const int f1 = d->flags1 & ~kPairRiders;
+    if (f1 == kFwd1 && (d->flags2 & ~MSAU_CONV_POOL) == kFwd2 && !(d->flags1 & kPairBwdRiders)) return PAIR_FWD;
+    if (f1 == kBwd1 && d->flags2 == kBwd2 && !(d->flags1 & kPairFwdRiders)) return PAIR_BWD;
+    return 0;
+}
+struct PairRoute {
+    int family, dir, inst;                       // PAIR_*, PAIR_FWD / PAIR_BWD, the instance's number in its family's table (0 = none)
+    int tw, tiles_x, tiles_y;                    // tile family: tile width (16 tw - 2 output columns) and tiles per image
+    int nstrips, SH, nseg, ntasks, workgroups;   // row family: strips, segment height, segments per strip, tasks, grid
+    int64_t plane_bytes;                         // bytes of one ReLU-mask plane in the layout of the instance (no instance: the tile kernels')
+    int slabs;                                   // MSAU_PAIR_WGRAD1: the slabs the launch writes, 0 = the flag is not set
+};
+// conv_rows.hip: the row-streaming instances for 8 and 16 channels, bf16.  The contract of msau_conv2d's families below: _case is
+// the number of the instance that runs the descriptor (0 = none; for a descriptor behind pair_route's own checks: direction, operands
+// every family needs), _launch launches exactly that instance, _split is its task split and mask-plane size.
+int msau_rowpair_case(int dtype, const msau_conv_pair_desc* d);
+void msau_rowpair_split(const msau_conv_pair_desc* d, PairRoute* r);
+int msau_rowpair_launch(hipStream_t s, const msau_conv_pair_desc* d, const PairRoute* r);
 // ownerconv.hip: the first conv fed with box lists (MSAU_CONV_OWNER)
 int msau_ownerconv_takes(int dtype, const msau_conv_desc* d);
 int msau_ownerconv_fwd(hipStream_t s, int dtype, const msau_conv_desc* d);
 int msau_ownerconv_wgrad(hipStream_t s, int dtype, const msau_wgrad_desc* d, int cch, int nchunks, int kext);
 int msau_ownerconv_slabs(const msau_wgrad_desc* d);
-int msau_rowpair_workgroups(const msau_conv_pair_desc* d);
-int msau_rowpair_launch(hipStream_t s, const msau_conv_pair_desc* d);
 // The instance families of msau_conv2d besides the tile kernel (conv_route in conv.hip picks one; DESIGN.md, "conv2d routing").
 // <family>_case: the number of the instance that runs the descriptor, 0 = none; pure host arithmetic.  <family>_launch: launches
 // exactly that instance -- a case it has no instance for is an MSAU_ERR_ARG error, never "try the next family".

@@ -703,7 +703,7 @@ class PairOp:
         if plain and os.environ.get("MSAU_PAIR_DCOUPLE", "1") != "0" and P.cfg.get("fuse_couple", True):
             b.flags1 |= L.PAIR_DCOUPLE
             b.dcp_dz, b.dcp_w, b.dcp_mask, b.dcp_dprev = _ptr(cp.out.grad), P.pack_ptr(cp.dcp_off), _ptr(out.data), _ptr(cp.x1.grad)
-            if L.load().msau_conv_pair_applicable(P.dtype, C.byref(b)) and L.load().msau_conv_pair_instance(P.dtype, C.byref(b)) == 1:
+            if L.load().msau_conv_pair_instance(P.dtype, C.byref(b)) == 1:          # (a tile instance: the only family with the prologue)
                 self.dcp = cp
                 cp.dgrad_in_pair = self
                 self.bbytes += 3 * n * esz                             # y (the mask) read, d(y) and d(prev) written; d(z) read in place of d(y)

@@ -79,8 +79,14 @@ def test_pool_in_the_conv_epilogue_is_bit_exact(monkeypatch, dtype, c, k, dual, 
 
 
 @pytest.mark.parametrize("dtype", DT)
-@pytest.mark.parametrize("C8,hw", [(8, (57, 61)), (16, (60, 129)), (8, (70, 250))])
-def test_pool_in_the_residual_pair_epilogue_is_bit_exact(monkeypatch, dtype, C8, hw):
+@pytest.mark.parametrize("C8,hw,env", [
+    pytest.param(8, (57, 61), {}, id="8-hw0"), pytest.param(16, (60, 129), {}, id="16-hw1"), pytest.param(8, (70, 250), {}, id="8-hw2"),
+    # the pooled tile instances no other case launches: without mask planes (both tile widths), and the wide 16-channel tile
+    # (bf16; by default the row kernel pools at 16 channels) with and without planes
+    pytest.param(8, (33, 31), {"MSAU_PAIR_BITS": "0"}, id="8-hw3-nobits"), pytest.param(8, (60, 129), {"MSAU_PAIR_BITS": "0"}, id="8-hw4-nobits"),
+    pytest.param(16, (60, 129), {"MSAU_PAIR_ROWS": "0"}, id="16-hw5-tiles"),
+    pytest.param(16, (60, 129), {"MSAU_PAIR_ROWS": "0", "MSAU_PAIR_BITS": "0"}, id="16-hw6-tiles-nobits")])
+def test_pool_in_the_residual_pair_epilogue_is_bit_exact(monkeypatch, dtype, C8, hw, env):
     """conv -> ReLU -> conv -> add -> ReLU (one msau_conv_pair launch) followed by the pool: fused vs stand-alone pool"""
     torch.manual_seed(12)
     B, (H, W), c = 4, hw, C8
@@ -107,7 +113,9 @@ def test_pool_in_the_residual_pair_epilogue_is_bit_exact(monkeypatch, dtype, C8,
         # only the tile kernels pool at 8 channels; without this the un-pooled mode would run the row-streaming kernel, which
         # sums in another order (16 channels: the row kernel pools too, both modes run it)
         monkeypatch.setenv("MSAU_PAIR_ROWS", "0")
-        L.load().msau_reload_env()
+    for k, v in env.items():
+        monkeypatch.setenv(k, v)
+    L.load().msau_reload_env()
     try:
         for mode in ("1", "0"):
             monkeypatch.setenv("MSAU_FUSE_POOL", mode)
@@ -117,6 +125,8 @@ def test_pool_in_the_residual_pair_epilogue_is_bit_exact(monkeypatch, dtype, C8,
         L.load().msau_reload_env()
     pool1, plan1 = took[0]
     assert plan1.pairs[0].active and pool1.fused_into is plan1.pairs[0] and took[1][0].fused_into is None
+    if env:
+        assert plan1.pairs[0].key.startswith("conv_pair_kernel") and bool(plan1.pairs[0].fdesc.bits_mid) == ("MSAU_PAIR_BITS" not in env)
     for a, b in zip(out["1"], out["0"]):
         if isinstance(a, dict):
             for n in a:
@@ -126,7 +136,7 @@ def test_pool_in_the_residual_pair_epilogue_is_bit_exact(monkeypatch, dtype, C8,
 
 
 @pytest.mark.parametrize("dtype", DT)
-@pytest.mark.parametrize("c,hw", [(8, (57, 61)), (16, (60, 129)), (8, (71, 250))])
+@pytest.mark.parametrize("c,hw", [(8, (57, 61)), (16, (60, 129)), (8, (71, 250)), (16, (33, 31))])       # (the last: the narrow 16-channel bf16 tile)
 def test_relu_masks_as_bit_planes_give_the_same_gradients(monkeypatch, dtype, c, hw):
     """the residual pair's backward reads (mid > 0) and (x > 0) from bit planes its forward wrote, instead of the tensors"""
     torch.manual_seed(16)
@@ -975,9 +985,13 @@ def test_both_data_gradients_of_the_64_channel_coupling_conv_in_one_launch(monke
         assert err(res["1"][3][n], ps[n].grad, True) < 1e-1, n
 
 
-@pytest.mark.parametrize("hw,B,pool", [((84, 64), 2, True), ((29, 33), 3, False), ((21, 16), 2, True), ((14, 14), 1, False), ((45, 100), 2, False),
-                                        ((45, 100), 6, False), ((84, 64), 8, True)])       # (the last two: sizes at which the stand-alone form is ONE two-output launch)
-def test_coupling_conv_data_gradients_as_the_prologue_of_the_pairs_backward_launch(monkeypatch, hw, B, pool):
+_DCP_CASES = [((84, 64), 2, True), ((29, 33), 3, False), ((21, 16), 2, True), ((14, 14), 1, False), ((45, 100), 2, False),
+              ((45, 100), 6, False), ((84, 64), 8, True)]                                  # (the last two: sizes at which the stand-alone form is ONE two-output launch)
+
+
+@pytest.mark.parametrize("hw,B,pool,bits", [pytest.param(*t, "1", id=f"hw{i}-{t[1]}-{t[2]}") for i, t in enumerate(_DCP_CASES)] + [
+    pytest.param((21, 16), 2, True, "0", id="hw7-2-True-nobits")])      # (the ReLU masks as tensors: the backward instances without planes)
+def test_coupling_conv_data_gradients_as_the_prologue_of_the_pairs_backward_launch(monkeypatch, hw, B, pool, bits):
     """MSAU_PAIR_DCOUPLE (round 5): the two-output data gradient of the coupling conv z = ReLU(Wc concat(prev, y) + bc)
     (model/model.py:143-148,246-252) at 32 channels as the prologue of the residual pair's backward launch -- the launch reads d(z),
     computes g = d(y) = (Wc[:, y]^T d(z)) . [y > 0] for its tile incl. the halo in LDS, writes g and d(prev) of its own pixels --
@@ -1014,6 +1028,7 @@ def test_coupling_conv_data_gradients_as_the_prologue_of_the_pairs_backward_laun
             plan.logits = z
         seen.append((plan, cp, out, prev))
     res, grads = {}, {}
+    monkeypatch.setenv("MSAU_PAIR_BITS", bits)
     try:
         for mode in ("1", "0"):
             monkeypatch.setenv("MSAU_PAIR_DCOUPLE", mode)
@@ -1024,7 +1039,7 @@ def test_coupling_conv_data_gradients_as_the_prologue_of_the_pairs_backward_laun
         monkeypatch.undo()
     (plan1, cp1, _, _), (plan0, cp0, _, _) = seen
     assert plan1.pairs[0].dcp is cp1 and cp1.dgrad_in_pair is plan1.pairs[0] and plan0.pairs[0].dcp is None and cp0.dgrad_in_pair is None
-    assert plan1.pairs[0].key.startswith("conv_pair_kernel")
+    assert plan1.pairs[0].key.startswith("conv_pair_kernel") and bool(plan1.pairs[0].bdesc.bits_mid) == (bits == "1")
     assert torch.equal(grads["1"][0], grads["0"][0]), "d(y)"
     assert torch.equal(grads["1"][1], grads["0"][1]), "d(prev)"
     for a, b in zip(res["1"], res["0"]):
