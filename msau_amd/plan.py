@@ -57,6 +57,27 @@ def _ptr(t: Optional[torch.Tensor]) -> Optional[int]:
     return None if t is None else t.data_ptr()
 
 
+def _env_on(name: str) -> bool:
+    """a switch that is on unless the environment says 0"""
+    return os.environ.get(name, "1") != "0"
+
+
+def _offer(d, flags_field: str, flag: int, operands: dict, probe):
+    """Offer a rider on the descriptor `d`, in place: set `flag` on d.<flags_field> (0: operands that ride without a flag of their
+    own) and the operand fields, ask `probe(d)` whether an instance takes the descriptor like this, and on refusal clear the flag
+    and null exactly those fields again -- a descriptor is launched by value, a refused operand must not stay behind in it.
+    Returns the probe's answer."""
+    setattr(d, flags_field, getattr(d, flags_field) | flag)
+    for name, value in operands.items():
+        setattr(d, name, value)
+    answer = probe(d)
+    if not answer:
+        setattr(d, flags_field, getattr(d, flags_field) & ~flag)
+        for name in operands:
+            setattr(d, name, None)
+    return answer
+
+
 class Launch(NamedTuple):
     """One record of a launch sequence, carrying its own description: `kind` (MSAU_OP_* + stream flags) and `args` are what
     msau_run_ops* executes; `key` (the kernel instance), `nbytes` and `flops` (algorithmic, per launch) are what the profiler,
@@ -81,6 +102,7 @@ class Act:
         self.data = None if plan.reuse else torch.zeros((plan.B, H, W, self.Cs), dtype=plan.tdtype, device=plan.device)
         self.grad: Optional[torch.Tensor] = None
         self.n_contrib = 0
+        self.lrn_producer: Optional["LrnOp"] = None     # the LRN that writes this tensor
         plan.acts.append(self)
 
     @property
@@ -139,6 +161,9 @@ class ConvOp(Op):
         self.proj: Optional["ProjBwd"] = None       # on an attention projection: the fused data-gradient launch of f, g, h
         self.dgrad2 = None                          # a 64 + 64-channel 1x1 conv: both data gradients in one launch (msau_dgrad2_1x1)
         self.dgrad_in_pair: Optional["PairOp"] = None   # on a coupling conv: the pair whose BACKWARD launch computes its two data gradients (MSAU_PAIR_DCOUPLE)
+        self.lrn: Optional["LrnOp"] = None          # the LRN / the pool that reads this conv's output and may run in its epilogue
+        self.pool: Optional["PoolOp"] = None        # (set by LrnOp / PoolOp)
+        self.wg_slab_off: Optional[int] = None      # slabs of the weight gradient that rides on the data-gradient launch (MSAU_CONV_WGRAD)
         if kind == "conv" and k == 1 and x2 is not None and relu_out and not relu_in and fwd_add is None and plan.ops:
             prod = plan.ops[-1]
             if isinstance(prod, ConvOp) and prod.out is x2 and prod.pair is not None and prod is prod.pair.c2 \
@@ -174,7 +199,7 @@ class ConvOp(Op):
         return [t for t in (self.x1, self.x2, self.fwd_add) if t is not None]
 
     def writes(self):
-        lrn, pool = getattr(self, "lrn", None), getattr(self, "pool", None)     # fused outputs are written by this launch too
+        lrn, pool = self.lrn, self.pool         # fused outputs are written by this launch too
         w = [self.out] + ([lrn.y] if lrn is not None else []) + ([pool.y] if pool is not None else [])
         if self.cpl is not None:         # a coupling conv that may ride on this launch: its outputs must not alias this launch's inputs
             w += [t for t in self.cpl.writes() if t not in w]
@@ -197,6 +222,44 @@ class ConvOp(Op):
         e.k2_real, e.k2_store = k2
         e.cch, e.nchunks, e.kchunk, e.dtype = g.cch, g.nchunks, g.kchunk, self.plan.dtype
         return e, g.nchunks * g.rows * g.kchunk
+
+    def _dgrad_desc(self, cout):
+        """geometry of a data-gradient launch with `cout` output channels: out.grad convolved with the flipped image (SAME conv:
+        the mirrored pad) or, for a transposed conv, its stride-2 conv.  The finalize probe, the MSAU_CONV_DOUT descriptor and
+        the per-source descriptors are all this."""
+        x1, out = self.x1, self.out
+        d = L.ConvDesc()
+        d.B, d.Hin, d.Win, d.Hout, d.Wout = self.plan.B, out.H, out.W, x1.H, x1.W
+        d.C1, d.C2, d.Cout = out.Cs, 0, cout
+        d.KH = d.KW = self.k
+        if self.kind == "conv":
+            d.dil, d.stride, d.ups = self.dil, 1, 1
+            d.pad_t = (self.k - 1) * self.dil - self.pad_t
+            d.pad_l = (self.k - 1) * self.dil - self.pad_l
+        else:
+            d.dil, d.stride, d.ups = 1, 2, 1
+            d.pad_t = d.pad_l = self.k // 2
+        return d
+
+    def _dgrad_image(self, cout_store, row_off, rows_real):
+        """pack offset of a SAME conv's data-gradient image: the weight rows [row_off, row_off + rows_real) of the concat, flipped
+        and transposed, stored `cout_store` wide"""
+        P, out = self.plan, self.out
+        g = self._geom(out.Cs, 0, cout_store, self.dil, 1, 1)
+        off = P.alloc_pack(g.bytes)
+        e, n = self._pack_entry(g, off, row_is_dim0=False, flip=True, row_off=row_off, rows_real=rows_real,
+                                k1=(out.C, out.Cs), k2=(0, 0))
+        P.add_pack_entry(e, n)
+        return off
+
+    @staticmethod
+    def _slab_count(wg):
+        """slabs of a weight-gradient launch: as many as fit the byte budget, at least the floor, never more than the cap or than
+        the launch has pixel tiles"""
+        cap = int(os.environ.get("MSAU_SLAB_CAP", "384"))
+        floor = int(os.environ.get("MSAU_SLAB_MIN", "64"))
+        budget = (int(os.environ.get("MSAU_SLAB_MB", "3")) << 20) // max(wg.slab_bytes, 1)
+        return max(1, min(wg.max_slabs, cap, max(floor, budget)))
 
     def finalize(self):
         P = self.plan
@@ -221,48 +284,28 @@ class ConvOp(Op):
         self.uentry = None
         self.dd_off = None           # one launch for both sources of a concat conv (MSAU_CONV_DOUT) when an instance has it
         if P.training and conv and x2 is not None and None not in self.slots and x1.C == x1.Cs == x2.C == x2.Cs \
-                and x1.Cs + x2.Cs <= 128 and os.environ.get("MSAU_FUSE_DGRAD", "1") != "0" and not P.generic_only:
-            proto = L.ConvDesc()
-            proto.B, proto.Hin, proto.Win, proto.Hout, proto.Wout = P.B, out.H, out.W, x1.H, x1.W
-            proto.C1, proto.C2, proto.Cout = out.Cs, 0, x1.Cs + x2.Cs
-            proto.KH = proto.KW = self.k
-            proto.dil, proto.stride, proto.ups = self.dil, 1, 1
-            proto.pad_t = (self.k - 1) * self.dil - self.pad_t
-            proto.pad_l = (self.k - 1) * self.dil - self.pad_l
-            info = _launch_info(P.dtype, proto)
-            if info[7] & 2:
-                gd = self._geom(out.Cs, 0, x1.Cs + x2.Cs, self.dil, 1, 1)
-                self.dd_off = P.alloc_pack(gd.bytes)
-                e, n = self._pack_entry(gd, self.dd_off, row_is_dim0=False, flip=True, row_off=0,
-                                        rows_real=x1.C + x2.C, k1=(out.C, out.Cs), k2=(0, 0))
-                P.add_pack_entry(e, n)
+                and x1.Cs + x2.Cs <= 128 and _env_on("MSAU_FUSE_DGRAD") and not P.generic_only:
+            if _launch_info(P.dtype, self._dgrad_desc(x1.Cs + x2.Cs))[7] & 2:
+                self.dd_off = self._dgrad_image(x1.Cs + x2.Cs, 0, x1.C + x2.C)
         # the same image for MSAU_PAIR_DCOUPLE where no two-output instance takes the launch (small images): the prologue of the
         # residual pair's backward launch only needs the packed weights
         self.dcp_off = self.dd_off
         if P.training and conv and self.k == 1 and x2 is not None and self.dd_off is None and None not in self.slots \
                 and x1.C == x1.Cs == x2.C == x2.Cs == out.Cs == 32 and P.dtype == L.BF16 and not P.generic_only \
                 and any(pr.c2.cpl is self for pr in P.pairs):
-            gd = self._geom(out.Cs, 0, x1.Cs + x2.Cs, self.dil, 1, 1)
-            self.dcp_off = P.alloc_pack(gd.bytes)
-            e, n = self._pack_entry(gd, self.dcp_off, row_is_dim0=False, flip=True, row_off=0,
-                                    rows_real=x1.C + x2.C, k1=(out.C, out.Cs), k2=(0, 0))
-            P.add_pack_entry(e, n)
+            self.dcp_off = self._dgrad_image(x1.Cs + x2.Cs, 0, x1.C + x2.C)
         if P.training and self.dd_off is None:
             for si, x in enumerate((x1, x2)):
                 if x is None or self.slots[si] is None:
                     continue
                 if conv:
-                    gd = self._geom(out.Cs, 0, x.Cs, self.dil, 1, 1)
-                    self.d_off[si] = P.alloc_pack(gd.bytes)
-                    e, n = self._pack_entry(gd, self.d_off[si], row_is_dim0=False, flip=True,
-                                            row_off=(0 if si == 0 else x1.C), rows_real=x.C,
-                                            k1=(out.C, out.Cs), k2=(0, 0))
-                else:
+                    self.d_off[si] = self._dgrad_image(x.Cs, 0 if si == 0 else x1.C, x.C)
+                else:               # transposed conv: its data gradient is the stride-2 conv with the image as it stands (no flip)
                     gd = self._geom(out.Cs, 0, x.Cs, 1, 2, 1)
                     self.d_off[si] = P.alloc_pack(gd.bytes)
                     e, n = self._pack_entry(gd, self.d_off[si], row_is_dim0=True, flip=False, row_off=0,
                                             rows_real=x.C, k1=(out.C, out.Cs), k2=(0, 0))
-                P.add_pack_entry(e, n)
+                    P.add_pack_entry(e, n)
 
     def bind(self):
         """Create the launch descriptors (all buffers exist now)."""
@@ -289,7 +332,7 @@ class ConvOp(Op):
             P.head_fused = bool(info[7] & 1) and d.flags == 0 and out.C <= 16
             if P.head_fused:
                 d.flags = L.CONV_HEAD
-        lrn = getattr(self, "lrn", None)
+        lrn = self.lrn
         if lrn is not None and conv and d.flags & ~L.CONV_RELU_IN == 0 and lrn.a.C == lrn.a.Cs:
             info = _launch_info(P.dtype, d)
             if info[7] & 4:                  # LocalResponseNorm(size=C) in this conv's epilogue: layers.py:145,161-162
@@ -297,7 +340,7 @@ class ConvOp(Op):
                 d.y2 = _ptr(lrn.y.data)
                 d.lrn_alpha_over_n, d.lrn_beta, d.lrn_k = 1e-4 / lrn.a.C, 0.75, 1.0
                 lrn.fused_into = self
-        pool = getattr(self, "pool", None)
+        pool = self.pool
         if pool is not None and conv and not (d.flags & (L.CONV_LRN | L.CONV_HEAD)):
             info = _launch_info(P.dtype, d)
             if info[7] & 8:                  # zero pad + MaxPool2d(2,2) in this conv's epilogue: model/model.py:158-160
@@ -310,14 +353,7 @@ class ConvOp(Op):
         if not P.training or out.grad is None:
             return
         if self.dd_off is not None:
-            dd = L.ConvDesc()
-            dd.B = P.B
-            dd.Hin, dd.Win, dd.Hout, dd.Wout = out.H, out.W, x1.H, x1.W
-            dd.C1, dd.C2, dd.Cout = out.Cs, 0, x1.Cs + x2.Cs
-            dd.KH = dd.KW = self.k
-            dd.dil, dd.stride, dd.ups = self.dil, 1, 1
-            dd.pad_t = (self.k - 1) * self.dil - self.pad_t
-            dd.pad_l = (self.k - 1) * self.dil - self.pad_l
+            dd = self._dgrad_desc(x1.Cs + x2.Cs)
             assert not self.relu_in
             fl = [0, 0]
             for si, x in enumerate((x1, x2)):
@@ -336,18 +372,7 @@ class ConvOp(Op):
             if x is None or self.slots[si] is None or self.dd_off is not None:
                 continue
             accum, maskb = x.slot_flags(self.slots[si])
-            dd = L.ConvDesc()
-            dd.B = P.B
-            dd.Hin, dd.Win, dd.Hout, dd.Wout = out.H, out.W, x.H, x.W
-            dd.C1, dd.C2, dd.Cout = out.Cs, 0, x.Cs
-            dd.KH = dd.KW = self.k
-            if conv:
-                dd.dil, dd.stride, dd.ups = self.dil, 1, 1
-                dd.pad_t = (self.k - 1) * self.dil - self.pad_t
-                dd.pad_l = (self.k - 1) * self.dil - self.pad_l
-            else:
-                dd.dil, dd.stride, dd.ups = 1, 2, 1
-                dd.pad_t = dd.pad_l = self.k // 2
+            dd = self._dgrad_desc(x.Cs)
             fl = 0
             if self.relu_in:
                 fl |= L.CONV_MASK_A
@@ -370,7 +395,7 @@ class ConvOp(Op):
         d1, d2 = self.ddesc
         if conv and self.k == 1 and x2 is not None and self.dd_off is None and d1 is not None and d2 is not None \
                 and P.dtype == L.BF16 and not P.generic_only and x1.C == x1.Cs == x2.C == x2.Cs == out.Cs == 64 \
-                and not ((d1.flags | d2.flags) & ~(L.CONV_ACCUM | L.CONV_MASK_B)) and os.environ.get("MSAU_DGRAD2", "1") != "0":
+                and not ((d1.flags | d2.flags) & ~(L.CONV_ACCUM | L.CONV_MASK_B)) and _env_on("MSAU_DGRAD2"):
             geo = [self._geom(out.Cs, 0, x.Cs, 1, 1, 1) for x in (x1, x2)]
             if all((gq.nchunks, gq.rows, gq.kchunk) == (1, 64, 64) for gq in geo):
                 a = L.Dgrad2Args()
@@ -404,8 +429,7 @@ class ConvOp(Op):
         wg = L.WgradGeom()
         w.nslabs = 1
         L.call("msau_wgrad_geometry", P.dtype, C.byref(w), C.byref(wg))
-        nslabs = max(1, min(wg.max_slabs, int(os.environ.get('MSAU_SLAB_CAP', '384')), max(int(os.environ.get('MSAU_SLAB_MIN', '64')), (int(os.environ.get('MSAU_SLAB_MB', '3')) << 20) // max(wg.slab_bytes, 1))))
-        w.nslabs = nslabs
+        w.nslabs = nslabs = self._slab_count(wg)
         slab_elems = wg.slab_bytes // 4
         self.slab_off = P.alloc_slab(nslabs * slab_elems)
         self.wdesc, self.wgeom = w, wg
@@ -433,27 +457,28 @@ class ConvOp(Op):
         dd = self.ddesc[0]
         if conv and self.k == 1 and x2 is not None and self.dd_off is not None and dd is not None and not self.relu_in \
                 and dd.flags == L.CONV_DOUT and dd.flags2 == L.CONV_MASK_B and u.kext == 16 and u.slab_elems == 256 and u.cch == 8 \
-                and u.nchunks == 2 and os.environ.get("MSAU_COUPLE_WGRAD", "1") != "0" and P.cfg.get("couple_wgrad", True):
-            dd.flags |= L.CONV_WGRAD
-            dd.wg_x1, dd.wg_slabs = _ptr(x1.data), 1                 # (placeholder: the slab arena does not exist yet)
-            ns = int(L.load().msau_conv2d_rider_slabs(P.dtype, C.byref(dd)))
-            if ns > 0:
+                and u.nchunks == 2 and _env_on("MSAU_COUPLE_WGRAD") and P.cfg.get("couple_wgrad", True):
+            # (wg_slabs = 1: a placeholder, the slab arena does not exist yet; the answer is the number of slabs the instance writes)
+            ns = _offer(dd, "flags", L.CONV_WGRAD, dict(wg_x1=_ptr(x1.data), wg_slabs=1),
+                        lambda q: max(0, int(L.load().msau_conv2d_rider_slabs(P.dtype, C.byref(q)))))
+            if ns:
                 dd.wg_nslabs = ns
                 self.wg_slab_off = P.alloc_slab(ns * 256)
                 u.slab_off, u.nslabs = self.wg_slab_off, ns
                 u.b_src_off, u.b_nslabs = self.wg_slab_off + 8, ns
                 self.wg_fused = True
-            else:
-                dd.flags &= ~L.CONV_WGRAD
-                dd.wg_x1 = dd.wg_slabs = None
 
     def late_bind(self):
+        """the pointers into the slab arena, which exists only after every bind"""
         P = self.plan
         if self.wdesc is not None:
             self.wdesc.slabs = P.slab_ptr(self.slab_off)
         if self.wg_fused and self.pair is None and self.ddesc[0] is not None and self.ddesc[0].flags & L.CONV_WGRAD:
             self.ddesc[0].wg_slabs = P.slab_ptr(self.wg_slab_off)
-        # ---- launch metadata for profiling / roofline accounting (bench.py)
+
+    def _meta(self):
+        """launch metadata for profiling / roofline accounting (bench.py): key, algorithmic bytes and flops of every launch"""
+        P = self.plan
         T = "f32" if P.dtype == L.F32 else "bf16"
         esz = 4 if P.dtype == L.F32 else 2
         taps = self.k * self.k
@@ -499,18 +524,15 @@ class ConvOp(Op):
             self.d2meta = ("dgrad2_1x1<bf16,C64>", self.out.npix * 64 * nops * esz, 2.0 * self.out.npix * 128 * self.out.C)
         if self.wdesc is not None:
             w, wg = self.wdesc, self.wgeom
-            ctn = -(-w.Cout // 16)
-            ctn = 4 if ctn == 3 else (8 if ctn > 4 else ctn)
-            nkw = -(-(wg.kext // 16) // 4)
-            nkw = 1 if nkw <= 1 else 2 if nkw <= 2 else 3 if nkw <= 3 else 5 if nkw <= 5 else 10
             if wg.lean == 2:
                 self.wkey = f"rowwgrad_kernel<{T},C{wg.cch},CO{w.Cout},K{w.KH}>"
             elif wg.lean:
                 self.wkey = f"wgrad_lean_kernel<{T},C{wg.cch},CO{w.Cout},K{w.KH}>"
-            else:
-                self.wkey = f"wgrad_kernel<{T},CT{ctn},NK{nkw}>"
-            self.wbytes = (w.B * w.Hin * w.Win * (w.C1 + w.C2) * wg.nchunks // wg.nchunks + w.B * w.Hout * w.Wout * w.Cout) * esz \
-                + w.nslabs * wg.slab_bytes
+            else:                                       # the generic kernel: its instance as the router names it
+                route = (L.i32 * 8)()
+                L.call("msau_wgrad_route", P.dtype, C.byref(w), route)
+                self.wkey = f"wgrad_kernel<{T},CT{route[1]},NK{route[2]}>"
+            self.wbytes = (w.B * w.Hin * w.Win * (w.C1 + w.C2) + w.B * w.Hout * w.Wout * w.Cout) * esz + w.nslabs * wg.slab_bytes
 
     def fwd_recs(self):
         if self.cpl_fused_into is not None:             # computed by the residual pair's forward launch
@@ -557,6 +579,7 @@ class PairOp:
         self.active = False
         self.fdesc = self.bdesc = None
         self.dcp: Optional[ConvOp] = None            # the coupling conv whose two data gradients this pair's backward launch computes
+        self.wg_slab_off: Optional[int] = None       # slabs of the first conv's weight gradient when it rides on the backward launch (MSAU_PAIR_WGRAD1)
         c1.pair = c2.pair = self
         plan.pairs.append(self)
 
@@ -564,8 +587,11 @@ class PairOp:
         """after both ConvOps are bound: build the fused descriptors if an instance takes the shape"""
         P, c1, c2 = self.plan, self.c1, self.c2
         x0, r1, out = c1.x1, c1.out, c2.out
-        if os.environ.get("MSAU_FUSE_PAIR", "1") == "0" or not P.cfg.get("fuse_pair", True) or P.generic_only:
+        if not _env_on("MSAU_FUSE_PAIR") or not P.cfg.get("fuse_pair", True) or P.generic_only:
             return
+        lib = L.load()
+        applicable = lambda q: lib.msau_conv_pair_applicable(P.dtype, C.byref(q))       # the probes of the rider offers below
+        instance = lambda q: lib.msau_conv_pair_instance(P.dtype, C.byref(q))           # (0 none, 1 a tile instance, 2 row-streaming)
         ok = (c1.kind == c2.kind == "conv" and c1.k == c2.k == 3 and c1.dil == c2.dil == 1 and c1.x2 is None and c2.x2 is None
               and c1.relu_in and c1.relu_out and c1.fwd_add is None and not c2.relu_in and c2.relu_out and c2.fwd_add is x0
               and c2.x1 is r1 and x0.C == x0.Cs == r1.C == out.C and x0.Cs in (8, 16, 32) and not c1.head and not c2.head
@@ -577,22 +603,17 @@ class PairOp:
         f.flags1, f.flags2 = L.PAIR_RELU_IN | L.PAIR_RELU_MID, L.CONV_ADD | L.CONV_RELU_OUT
         f.x, f.w1, f.b1, f.mid = _ptr(x0.data), P.pack_ptr(c1.w_off), P.pack_ptr(c1.b_off), _ptr(r1.data)
         f.w2, f.b2, f.add, f.y = P.pack_ptr(c2.w_off), P.pack_ptr(c2.b_off), _ptr(x0.data), _ptr(out.data)
-        if not L.load().msau_conv_pair_applicable(P.dtype, C.byref(f)):
+        if not applicable(f):
             return
-        pool = getattr(c2, "pool", None)
+        pool = c2.pool
         if pool is not None and x0.Cs < int(os.environ.get("MSAU_PAIR_POOL_MINC", "16")):
             # measured: at 8 channels the pooled-output variant of the pair launch (97 VGPRs, 4 waves per SIMD instead of 6)
             # costs 12 us for a 10.8 us pool launch; at 16 channels 3.3 us for 8.6 us
             pool.fused_into = None
             pool = None
         if pool is not None:                 # the pooled output rides on the fused launch (c2's own descriptor is not launched)
-            f.flags2 |= L.CONV_POOL
-            f.pool_y, f.pool_idx = _ptr(pool.y.data), _ptr(pool.idx)
-            if L.load().msau_conv_pair_applicable(P.dtype, C.byref(f)):
-                pool.fused_into = self
-            else:
-                f.flags2 &= ~L.CONV_POOL
-                pool.fused_into = None
+            took = _offer(f, "flags2", L.CONV_POOL, dict(pool_y=_ptr(pool.y.data), pool_idx=_ptr(pool.idx)), applicable)
+            pool.fused_into = self if took else None
         self.fdesc = f
         T = "f32" if P.dtype == L.F32 else "bf16"
         esz = 4 if P.dtype == L.F32 else 2
@@ -610,24 +631,22 @@ class PairOp:
                 b.flags1, b.flags2 = L.PAIR_MASK_MID, d1.flags
                 b.x, b.w1, b.b1, b.mask_mid, b.mid = _ptr(out.grad), P.pack_ptr(c2.d_off[0]), None, d2.mask_b, _ptr(r1.grad)
                 b.w2, b.b2, b.add, b.mask_a, b.mask_b, b.y = P.pack_ptr(c1.d_off[0]), None, d1.add, d1.mask_a, d1.mask_b, d1.y
-                use_bits = os.environ.get("MSAU_PAIR_BITS", "1") != "0"
-                if use_bits:
-                    b.bits_mid = b.bits_a = 1       # placeholders (the planes are allocated below): the row-streaming instances
-                                                    # take the backward flag set only WITH planes, so the probe must carry them
-                if L.load().msau_conv_pair_applicable(P.dtype, C.byref(b)):     # MASK_A + ADD of the input tensor only
+                use_bits = _env_on("MSAU_PAIR_BITS")
+                # placeholders (the planes are allocated below): the row-streaming instances take the backward flag set only
+                # WITH planes, so the probe must carry them
+                planes = dict(bits_mid=1, bits_a=1) if use_bits else {}
+                if _offer(b, "flags1", 0, planes, applicable):                  # MASK_A + ADD of the input tensor only
                     self.bdesc = b
-                else:
-                    b.bits_mid = b.bits_a = None
                 self.bbytes = 5 * n * esz               # g (also the ADD operand), r1 mask, x0 mask read once; g_r1, dx written once
                 if self.bdesc is not None and use_bits:
                     # the two ReLU masks as bit planes: written by the forward launch, read by the backward launch; the
                     # layout (and so the size) belongs to the instance that takes the shape (msau_conv_pair_bits_bytes)
-                    nbits = int(L.load().msau_conv_pair_bits_bytes(P.dtype, C.byref(b)))
-                    if nbits != int(L.load().msau_conv_pair_bits_bytes(P.dtype, C.byref(f))):
+                    nbits = int(lib.msau_conv_pair_bits_bytes(P.dtype, C.byref(b)))
+                    if nbits != int(lib.msau_conv_pair_bits_bytes(P.dtype, C.byref(f))):
                         # the two launches would go to different instances (a forward flag only the tile kernels have)
                         f.flags1 |= L.PAIR_TILES
                         b.flags1 |= L.PAIR_TILES
-                        nbits = int(L.load().msau_conv_pair_bits_bytes(P.dtype, C.byref(b)))
+                        nbits = int(lib.msau_conv_pair_bits_bytes(P.dtype, C.byref(b)))
                     self.bits_mid = torch.zeros((nbits,), dtype=torch.uint8, device=P.device)
                     self.bits_a = torch.zeros_like(self.bits_mid)
                     for dsc in (f, b):
@@ -635,84 +654,69 @@ class PairOp:
                     self.fbytes += 2 * nbits
                     self.bbytes = 3 * n * esz + 2 * nbits
                 # the block's input is an LRN output nothing else reads: its backward rides on this launch (conv_rows.hip)
-                lrn = getattr(x0, "lrn_producer", None)
+                lrn = x0.lrn_producer
                 if self.bdesc is not None and lrn is not None and x0.n_contrib == 1 and not (d1.flags & L.CONV_ACCUM) \
                         and lrn.a.grad is not None and lrn.a.n_contrib == 1 and not lrn.a.relu_out and lrn.a.C == lrn.a.Cs == x0.Cs \
-                        and os.environ.get("MSAU_FUSE_LRN_BWD", "1") != "0":
-                    b.flags1 |= L.PAIR_LRN_BWD
-                    b.lrn_a, b.lrn_da = _ptr(lrn.a.data), _ptr(lrn.a.grad)
+                        and _env_on("MSAU_FUSE_LRN_BWD"):
                     b.lrn_alpha_over_n, b.lrn_beta, b.lrn_k = 1e-4 / lrn.a.C, 0.75, 1.0
-                    if L.load().msau_conv_pair_instance(P.dtype, C.byref(b)) == 2:
+                    if _offer(b, "flags1", L.PAIR_LRN_BWD, dict(lrn_a=_ptr(lrn.a.data), lrn_da=_ptr(lrn.a.grad)),
+                              lambda q: instance(q) == 2):
                         lrn.bwd_fused_into = self
                         self.bbytes += n * esz              # a read, da written instead of dx
-                    else:
-                        b.flags1 &= ~L.PAIR_LRN_BWD
-                        b.lrn_a = b.lrn_da = None
                 # the first conv's weight gradient rides on this launch too: its g operand is the row the walk has just produced
                 u = c1.uentry
                 if self.bdesc is not None and u is not None and c1.wdesc is not None and c1.relu_in and r1.n_contrib == 1 \
-                        and u.kext == 80 and u.slab_elems == 640 and os.environ.get("MSAU_PAIR_WGRAD", "1") != "0":
-                    b.flags1 |= L.PAIR_WGRAD1
-                    b.wg1_x, b.wg1_slabs = _ptr(x0.data), 1                 # (placeholder: the slab arena does not exist yet)
-                    ns = int(L.load().msau_conv_pair_wgrad_slabs(P.dtype, C.byref(b)))
-                    if ns > 0:
+                        and u.kext == 80 and u.slab_elems == 640 and _env_on("MSAU_PAIR_WGRAD"):
+                    # (wg1_slabs = 1: a placeholder, the slab arena does not exist yet; the answer is the number of slabs)
+                    ns = _offer(b, "flags1", L.PAIR_WGRAD1, dict(wg1_x=_ptr(x0.data), wg1_slabs=1),
+                                lambda q: max(0, int(lib.msau_conv_pair_wgrad_slabs(P.dtype, C.byref(q)))))
+                    if ns:
                         b.wg1_nslabs = ns
                         self.wg_slab_off = P.alloc_slab(ns * 640)
                         u.slab_off, u.nslabs = self.wg_slab_off, ns
                         u.b_src_off, u.b_nslabs = self.wg_slab_off + 72, ns
                         c1.wg_fused = True
                         self.bbytes += ns * 640 * 4                      # x0 read instead of the intermediate gradient written; the slabs
-                    else:
-                        b.flags1 &= ~L.PAIR_WGRAD1
-                        b.wg1_x = b.wg1_slabs = None
         # the coupling conv that reads this block's output (model/model.py:143-148,246-252) rides on the forward launch where an
         # instance has it (row-streaming 8 / 16 channels): one launch and one read of the block's output less per coupled level
         cp = c2.cpl
         self.cpl = None
-        if cp is not None and not (f.flags2 & L.CONV_POOL) and cp.x2 is out and getattr(cp, "lrn", None) is None and not cp.head \
-                and os.environ.get("MSAU_PAIR_COUPLE", "1") != "0" and P.cfg.get("fuse_couple", True):
-            f.flags1 |= L.PAIR_COUPLE
-            f.cpl_prev, f.cpl_w, f.cpl_b, f.cpl_y = _ptr(cp.x1.data), P.pack_ptr(cp.w_off), P.pack_ptr(cp.b_off), _ptr(cp.out.data)
-            cpool = getattr(cp, "pool", None)                        # the pool behind the coupling conv (encoder levels): it moves along
+        if cp is not None and not (f.flags2 & L.CONV_POOL) and cp.x2 is out and cp.lrn is None and not cp.head \
+                and _env_on("MSAU_PAIR_COUPLE") and P.cfg.get("fuse_couple", True):
+            operands = dict(cpl_prev=_ptr(cp.x1.data), cpl_w=P.pack_ptr(cp.w_off), cpl_b=P.pack_ptr(cp.b_off), cpl_y=_ptr(cp.out.data))
+            cpool = cp.pool                        # the pool behind the coupling conv (encoder levels): it moves along ...
             if cpool is not None:
-                f.cpl_pool_y, f.cpl_pool_idx = _ptr(cpool.y.data), _ptr(cpool.idx)
-                if not L.load().msau_conv_pair_applicable(P.dtype, C.byref(f)):
-                    f.cpl_pool_y = f.cpl_pool_idx = None             # ... or stays where it was (the coupling launch's epilogue / a launch of its own)
-                    cpool = None
-            if L.load().msau_conv_pair_applicable(P.dtype, C.byref(f)):
+                pooled = dict(operands, cpl_pool_y=_ptr(cpool.y.data), cpl_pool_idx=_ptr(cpool.idx))
+                if _offer(f, "flags1", L.PAIR_COUPLE, pooled, applicable):
+                    operands = pooled
+                else:
+                    cpool = None                   # ... or stays where it was (the coupling launch's epilogue / a launch of its own)
+            if _offer(f, "flags1", L.PAIR_COUPLE, operands, applicable):
                 self.cpl = cp
                 cp.cpl_fused_into = self
                 if cpool is not None:
                     cpool.fused_into = self
-                elif getattr(cp, "pool", None) is not None and cp.pool.fused_into is cp:
+                elif cp.pool is not None and cp.pool.fused_into is cp:
                     cp.pool.fused_into = None                        # (the coupling launch is gone: the pool runs on its own)
                 self.fbytes += 2 * n * esz + ((n // 4) * (esz + 1) if f.cpl_pool_y else 0)     # prev read, z written (+ pooled z, positions)
-            else:
-                f.flags1 &= ~L.PAIR_COUPLE
-                f.cpl_prev = f.cpl_w = f.cpl_b = f.cpl_y = f.cpl_pool_y = f.cpl_pool_idx = None
         # ... and its two-output data gradient becomes the PROLOGUE of the backward launch where an instance has that (the 32-channel
         # tile pair): the launch reads d(z) instead of d(y), computes d(y) for its tile and writes d(y) and d(prev) of its own pixels
         b = self.bdesc
         plain = False                                  # d(prev) a plain write, d(y) masked by y and nothing else: what the prologue implements
-        if b is not None and cp is not None and cp.x2 is out and getattr(cp, "dcp_off", None) is not None and out.n_contrib == 1:
+        if b is not None and cp is not None and cp.x2 is out and cp.dcp_off is not None and out.n_contrib == 1:
             d1, d2 = cp.ddesc
             if cp.dd_off is not None:
                 plain = d1 is not None and d1.flags == L.CONV_DOUT and d1.flags2 == L.CONV_MASK_B and d1.mask_b2 == _ptr(out.data)
             else:
                 plain = d1 is not None and d2 is not None and d1.flags == 0 and d2.flags == L.CONV_MASK_B and d2.mask_b == _ptr(out.data)
-        if plain and os.environ.get("MSAU_PAIR_DCOUPLE", "1") != "0" and P.cfg.get("fuse_couple", True):
-            b.flags1 |= L.PAIR_DCOUPLE
-            b.dcp_dz, b.dcp_w, b.dcp_mask, b.dcp_dprev = _ptr(cp.out.grad), P.pack_ptr(cp.dcp_off), _ptr(out.data), _ptr(cp.x1.grad)
-            if L.load().msau_conv_pair_instance(P.dtype, C.byref(b)) == 1:          # (a tile instance: the only family with the prologue)
+        if plain and _env_on("MSAU_PAIR_DCOUPLE") and P.cfg.get("fuse_couple", True):
+            operands = dict(dcp_dz=_ptr(cp.out.grad), dcp_w=P.pack_ptr(cp.dcp_off), dcp_mask=_ptr(out.data), dcp_dprev=_ptr(cp.x1.grad))
+            if _offer(b, "flags1", L.PAIR_DCOUPLE, operands, lambda q: instance(q) == 1):   # (a tile instance: the only family with the prologue)
                 self.dcp = cp
                 cp.dgrad_in_pair = self
                 self.bbytes += 3 * n * esz                             # y (the mask) read, d(y) and d(prev) written; d(z) read in place of d(y)
-            else:
-                b.flags1 &= ~L.PAIR_DCOUPLE
-                b.dcp_dz = b.dcp_w = b.dcp_mask = b.dcp_dprev = None
         # label by the instance that takes the launches (the backward descriptor, once it has its planes, decides for both)
-        probe = self.bdesc if self.bdesc is not None else f
-        if L.load().msau_conv_pair_instance(P.dtype, C.byref(probe)) == 2:
+        if instance(self.bdesc if self.bdesc is not None else f) == 2:
             self.key = f"rowpair_kernel<{T},C{x0.Cs}>"
         self.active = True
 
@@ -823,7 +827,7 @@ class LrnOp(Op):
         self.bwd_fused_into = None         # the PairOp whose data-gradient launch also runs this backward (MSAU_PAIR_LRN_BWD)
         y.lrn_producer = self
         prod = plan.ops[-1] if plan.ops else None
-        if isinstance(prod, ConvOp) and prod.out is a and os.environ.get("MSAU_FUSE_LRN", "1") != "0":
+        if isinstance(prod, ConvOp) and prod.out is a and _env_on("MSAU_FUSE_LRN"):
             prod.lrn = self
         plan.ops.append(self)
 
@@ -868,7 +872,7 @@ class PoolOp(Op):
         self.stage = plan._cur_stage
         self.fused_into = None             # the ConvOp / PairOp whose epilogue writes y and idx (MSAU_CONV_POOL)
         prod = plan.ops[-1] if plan.ops else None
-        if isinstance(prod, ConvOp) and prod.out is x and os.environ.get("MSAU_FUSE_POOL", "1") != "0":
+        if isinstance(prod, ConvOp) and prod.out is x and _env_on("MSAU_FUSE_POOL"):
             prod.pool = self
         plan.ops.append(self)
 
@@ -978,7 +982,7 @@ class ProjBwd:
         P, f, g, h = self.plan, self.f, self.g, self.h
         x = f.x1
         df, dg, dh = f.ddesc[0], g.ddesc[0], h.ddesc[0]
-        if P.dtype != L.BF16 or P.generic_only or os.environ.get("MSAU_ATTN_PROJ_FUSE", "1") == "0" or None in (df, dg, dh):
+        if P.dtype != L.BF16 or P.generic_only or not _env_on("MSAU_ATTN_PROJ_FUSE") or None in (df, dg, dh):
             return
         if not (x.C == x.Cs == 64 and f.out.Cs == g.out.Cs == 8 and h.out.Cs == 64 and f.k == g.k == h.k == 1
                 and g.x1 is x and h.x1 is x and f.x2 is None and g.x2 is None and h.x2 is None
@@ -1053,7 +1057,7 @@ class Plan:
         # The weight gradients form no dependency chain (each reads a finished out.grad and writes its own slabs),
         # so they run on a side stream beside the data-gradient chain.  Measured 2026-10-03 with the lean kernels:
         # 5.76 -> 5.20 ms/step (with the first, generic kernels it was 4 % slower: both chains were issue-bound).
-        self.overlap_wgrad = bool(cfg.get("overlap_wgrad", os.environ.get("MSAU_OVERLAP_WGRAD", "1") != "0")) and \
+        self.overlap_wgrad = bool(cfg.get("overlap_wgrad", _env_on("MSAU_OVERLAP_WGRAD"))) and \
             str(device).startswith("cuda")
         self._side = None
         # bit-reproducible training steps: costs 4 % (the LRN backward launches wait for the weight-gradient stream)
@@ -1288,6 +1292,7 @@ class Plan:
         for op in self.ops:
             if isinstance(op, ConvOp):
                 op.late_bind()
+                op._meta()
         for pr in self.pairs:
             pr.late_bind()
         boundary = self._boundary_launches()
@@ -1296,7 +1301,7 @@ class Plan:
         # branch: its launches go to the side stream -- idle during the forward -- beside the stage's decoder, and the consumer of its
         # output joins.  Training plans only (forward-only plans recycle activation buffers by sequential liveness).
         side_ops, join_ops = set(), set()
-        if self.training and self.overlap_wgrad and os.environ.get("MSAU_ATTN_SIDE", "1") != "0":
+        if self.training and self.overlap_wgrad and _env_on("MSAU_ATTN_SIDE"):
             for op in self.ops:
                 if isinstance(op, AttnCoreOp):
                     branch = [c for c in self.ops if isinstance(c, ConvOp) and c.out in (op.f, op.g, op.h)]
@@ -1371,7 +1376,7 @@ class Plan:
                                    device=self.device) if self.aux is not None else None
         if self.training:
             # label counts: a sample spread over K workgroups (msau_label_counts_split), the K integers added up by the CE launch
-            self.counts_k = max(1, min(16, 256 // self.B)) if self.B <= 1024 and os.environ.get("MSAU_LABEL_SPLIT", "1") != "0" else 1
+            self.counts_k = max(1, min(16, 256 // self.B)) if self.B <= 1024 and _env_on("MSAU_LABEL_SPLIT") else 1
             self.counts = torch.zeros((self.B * self.counts_k,), dtype=torch.int32, device=self.device)
             self.ce_ws = torch.zeros((int(L.load().msau_ce_ws_floats(self.B * HW)),), dtype=torch.float32, device=self.device)
             self.ce_multi_ws = torch.zeros((int(L.load().msau_ce_multi_ws_floats(self.B * HW)),), dtype=torch.float32, device=self.device)
@@ -1410,7 +1415,8 @@ class Plan:
             for t in op.writes():
                 if t.data is None:
                     take(t)
-            for t in set(op.reads()) | set(op.writes()):
+            for t in dict.fromkeys(op.reads() + op.writes()):       # (each once, in a fixed order: the order of release decides which
+                                                                    #  buffer the next producer takes, and a set's follows addresses)
                 if last_read.get(id(t), -1) <= i and (t in op.reads() or id(t) not in last_read):
                     release(t)
         for a in self.acts:                       # anything no op touches (custom builders)
@@ -1531,7 +1537,7 @@ class Plan:
         """the net's first conv if msau_conv2d takes it with MSAU_CONV_NCHW (the API's fp32 NCHW tensor as its input), else None"""
         if not hasattr(self, "_nchw_conv"):
             c = next((op for op in self.ops if isinstance(op, ConvOp) and op.x1 is self.x_in and op.x2 is None), None)
-            ok = c is not None and os.environ.get("MSAU_FIRST_NCHW", "1") != "0" and not (c.pair is not None and c.pair.active) \
+            ok = c is not None and _env_on("MSAU_FIRST_NCHW") and not (c.pair is not None and c.pair.active) \
                 and not (c.fdesc.flags & ~L.CONV_RELU_OUT)
             if ok:
                 info = _launch_info(self.dtype, c.fdesc)
@@ -1576,7 +1582,7 @@ class Plan:
         self._feed_nchw(None)
         if not hasattr(self, "_ids_conv"):
             c = next((op for op in self.ops if isinstance(op, ConvOp) and op.x1 is self.x_in and op.x2 is None), None)
-            ok = c is not None and os.environ.get("MSAU_IDS_DIRECT", "1") != "0" and not (c.pair is not None and c.pair.active)
+            ok = c is not None and _env_on("MSAU_IDS_DIRECT") and not (c.pair is not None and c.pair.active)
             if ok:
                 probe = L.ConvDesc.from_buffer_copy(c.fdesc)
                 probe.flags |= L.CONV_IDS
@@ -1614,7 +1620,7 @@ class Plan:
         if not hasattr(self, "_owner_conv"):
             c = next((op for op in self.ops if isinstance(op, ConvOp) and op.x1 is self.x_in and op.x2 is None), None)
             # (a ragged plan's conv carries MSAU_CONV_EXTENT: the box-list instance implements it -- info[7] & 128 with both flags set)
-            ok = c is not None and os.environ.get("MSAU_OWNER_CONV", "1") != "0" and not (c.pair is not None and c.pair.active) \
+            ok = c is not None and _env_on("MSAU_OWNER_CONV") and not (c.pair is not None and c.pair.active) \
                 and not (c.fdesc.flags & ~(L.CONV_RELU_OUT | L.CONV_EXTENT))
             if ok:
                 info = _launch_info(self.dtype, c.fdesc)
@@ -1818,7 +1824,7 @@ class Plan:
             labels = self._labels_buf
         lg, ax = self.logits, self.aux
         if lg.Cs <= 16 and self.B * HW < (1 << 31) and (ax is None or (ax.C, ax.Cs) == (lg.C, lg.Cs)) \
-                and os.environ.get("MSAU_CE_MULTI", "1") != "0":
+                and _env_on("MSAU_CE_MULTI"):
             K = self.counts_k
             if K > 1:
                 L.call("msau_label_counts_split", s, labels.data_ptr(), self.counts.data_ptr(), self.B, HW, K, key="msau_label_counts")
