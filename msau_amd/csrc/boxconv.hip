@@ -4,7 +4,8 @@
 // PARITY UNPINNED: the reference imports `BoxConv2d` from the third-party package `box_convolution`
 // (github shrubb/box-convolutions), which is neither vendored nor installed here and has no fixtures in the reference
 // tree.  The arithmetic below follows the published definition and is checked against this repository's own CPU
-// restatement (oracle/box_oracle.py) only -- "self-consistent", not "reference-identical".
+// restatement (oracle/box_oracle.py) only -- "self-consistent", not "reference-identical".  Every kernel here is held element by
+// element to a float64 reference of the definition below (tests/box_util.py, tests/test_box_ops_gpu.py).
 //
 // Definition used (pixels are unit squares [i, i+1) x [j, j+1), the image is zero outside):
 //   out[b, y, x, c*F + f] = 1/A * integral over rows [y + hmin, y + hmax + 1) x columns [x + wmin, x + wmax + 1) of in[b, ., ., c]
@@ -119,12 +120,17 @@ __global__ __launch_bounds__(256) void box_integral_rows_kernel(float* __restric
 
 __device__ __forceinline__ float lerp_ii(const float* __restrict__ plane, int W1, int i, float fi, int j, float fj, int H, int W) {
     // bilinear interpolation of II at (i + fi, j + fj), i in [0, H], j in [0, W]; taps beyond the last row / column have
-    // weight 0 there (fi = 0 when i == H), so clamp the index instead of branching
+    // weight 0 there (fi = 0 when i == H), so clamp the index instead of branching.
+    // Weighted form, (1 - f) a + f b, not a + f (b - a): the difference form rounds (b - a) at the size of the LARGER neighbour
+    // whatever its weight, and the integral image of a signed tensor (the output gradient) is not smooth near the image's top and
+    // left borders -- with f near 1 and |a| >> |b| that error is many ulps of the result.  Here every rounding is relative to a
+    // weighted tap; same number of multiply-adds.  (tests/box_util.py holds the filter to 2^-21 of sum |weight * II| / A.)
     const int i1 = min(i + 1, H), j1 = min(j + 1, W);
     const float a = plane[(int64_t)i * W1 + j], b = plane[(int64_t)i * W1 + j1];
     const float c = plane[(int64_t)i1 * W1 + j], d = plane[(int64_t)i1 * W1 + j1];
-    const float top = a + fj * (b - a), bot = c + fj * (d - c);
-    return top + fi * (bot - top);
+    const float gi = 1.f - fi, gj = 1.f - fj;
+    const float top = fmaf(fj, b, gj * a), bot = fmaf(fj, d, gj * c);
+    return fmaf(fi, bot, gi * top);
 }
 
 __device__ __forceinline__ void split(float v, float hi, int& i, float& f) {
@@ -194,6 +200,8 @@ __global__ __launch_bounds__(256) void box_filter_kernel(const float* __restrict
 //   dS/dhmax =  row integral of row floor(y + hmax + 1) over the box columns      dS/dhmin = -row integral of row floor(y + hmin)
 //   dS/dwmax =  column integral of column floor(x + wmax + 1) over the box rows   dS/dwmin = -column integral of column floor(x + wmin)
 //   dO/dhmax = (dS/dhmax - O * (wmax - wmin + 1)) / A   ... (A depends on the parameters through the normalisation)
+// One rule for every edge term: the derivative towards +, i.e. the line integral of row floor(p) when the edge position p
+// satisfies 0 <= p < H (column floor(p), 0 <= p < W), nothing otherwise; p == 0 counts as inside, p == H does not.
 constexpr int kPgRows = 8;
 template <typename T>
 __global__ __launch_bounds__(256) void box_pgrad_kernel(const float* __restrict__ ii, const float* __restrict__ params, const T* __restrict__ gout,
@@ -250,9 +258,10 @@ __global__ __launch_bounds__(256) void box_pgrad_kernel(const float* __restrict_
             const float F11 = A[0] + fi1 * (A[1] - A[0]), F21 = A[2] + fi2 * (A[3] - A[2]);
             const float F12 = Bc[0] + fi1 * (Bc[1] - Bc[0]), F22 = Bc[2] + fi2 * (Bc[3] - Bc[2]);
             const float O = (F22 - F12 - F21 + F11) * inv_area;
-            // an edge that is clamped to the image border does not move the integral
-            const bool r1in = r1 > 0.f && r1 < (float)H, r2in = r2 > 0.f && r2 < (float)H;
-            const bool c1in = c1 > 0.f && c1 < (float)W, c2in = c2 > 0.f && c2 < (float)W;
+            // the derivative TOWARDS +: an edge at p moves into row floor(p) (p == 0: row 0, as at every other integer, where
+            // fi == 0 selects row p); below 0 and from H on it is clamped to the border and does not move the integral
+            const bool r1in = r1 >= 0.f && r1 < (float)H, r2in = r2 >= 0.f && r2 < (float)H;
+            const bool c1in = c1 >= 0.f && c1 < (float)W, c2in = c2 >= 0.f && c2 < (float)W;
             const float dS_hmax = r2in ? (Bc[3] - Bc[2]) - (A[3] - A[2]) : 0.f;              // row integral along the bottom edge
             const float dS_hmin = r1in ? -((Bc[1] - Bc[0]) - (A[1] - A[0])) : 0.f;
             const float dS_wmax = c2in ? (dB[2] + fi2 * (dB[3] - dB[2])) - (dB[0] + fi1 * (dB[1] - dB[0])) : 0.f;   // column integral, right edge
