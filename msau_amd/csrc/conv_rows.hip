@@ -1830,7 +1830,11 @@ int msau_rowconv_launch(hipStream_t s, const msau_conv_desc* d, int kchunk, int 
 }
 
 // ---- weight gradients (msau_conv2d_wgrad descriptors)
-int msau_rowwgrad_takes(int dtype, const msau_wgrad_desc* d, int cch, int nchunks, int kextc) {
+// the number of the instance <RELU, KS> of rowwgrad8_kernel
+constexpr int rowwgrad_id(bool relu, int ks) { return 2 * ks + relu; }
+
+// The row-streaming instance msau_conv2d_wgrad launches for `d`, 0 = none.  cch / nchunks / kextc: the generic geometry.
+int msau_rowwgrad_case(int dtype, const msau_wgrad_desc* d, int cch, int nchunks, int kextc) {
     const RowsEnv& e = rows_env();
     if (!e.on || !e.wgrad || dtype != MSAU_BF16) return 0;
     if (d->C1 != 8 || d->C2 != 0 || d->Cout != 8 || (d->KH != 3 && d->KH != 4) || d->KW != d->KH || d->dil != 1 || d->stride != 1) return 0;
@@ -1840,10 +1844,10 @@ int msau_rowwgrad_takes(int dtype, const msau_wgrad_desc* d, int cch, int nchunk
     if (d->KH == 4 && !e.wgrad4) return 0;
     if ((int64_t)d->Hout * d->Wout * 16 >= (1ll << 31)) return 0;
     if ((int64_t)d->B * cdiv(d->Wout, 30) * cdiv(d->Hout, 8) < e.min_tasks) return 0;
-    return 1;
+    return rowwgrad_id(d->flags & MSAU_CONV_RELU_IN, d->KH);
 }
 
-int msau_rowwgrad_launch(hipStream_t s, const msau_wgrad_desc* d) {
+int msau_rowwgrad_launch(hipStream_t s, const msau_wgrad_desc* d, int which) {
     RowWgradArgs a;
     a.d = *d;
     a.nstrips = cdiv(d->Wout, 30);
@@ -1862,12 +1866,14 @@ int msau_rowwgrad_launch(hipStream_t s, const msau_wgrad_desc* d) {
     a.row_bytes = d->Wout * 16;
     a.img_bytes = (unsigned)d->Hout * (unsigned)a.row_bytes;
     a.kext = d->KH == 4 ? 144 : 80;
-    const bool relu = d->flags & MSAU_CONV_RELU_IN;
-    if (d->KH == 4) {
-        if (relu) hipLaunchKernelGGL((rowwgrad8_kernel<true, 4>), dim3(d->nslabs), dim3(64 * WG_WAVES), 0, s, a);
-        else hipLaunchKernelGGL((rowwgrad8_kernel<false, 4>), dim3(d->nslabs), dim3(64 * WG_WAVES), 0, s, a);
-    } else if (relu) hipLaunchKernelGGL((rowwgrad8_kernel<true>), dim3(d->nslabs), dim3(64 * WG_WAVES), 0, s, a);
-    else hipLaunchKernelGGL((rowwgrad8_kernel<false>), dim3(d->nslabs), dim3(64 * WG_WAVES), 0, s, a);
+    const dim3 grid(d->nslabs), block(64 * WG_WAVES);
+    switch (which) {
+        case rowwgrad_id(false, 3): hipLaunchKernelGGL((rowwgrad8_kernel<false, 3>), grid, block, 0, s, a); break;
+        case rowwgrad_id(true, 3): hipLaunchKernelGGL((rowwgrad8_kernel<true, 3>), grid, block, 0, s, a); break;
+        case rowwgrad_id(false, 4): hipLaunchKernelGGL((rowwgrad8_kernel<false, 4>), grid, block, 0, s, a); break;
+        case rowwgrad_id(true, 4): hipLaunchKernelGGL((rowwgrad8_kernel<true, 4>), grid, block, 0, s, a); break;
+        default: return msau_set_error(MSAU_ERR_ARG, "rowwgrad: no instance %d", which);
+    }
     MSAU_CHECK_LAUNCH("rowwgrad8_kernel");
     return 0;
 }

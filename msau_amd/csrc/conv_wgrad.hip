@@ -11,6 +11,10 @@
 // writes ONE slab at the end: no atomics, results are bitwise reproducible for a fixed nslabs.
 //
 // Replaces autograd's conv2d weight/bias gradient reached from train_chargrid_funsd_msau.py:57.
+//
+// Behind the kernel: wgrad_geom (the generic geometry), WGRAD_TILE_TABLE (this kernel's instances), wgrad_route (which family and
+// instance runs a descriptor: this kernel, or one of wgrad_lean.hip / conv_rows.hip / ownerconv.hip) and the entry points, each of
+// which asks wgrad_route once.
 #include "msau_common.h"
 
 namespace {
@@ -254,70 +258,76 @@ int launch_wgrad(hipStream_t s, const WArgs& a, dim3 grid, int lds) {
     return 0;
 }
 
-template <typename T, int CTN>
-int launch_wgrad_nkw(hipStream_t s, const WArgs& a, int NKW, dim3 grid, int lds) {
-    if constexpr (CTN == 8) {
-        switch (NKW) {
-            case 1: return launch_wgrad<T, CTN, 1>(s, a, grid, lds);
-            case 2: return launch_wgrad<T, CTN, 2>(s, a, grid, lds);
-            case 3: return launch_wgrad<T, CTN, 3>(s, a, grid, lds);
-            default: return launch_wgrad<T, CTN, 5>(s, a, grid, lds);
-        }
-    } else {
-        switch (NKW) {
-            case 1: return launch_wgrad<T, CTN, 1>(s, a, grid, lds);
-            case 2: return launch_wgrad<T, CTN, 2>(s, a, grid, lds);
-            case 3: return launch_wgrad<T, CTN, 3>(s, a, grid, lds);
-            case 5: return launch_wgrad<T, CTN, 5>(s, a, grid, lds);
-            default: return launch_wgrad<T, CTN, 10>(s, a, grid, lds);
-        }
-    }
-}
+// WGRAD_TILE_TABLE is the one list of the instances wgrad_kernel<T, CTN, NKW> is compiled for, X(CTN, NKW, fp32 too), read by
+// wtile_instance() both as the query "does this instance exist" (wgrad_route) and as the launch switch (msau_conv2d_wgrad).
+// fp32 launches in slices of at most 64 output channels, i.e. CTN <= 4: no descriptor names a wider fp32 instance.
+#define WGRAD_TILE_TABLE(X)                                      \
+    X(1, 1, 1) X(1, 2, 1) X(1, 3, 1) X(1, 5, 1) X(1, 10, 1)        \
+    X(2, 1, 1) X(2, 2, 1) X(2, 3, 1) X(2, 5, 1) X(2, 10, 1)        \
+    X(4, 1, 1) X(4, 2, 1) X(4, 3, 1) X(4, 5, 1) X(4, 10, 1)        \
+    X(8, 1, 0) X(8, 2, 0) X(8, 3, 0) X(8, 5, 0)
 
+// a == nullptr: 1 if the instance exists for T, else 0.  Otherwise: launch it (0, or an error -- never another instance)
 template <typename T>
-int launch_wgrad_ct(hipStream_t s, const WArgs& a, int CTN, int NKW, dim3 grid, int lds) {
-    switch (CTN) {
-        case 1: return launch_wgrad_nkw<T, 1>(s, a, NKW, grid, lds);
-        case 2: return launch_wgrad_nkw<T, 2>(s, a, NKW, grid, lds);
-        case 3: case 4: return launch_wgrad_nkw<T, 4>(s, a, NKW, grid, lds);
-        default: return launch_wgrad_nkw<T, 8>(s, a, NKW, grid, lds);
+int wtile_instance(int CTN, int NKW, hipStream_t s, const WArgs* a, dim3 grid, int lds) {
+    switch (CTN * 16 + NKW) {
+#define WTILE_ROW(CT, NK, F32)                                                                                  \
+        case CT * 16 + NK:                                                                                      \
+            if constexpr (F32 || sizeof(T) == 2) return a ? launch_wgrad<T, CT, NK>(s, *a, grid, lds) : 1;      \
+            break;
+        WGRAD_TILE_TABLE(WTILE_ROW)
+#undef WTILE_ROW
     }
+    return a ? msau_set_error(MSAU_ERR_ARG, "wgrad: no instance CTN %d NKW %d", CTN, NKW) : 0;
 }
 
-}  // namespace
-
-// wgrad_lean.hip: compile-time-specialised instances
-int msau_wgrad_lean_instance(int dtype, const msau_wgrad_desc* d, int cch);
-int msau_wgrad_lean_try(hipStream_t s, int dtype, const msau_wgrad_desc* d, int cch, int nchunks, int kextc);
-int msau_wgrad_lean_group(hipStream_t s, int dtype, const msau_wgrad_desc* const* ds, int n, int cch, int nchunks, int kextc);
-
-namespace {
-
-// the one routing decision (include/msau_hip.h, msau_wgrad_route): family, and for the generic kernel its instance and slices
-enum { WF_NONE = 0, WF_TILE = 1, WF_LEAN = 2, WF_SPECIAL = 3, WF_IN64 = 4, WF_IN64_IDS = 5, WF_ROWS = 6, WF_OWNER = 7 };
-struct WRoute { int family, CTN, NKW, slices; };
-
+// The one routing decision (include/msau_hip.h, msau_wgrad_route; DESIGN.md, "Weight-gradient routing"): the geometry, the tiles,
+// the family and its instance.  Pure host arithmetic on the descriptor's numbers: no pointer is read.  Every entry point below calls
+// it once and reads the answer; a family's _launch gets exactly the instance named here.
 int wgrad_route(int dtype, const msau_wgrad_desc* d, WGeom* g, WRoute* r) {
-    *r = WRoute{WF_NONE, 0, 0, 0};
-    int rc = wgrad_geom(dtype, d, g);
+    *r = WRoute{};
+    const int rc = wgrad_geom(dtype, d, g);
     if (rc) return rc;
-    r->slices = 1;
-    if (d->flags & MSAU_CONV_OWNER) { r->family = WF_OWNER; return 0; }       // ownerconv.hip: per-box sums of g instead of a painted input tensor
-    if (msau_rowwgrad_takes(dtype, d, g->cch, g->nchunks, g->kextc)) { r->family = WF_ROWS; return 0; }      // conv_rows.hip: every row of x and g read once
-    const int inst = d->Cout <= g->slice ? msau_wgrad_lean_instance(dtype, d, g->cch) : 0;
-    if (d->flags & MSAU_CONV_IDS) {
-        r->slices = 0;
-        MSAU_CHECK_ARG(inst == WF_IN64, "wgrad: MSAU_CONV_IDS is implemented by the bf16 64 -> 8 3x3 instance only");
-        MSAU_CHECK_ARG(g->nchunks == 1 && !d->C2, "wgrad: MSAU_CONV_IDS needs one 64-channel one-hot source");
-        r->family = WF_IN64_IDS; r->slices = 1;
-        return 0;
+    r->cch = g->cch; r->nchunks = g->nchunks; r->kextc = g->kextc;
+    r->tiles_x = cdiv(d->Wout, 16); r->tiles_y = cdiv(d->Hout, 16); r->ntiles = d->B * r->tiles_x * r->tiles_y;
+    int inst;
+    if (d->flags & MSAU_CONV_OWNER) {                                          // ownerconv.hip: per-box sums of g instead of a painted input tensor
+        MSAU_CHECK_ARG(msau_ownerconv_wgrad_case(dtype, d, g->cch, g->nchunks, g->kextc),
+                       "wgrad: MSAU_CONV_OWNER is the 3x3 C -> 8 conv of the net's input, no other flag but EXTENT");
+        r->family = WF_OWNER;
+    } else if ((inst = msau_rowwgrad_case(dtype, d, g->cch, g->nchunks, g->kextc))) {      // conv_rows.hip: every row of x and g read once
+        r->family = WF_ROWS; r->inst = inst;
+    } else if ((inst = msau_wgrad_lean_case(dtype, d, g->cch, g->kextc)) || (d->flags & MSAU_CONV_IDS)) {
+        const int family = inst & 7;                                           // WF_LEAN, WF_SPECIAL or WF_IN64
+        if (d->flags & MSAU_CONV_IDS) {
+            MSAU_CHECK_ARG(family == WF_IN64, "wgrad: MSAU_CONV_IDS is implemented by the bf16 64 -> 8 3x3 instance only");
+            MSAU_CHECK_ARG(g->nchunks == 1 && !d->C2, "wgrad: MSAU_CONV_IDS needs one 64-channel one-hot source");
+        }
+        r->family = (d->flags & MSAU_CONV_IDS) ? WF_IN64_IDS : family; r->inst = inst;
+    } else {
+        const int CTN = g->CTN == 3 ? 4 : (g->CTN > 4 ? 8 : g->CTN);          // CTN as instantiated: the one place that maps it
+        MSAU_CHECK_ARG(dtype == MSAU_F32 ? wtile_instance<float>(CTN, g->NKW, nullptr, nullptr, dim3(), 0)
+                                         : wtile_instance<bf16_t>(CTN, g->NKW, nullptr, nullptr, dim3(), 0),
+                       "wgrad: Cout %d with K %d unsupported", d->Cout, g->kextc);
+        r->family = WF_TILE; r->CTN = CTN; r->NKW = g->NKW;
     }
-    if (inst) { r->family = inst; return 0; }
-    r->slices = 0;
-    const int CTN = g->CTN == 3 ? 4 : (g->CTN > 4 ? 8 : g->CTN);              // CTN as instantiated (3 -> 4)
-    MSAU_CHECK_ARG(!(CTN == 8 && g->NKW > 5), "wgrad: Cout %d with K %d unsupported", d->Cout, g->kextc);
-    r->family = WF_TILE; r->CTN = CTN; r->NKW = g->NKW; r->slices = cdiv(d->Cout, g->slice);
+    r->slices = r->family == WF_TILE ? cdiv(d->Cout, g->slice) : 1;
     return 0;
+}
+
+// written once: every family but the box-list one fills d->nslabs slabs from the tiles
+int wgrad_check_nslabs(const msau_wgrad_desc* d, const WRoute& r) {
+    MSAU_CHECK_ARG(d->nslabs >= 1 && d->nslabs <= r.ntiles, "wgrad: nslabs %d not in [1,%d]", d->nslabs, r.ntiles);
+    return 0;
+}
+
+// up to 4 weight gradients share a grid (msau_conv2d_wgrad_group) when the first is a lean or dilated / stride-2 instance (the row
+// kernel and the 64 -> 8 one run one layer per launch) and the others have its shape
+bool wgrad_groupable(const WRoute& r, const msau_wgrad_desc* a, const msau_wgrad_desc* b) {
+    if (r.family != WF_LEAN && r.family != WF_SPECIAL) return false;
+    return a->B == b->B && a->Hin == b->Hin && a->Win == b->Win && a->Hout == b->Hout && a->Wout == b->Wout && a->C1 == b->C1 &&
+           a->C2 == b->C2 && a->Cout == b->Cout && a->KH == b->KH && a->KW == b->KW && a->dil == b->dil && a->pad_t == b->pad_t &&
+           a->pad_l == b->pad_l && a->stride == b->stride && a->nslabs == b->nslabs;
 }
 
 }  // namespace
@@ -325,10 +335,10 @@ int wgrad_route(int dtype, const msau_wgrad_desc* d, WGeom* g, WRoute* r) {
 extern "C" int msau_wgrad_route(int dtype, const msau_wgrad_desc* d, int32_t info[8]) {
     MSAU_CHECK_ARG(d && info, "wgrad_route: null pointer");
     for (int i = 0; i < 8; ++i) info[i] = 0;
-    WGeom g = {};                                                              // (filled whenever the geometry exists, refused or not)
+    WGeom g;
     WRoute r;
     const int rc = wgrad_route(dtype, d, &g, &r);
-    info[5] = g.cch; info[6] = g.nchunks; info[7] = g.kextc;
+    info[5] = r.cch; info[6] = r.nchunks; info[7] = r.kextc;                   // (filled whenever the geometry exists, refused or not)
     if (rc) return rc;
     info[0] = r.family; info[1] = r.CTN; info[2] = r.NKW; info[3] = r.family == WF_TILE && g.compact; info[4] = r.slices;
     return 0;
@@ -337,12 +347,11 @@ extern "C" int msau_wgrad_route(int dtype, const msau_wgrad_desc* d, int32_t inf
 extern "C" int msau_wgrad_geometry(int dtype, const msau_wgrad_desc* d, msau_wgrad_geom* out) {
     WGeom g;
     WRoute r;
-    int rc = wgrad_geom(dtype, d, &g);
-    if (rc) return rc;
-    out->cch = g.cch; out->nchunks = g.nchunks; out->kext = g.kextc;
-    out->max_slabs = d->B * cdiv(d->Hout, 16) * cdiv(d->Wout, 16);
-    out->slab_bytes = (int64_t)g.nchunks * d->Cout * g.kextc * 4;
-    wgrad_route(dtype, d, &g, &r);                                             // (a descriptor no kernel takes: lean 0)
+    const int rc = wgrad_route(dtype, d, &g, &r);
+    if (!r.kextc) return rc;                                                   // no geometry.  (One that no kernel takes: lean 0)
+    out->cch = r.cch; out->nchunks = r.nchunks; out->kext = r.kextc;
+    out->max_slabs = r.ntiles;
+    out->slab_bytes = (int64_t)r.nchunks * d->Cout * r.kextc * 4;
     out->lean = r.family == WF_ROWS ? 2 : r.family >= WF_LEAN && r.family <= WF_IN64_IDS;
     out->reserved = 0;
     return 0;
@@ -356,15 +365,10 @@ extern "C" int msau_conv2d_wgrad(void* stream, int dtype, const msau_wgrad_desc*
     int rc = wgrad_route(dtype, d, &g, &r);
     if (rc) return rc;
     hipStream_t s = static_cast<hipStream_t>(stream);
-    if (r.family == WF_OWNER) return msau_ownerconv_wgrad(s, dtype, d, g.cch, g.nchunks, g.kextc);
-    const int tiles_x = cdiv(d->Wout, 16), tiles_y = cdiv(d->Hout, 16), ntiles = d->B * tiles_x * tiles_y;
-    MSAU_CHECK_ARG(d->nslabs >= 1 && d->nslabs <= ntiles, "wgrad: nslabs %d not in [1,%d]", d->nslabs, ntiles);
-    if (r.family == WF_ROWS) return msau_rowwgrad_launch(s, d);
-    if (r.family != WF_TILE) {
-        rc = msau_wgrad_lean_try(s, dtype, d, g.cch, g.nchunks, g.kextc);
-        if (rc == 0) return msau_set_error(MSAU_ERR_ARG, "wgrad: the route names family %d, wgrad_lean.hip has no instance", r.family);
-        return rc < 0 ? rc : 0;
-    }
+    if (r.family == WF_OWNER) return msau_ownerconv_wgrad_launch(s, dtype, d, &r);       // (its slabs are parts of the box range: msau_owner_slabs)
+    if ((rc = wgrad_check_nslabs(d, r))) return rc;
+    if (r.family == WF_ROWS) return msau_rowwgrad_launch(s, d, r.inst);
+    if (r.family != WF_TILE) return msau_wgrad_lean_launch(s, dtype, &d, 1, &r);
     dim3 grid(d->nslabs, g.nchunks);
     // wide outputs: one launch per slice; every slice writes its rows of the same slabs
     for (int co0 = 0; co0 < d->Cout; co0 += g.slice) {
@@ -375,41 +379,33 @@ extern "C" int msau_conv2d_wgrad(void* stream, int dtype, const msau_wgrad_desc*
         a.cch = g.cch; a.nchunks = g.nchunks; a.kreal = g.kreal; a.kextc = g.kextc; a.NKT = g.NKT;
         a.TIH = g.TIH; a.TIW = g.TIW; a.PSx = g.PSx; a.PSg = g.PSg;
         a.x_bytes = g.x_bytes; a.g_bytes = g.g_bytes; a.tab_bytes = g.tab_bytes;
-        a.tiles_x = tiles_x; a.tiles_y = tiles_y; a.ntiles = ntiles;
-        rc = dtype == MSAU_F32 ? launch_wgrad_ct<float>(s, a, r.CTN, r.NKW, grid, g.total) : launch_wgrad_ct<bf16_t>(s, a, r.CTN, r.NKW, grid, g.total);
+        a.tiles_x = r.tiles_x; a.tiles_y = r.tiles_y; a.ntiles = r.ntiles;
+        rc = dtype == MSAU_F32 ? wtile_instance<float>(r.CTN, r.NKW, s, &a, grid, g.total) : wtile_instance<bf16_t>(r.CTN, r.NKW, s, &a, grid, g.total);
         if (rc) return rc;
     }
     return 0;
 }
 
 // ---- grouped launch: up to 4 weight gradients of one shape in one grid (include/msau_hip.h)
-extern "C" int msau_owner_slabs(const msau_wgrad_desc* d) { return d ? msau_ownerconv_slabs(d) : 0; }
-
 extern "C" int msau_conv2d_wgrad_groupable(int dtype, const msau_wgrad_desc* a, const msau_wgrad_desc* b) {
     if (!a || !b) return 0;
     WGeom g;
     WRoute r;
-    if (wgrad_route(dtype, a, &g, &r)) return 0;
-    if (r.family != WF_LEAN && r.family != WF_SPECIAL) return 0;      // (the row kernel and the 64 -> 8 one run one layer per launch)
-    return a->B == b->B && a->Hin == b->Hin && a->Win == b->Win && a->Hout == b->Hout && a->Wout == b->Wout && a->C1 == b->C1 &&
-           a->C2 == b->C2 && a->Cout == b->Cout && a->KH == b->KH && a->KW == b->KW && a->dil == b->dil && a->pad_t == b->pad_t &&
-           a->pad_l == b->pad_l && a->stride == b->stride && a->nslabs == b->nslabs;
+    return wgrad_route(dtype, a, &g, &r) == 0 && wgrad_groupable(r, a, b);
 }
 
 extern "C" int msau_conv2d_wgrad_group(void* stream, int dtype, const msau_wgrad_desc* const* ds, int n) {
     MSAU_CHECK_ARG(ds && n >= 1 && n <= 4, "wgrad_group: 1..4 launches");
+    WGeom g;
+    WRoute r;
+    int rc = 0;
     for (int i = 0; i < n; ++i) {
         MSAU_CHECK_ARG(ds[i] && ds[i]->x1 && ds[i]->g && ds[i]->slabs && (ds[i]->C2 == 0 || ds[i]->x2), "wgrad_group: null pointer");
-        MSAU_CHECK_ARG(i == 0 || msau_conv2d_wgrad_groupable(dtype, ds[0], ds[i]), "wgrad_group: launch %d differs in shape from launch 0", i);
+        if (i == 0 && n > 1) rc = wgrad_route(dtype, ds[0], &g, &r);
+        MSAU_CHECK_ARG(i == 0 || (rc == 0 && wgrad_groupable(r, ds[0], ds[i])), "wgrad_group: launch %d differs in shape from launch 0", i);
     }
     if (n == 1) return msau_conv2d_wgrad(stream, dtype, ds[0]);
-    WGeom g;
-    int rc = wgrad_geom(dtype, ds[0], &g);
-    if (rc) return rc;
-    const int ntiles = ds[0]->B * cdiv(ds[0]->Wout, 16) * cdiv(ds[0]->Hout, 16);
-    MSAU_CHECK_ARG(ds[0]->nslabs >= 1 && ds[0]->nslabs <= ntiles, "wgrad: nslabs %d not in [1,%d]", ds[0]->nslabs, ntiles);
-    rc = msau_wgrad_lean_group(static_cast<hipStream_t>(stream), dtype, ds, n, g.cch, g.nchunks, g.kextc);
-    if (rc == 1) return 0;
-    if (rc < 0) return rc;
-    return msau_set_error(MSAU_ERR_ARG, "wgrad_group: no shared-grid instance for this shape");
+    if ((rc = wgrad_check_nslabs(ds[0], r))) return rc;
+    return msau_wgrad_lean_launch(static_cast<hipStream_t>(stream), dtype, ds, n, &r);
 }
+

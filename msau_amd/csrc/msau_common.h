@@ -48,8 +48,6 @@ int msau_rowpair_launch(hipStream_t s, const msau_conv_pair_desc* d, const PairR
 // ownerconv.hip: the first conv fed with box lists (MSAU_CONV_OWNER)
 int msau_ownerconv_takes(int dtype, const msau_conv_desc* d);
 int msau_ownerconv_fwd(hipStream_t s, int dtype, const msau_conv_desc* d);
-int msau_ownerconv_wgrad(hipStream_t s, int dtype, const msau_wgrad_desc* d, int cch, int nchunks, int kext);
-int msau_ownerconv_slabs(const msau_wgrad_desc* d);
 // The instance families of msau_conv2d besides the tile kernel (conv_route in conv.hip picks one; DESIGN.md, "conv2d routing").
 // <family>_case: the number of the instance that runs the descriptor, 0 = none; pure host arithmetic.  <family>_launch: launches
 // exactly that instance -- a case it has no instance for is an MSAU_ERR_ARG error, never "try the next family".
@@ -66,9 +64,26 @@ int msau_conv_lean_launch(hipStream_t s, int dtype, const msau_conv_desc* d, int
 // conv_first.hip: the first conv fed with the fp32 NCHW input tensor (MSAU_CONV_NCHW); one instance
 int msau_firstconv_takes(int dtype, const msau_conv_desc* d);
 int msau_firstconv_launch(hipStream_t s, int dtype, const msau_conv_desc* d, int real_channels);
-// ... and of msau_conv2d_wgrad for the 8 -> 8 3x3 weight gradients (dispatched from conv_wgrad.hip)
-int msau_rowwgrad_takes(int dtype, const msau_wgrad_desc* d, int cch, int nchunks, int kextc);
-int msau_rowwgrad_launch(hipStream_t s, const msau_wgrad_desc* d);
+// ---- msau_conv2d_wgrad (wgrad_route in conv_wgrad.hip picks the family and the instance; DESIGN.md, "Weight-gradient routing").
+// The same contract: _case and _launch of the families besides the tile kernel, which is conv_wgrad.hip's own.
+enum { WF_NONE = 0, WF_TILE = 1, WF_LEAN = 2, WF_SPECIAL = 3, WF_IN64 = 4, WF_IN64_IDS = 5, WF_ROWS = 6, WF_OWNER = 7 };   // = info[0] of msau_wgrad_route
+struct WRoute {
+    int family, inst;                            // WF_*, the instance's number in its family's table (lean, special, 64 -> 8, rows; else 0)
+    int CTN, NKW, slices;                        // tile family: its instance and the launches of one call
+    int cch, nchunks, kextc;                     // the generic geometry (wgrad_geom): all 0 = there is none
+    int tiles_x, tiles_y, ntiles;                // 16 x 16 output tiles per image and of the batch = the most slabs a launch can fill
+};
+// wgrad_lean.hip: the compile-time-specialised instances, the dilated / stride-2 ones and the 64 -> 8 kernel; the number's low three
+// bits are the family (WF_LEAN, WF_SPECIAL, WF_IN64).  _launch: ds[0..n) share one grid, n > 1 for WF_LEAN / WF_SPECIAL only
+int msau_wgrad_lean_case(int dtype, const msau_wgrad_desc* d, int cch, int kextc);
+int msau_wgrad_lean_launch(hipStream_t s, int dtype, const msau_wgrad_desc* const* ds, int n, const WRoute* r);
+// conv_rows.hip: the row-streaming 8 -> 8 instances <RELU, KS>
+int msau_rowwgrad_case(int dtype, const msau_wgrad_desc* d, int cch, int nchunks, int kextc);
+int msau_rowwgrad_launch(hipStream_t s, const msau_wgrad_desc* d, int which);
+// ownerconv.hip: the first conv fed with box lists (MSAU_CONV_OWNER); one instance.  _case reads no pointer: the context behind
+// d->x1 is the launch's to check
+int msau_ownerconv_wgrad_case(int dtype, const msau_wgrad_desc* d, int cch, int nchunks, int kextc);
+int msau_ownerconv_wgrad_launch(hipStream_t s, int dtype, const msau_wgrad_desc* d, const WRoute* r);
 
 #define MSAU_CHECK_ARG(cond, ...)                                   \
     do {                                                            \

@@ -306,27 +306,32 @@ int msau_ownerconv_fwd(hipStream_t s, int dtype, const msau_conv_desc* d) {
 }
 
 // slabs an MSAU_CONV_OWNER weight gradient writes (= ways the box range is split): what the slab reduction must be told
-int msau_ownerconv_slabs(const msau_wgrad_desc* d) {
+extern "C" int msau_owner_slabs(const msau_wgrad_desc* d) {
+    if (!d) return 0;
     int k = 96;                                                     // (32: 50 us for the 2605 boxes of the bench's cfg-4 batch; each part is a dependent chain of loads)
     if (k > d->nslabs) k = d->nslabs;
     return k < 1 ? 1 : k;
 }
 
-int msau_ownerconv_wgrad(hipStream_t s, int dtype, const msau_wgrad_desc* d, int cch, int nchunks, int kext) {
+// 1: the one instance runs `d` -- the 3x3 C -> 8 conv of the net's input, no other flag but EXTENT; 0: wgrad_route refuses it
+int msau_ownerconv_wgrad_case(int dtype, const msau_wgrad_desc* d, int cch, int nchunks, int kext) {
+    return d->Cout == 8 && d->C2 == 0 && d->KH == 3 && d->KW == 3 && d->dil == 1 && d->stride == 1 && d->pad_t == 1 && d->pad_l == 1 &&
+           kext >= 9 * cch + 1 && cch * nchunks >= d->C1 && !(d->flags & ~(MSAU_CONV_OWNER | MSAU_CONV_EXTENT));
+}
+
+int msau_ownerconv_wgrad_launch(hipStream_t s, int dtype, const msau_wgrad_desc* d, const WRoute* r) {
+    const int cch = r->cch, nchunks = r->nchunks, kext = r->kextc;
     const msau_owner_ctx* c = static_cast<const msau_owner_ctx*>(d->x1);
     MSAU_CHECK_ARG(c && c->owner && c->feats && c->sums && c->csum && c->csum_blocks >= 1 && c->n_boxes >= 0 && (c->n_boxes == 0 || c->boxes) &&
                    c->C > 0 && c->C <= d->C1, "wgrad: bad MSAU_CONV_OWNER context");
-    MSAU_CHECK_ARG(d->Cout == 8 && d->C2 == 0 && d->KH == 3 && d->KW == 3 && d->dil == 1 && d->stride == 1 && d->pad_t == 1 && d->pad_l == 1 &&
-                   kext >= 9 * cch + 1 && cch * nchunks >= d->C1 && !(d->flags & ~(MSAU_CONV_OWNER | MSAU_CONV_EXTENT)),
-                   "wgrad: MSAU_CONV_OWNER is the 3x3 C -> 8 conv of the net's input, no other flag but EXTENT");
     // MSAU_CONV_EXTENT (ragged batch) needs no extents here: g is 0 outside them (the plan's invariant) and the owner map of
     // msau_raster_owner_ext is -1 there, so the sums are those of the dense launch; only the ORDER of the per-box sums is anchored on the
     // canvas (owner_sums_kernel<ANCH>), so that the part of a box outside its document cannot change a bit
     const int64_t npix = (int64_t)d->B * d->Hout * d->Wout;
     int rc = msau_channel_sum(s, dtype, d->g, npix, 8, c->csum, c->csum_blocks);
     if (rc) return rc;
-    // the box range is split `ksplit` ways: each part writes one slab, the slab reduction (told nslabs = msau_ownerconv_slabs) adds them up
-    const int ksplit = msau_ownerconv_slabs(d);
+    // the box range is split `ksplit` ways: each part writes one slab, the slab reduction (told nslabs = msau_owner_slabs) adds them up
+    const int ksplit = msau_owner_slabs(d);
     const size_t slab_elems = (size_t)nchunks * 8 * kext;
     hipError_t e = hipMemsetAsync(d->slabs, 0, (size_t)ksplit * slab_elems * 4, s);      // padded channels, ones / padding columns
     if (e != hipSuccess) return msau_set_error(MSAU_ERR_HIP, "wgrad: memset: %s", hipGetErrorString(e));

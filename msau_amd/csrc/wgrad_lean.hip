@@ -1,7 +1,9 @@
-// Lean instances of the weight-gradient kernel (see conv_wgrad.hip for the algorithm): stride 1, no
-// dilation, k in {1,3}, channel counts per chunk known at compile time, so every divisor, LDS stride
-// and tap offset is a constant and the column-group offsets live in registers instead of an LDS table.
+// Lean instances of the weight-gradient kernel (see conv_wgrad.hip for the algorithm): kernel size, dilation, stride and
+// the channel counts per chunk known at compile time, so every divisor, LDS stride and tap offset is a constant and the
+// column-group offsets live in registers instead of an LDS table; and the role-swapped 64 -> 8 kernel of the net's first conv.
 // Same slab layout as wgrad_kernel: slabs[workgroup][chunk][Cout][kext], k = [tap][channel] + ones column.
+// Host side (behind the kernels): WLEAN_TABLE lists the instances, msau_wgrad_lean_case names the one that runs a descriptor and
+// msau_wgrad_lean_launch launches exactly it (msau_common.h has the contract; wgrad_route in conv_wgrad.hip is the caller).
 #include "msau_common.h"
 #include <cstdlib>
 
@@ -561,21 +563,16 @@ __global__ __launch_bounds__(256) void wgrad_in64_kernel(const WLeanArgs a) {
 }
 
 int launch_wgrad_in64(hipStream_t s, const WLeanArgs& a) {
-    if (a.kextc != 592) return 0;
-    if (a.d.flags & MSAU_CONV_IDS) {
-        if (a.nchunks != 1 || a.d.C2) return msau_set_error(MSAU_ERR_ARG, "wgrad: MSAU_CONV_IDS needs one 64-channel one-hot source");
-        hipLaunchKernelGGL(wgrad_in64_kernel<true>, dim3(a.d.nslabs, 1), dim3(256), WIn64::LDS, s, a);
-    } else
-    hipLaunchKernelGGL(wgrad_in64_kernel<false>, dim3(a.d.nslabs, a.nchunks), dim3(256), WIn64::LDS, s, a);
+    if (a.d.flags & MSAU_CONV_IDS) hipLaunchKernelGGL(wgrad_in64_kernel<true>, dim3(a.d.nslabs, 1), dim3(256), WIn64::LDS, s, a);
+    else hipLaunchKernelGGL(wgrad_in64_kernel<false>, dim3(a.d.nslabs, a.nchunks), dim3(256), WIn64::LDS, s, a);
     MSAU_CHECK_LAUNCH("wgrad_in64_kernel");
-    return 1;
+    return 0;
 }
 
 template <typename T, int C8, int CO8, int KS, int DIL = 1, int STRIDE = 1>
 int launch_wlean(hipStream_t s, const WLeanMulti& m, int n) {
     using Cfg = WLeanCfg<T, C8, CO8, KS, DIL, STRIDE>;
     const WLeanArgs& a = m.a[0];
-    if (Cfg::KEXT != a.kextc) return 0;                              // geometry disagrees with the generic planner
     static bool attr_set = false;
     if (!attr_set && Cfg::LDS > 60 * 1024) {
         hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&wgrad_lean_kernel<T, C8, CO8, KS, DIL, STRIDE>),
@@ -585,109 +582,89 @@ int launch_wlean(hipStream_t s, const WLeanMulti& m, int n) {
     }
     hipLaunchKernelGGL((wgrad_lean_kernel<T, C8, CO8, KS, DIL, STRIDE>), dim3(a.d.nslabs, a.nchunks, n), dim3(Cfg::NTH), Cfg::LDS, s, m);
     MSAU_CHECK_LAUNCH("wgrad_lean_kernel");
-    return 1;
-}
-
-template <typename T, int KS>
-int wlean_dispatch(hipStream_t s, const WLeanMulti& m, int n, int c8, int co8) {
-#define WL_CASE(C, O) if (c8 == C && co8 == O) return launch_wlean<T, C, O, KS>(s, m, n);
-    WL_CASE(1, 1) WL_CASE(1, 2) WL_CASE(2, 1) WL_CASE(2, 2) WL_CASE(2, 4) WL_CASE(4, 2) WL_CASE(4, 4) WL_CASE(8, 1)
-    WL_CASE(4, 8) WL_CASE(8, 4) WL_CASE(8, 8)
-#undef WL_CASE
     return 0;
 }
 
-// dilated 3x3 (encoder level-entry convs) and the stride-2 form (transposed-conv weight gradient, roles swapped)
+// The number of an instance packs its family (the low three bits: WF_LEAN, WF_SPECIAL or WF_IN64) and its template arguments.
+// cch <= 64 and KS <= 7 by wgrad_geom; msau_wgrad_lean_case keeps dil inside its four bits.
+constexpr int wlean_id(int fam, int c8, int co8, int ks, int dil, int stride) {
+    return fam | c8 << 3 | ks << 7 | stride << 10 | dil << 12 | co8 << 16;
+}
+// WLEAN_TABLE is the one list of the instances that exist, X(family, C8, CO8, KS, DIL, STRIDE, fp32 too): the eleven channel shapes
+// (ten of them in WLEAN_SHAPES, 64 -> 64 beside them) at 1x1 and 3x3 and 8 -> 8 at 4x4; the dilated 3x3 (encoder level-entry convs) and the stride-2 form (transposed-conv weight gradient,
+// roles swapped); the 64 -> 8 kernel (wgrad_in64_kernel, not a wgrad_lean_kernel).  Not fp32: no fp32 descriptor has a chunk of the
+// size -- wgrad_geom stages 64 channels of a 3x3 halo beside 64 output channels, and 32 channels of the 32 x 32 / 33 x 33 halo of the
+// last dilated / stride-2 shape, in chunks of half that (the 150 KB limit), and the generic kernel takes them.
+#define WLEAN_SHAPES(X, KS)                                                                                                     \
+    X(WF_LEAN, 1, 1, KS, 1, 1, 1) X(WF_LEAN, 1, 2, KS, 1, 1, 1) X(WF_LEAN, 2, 1, KS, 1, 1, 1) X(WF_LEAN, 2, 2, KS, 1, 1, 1)     \
+    X(WF_LEAN, 2, 4, KS, 1, 1, 1) X(WF_LEAN, 4, 2, KS, 1, 1, 1) X(WF_LEAN, 4, 4, KS, 1, 1, 1) X(WF_LEAN, 8, 1, KS, 1, 1, 1)     \
+    X(WF_LEAN, 4, 8, KS, 1, 1, 1) X(WF_LEAN, 8, 4, KS, 1, 1, 1)
+#define WLEAN_TABLE(X)                                                                                                          \
+    WLEAN_SHAPES(X, 1) WLEAN_SHAPES(X, 3) X(WF_LEAN, 8, 8, 1, 1, 1, 1) X(WF_LEAN, 8, 8, 3, 1, 1, 0) X(WF_LEAN, 1, 1, 4, 1, 1, 1)   \
+    X(WF_SPECIAL, 1, 2, 3, 2, 1, 1) X(WF_SPECIAL, 2, 4, 3, 4, 1, 1) X(WF_SPECIAL, 4, 8, 3, 8, 1, 0)                             \
+    X(WF_SPECIAL, 1, 2, 3, 1, 2, 1) X(WF_SPECIAL, 2, 4, 3, 1, 2, 1) X(WF_SPECIAL, 4, 8, 3, 1, 2, 0)                             \
+    X(WF_IN64, 8, 1, 3, 1, 1, 0)
+
+// The one reader of the table.  m == nullptr: 1 if instance `id` exists for T and its k extent is the generic geometry's, else 0.
+// Otherwise: launch it for m->a[0..n) (0, or an error -- never "not mine").  The same conditions either way, so
+// msau_wgrad_lean_case is non-zero exactly when msau_wgrad_lean_launch launches.
 template <typename T>
-int wlean_special(hipStream_t s, const WLeanMulti& m, int n, int c8, int co8, int dil, int stride) {
-    if (stride == 2 && dil == 1) {
-        if (c8 == 1 && co8 == 2) return launch_wlean<T, 1, 2, 3, 1, 2>(s, m, n);
-        if (c8 == 2 && co8 == 4) return launch_wlean<T, 2, 4, 3, 1, 2>(s, m, n);
-        if (c8 == 4 && co8 == 8) return launch_wlean<T, 4, 8, 3, 1, 2>(s, m, n);
-        return 0;
+int wlean_instance(int id, int kextc, hipStream_t s, const WLeanMulti* m, int n) {
+    switch (id) {
+#define WLEAN_ROW(FAM, C8, CO8, KS, DIL, STRIDE, F32)                                                                           \
+        case wlean_id(FAM, C8, CO8, KS, DIL, STRIDE):                                                                           \
+            if constexpr (FAM == WF_IN64) {                                                                                     \
+                if (sizeof(T) == 2 && kextc == 592) return m ? launch_wgrad_in64(s, m->a[0]) : 1;                                \
+            } else if constexpr (F32 || sizeof(T) == 2) {                                                                       \
+                if (WLeanCfg<T, C8, CO8, KS, DIL, STRIDE>::KEXT == kextc) return m ? launch_wlean<T, C8, CO8, KS, DIL, STRIDE>(s, *m, n) : 1; \
+            }                                                                                                                   \
+            break;
+        WLEAN_TABLE(WLEAN_ROW)
+#undef WLEAN_ROW
     }
-    if (stride == 1) {
-        if (dil == 2 && c8 == 1 && co8 == 2) return launch_wlean<T, 1, 2, 3, 2, 1>(s, m, n);
-        if (dil == 4 && c8 == 2 && co8 == 4) return launch_wlean<T, 2, 4, 3, 4, 1>(s, m, n);
-        if (dil == 8 && c8 == 4 && co8 == 8) return launch_wlean<T, 4, 8, 3, 8, 1>(s, m, n);
-    }
-    return 0;
+    return m ? msau_set_error(MSAU_ERR_ARG, "wgrad_lean: no instance %#x with k extent %d", id, kextc) : 0;
 }
 
-static bool wlean_special_shape(int c8, int co8, int dil, int stride) {
-    if (stride == 2 && dil == 1) return (c8 == 1 && co8 == 2) || (c8 == 2 && co8 == 4) || (c8 == 4 && co8 == 8);
-    if (stride == 1) return (dil == 2 && c8 == 1 && co8 == 2) || (dil == 4 && c8 == 2 && co8 == 4) || (dil == 8 && c8 == 4 && co8 == 8);
-    return false;
-}
-
-}  // namespace
-
-static const int kLeanShapes[][2] = {{1, 1}, {1, 2}, {2, 1}, {2, 2}, {2, 4}, {4, 2}, {4, 4}, {8, 1}, {4, 8}, {8, 4}, {8, 8}};
-
-int msau_wgrad_lean_applicable(int dtype, const msau_wgrad_desc* d, int cch) {
-    if (d->KH != d->KW || (d->KH != 1 && d->KH != 3 && d->KH != 4)) return 0;
-    const bool special = d->stride != 1 || d->dil != 1;
-    if (special) {
-        if (d->KH != 3 || d->C2 || cch != d->C1 || !wlean_special_shape(cch / 8, d->Cout / 8, d->dil, d->stride)) return 0;
-        if (d->pad_t != d->dil || d->pad_l != d->dil) return 0;
-    } else {
-        if (d->Hin != d->Hout || d->Win != d->Wout || d->pad_t < 0 || d->pad_l < 0 || d->pad_t >= d->KH || d->pad_l >= d->KW) return 0;
-    }
-    if (d->KH == 4 && !(cch == 8 && d->Cout == 8)) return 0;
-    const int esz = dtype == MSAU_F32 ? 4 : 2;
-    if ((int64_t)d->Hin * d->Win * (d->C1 > d->C2 ? d->C1 : d->C2) * esz >= (1ll << 31)) return 0;
-    if ((int64_t)d->Hout * d->Wout * d->Cout * esz >= (1ll << 31)) return 0;
-    const int tx = cdiv(d->Wout, 16), ty = cdiv(d->Hout, 16);
-    if ((int64_t)d->B * tx * ty >= (1 << 20) || tx >= 4096 || ty >= 4096) return 0;
-    if (special) return 1;
-    for (auto& sh : kLeanShapes)
-        if (sh[0] == cch / 8 && sh[1] == d->Cout / 8 && cch % 8 == 0) return 1;
-    return 0;
-}
-
-static void wlean_fill(WLeanArgs& a, const msau_wgrad_desc* d, int nchunks, int kextc) {
-    a.d = *d;
-    a.kextc = kextc; a.nchunks = nchunks;
-    a.tiles_x = cdiv(d->Wout, 16); a.tiles_y = cdiv(d->Hout, 16);
-    a.ntiles = d->B * a.tiles_x * a.tiles_y;
-    a.mag_tx = (unsigned)((0x100000000ull + a.tiles_x - 1) / a.tiles_x);
-    a.mag_ty = (unsigned)((0x100000000ull + a.tiles_y - 1) / a.tiles_y);
-}
-
-static bool wlean_in64(int dtype, const msau_wgrad_desc* d, int cch) {
+bool wlean_in64(int dtype, const msau_wgrad_desc* d, int cch) {
     static const bool in64_off = std::getenv("MSAU_WGRAD_IN64") && std::getenv("MSAU_WGRAD_IN64")[0] == '0';
     return !in64_off && dtype == MSAU_BF16 && d->stride == 1 && d->dil == 1 && d->KH == 3 && cch == 64 && d->Cout == 8 &&
            d->pad_t <= 2 && d->pad_l <= 2;
 }
 
-// 1 = handled, 0 = not applicable (use the generic kernel), < 0 = error.  cch/nchunks/kextc are the generic geometry.
-// ds[0..n): launches of ONE instance and geometry (msau_conv2d_wgrad_group checks that), n <= kWGroup.
-int msau_wgrad_lean_group(hipStream_t s, int dtype, const msau_wgrad_desc* const* ds, int n, int cch, int nchunks, int kextc) {
-    const msau_wgrad_desc* d = ds[0];
-    if (n < 1 || n > kWGroup || !msau_wgrad_lean_applicable(dtype, d, cch)) return 0;
-    WLeanMulti m;
-    for (int i = 0; i < n; ++i) wlean_fill(m.a[i], ds[i], nchunks, kextc);
-    for (int i = n; i < kWGroup; ++i) m.a[i] = m.a[0];
-    if (d->stride != 1 || d->dil != 1)
-        return dtype == MSAU_F32 ? wlean_special<float>(s, m, n, cch / 8, d->Cout / 8, d->dil, d->stride)
-                                 : wlean_special<bf16_t>(s, m, n, cch / 8, d->Cout / 8, d->dil, d->stride);
-    if (wlean_in64(dtype, d, cch)) {
-        if (n != 1) return 0;
-        return launch_wgrad_in64(s, m.a[0]);
+}  // namespace
+
+// The instance that runs `d`, 0 = none (the generic kernel).  cch / kextc: the generic geometry.
+int msau_wgrad_lean_case(int dtype, const msau_wgrad_desc* d, int cch, int kextc) {
+    if (d->KH != d->KW || d->dil > 8) return 0;
+    const bool special = d->stride != 1 || d->dil != 1;
+    if (special) {
+        if (d->C2 || cch != d->C1 || d->pad_t != d->dil || d->pad_l != d->dil) return 0;
+    } else {
+        if (d->Hin != d->Hout || d->Win != d->Wout || d->pad_t < 0 || d->pad_l < 0 || d->pad_t >= d->KH || d->pad_l >= d->KW) return 0;
     }
-    if (d->KH == 4) return dtype == MSAU_F32 ? launch_wlean<float, 1, 1, 4>(s, m, n) : launch_wlean<bf16_t, 1, 1, 4>(s, m, n);
-    if (dtype == MSAU_F32) return d->KH == 3 ? wlean_dispatch<float, 3>(s, m, n, cch / 8, d->Cout / 8) : wlean_dispatch<float, 1>(s, m, n, cch / 8, d->Cout / 8);
-    return d->KH == 3 ? wlean_dispatch<bf16_t, 3>(s, m, n, cch / 8, d->Cout / 8) : wlean_dispatch<bf16_t, 1>(s, m, n, cch / 8, d->Cout / 8);
+    const int esz = dtype == MSAU_F32 ? 4 : 2;
+    if ((int64_t)d->Hin * d->Win * (d->C1 > d->C2 ? d->C1 : d->C2) * esz >= (1ll << 31)) return 0;
+    if ((int64_t)d->Hout * d->Wout * d->Cout * esz >= (1ll << 31)) return 0;
+    const int tx = cdiv(d->Wout, 16), ty = cdiv(d->Hout, 16);
+    if ((int64_t)d->B * tx * ty >= (1 << 20) || tx >= 4096 || ty >= 4096) return 0;
+    const int fam = special ? WF_SPECIAL : wlean_in64(dtype, d, cch) ? WF_IN64 : WF_LEAN;
+    const int id = wlean_id(fam, cch / 8, d->Cout / 8, d->KH, d->dil, d->stride);
+    return (dtype == MSAU_F32 ? wlean_instance<float>(id, kextc, nullptr, nullptr, 0) : wlean_instance<bf16_t>(id, kextc, nullptr, nullptr, 0)) ? id : 0;
 }
 
-int msau_wgrad_lean_try(hipStream_t s, int dtype, const msau_wgrad_desc* d, int cch, int nchunks, int kextc) {
-    return msau_wgrad_lean_group(s, dtype, &d, 1, cch, nchunks, kextc);
+// ds[0..n): launches of instance r->inst and ONE geometry (msau_conv2d_wgrad_group checks that) in one grid
+int msau_wgrad_lean_launch(hipStream_t s, int dtype, const msau_wgrad_desc* const* ds, int n, const WRoute* r) {
+    MSAU_CHECK_ARG(n >= 1 && n <= ((r->inst & 7) == WF_IN64 ? 1 : kWGroup), "wgrad_lean: %d launches in one grid", n);
+    WLeanMulti m;
+    for (int i = 0; i < n; ++i) {
+        WLeanArgs& a = m.a[i];
+        a.d = *ds[i];
+        a.kextc = r->kextc; a.nchunks = r->nchunks;
+        a.tiles_x = r->tiles_x; a.tiles_y = r->tiles_y; a.ntiles = r->ntiles;
+        a.mag_tx = (unsigned)((0x100000000ull + a.tiles_x - 1) / a.tiles_x);
+        a.mag_ty = (unsigned)((0x100000000ull + a.tiles_y - 1) / a.tiles_y);
+    }
+    for (int i = n; i < kWGroup; ++i) m.a[i] = m.a[0];
+    return dtype == MSAU_F32 ? wlean_instance<float>(r->inst, r->kextc, s, &m, n) : wlean_instance<bf16_t>(r->inst, r->kextc, s, &m, n);
 }
 
-// the instance msau_wgrad_lean_group launches for one descriptor (host only; msau_wgrad_route in conv_wgrad.hip): 0 none,
-// 2 a lean shape, 3 a dilated / stride-2 one, 4 the 64 -> 8 kernel
-int msau_wgrad_lean_instance(int dtype, const msau_wgrad_desc* d, int cch) {
-    if (!msau_wgrad_lean_applicable(dtype, d, cch)) return 0;
-    if (d->stride != 1 || d->dil != 1) return 3;
-    return wlean_in64(dtype, d, cch) ? 4 : 2;
-}

@@ -524,13 +524,13 @@ class ConvOp(Op):
             self.d2meta = ("dgrad2_1x1<bf16,C64>", self.out.npix * 64 * nops * esz, 2.0 * self.out.npix * 128 * self.out.C)
         if self.wdesc is not None:
             w, wg = self.wdesc, self.wgeom
-            if wg.lean == 2:
-                self.wkey = f"rowwgrad_kernel<{T},C{wg.cch},CO{w.Cout},K{w.KH}>"
-            elif wg.lean:
-                self.wkey = f"wgrad_lean_kernel<{T},C{wg.cch},CO{w.Cout},K{w.KH}>"
-            else:                                       # the generic kernel: its instance as the router names it
-                route = (L.i32 * 8)()
-                L.call("msau_wgrad_route", P.dtype, C.byref(w), route)
+            route = (L.i32 * 8)()                       # (family, CTN, NKW, compact, slices, cch, nchunks, kext)
+            L.call("msau_wgrad_route", P.dtype, C.byref(w), route)
+            if route[0] == 6:                           # the row-streaming family
+                self.wkey = f"rowwgrad_kernel<{T},C{route[5]},CO{w.Cout},K{w.KH}>"
+            elif 2 <= route[0] <= 5:                    # lean, dilated / stride-2, the 64 -> 8 kernel dense or fed with ids
+                self.wkey = f"wgrad_lean_kernel<{T},C{route[5]},CO{w.Cout},K{w.KH}>"
+            else:                                       # the generic kernel: its instance as the router names it (box lists: none)
                 self.wkey = f"wgrad_kernel<{T},CT{route[1]},NK{route[2]}>"
             self.wbytes = (w.B * w.Hin * w.Win * (w.C1 + w.C2) + w.B * w.Hout * w.Wout * w.Cout) * esz + w.nslabs * wg.slab_bytes
 

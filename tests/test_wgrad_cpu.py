@@ -21,8 +21,8 @@ F64 = torch.float64
 CINS = list(range(8, 129, 8)) + [192, 768]
 COUTS = list(range(8, 137, 8)) + [192, 256]
 KS, DILS, STRIDES = (1, 3, 4, 5, 7), (1, 2, 4, 8, 16, 32), (1, 2)
-# every instantiation of wgrad_kernel<T, CTN, NKW> (launch_wgrad_nkw in csrc/conv_wgrad.hip), per type
-INSTANTIATED = [(ctn, nkw) for ctn in (1, 2, 4) for nkw in (1, 2, 3, 5, 10)] + [(8, nkw) for nkw in (1, 2, 3, 5)]
+# every instantiation of wgrad_kernel<T, CTN, NKW> (WGRAD_TILE_TABLE in csrc/conv_wgrad.hip), per type
+INSTANTIATED = U.TILE_TABLE
 
 
 @pytest.fixture
@@ -196,12 +196,12 @@ def test_the_gpu_table_reaches_every_instance_the_route_can_name(swept, wenv):
     missing = {k: v for k, v in shapes.items() if k not in have_shapes}
     assert not missing, f"lean instances (dtype, family, k, dil, stride, cch, Cout) the sweep reaches and no GPU case runs: {missing}"
     assert {U.IN64_IDS, U.ROWS} <= {k[1] for k in have}
-    # instantiated, and no descriptor of the sweep reaches them (kept: removing them is another change)
+    # nothing is instantiated that no descriptor of the sweep reaches
     for dtype in (L.F32, L.BF16):
-        dead = [p for p in INSTANTIATED if not any(k[0] == dtype and k[1] == U.GENERIC and (k[2], k[3]) == p for k in reach)]
+        dead = [p for p in INSTANTIATED[dtype] if not any(k[0] == dtype and k[1] == U.GENERIC and (k[2], k[3]) == p for k in reach)]
         print(f"\nwgrad_kernel<{U.TNAME[dtype]}, CTN, NKW> instantiated and unreachable: {dead}")
-        assert dead == ([(8, 1), (8, 2), (8, 3), (8, 5)] if dtype == L.F32 else [])       # fp32 slices are 64 channels wide: CTN <= 4
-        assert all((k[2], k[3]) in INSTANTIATED for k in reach if k[0] == dtype and k[1] == U.GENERIC)
+        assert dead == []
+        assert all((k[2], k[3]) in INSTANTIATED[dtype] for k in reach if k[0] == dtype and k[1] == U.GENERIC)
 
 
 def test_geometry_and_groupable_take_the_routes_decision(swept):

@@ -10,7 +10,7 @@ What this found: the 64 -> 8 role-swapped kernel wrote the bias gradient (the "o
 chunks behind it (Cin = 128: got 0, want sum g, e.g. 48.32), where every other kernel and the slab layout of include/msau_hip.h
 have it in every chunk.  msau_wgrad_reduce reads chunk 0, so no gradient was wrong; the kernel now writes it in every chunk.
 
-645 tests, about 6 s on an MI355X.  Worst error / bound of the random runs per family (`pytest -s` prints them): generic 0.016,
+653 tests, about 6 s on an MI355X.  Worst error / bound of the random runs per family (`pytest -s` prints them): generic 0.016,
 lean 0.013, dilated / stride-2 0.016, 64 -> 8 0.003, id-fed 0.0002, row-streaming 0.002.
 """
 import ctypes as C
@@ -220,10 +220,11 @@ def test_id_fed_launch_writes_the_bits_of_the_dense_one(pad):
 
 
 @pytest.mark.parametrize("kind", ["int", "rand"])
-@pytest.mark.parametrize("n", [2, 4])
+@pytest.mark.parametrize("n", [2, 3, 4])
 @pytest.mark.parametrize("c", GROUPED, ids=[c.id for c in GROUPED])
 def test_grouped_launch_against_the_reference(c, n, kind):
-    """msau_conv2d_wgrad_group: n launches of one shape in one grid, each layer's slabs against ITS reference"""
+    """msau_conv2d_wgrad_group: n launches of one shape in one grid, each layer's slabs against ITS reference (n = 3: the one padded
+    slot of the argument struct is neither empty nor absent)"""
     lib = L.load()
     rc, info = U.route(c.dtype, U.descriptor(c))
     assert rc == 0 and info[0] == c.family

@@ -33,6 +33,14 @@ TILE, REFUSED, GENERIC, LEAN, SPECIAL, IN64, IN64_IDS, ROWS, OWNER = 16, 0, 1, 2
 FAMILY = {REFUSED: "refused", GENERIC: "generic", LEAN: "lean", SPECIAL: "special", IN64: "in64", IN64_IDS: "in64-ids", ROWS: "rows",
           OWNER: "owner"}
 TNAME = {L.F32: "f32", L.BF16: "bf16"}
+# WGRAD_TILE_TABLE of csrc/conv_wgrad.hip: the instantiations of wgrad_kernel<T, CTN, NKW>, per type (fp32 slices are 64 channels wide: CTN <= 4)
+TILE_TABLE = {L.F32: [(ctn, nkw) for ctn in (1, 2, 4) for nkw in (1, 2, 3, 5, 10)]}
+TILE_TABLE[L.BF16] = TILE_TABLE[L.F32] + [(8, nkw) for nkw in (1, 2, 3, 5)]
+# WLEAN_TABLE of csrc/wgrad_lean.hip: (family, cch / 8, Cout / 8, k, dil, stride), per type
+_LEAN_BOTH = [(LEAN, c8, co8, k, 1, 1) for k in (1, 3) for c8, co8 in ((1, 1), (1, 2), (2, 1), (2, 2), (2, 4), (4, 2), (4, 4), (8, 1), (4, 8), (8, 4))] + \
+             [(LEAN, 8, 8, 1, 1, 1), (LEAN, 1, 1, 4, 1, 1), (SPECIAL, 1, 2, 3, 2, 1), (SPECIAL, 2, 4, 3, 4, 1), (SPECIAL, 1, 2, 3, 1, 2), (SPECIAL, 2, 4, 3, 1, 2)]
+LEAN_TABLE = {L.F32: _LEAN_BOTH,
+              L.BF16: _LEAN_BOTH + [(LEAN, 8, 8, 3, 1, 1), (SPECIAL, 4, 8, 3, 8, 1), (SPECIAL, 4, 8, 3, 1, 2), (IN64, 8, 1, 3, 1, 1)]}
 
 
 def torch_dtype(dtype):
