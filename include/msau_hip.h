@@ -918,6 +918,41 @@ int msau_unet_eval(void* stream, int dtype, const void* logits, const void* aux,
                    int W, int C, int Cs);
 
 /* ------------------------------------------------------------------------------------------
+ * UNetLoss under another cost: the focal loss and the soft Dice loss beside the cross entropy, for training
+ * (msau_unet_cost: the argument list of msau_unet_ce behind `kind, param`) and for validation (msau_unet_cost_eval: that of
+ * msau_unet_eval).  Active pixels, extents, heads, class weights v = cw, loss3 / doc_loss / doc_counts and the gradient's zeros are
+ * those of msau_unet_ce / msau_unet_eval; p = softmax over the C classes, y the label, p_t = p[y], nll = -log p_t.
+ *   MSAU_COST_CE    : param unread; the bits of msau_unet_ce / msau_unet_eval (they are called).
+ *   MSAU_COST_FOCAL : param = gamma >= 0.  L_b = sum_p v_y (1 - p_t)^gamma nll / D_b, D_b the cross entropy's denominator;
+ *                     dlogits = CE's times m = (1 - p_t)^gamma + gamma p_t (1 - p_t)^(gamma - 1) nll.  gamma = 0 gives the CE bits;
+ *                     where 1 - p_t rounds to 0 (gamma > 0) the pixel has loss 0 and gradient 0.  One launch of msau_unet_ce's
+ *                     shape and its finish; ws as msau_unet_ce's.
+ *   MSAU_COST_DICE  : param = smooth eps > 0.  Per document and class over the active pixels I_c = sum p_c [y = c], P_c = sum p_c,
+ *                     Y_c = sum [y = c];  L_b = 1 - sum_c v_c (2 I_c + eps) / (P_c + Y_c + eps) / V,  V = sum_c v_c (L_b = 0 when
+ *                     V = 0); every class counts.  dlogits[j] = head_weight / B * p_j (a_j - sum_c a_c p_c), a_c = hit_c at c = y,
+ *                     else miss_c;  miss_c = (v_c / V)(2 I_c + eps) / den_c^2,  hit_c = miss_c - (v_c / V) 2 / den_c.
+ *                     Training ALWAYS takes hist_partial (Y_c: the K rows of msau_label_hist per head, as for class weights) and
+ *                     runs a K x B reduction that writes per-slab (I, P) rows, a coefficient step (the rows in index order) with
+ *                     msau_unet_ce's finish, and a gradient pass of msau_unet_ce's shape that reads the (hit, miss) table from
+ *                     global memory.  Validation takes its own histograms (min(K, 64) rows) into ws.
+ * No floating-point atomics, every output written, every summation order fixed: equal arguments give equal bits.
+ * msau_unet_cost_ws_floats: floats of ws for msau_unet_cost (Dice: for any K <= 64); msau_unet_cost_eval_ws_bytes: bytes of ws for
+ * msau_unet_cost_eval.  An unknown kind, a gamma that is negative or not finite, a smooth that is not positive and finite, and Dice
+ * training without hist_partial are MSAU_ERR_ARG before anything is launched.
+ * ------------------------------------------------------------------------------------------ */
+#define MSAU_COST_CE 0
+#define MSAU_COST_FOCAL 1
+#define MSAU_COST_DICE 2
+int64_t msau_unet_cost_ws_floats(int kind, int B, int H, int W, int C);
+int msau_unet_cost(void* stream, int dtype, int kind, float param, const void* logits, const void* aux, const int64_t* labels,
+                   const int64_t* aux_labels, const int32_t* extent, const float* class_w, const int32_t* hist_partial, int K,
+                   void* dlogits, void* daux, float* loss3, float* ws, int B, int H, int W, int C, int Cs);
+int64_t msau_unet_cost_eval_ws_bytes(int kind, int B, int K, int C);
+int msau_unet_cost_eval(void* stream, int dtype, int kind, float param, const void* logits, const void* aux, const int64_t* labels,
+                        const int64_t* aux_labels, const int32_t* extent, const float* class_w, int K, float* doc_loss,
+                        int32_t* doc_counts, void* ws, int B, int H, int W, int C, int Cs);
+
+/* ------------------------------------------------------------------------------------------
  * Key-value training, the generator's affine / rotation augmentation (data_generator/data_generator_text.py:303-344,
  * utils/image_util.py:38-55; msau_amd/training/kv_warp.py states what is computed, csrc/warp.hip how).
  *   msau_kv_warp_train : the canvases msau_kv_paint_train leaves (ids int32, labels / aux_labels int64 [B][H][W], src_sizes int32

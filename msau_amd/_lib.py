@@ -13,6 +13,7 @@ LIB_PATH = os.environ.get("MSAU_HIP_LIB", os.path.join(HERE, "libmsau_hip.so"))
 
 F32, BF16 = 0, 1
 OPTIM_ADAM, OPTIM_RMSPROP, OPTIM_MOMENTUM, OPTIM_MAX_SKIP = 0, 1, 2, 8
+COST_CE, COST_FOCAL, COST_DICE = 0, 1, 2
 
 CONV_RELU_IN, CONV_RELU_OUT, CONV_ADD, CONV_ACCUM, CONV_MASK_A, CONV_MASK_B, CONV_HEAD, CONV_DOUT = 1, 2, 4, 8, 16, 32, 64, 128
 CONV_LRN, CONV_POOL, CONV_IDS, CONV_OWNER, CONV_NCHW, CONV_WGRAD, CONV_ELU = 256, 512, 1024, 2048, 4096, 8192, 32768
@@ -237,6 +238,10 @@ _SIGNATURES = {
     "msau_unet_ce": (C.c_int, [vp, C.c_int] + [vp] * 7 + [C.c_int, vp, vp, vp, vp] + [C.c_int] * 5),
     "msau_unet_eval_ws_bytes": (i64, [C.c_int, C.c_int]),
     "msau_unet_eval": (C.c_int, [vp, C.c_int] + [vp] * 6 + [C.c_int, vp, vp, vp] + [C.c_int] * 5),
+    "msau_unet_cost_ws_floats": (i64, [C.c_int] * 5),
+    "msau_unet_cost": (C.c_int, [vp, C.c_int, C.c_int, f32] + [vp] * 7 + [C.c_int, vp, vp, vp, vp] + [C.c_int] * 5),
+    "msau_unet_cost_eval_ws_bytes": (i64, [C.c_int] * 4),
+    "msau_unet_cost_eval": (C.c_int, [vp, C.c_int, C.c_int, f32] + [vp] * 6 + [C.c_int, vp, vp, vp] + [C.c_int] * 5),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)

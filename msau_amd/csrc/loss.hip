@@ -4,6 +4,7 @@
 // kernel of the family: that, not a comment, is what makes the register and the cache forms (and the training and the evaluation
 // kernels) agree bit for bit.  Accumulation in fp32, every summation order fixed.
 #include "msau_common.h"
+#include "loss_cost.h"
 
 namespace {
 
@@ -72,6 +73,15 @@ __device__ __forceinline__ void ce_grad_store_wide(T* __restrict__ dst, const T*
         if (active && c < C) g = w * (__expf((float)l[c] - lse) - (c == lab ? 1.f : 0.f));
         dst[c] = (T)g;
     }
+}
+
+// The focal loss as two factors on the CE weight w of an active pixel (msau_focal_factor, loss_cost.h): the loss term is
+// wl * nll, the gradient wg * (softmax - onehot).  xl: the pixel's logit at its label.  gamma = 0 leaves w in both, bit for bit.
+__device__ __forceinline__ void focal_weights(float w, float lse, float xl, float gamma, float& wl, float& wg) {
+    float f, m;
+    msau_focal_factor(__expf(xl - lse), lse - xl, gamma, &f, &m);
+    wl = w * f;
+    wg = w * m;
 }
 
 // The workgroup sum, reproducible, in two halves so that several values share one barrier: wave_sum adds the lanes of a wave by
@@ -346,11 +356,12 @@ __device__ __forceinline__ void unet_ce_block_sums(float l0, float l1, float* re
 // Both heads in one launch, the logits of a pixel in registers (Cs = 8 * CS8 <= 32: every index is a compile-time constant).
 // A thread's weight of head t at pixel p of document b: hw_t * cw[lab] / (B * D_b(t)) inside the extent with lab in [0, C), else 0;
 // the loss partials carry the weight WITHOUT hw_t (loss3[1], loss3[2] are the heads' own losses).
-template <typename T, int NL, int CS8>
+// FOCAL: the focal loss with parameter gamma (focal_weights); otherwise gamma is not read.
+template <typename T, int NL, int CS8, bool FOCAL>
 __global__ void unet_ce_kernel(const T* __restrict__ l0, const T* __restrict__ l1, const int64_t* __restrict__ lab0,
                                const int64_t* __restrict__ lab1, const int32_t* __restrict__ extent, const float* __restrict__ cw,
                                const int32_t* __restrict__ hist, int K, T* __restrict__ d0, T* __restrict__ d1,
-                               float* __restrict__ ws, int B, int H, int W, int C) {
+                               float* __restrict__ ws, int B, int H, int W, int C, float gamma) {
     constexpr int Cs = CS8 * 8;
     __shared__ float red[2 * kWaves];
     __shared__ float inv[2 * kCeMaxB];
@@ -373,19 +384,21 @@ __global__ void unet_ce_kernel(const T* __restrict__ l0, const T* __restrict__ l
             float xl;
             const float lse = pixel_lse<T, CS8>((t ? l1 : l0) + p * Cs, C, lab, x, xl);
             const bool act = on && w != 0.f;
-            if (act) local[t] += w * (lse - xl);
-            ce_grad_store<T, CS8>((t ? d1 : d0) + p * Cs, x, lse, hwt * w, lab, C, act);
+            float wl = w, wg = w;
+            if (FOCAL && act) focal_weights(w, lse, xl, gamma, wl, wg);
+            if (act) local[t] += wl * (lse - xl);
+            ce_grad_store<T, CS8>((t ? d1 : d0) + p * Cs, x, lse, hwt * wg, lab, C, act);
         }
     }
     unet_ce_block_sums(local[0], local[1], red, ws);
 }
 
 // Any class count (Cs > 32): the logits of a pixel are read three times from the cache.
-template <typename T>
+template <typename T, bool FOCAL>
 __global__ void unet_ce_wide_kernel(const T* __restrict__ l0, const T* __restrict__ l1, const int64_t* __restrict__ lab0,
                                     const int64_t* __restrict__ lab1, const int32_t* __restrict__ extent, const float* __restrict__ cw,
                                     const int32_t* __restrict__ hist, int K, T* __restrict__ d0, T* __restrict__ d1,
-                                    float* __restrict__ ws, int B, int H, int W, int C, int Cs) {
+                                    float* __restrict__ ws, int B, int H, int W, int C, int Cs, float gamma) {
     __shared__ float red[2 * kWaves];
     __shared__ float inv[2 * kCeMaxB];
     const int NL = l1 ? 2 : 1;
@@ -406,8 +419,11 @@ __global__ void unet_ce_wide_kernel(const T* __restrict__ l0, const T* __restric
             const float w = on ? inv[t * B + b] * (cw ? cw[lab] : 1.f) : 0.f;
             const float lse = pixel_lse_wide(l, C);
             const bool act = on && w != 0.f;
-            if (act) local[t] += w * (lse - (float)l[lab]);
-            ce_grad_store_wide((t ? d1 : d0) + p * Cs, l, lse, hwt * w, lab, C, Cs, act);
+            const float xl = act ? (float)l[lab] : 0.f;
+            float wl = w, wg = w;
+            if (FOCAL && act) focal_weights(w, lse, xl, gamma, wl, wg);
+            if (act) local[t] += wl * (lse - xl);
+            ce_grad_store_wide((t ? d1 : d0) + p * Cs, l, lse, hwt * wg, lab, C, Cs, act);
         }
     }
     unet_ce_block_sums(local[0], local[1], red, ws);
@@ -438,12 +454,16 @@ __global__ __launch_bounds__(256) void unet_ce_finish_kernel(const float* __rest
 struct UnetEvalRow { float num[2], den[2]; int32_t cnt[2][2]; };    // per head: sum cw * nll, sum cw; (labelled, correct)
 
 // one pixel of one head into the thread's sums.  lse / xl: the pixel's log-sum-exp and its logit at the label; pred: its first maximum
-__device__ __forceinline__ void unet_eval_add(int lab, bool on, float lse, float xl, int pred, const float* __restrict__ cw,
+// FOCAL: the numerator takes the focal term (focal_weights), the denominator stays CE's
+template <bool FOCAL>
+__device__ __forceinline__ void unet_eval_add(int lab, bool on, float lse, float xl, int pred, const float* __restrict__ cw, float gamma,
                                               float& num, float& den, int& labelled, int& correct) {
     if (!on) return;
     const float w = cw ? cw[lab] : 1.f;
     den += w;
-    if (w != 0.f) num += w * (lse - xl);
+    float wl = w, wg = w;
+    if (FOCAL && w != 0.f) focal_weights(w, lse, xl, gamma, wl, wg);
+    if (w != 0.f) num += wl * (lse - xl);
     if (lab >= 1) { labelled += 1; correct += pred == lab; }
 }
 
@@ -485,11 +505,11 @@ struct UnetEvalSlab {
     __device__ __forceinline__ int offset(int i, int W) const { const int y = i / ew; return (r0 + y) * W + (i - y * ew); }
 };
 
-template <typename T, int NL, int CS8>
+template <typename T, int NL, int CS8, bool FOCAL>
 __global__ __launch_bounds__(256) void unet_eval_kernel(const T* __restrict__ l0, const T* __restrict__ l1,
                                                         const int64_t* __restrict__ lab0, const int64_t* __restrict__ lab1,
                                                         const int32_t* __restrict__ extent, const float* __restrict__ cw,
-                                                        UnetEvalRow* __restrict__ rows, int H, int W, int C) {
+                                                        UnetEvalRow* __restrict__ rows, int H, int W, int C, float gamma) {
     constexpr int Cs = CS8 * 8;
     const int b = blockIdx.y, k = blockIdx.x, K = gridDim.x;
     const UnetEvalSlab slab(extent, b, k, K, H, W);
@@ -511,18 +531,18 @@ __global__ __launch_bounds__(256) void unet_eval_kernel(const T* __restrict__ l0
 #pragma unroll
             for (int c = 0; c < Cs; ++c)
                 if (c < C) first_max(x[c], c, bv, pred);
-            unet_eval_add(lab, on, lse, xl, pred, cw, num[t], den[t], cnt[t][0], cnt[t][1]);
+            unet_eval_add<FOCAL>(lab, on, lse, xl, pred, cw, gamma, num[t], den[t], cnt[t][0], cnt[t][1]);
         }
     }
     unet_eval_block_row(num, den, cnt, rows + (int64_t)b * K + k);
 }
 
 // Any class count (Cs > 32): the logits of a pixel are read from the cache.
-template <typename T>
+template <typename T, bool FOCAL>
 __global__ __launch_bounds__(256) void unet_eval_wide_kernel(const T* __restrict__ l0, const T* __restrict__ l1,
                                                              const int64_t* __restrict__ lab0, const int64_t* __restrict__ lab1,
                                                              const int32_t* __restrict__ extent, const float* __restrict__ cw,
-                                                             UnetEvalRow* __restrict__ rows, int H, int W, int C, int Cs) {
+                                                             UnetEvalRow* __restrict__ rows, int H, int W, int C, int Cs, float gamma) {
     const int b = blockIdx.y, k = blockIdx.x, K = gridDim.x;
     const int NL = l1 ? 2 : 1;
     const UnetEvalSlab slab(extent, b, k, K, H, W);
@@ -540,7 +560,7 @@ __global__ __launch_bounds__(256) void unet_eval_wide_kernel(const T* __restrict
             int pred = 0;
             float bv = -INFINITY;
             for (int c = 0; c < C; ++c) first_max((float)l[c], c, bv, pred);
-            unet_eval_add(lab, on, lse, on ? (float)l[lab] : 0.f, pred, cw, num[t], den[t], cnt[t][0], cnt[t][1]);
+            unet_eval_add<FOCAL>(lab, on, lse, on ? (float)l[lab] : 0.f, pred, cw, gamma, num[t], den[t], cnt[t][0], cnt[t][1]);
         }
     }
     unet_eval_block_row(num, den, cnt, rows + (int64_t)b * K + k);
@@ -564,6 +584,226 @@ __global__ __launch_bounds__(256) void unet_eval_finish_kernel(const UnetEvalRow
     doc_loss[i] = d > 0.f ? n / d : 0.f;
     doc_counts[2 * i] = labelled;
     doc_counts[2 * i + 1] = correct;
+}
+
+// =============================================================================================
+// the soft Dice loss under UNetLoss's rules: per document and class the sums I_c = sum p_c [y = c] and P_c = sum p_c
+// over the active pixels (unet_dice_sums_kernel, grid K x B over the slabs of unet_eval_kernel), the coefficient step
+// (unet_dice_coef_kernel: the K rows in index order, Y_c from msau_label_hist's rows, msau_dice_coef of loss_cost.h), and for
+// training the gradient pass (unet_dice_grad_kernel, of unet_ce_kernel's shape) that reads the (hit, miss) table from global memory.
+// =============================================================================================
+constexpr int kDiceChunk = 32;                                       // classes a thread of the cache form sums per sweep of its slab
+
+// The workgroup's sums of N classes -> row[0][c0 + c] = I, row[1][c0 + c] = P (row: [2][C]) for c0 + c < C: lanes by shuffle, the four
+// waves paired.  red: 2 * N * 4 floats; may be called again after it returns.
+template <int N>
+__device__ __forceinline__ void dice_block_rows(const float (&I)[N], const float (&P)[N], float* red, float* __restrict__ row, int c0, int C) {
+#pragma unroll
+    for (int c = 0; c < N; ++c) {
+        wave_sum(I[c], red + (2 * c) * 4);
+        wave_sum(P[c], red + (2 * c + 1) * 4);
+    }
+    __syncthreads();
+    for (int i = threadIdx.x; i < 2 * N; i += 256) {
+        const int c = c0 + (i >> 1);
+        if (c < C) row[(i & 1) * C + c] = add_waves<4, true>(red + i * 4);
+    }
+    __syncthreads();
+}
+
+// part[((t * B + b) * K + k)][2][C] is WRITTEN by workgroup k of document b for head t; a thread adds its pixels in slab order
+template <typename T, int NL, int CS8>
+__global__ __launch_bounds__(256) void unet_dice_sums_kernel(const T* __restrict__ l0, const T* __restrict__ l1,
+                                                             const int64_t* __restrict__ lab0, const int64_t* __restrict__ lab1,
+                                                             const int32_t* __restrict__ extent, float* __restrict__ part, int B, int H,
+                                                             int W, int C) {
+    constexpr int Cs = CS8 * 8;
+    __shared__ float red[2 * Cs * 4];
+    const int b = blockIdx.y, k = blockIdx.x, K = gridDim.x;
+    const UnetEvalSlab slab(extent, b, k, K, H, W);
+    const int64_t base = (int64_t)b * H * W;
+#pragma unroll
+    for (int t = 0; t < NL; ++t) {
+        float I[Cs], P[Cs];
+#pragma unroll
+        for (int c = 0; c < Cs; ++c) I[c] = P[c] = 0.f;
+        for (int i = threadIdx.x; i < slab.n; i += 256) {
+            const int64_t p = base + slab.offset(i, W);
+            const int64_t lab64 = (t ? lab1 : lab0)[p];
+            if (lab64 < 0 || lab64 >= C) continue;
+            const int lab = (int)lab64;
+            float x[Cs];
+            float xl;
+            const float lse = pixel_lse<T, CS8>((t ? l1 : l0) + p * Cs, C, lab, x, xl);
+#pragma unroll
+            for (int c = 0; c < Cs; ++c) {
+                const float pc = c < C ? __expf(x[c] - lse) : 0.f;
+                P[c] += pc;
+                I[c] += c == lab ? pc : 0.f;
+            }
+        }
+        dice_block_rows<Cs>(I, P, red, part + (((int64_t)t * B + b) * K + k) * 2 * C, 0, C);
+    }
+}
+
+// Any class count (Cs > 32): kDiceChunk classes per sweep of the slab, the logits of a pixel read from the cache in every sweep
+template <typename T>
+__global__ __launch_bounds__(256) void unet_dice_sums_wide_kernel(const T* __restrict__ l0, const T* __restrict__ l1,
+                                                                  const int64_t* __restrict__ lab0, const int64_t* __restrict__ lab1,
+                                                                  const int32_t* __restrict__ extent, float* __restrict__ part, int B,
+                                                                  int H, int W, int C, int Cs) {
+    __shared__ float red[2 * kDiceChunk * 4];
+    const int b = blockIdx.y, k = blockIdx.x, K = gridDim.x;
+    const int NL = l1 ? 2 : 1;
+    const UnetEvalSlab slab(extent, b, k, K, H, W);
+    const int64_t base = (int64_t)b * H * W;
+    for (int t = 0; t < NL; ++t) {
+        for (int c0 = 0; c0 < C; c0 += kDiceChunk) {
+            float I[kDiceChunk], P[kDiceChunk];
+#pragma unroll
+            for (int c = 0; c < kDiceChunk; ++c) I[c] = P[c] = 0.f;
+            for (int i = threadIdx.x; i < slab.n; i += 256) {
+                const int64_t p = base + slab.offset(i, W);
+                const int64_t lab64 = (t ? lab1 : lab0)[p];
+                if (lab64 < 0 || lab64 >= C) continue;
+                const int lab = (int)lab64;
+                const T* l = (t ? l1 : l0) + p * Cs;
+                const float lse = pixel_lse_wide(l, C);
+#pragma unroll
+                for (int c = 0; c < kDiceChunk; ++c) {
+                    const float pc = c0 + c < C ? __expf((float)l[c0 + c] - lse) : 0.f;
+                    P[c] += pc;
+                    I[c] += c0 + c == lab ? pc : 0.f;
+                }
+            }
+            dice_block_rows<kDiceChunk>(I, P, red, part + (((int64_t)t * B + b) * K + k) * 2 * C, c0, C);
+        }
+    }
+}
+
+// The coefficient step: grid (B, heads), thread c takes class c (C <= 256).  The K rows of `part` and the Kh rows of the head's label
+// histogram are added in index order; tab[(t * B + b) * C + c] = (hit, miss) when tab is given; the document's loss, the classes
+// added lanes-then-waves, times `scale` -> doc_loss[b * sb + t * st].  Every output is written.
+__global__ __launch_bounds__(256) void unet_dice_coef_kernel(const float* __restrict__ part, int K, const int32_t* __restrict__ hist, int Kh,
+                                                             const float* __restrict__ cw, float eps, float2* __restrict__ tab,
+                                                             float* __restrict__ doc_loss, int sb, int st, float scale, int B, int C) {
+    __shared__ float red[4];
+    const int b = blockIdx.x, t = blockIdx.y, c = threadIdx.x;
+    float V = 0.f;                                                   // every thread the same sum, classes in index order
+    for (int i = 0; i < C; ++i) V += cw ? cw[i] : 1.f;
+    float term = 0.f;
+    if (c < C) {
+        const float* rows = part + ((int64_t)t * B + b) * K * 2 * C;
+        const int32_t* h = hist + ((int64_t)t * B + b) * Kh * C;
+        float I = 0.f, P = 0.f;
+        int n = 0;
+        for (int k = 0; k < K; ++k) { I += rows[(int64_t)k * 2 * C + c]; P += rows[(int64_t)k * 2 * C + C + c]; }
+        for (int k = 0; k < Kh; ++k) n += h[k * C + c];
+        float hit, miss;
+        msau_dice_coef(I, P, (float)n, eps, V > 0.f ? (cw ? cw[c] : 1.f) / V : 0.f, &term, &hit, &miss);
+        if (tab) tab[((int64_t)t * B + b) * C + c] = make_float2(hit, miss);
+    }
+    const float s = block_sum<4, true>(term, red);
+    if (threadIdx.x == 0) doc_loss[b * sb + t * st] = scale * msau_dice_loss(V, s);
+}
+
+// The pixel's Dice gradient g[j] = sc * p_j * (a_j - sum_c a_c p_c), a_c = hit_c at the label, else miss_c (tab: the document's C
+// (hit, miss) pairs), the sum by fmaf in channel order; zero in the padded channels and everywhere on an inactive pixel; all Cs
+// stored channels are written.  Register form: x[] as pixel_lse left it (it leaves holding the probabilities).
+template <typename T, int CS8>
+__device__ __forceinline__ void dice_grad_store(T* __restrict__ dst, float (&x)[CS8 * 8], float lse, const float2* __restrict__ tab,
+                                                float sc, int lab, int C, bool active) {
+    float a[CS8 * 8];
+    float s = 0.f;
+#pragma unroll
+    for (int c = 0; c < CS8 * 8; ++c) {
+        const bool real = active && c < C;
+        const float2 hm = real ? tab[c] : make_float2(0.f, 0.f);
+        x[c] = real ? __expf(x[c] - lse) : 0.f;
+        a[c] = c == lab ? hm.x : hm.y;
+        s = fmaf(a[c], x[c], s);
+    }
+#pragma unroll
+    for (int c0 = 0; c0 < CS8 * 8; c0 += 8) {
+        typename Vec8<T>::type o;
+#pragma unroll
+        for (int jj = 0; jj < 8; ++jj) {
+            const int c = c0 + jj;
+            float g = 0.f;
+            if (active && c < C) g = sc * (x[c] * (a[c] - s));
+            o[jj] = (T)g;
+        }
+        store8<T>(dst + c0, o);
+    }
+}
+
+// Cache-read form: the pixel's logits and the table are read twice.
+template <typename T>
+__device__ __forceinline__ void dice_grad_store_wide(T* __restrict__ dst, const T* __restrict__ l, float lse, const float2* __restrict__ tab,
+                                                     float sc, int lab, int C, int Cs, bool active) {
+    float s = 0.f;
+    if (active)
+        for (int c = 0; c < C; ++c) {
+            const float2 hm = tab[c];
+            s = fmaf(c == lab ? hm.x : hm.y, __expf((float)l[c] - lse), s);
+        }
+    for (int c = 0; c < Cs; ++c) {
+        float g = 0.f;
+        if (active && c < C) {
+            const float2 hm = tab[c];
+            g = sc * (__expf((float)l[c] - lse) * ((c == lab ? hm.x : hm.y) - s));
+        }
+        dst[c] = (T)g;
+    }
+}
+
+// The gradient pass, of unet_ce_kernel's shape: every pixel of the canvas, both heads, sc = head weight / B
+template <typename T, int NL, int CS8>
+__global__ void unet_dice_grad_kernel(const T* __restrict__ l0, const T* __restrict__ l1, const int64_t* __restrict__ lab0,
+                                      const int64_t* __restrict__ lab1, const int32_t* __restrict__ extent, const float2* __restrict__ tab,
+                                      T* __restrict__ d0, T* __restrict__ d1, int B, int H, int W, int C) {
+    constexpr int Cs = CS8 * 8;
+    const float sc = (NL == 2 ? 0.5f : 1.f) / (float)B;
+    const int hw = H * W;
+    const int64_t total = (int64_t)B * hw;
+    for (int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; p < total; p += (int64_t)gridDim.x * blockDim.x) {
+        const int b = (int)((unsigned)p / (unsigned)hw);               // total < 2^31 (checked by the host)
+        const int j = (int)p - b * hw;
+        const bool in = extent ? pos_in_extent(j, W, extent[2 * b], extent[2 * b + 1]) : true;
+#pragma unroll
+        for (int t = 0; t < NL; ++t) {
+            const int64_t lab64 = (t ? lab1 : lab0)[p];
+            const bool on = in && lab64 >= 0 && lab64 < C;
+            const int lab = on ? (int)lab64 : -1;
+            float x[Cs];
+            float xl;
+            const float lse = pixel_lse<T, CS8>((t ? l1 : l0) + p * Cs, C, lab, x, xl);
+            dice_grad_store<T, CS8>((t ? d1 : d0) + p * Cs, x, lse, tab + ((int64_t)t * B + b) * C, sc, lab, C, on);
+        }
+    }
+}
+
+template <typename T>
+__global__ void unet_dice_grad_wide_kernel(const T* __restrict__ l0, const T* __restrict__ l1, const int64_t* __restrict__ lab0,
+                                           const int64_t* __restrict__ lab1, const int32_t* __restrict__ extent,
+                                           const float2* __restrict__ tab, T* __restrict__ d0, T* __restrict__ d1, int B, int H, int W,
+                                           int C, int Cs) {
+    const int NL = l1 ? 2 : 1;
+    const float sc = (NL == 2 ? 0.5f : 1.f) / (float)B;
+    const int hw = H * W;
+    const int64_t total = (int64_t)B * hw;
+    for (int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; p < total; p += (int64_t)gridDim.x * blockDim.x) {
+        const int b = (int)((unsigned)p / (unsigned)hw);
+        const int j = (int)p - b * hw;
+        const bool in = extent ? pos_in_extent(j, W, extent[2 * b], extent[2 * b + 1]) : true;
+        for (int t = 0; t < NL; ++t) {
+            const T* l = (t ? l1 : l0) + p * Cs;
+            const int64_t lab64 = (t ? lab1 : lab0)[p];
+            const bool on = in && lab64 >= 0 && lab64 < C;
+            const float lse = pixel_lse_wide(l, C);
+            dice_grad_store_wide((t ? d1 : d0) + p * Cs, l, lse, tab + ((int64_t)t * B + b) * C, sc, on ? (int)lab64 : -1, C, Cs, on);
+        }
+    }
 }
 
 // Evaluation counts (the per-epoch accuracy / classification report of train_chargrid_funsd_msau.py): for every pixel whose
@@ -756,27 +996,106 @@ extern "C" int msau_label_hist(void* stream, const int64_t* labels, const int32_
 static int unet_ce_blocks(int64_t npix) { return grid_for(npix, 2048); }
 extern "C" int64_t msau_unet_ce_ws_floats(int64_t npix_total) { return 2 * unet_ce_blocks(npix_total); }
 
-extern "C" int msau_unet_ce(void* stream, int dtype, const void* logits, const void* aux, const int64_t* labels,
-                            const int64_t* aux_labels, const int32_t* extent, const float* class_w, const int32_t* hist_partial, int K,
-                            void* dlogits, void* daux, float* loss3, float* ws, int B, int H, int W, int C, int Cs) {
-    MSAU_CHECK_ARG(logits && labels && dlogits && loss3 && ws && (!aux || (daux && aux_labels)), "unet_ce: null pointer");
-    MSAU_CHECK_ARG(!class_w || (hist_partial && K >= 1 && K <= 64), "unet_ce: class weights need the label histograms (1 <= K <= 64)");
+// msau_unet_ce (FOCAL false, gamma unread) and the focal loss of msau_unet_cost: the same checks, the same two launches.  `fn`
+// names the entry point in the messages.
+template <bool FOCAL>
+static int unet_ce_run(const char* fn, float gamma, void* stream, int dtype, const void* logits, const void* aux, const int64_t* labels,
+                       const int64_t* aux_labels, const int32_t* extent, const float* class_w, const int32_t* hist_partial, int K,
+                       void* dlogits, void* daux, float* loss3, float* ws, int B, int H, int W, int C, int Cs) {
+    MSAU_CHECK_ARG(logits && labels && dlogits && loss3 && ws && (!aux || (daux && aux_labels)), "%s: null pointer", fn);
+    MSAU_CHECK_ARG(!class_w || (hist_partial && K >= 1 && K <= 64), "%s: class weights need the label histograms (1 <= K <= 64)", fn);
     MSAU_CHECK_ARG(B > 0 && B <= kCeMaxB && H > 0 && W > 0 && (int64_t)B * H * W < (1ll << 31) && C > 0 && C <= Cs && Cs % 8 == 0 && Cs <= 256,
-                   "unet_ce: bad dims (B <= %d, B*H*W < 2^31, n_class <= 256)", kCeMaxB);
+                   "%s: bad dims (B <= %d, B*H*W < 2^31, n_class <= 256)", fn, kCeMaxB);
     hipStream_t s = static_cast<hipStream_t>(stream);
     const int nb = unet_ce_blocks((int64_t)B * H * W);
-#define UNET_CE(T, NL, C8) hipLaunchKernelGGL((unet_ce_kernel<T, NL, C8>), dim3(nb), dim3(kThreads), 0, s, static_cast<const T*>(logits), \
+#define UNET_CE(T, NL, C8) hipLaunchKernelGGL((unet_ce_kernel<T, NL, C8, FOCAL>), dim3(nb), dim3(kThreads), 0, s, static_cast<const T*>(logits), \
         static_cast<const T*>(aux), labels, aux_labels, extent, class_w, hist_partial, K, static_cast<T*>(dlogits), static_cast<T*>(daux), \
-        ws, B, H, W, C)
-#define UNET_CE_WIDE(T) hipLaunchKernelGGL((unet_ce_wide_kernel<T>), dim3(nb), dim3(kThreads), 0, s, static_cast<const T*>(logits), \
+        ws, B, H, W, C, gamma)
+#define UNET_CE_WIDE(T) hipLaunchKernelGGL((unet_ce_wide_kernel<T, FOCAL>), dim3(nb), dim3(kThreads), 0, s, static_cast<const T*>(logits), \
         static_cast<const T*>(aux), labels, aux_labels, extent, class_w, hist_partial, K, static_cast<T*>(dlogits), static_cast<T*>(daux), \
-        ws, B, H, W, C, Cs)
+        ws, B, H, W, C, Cs, gamma)
     LOSS_LADDER_32(dtype, aux, Cs, UNET_CE, UNET_CE_WIDE);
 #undef UNET_CE_WIDE
 #undef UNET_CE
-    MSAU_CHECK_LAUNCH("unet_ce");
+    MSAU_CHECK_LAUNCH(fn);
     hipLaunchKernelGGL(unet_ce_finish_kernel, dim3(1), dim3(256), 0, s, ws, nb, aux ? 1 : 0, loss3);
     MSAU_CHECK_LAUNCH("unet_ce_finish");
+    return 0;
+}
+
+extern "C" int msau_unet_ce(void* stream, int dtype, const void* logits, const void* aux, const int64_t* labels,
+                            const int64_t* aux_labels, const int32_t* extent, const float* class_w, const int32_t* hist_partial, int K,
+                            void* dlogits, void* daux, float* loss3, float* ws, int B, int H, int W, int C, int Cs) {
+    return unet_ce_run<false>("unet_ce", 0.f, stream, dtype, logits, aux, labels, aux_labels, extent, class_w, hist_partial, K, dlogits, daux,
+                              loss3, ws, B, H, W, C, Cs);
+}
+
+// the cost of msau_unet_cost / msau_unet_cost_eval: checked before anything else, and without a device
+static int unet_cost_check(const char* fn, int kind, float param) {
+    MSAU_CHECK_ARG(kind == MSAU_COST_CE || kind == MSAU_COST_FOCAL || kind == MSAU_COST_DICE, "%s: unknown cost %d", fn, kind);
+    MSAU_CHECK_ARG(kind != MSAU_COST_FOCAL || (param >= 0.f && param < INFINITY), "%s: focal gamma = %g (finite, >= 0)", fn, (double)param);
+    MSAU_CHECK_ARG(kind != MSAU_COST_DICE || (param > 0.f && param < INFINITY), "%s: dice smooth = %g (finite, > 0)", fn, (double)param);
+    return 0;
+}
+
+// the Dice sums of both heads: part[heads][B][K][2][C] written
+static int launch_dice_sums(hipStream_t s, int dtype, const void* logits, const void* aux, const int64_t* labels, const int64_t* aux_labels,
+                            const int32_t* extent, float* part, int K, int B, int H, int W, int C, int Cs) {
+    const dim3 grid(K, B);
+#define DICE_SUMS(T, NL, C8) hipLaunchKernelGGL((unet_dice_sums_kernel<T, NL, C8>), grid, dim3(256), 0, s, static_cast<const T*>(logits), \
+        static_cast<const T*>(aux), labels, aux_labels, extent, part, B, H, W, C)
+#define DICE_SUMS_WIDE(T) hipLaunchKernelGGL((unet_dice_sums_wide_kernel<T>), grid, dim3(256), 0, s, static_cast<const T*>(logits), \
+        static_cast<const T*>(aux), labels, aux_labels, extent, part, B, H, W, C, Cs)
+    LOSS_LADDER_32(dtype, aux, Cs, DICE_SUMS, DICE_SUMS_WIDE);
+#undef DICE_SUMS_WIDE
+#undef DICE_SUMS
+    MSAU_CHECK_LAUNCH("unet_dice_sums");
+    return 0;
+}
+
+// Dice training workspace, in floats: [2 B] the documents' losses / B, [2 B C] (hit, miss) pairs, [2 B 64 2 C] the slab rows (K <= 64)
+static int64_t dice_tab_at(int B) { return 2 * (int64_t)B; }
+static int64_t dice_part_at(int B, int C) { return dice_tab_at(B) + 4 * (int64_t)B * C; }
+
+extern "C" int64_t msau_unet_cost_ws_floats(int kind, int B, int H, int W, int C) {
+    if (B <= 0 || H <= 0 || W <= 0 || C <= 0) return 0;
+    if (kind == MSAU_COST_DICE) return dice_part_at(B, C) + 2 * (int64_t)B * 64 * 2 * C;
+    return msau_unet_ce_ws_floats((int64_t)B * H * W);
+}
+
+extern "C" int msau_unet_cost(void* stream, int dtype, int kind, float param, const void* logits, const void* aux, const int64_t* labels,
+                              const int64_t* aux_labels, const int32_t* extent, const float* class_w, const int32_t* hist_partial, int K,
+                              void* dlogits, void* daux, float* loss3, float* ws, int B, int H, int W, int C, int Cs) {
+    if (int e = unet_cost_check("unet_cost", kind, param)) return e;
+    MSAU_CHECK_ARG(kind != MSAU_COST_DICE || (hist_partial && K >= 1 && K <= 64), "unet_cost: dice needs the label histograms (1 <= K <= 64)");
+    if (kind == MSAU_COST_CE)
+        return msau_unet_ce(stream, dtype, logits, aux, labels, aux_labels, extent, class_w, hist_partial, K, dlogits, daux, loss3, ws, B, H, W, C, Cs);
+    if (kind == MSAU_COST_FOCAL)
+        return unet_ce_run<true>("unet_cost", param, stream, dtype, logits, aux, labels, aux_labels, extent, class_w, hist_partial, K, dlogits,
+                                 daux, loss3, ws, B, H, W, C, Cs);
+    MSAU_CHECK_ARG(logits && labels && dlogits && loss3 && ws && (!aux || (daux && aux_labels)), "unet_cost: null pointer");
+    MSAU_CHECK_ARG(B > 0 && B <= kCeMaxB && H > 0 && W > 0 && (int64_t)B * H * W < (1ll << 31) && C > 0 && C <= Cs && Cs % 8 == 0 && Cs <= 256,
+                   "unet_cost: bad dims (B <= %d, B*H*W < 2^31, n_class <= 256)", kCeMaxB);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const int nl = aux ? 2 : 1;
+    float* part = ws + dice_part_at(B, C);
+    float2* tab = reinterpret_cast<float2*>(ws + dice_tab_at(B));
+    if (int e = launch_dice_sums(s, dtype, logits, aux, labels, aux_labels, extent, part, K, B, H, W, C, Cs)) return e;
+    // the documents' losses / B of head t -> ws[t * B + b]: unet_ce_finish_kernel then adds each head's B values as it adds block partials
+    hipLaunchKernelGGL(unet_dice_coef_kernel, dim3(B, nl), dim3(256), 0, s, part, K, hist_partial, K, class_w, param, tab, ws, 1, B,
+                       1.f / (float)B, B, C);
+    MSAU_CHECK_LAUNCH("unet_dice_coef");
+    hipLaunchKernelGGL(unet_ce_finish_kernel, dim3(1), dim3(256), 0, s, ws, B, aux ? 1 : 0, loss3);
+    MSAU_CHECK_LAUNCH("unet_ce_finish");
+    const int nb = unet_ce_blocks((int64_t)B * H * W);
+#define DICE_GRAD(T, NL, C8) hipLaunchKernelGGL((unet_dice_grad_kernel<T, NL, C8>), dim3(nb), dim3(kThreads), 0, s, static_cast<const T*>(logits), \
+        static_cast<const T*>(aux), labels, aux_labels, extent, tab, static_cast<T*>(dlogits), static_cast<T*>(daux), B, H, W, C)
+#define DICE_GRAD_WIDE(T) hipLaunchKernelGGL((unet_dice_grad_wide_kernel<T>), dim3(nb), dim3(kThreads), 0, s, static_cast<const T*>(logits), \
+        static_cast<const T*>(aux), labels, aux_labels, extent, tab, static_cast<T*>(dlogits), static_cast<T*>(daux), B, H, W, C, Cs)
+    LOSS_LADDER_32(dtype, aux, Cs, DICE_GRAD, DICE_GRAD_WIDE);
+#undef DICE_GRAD_WIDE
+#undef DICE_GRAD
+    MSAU_CHECK_LAUNCH("unet_dice_grad");
     return 0;
 }
 
@@ -784,26 +1103,69 @@ extern "C" int64_t msau_unet_eval_ws_bytes(int B, int K) {
     return B > 0 && K > 0 ? (int64_t)B * K * (int64_t)sizeof(UnetEvalRow) : 0;
 }
 
-extern "C" int msau_unet_eval(void* stream, int dtype, const void* logits, const void* aux, const int64_t* labels,
-                              const int64_t* aux_labels, const int32_t* extent, const float* class_w, int K, float* doc_loss,
-                              int32_t* doc_counts, void* ws, int B, int H, int W, int C, int Cs) {
-    MSAU_CHECK_ARG(logits && labels && doc_loss && doc_counts && ws && (!aux || aux_labels), "unet_eval: null pointer");
-    MSAU_CHECK_ARG(K >= 1 && K <= 256, "unet_eval: K = %d workgroups per document (1 <= K <= 256)", K);
+// msau_unet_eval (FOCAL false, gamma unread) and the focal rows of msau_unet_cost_eval
+template <bool FOCAL>
+static int unet_eval_run(const char* fn, float gamma, void* stream, int dtype, const void* logits, const void* aux, const int64_t* labels,
+                         const int64_t* aux_labels, const int32_t* extent, const float* class_w, int K, float* doc_loss,
+                         int32_t* doc_counts, void* ws, int B, int H, int W, int C, int Cs) {
+    MSAU_CHECK_ARG(logits && labels && doc_loss && doc_counts && ws && (!aux || aux_labels), "%s: null pointer", fn);
+    MSAU_CHECK_ARG(K >= 1 && K <= 256, "%s: K = %d workgroups per document (1 <= K <= 256)", fn, K);
     MSAU_CHECK_ARG(B > 0 && B <= kCeMaxB && H > 0 && W > 0 && (int64_t)B * H * W < (1ll << 31) && C > 0 && C <= Cs && Cs % 8 == 0 && Cs <= 256,
-                   "unet_eval: bad dims (B <= %d, B*H*W < 2^31, n_class <= 256)", kCeMaxB);
+                   "%s: bad dims (B <= %d, B*H*W < 2^31, n_class <= 256)", fn, kCeMaxB);
     hipStream_t s = static_cast<hipStream_t>(stream);
     UnetEvalRow* rows = static_cast<UnetEvalRow*>(ws);
     const dim3 grid(K, B);
-#define UNET_EVAL(T, NL, C8) hipLaunchKernelGGL((unet_eval_kernel<T, NL, C8>), grid, dim3(256), 0, s, static_cast<const T*>(logits), \
-        static_cast<const T*>(aux), labels, aux_labels, extent, class_w, rows, H, W, C)
-#define UNET_EVAL_WIDE(T) hipLaunchKernelGGL((unet_eval_wide_kernel<T>), grid, dim3(256), 0, s, static_cast<const T*>(logits), \
-        static_cast<const T*>(aux), labels, aux_labels, extent, class_w, rows, H, W, C, Cs)
+#define UNET_EVAL(T, NL, C8) hipLaunchKernelGGL((unet_eval_kernel<T, NL, C8, FOCAL>), grid, dim3(256), 0, s, static_cast<const T*>(logits), \
+        static_cast<const T*>(aux), labels, aux_labels, extent, class_w, rows, H, W, C, gamma)
+#define UNET_EVAL_WIDE(T) hipLaunchKernelGGL((unet_eval_wide_kernel<T, FOCAL>), grid, dim3(256), 0, s, static_cast<const T*>(logits), \
+        static_cast<const T*>(aux), labels, aux_labels, extent, class_w, rows, H, W, C, Cs, gamma)
     LOSS_LADDER_32(dtype, aux, Cs, UNET_EVAL, UNET_EVAL_WIDE);
 #undef UNET_EVAL_WIDE
 #undef UNET_EVAL
-    MSAU_CHECK_LAUNCH("unet_eval");
+    MSAU_CHECK_LAUNCH(fn);
     hipLaunchKernelGGL(unet_eval_finish_kernel, dim3((2 * B + 255) / 256), dim3(256), 0, s, rows, B, K, doc_loss, doc_counts);
     MSAU_CHECK_LAUNCH("unet_eval_finish");
+    return 0;
+}
+
+extern "C" int msau_unet_eval(void* stream, int dtype, const void* logits, const void* aux, const int64_t* labels,
+                              const int64_t* aux_labels, const int32_t* extent, const float* class_w, int K, float* doc_loss,
+                              int32_t* doc_counts, void* ws, int B, int H, int W, int C, int Cs) {
+    return unet_eval_run<false>("unet_eval", 0.f, stream, dtype, logits, aux, labels, aux_labels, extent, class_w, K, doc_loss, doc_counts, ws,
+                                B, H, W, C, Cs);
+}
+
+// Dice evaluation workspace, in bytes: msau_unet_eval's rows, then [2 B K 2 C] floats of slab rows, then [2 B min(K, 64) C] int32
+// of label histograms
+static int dice_eval_kh(int K) { return K < 64 ? K : 64; }
+extern "C" int64_t msau_unet_cost_eval_ws_bytes(int kind, int B, int K, int C) {
+    const int64_t rows = msau_unet_eval_ws_bytes(B, K);
+    if (kind != MSAU_COST_DICE || rows == 0 || C <= 0) return rows;
+    return rows + 4 * (2 * (int64_t)B * K * 2 * C + 2 * (int64_t)B * dice_eval_kh(K) * C);
+}
+
+extern "C" int msau_unet_cost_eval(void* stream, int dtype, int kind, float param, const void* logits, const void* aux,
+                                   const int64_t* labels, const int64_t* aux_labels, const int32_t* extent, const float* class_w, int K,
+                                   float* doc_loss, int32_t* doc_counts, void* ws, int B, int H, int W, int C, int Cs) {
+    if (int e = unet_cost_check("unet_cost_eval", kind, param)) return e;
+    if (kind == MSAU_COST_FOCAL)
+        return unet_eval_run<true>("unet_cost_eval", param, stream, dtype, logits, aux, labels, aux_labels, extent, class_w, K, doc_loss,
+                                   doc_counts, ws, B, H, W, C, Cs);
+    // the counts (and, for the cross entropy, the losses) are msau_unet_eval's own
+    if (int e = msau_unet_eval(stream, dtype, logits, aux, labels, aux_labels, extent, class_w, K, doc_loss, doc_counts, ws, B, H, W, C, Cs)) return e;
+    if (kind == MSAU_COST_CE) return 0;
+    // Dice: the sums over the same K slabs, the label histograms taken here, and the coefficient step writes doc_loss[b][t] over the
+    // cross entropy's (head 1 of a one-head call keeps msau_unet_eval's 0)
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const int nl = aux ? 2 : 1, Kh = dice_eval_kh(K);
+    float* part = reinterpret_cast<float*>(static_cast<char*>(ws) + msau_unet_eval_ws_bytes(B, K));
+    int32_t* hist = reinterpret_cast<int32_t*>(part + 2 * (int64_t)B * K * 2 * C);
+    for (int t = 0; t < nl; ++t)
+        if (int e = msau_label_hist(stream, t ? aux_labels : labels, extent, hist + (int64_t)t * B * Kh * C, B, H, W, C, Kh)) return e;
+    if (int e = launch_dice_sums(s, dtype, logits, aux, labels, aux_labels, extent, part, K, B, H, W, C, Cs)) return e;
+    hipLaunchKernelGGL(unet_dice_coef_kernel, dim3(B, nl), dim3(256), 0, s, part, K, hist, Kh, class_w, param, static_cast<float2*>(nullptr),
+                       doc_loss, 2, 1, 1.f, B, C);
+    MSAU_CHECK_LAUNCH("unet_dice_coef");
     return 0;
 }
 

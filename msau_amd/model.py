@@ -26,7 +26,7 @@ import torch
 import torch.nn as nn
 
 from . import _lib as L
-from .plan import Plan
+from .plan import Plan, unet_cost
 
 DTYPES = {"fp32": L.F32, "float32": L.F32, "bf16": L.BF16, "bfloat16": L.BF16}
 
@@ -664,7 +664,7 @@ class MSAUWrapper(nn.Module):
         return (dict(nhwc_ready=True, nhwc_clean=True), labels, *lown)
 
     @torch.no_grad()
-    def eval_unet(self, ids: torch.Tensor, labels: torch.Tensor, aux_labels: torch.Tensor, sizes=None, class_weights=None):
+    def eval_unet(self, ids: torch.Tensor, labels: torch.Tensor, aux_labels: torch.Tensor, sizes=None, class_weights=None, cost=None):
         """Validation of a group of documents on the device: the forward-only plan fed with the character-id mask (`ids` int32
         [B,H,W], as `TrainEngine.step_ids` takes it), then UNetLoss and the reference's accuracy per document in one launch
         (msau_unet_eval) on the logits both heads left in the plan -- nothing is exported, no one-hot tensor exists and nothing
@@ -673,7 +673,9 @@ class MSAUWrapper(nn.Module):
         and head (0 = final, 1 = auxiliary; zeros without an auxiliary head) the loss the document has alone, and (labelled,
         correct) over its pixels with a label in [1, n_class), the prediction being `argmax` of the fp32 logits `forward` returns.
         msau_amd.training.kv_trainer.summarize turns rows into the reference's epoch figures.  No training plan is built or
-        touched, parameters and gradients are left alone."""
+        touched, parameters and gradients are left alone.  `cost` as `TrainEngine.step_unet` takes it: the documents' losses are
+        then those of that cost (msau_unet_cost_eval) -- validate with the loss that is trained."""
+        cost = unet_cost(cost)
         cw = _device_class_weights(self, class_weights, self.n_class, self._flat.device)
         ids = self._check_ids(ids)
         B, H, W = ids.shape
@@ -683,15 +685,16 @@ class MSAUWrapper(nn.Module):
         plan = self._plan(B, H, W, ids.device, False, sizes)
         aux_labels = aux_labels.reshape(B, H, W).contiguous().long() if plan.aux is not None else None
         plan.forward(self._flat, None, export=False, ids=ids)
-        return plan.eval_unet(labels, aux_labels, cw)
+        return plan.eval_unet(labels, aux_labels, cw, cost=cost)
 
-    def eval_kv(self, tables, class_weights=None, round_to: int = 16):
+    def eval_kv(self, tables, class_weights=None, round_to: int = 16, cost=None):
         """`eval_unet` on a group of key-value documents given as their training tables (`KVTrainBatches.validation()`): one
         upload of the packed tables, one painter launch (kv_data.paint_train_device; a table that is not `ok` is painted on the
         host, as in `TrainEngine.step_kv`), the forward and the evaluation launch."""
+        cost = unet_cost(cost)
         from .training import kv_data
         ids, labels, aux_labels, sizes = kv_data.paint_train_device(tables, round_to=round_to, device=self._flat.device)
-        return self.eval_unet(ids, labels, aux_labels, sizes=sizes, class_weights=class_weights)
+        return self.eval_unet(ids, labels, aux_labels, sizes=sizes, class_weights=class_weights, cost=cost)
 
     def save(self, path):
         torch.save(self.state_dict(), path)
@@ -1112,7 +1115,7 @@ class TrainEngine:
         return _device_class_weights(self, class_weights, n_class, self.model._flat.device)
 
     def step_unet(self, ids: torch.Tensor, labels: torch.Tensor, aux_labels: torch.Tensor, sizes=None, class_weights=None,
-                  stats=None) -> torch.Tensor:
+                  stats=None, cost=None) -> torch.Tensor:
         """`step_ids` with the loss the reference trains the key-value model with (model/training/cost.py `UNetLoss`): cross entropy
         over EVERY pixel of a document, class 0 counted, 0.5 * final + 0.5 * auxiliary, each head against its OWN label map
         (`labels` for the last stage, `aux_labels` for the auxiliary one; int64 [B,H,W]), optional `class_weights` (a sequence or
@@ -1122,36 +1125,41 @@ class TrainEngine:
         B = 1 exactly UNetLoss.  Backward, gradient exchange and optimiser are those of `step_ids`.  Eager only.
         `stats`: a pair of device tensors (fp32 [B, 2], int32 [B, 2, 2]); the rows of `MSAUWrapper.eval_unet` -- per document the
         losses and (labelled, correct) of this step's forward, the training accuracy of the reference's epoch print -- are then
-        written into it by one more launch between the forward and the loss kernel.  None: no such launch."""
+        written into it by one more launch between the forward and the loss kernel.  None: no such launch.
+        `cost` (msau_amd.plan.unet_cost checks it; ValueError for an unknown name or a bad parameter): None or
+        {"cost_name": "cross_entropy"} is the loss above; {"cost_name": "focal", "gamma": 2.0} and {"cost_name": "dice", "smooth": 1.0}
+        train the focal and the soft Dice loss under the same rules, and `stats` then holds that loss."""
         self._eager("step_unet")
+        cost = unet_cost(cost)
         cw = self._class_weights(class_weights, self.model.n_class)
         ids = self.model._check_ids(ids)
         B, H, W = ids.shape
         sizes = self.model._check_sizes_for(sizes, B, H, W)
         plan = self.model._plan(B, H, W, ids.device, True, sizes)
-        return self._step_unet(plan, labels, aux_labels, cw, stats, ids=ids)
+        return self._step_unet(plan, labels, aux_labels, cw, stats, cost, ids=ids)
 
-    def _step_unet(self, plan: Plan, labels, aux_labels, cw, stats, **feed) -> torch.Tensor:
+    def _step_unet(self, plan: Plan, labels, aux_labels, cw, stats, cost, **feed) -> torch.Tensor:
         """the tail `step_unet` and `step_unet_nhwc` share: the label maps as the loss kernel takes them, UNetLoss, `_step`"""
         B, H, W = plan.B, plan.H, plan.W
         labels = labels.reshape(B, H, W).contiguous().long()
         aux_labels = aux_labels.reshape(B, H, W).contiguous().long() if plan.aux is not None else None
         if stats is None:
-            loss_grads = lambda p: p.loss_grads_unet(labels, aux_labels, cw)
+            loss_grads = lambda p: p.loss_grads_unet(labels, aux_labels, cw, cost=cost)
         else:
             def loss_grads(p):
-                p.eval_unet(labels, aux_labels, cw, out=stats)
-                return p.loss_grads_unet(labels, aux_labels, cw)
+                p.eval_unet(labels, aux_labels, cw, out=stats, cost=cost)
+                return p.loss_grads_unet(labels, aux_labels, cw, cost=cost)
         return self._step(plan, None, loss_grads=loss_grads, **feed)
 
     def step_unet_nhwc(self, grid: torch.Tensor, labels: torch.Tensor, aux_labels: torch.Tensor, sizes=None, class_weights=None,
-                       stats=None) -> torch.Tensor:
+                       stats=None, cost=None) -> torch.Tensor:
         """`step_unet` for an input that is ALREADY on the device in the kernels' layout ([B][H][W][Cs], storage dtype, as
         `step_nhwc` takes it): a one-hot, multi-hot or zero-hot grid, e.g. what the warp kernel leaves (msau_kv_warp_train).  When
         `grid` is the plan's own input buffer nothing is copied; otherwise one device copy.  `labels`,
-        `aux_labels`, `sizes`, `class_weights` and `stats` as in `step_unet`; with `sizes` the buffer is zeroed outside the documents
+        `aux_labels`, `sizes`, `class_weights`, `stats` and `cost` as in `step_unet`; with `sizes` the buffer is zeroed outside the documents
         before the sweep.  On the one-hot grid of an id canvas the step is bit-identical to `step_unet` on the ids.  Eager only."""
         self._eager("step_unet_nhwc")
+        cost = unet_cost(cost)
         cw = self._class_weights(class_weights, self.model.n_class)
         B, H, W, _ = grid.shape
         sizes = self.model._check_sizes_for(sizes, B, H, W)
@@ -1162,14 +1170,14 @@ class TrainEngine:
                              f"{tuple(grid.shape)} {grid.dtype}")
         if grid.data_ptr() != buf.data_ptr():
             buf.copy_(grid)
-        return self._step_unet(plan, labels, aux_labels, cw, stats, nhwc_ready=True)
+        return self._step_unet(plan, labels, aux_labels, cw, stats, cost, nhwc_ready=True)
 
-    def step_kv(self, tables, class_weights=None, round_to: int = 16, stats=None) -> torch.Tensor:
+    def step_kv(self, tables, class_weights=None, round_to: int = 16, stats=None, cost=None) -> torch.Tensor:
         """One optimisation step on a group of key-value documents given as their training tables
         (msau_amd.training.kv_data.train_table / KVTrainBatches): one upload of the packed tables, one launch that paints the id
         canvas and both label canvases (msau_kv_paint_train), then `step_unet` on them with the documents' sizes.  No per-pixel
         array is built on the host and nothing waits for the device -- except for a document whose table is not `ok`, which is
-        painted on the host and uploaded (kv_data.STATS counts them).  `stats` as in `step_unet`.
+        painted on the host and uploaded (kv_data.STATS counts them).  `stats` and `cost` as in `step_unet`.
         When a table carries a `warp` (the generator's affine or rotation augmentation: kv_warp.py, `KVTrainBatches(kwargs_dat=...)`)
         the painted canvases are resampled on the device: paint -> msau_kv_warp_train, which writes the multi-hot input straight
         into the plan's input buffer and the two warped label maps -> the tail of `step_unet_nhwc`, on the warped sizes and their
@@ -1178,11 +1186,12 @@ class TrainEngine:
         `kv_warp.warp_host` and uploaded (kv_data.STATS["host_warped"]).  A group without warps takes the path above, launch for
         launch."""
         self._eager("step_kv")
+        cost = unet_cost(cost)
         from .training import kv_data
         dev = self.model._flat.device
         ids, labels, aux_labels, sizes = kv_data.paint_train_device(tables, round_to=round_to, device=dev)
         if all(t.warp is None for t in tables):
-            return self.step_unet(ids, labels, aux_labels, sizes=sizes, class_weights=class_weights, stats=stats)
+            return self.step_unet(ids, labels, aux_labels, sizes=sizes, class_weights=class_weights, stats=stats, cost=cost)
         from .training import kv_warp
         m = self.model
         cw = self._class_weights(class_weights, m.n_class)
@@ -1196,7 +1205,7 @@ class TrainEngine:
             kv_warp.upload_host_warp(b, tables[b], warps[b], grid, wl, wa, m.channels, m.n_class)
             kv_data.STATS["host_warped"] += 1
         # (the kernel and the host warp leave zeros outside the warped extents: nothing to clear)
-        return self._step_unet(plan, wl, wa, cw, stats, nhwc_ready=True, nhwc_clean=True)
+        return self._step_unet(plan, wl, wa, cw, stats, cost, nhwc_ready=True, nhwc_clean=True)
 
     def input_nhwc(self, B: int, H: int, W: int) -> torch.Tensor:
         """The training plan's own input buffer for this shape, [B][H][W][Cs] in the storage dtype: the zero-copy target of

@@ -89,6 +89,36 @@ class Launch(NamedTuple):
     flops: float = 0.0
 
 
+class UnetCost(NamedTuple):
+    """a checked cost of the UNetLoss kernels: msau_unet_cost's `kind` and `param`"""
+    kind: int
+    param: float
+
+
+def unet_cost(cost) -> Optional[UnetCost]:
+    """The one place a `cost` is checked: None, a dict as `UNetLoss` takes it -- {"cost_name": "cross_entropy"},
+    {"cost_name": "focal", "gamma": 2.0} (gamma >= 0, default 2) or {"cost_name": "dice", "smooth": 1.0} (smooth > 0, default 1);
+    other keys are `UNetLoss`'s own -- or what this function returned.  -> None for the cross entropy (today's launches), else the
+    UnetCost.  ValueError for anything else."""
+    if cost is None or isinstance(cost, UnetCost):
+        return cost
+    if not isinstance(cost, dict):
+        raise ValueError(f"cost: a dict with a cost_name, got {type(cost).__name__}")
+    name = cost.get("cost_name", "cross_entropy")
+    if name == "cross_entropy":
+        return None
+    if name not in ("focal", "dice"):
+        raise ValueError(f"cost_name {name!r}: one of cross_entropy, focal, dice")
+    key, kind, default = ("gamma", L.COST_FOCAL, 2.0) if name == "focal" else ("smooth", L.COST_DICE, 1.0)
+    try:
+        param = float(cost.get(key, default))
+    except (TypeError, ValueError):
+        raise ValueError(f"cost: {key} = {cost.get(key)!r} is not a number") from None
+    if not math.isfinite(param) or param < 0 or (name == "dice" and param == 0):
+        raise ValueError(f"cost: {name} wants a finite {key} {'>= 0' if name == 'focal' else '> 0'}, got {param}")
+    return UnetCost(kind, param)
+
+
 class Act:
     """An activation tensor [B,H,W,Cs] (+ its gradient buffer)."""
 
@@ -1844,23 +1874,35 @@ class Plan:
                    1.0 / self.B)
         return self.loss_buf
 
-    def unet_launches(self, weighted: bool) -> List[Launch]:
+    def unet_launches(self, weighted: bool, cost=None) -> List[Launch]:
         """the launches of `loss_grads_unet`, stated as `_boundary_launches` states those of `loss_grads` (which they replace in a
-        key-value training step): key and algorithmic bytes, for the step's accounting and a profiler's attribution"""
+        key-value training step): key and algorithmic bytes, for the step's accounting and a profiler's attribution.  `cost` as
+        `loss_grads_unet` takes it: the focal loss moves the cross entropy's bytes under its own key; the Dice loss always takes
+        the histograms and reads label and logits once more (the reduction behind its gradient pass)."""
+        cost = unet_cost(cost)
         esz = 4 if self.dtype == L.F32 else 2
         HW, lg = self.H * self.W, self.logits
         nl = 2 if self.aux is not None else 1
-        out = [Launch(0, None, "msau_label_hist", self.B * HW * 8)] * (nl if weighted else 0)
-        out.append(Launch(0, None, "msau_unet_ce", self.B * HW * nl * (8 + 2 * lg.Cs * esz)))
+        dice = cost is not None and cost.kind == L.COST_DICE
+        out = [Launch(0, None, "msau_label_hist", self.B * HW * 8)] * (nl if weighted or dice else 0)
+        nbytes = self.B * HW * nl * (8 + 2 * lg.Cs * esz)
+        if dice:
+            nbytes += self.B * HW * nl * (8 + lg.Cs * esz)
+        out.append(Launch(0, None, "msau_unet_ce" if cost is None else "msau_unet_cost", nbytes))
         return out
 
-    def loss_grads_unet(self, labels: torch.Tensor, aux_labels: Optional[torch.Tensor], class_w: Optional[torch.Tensor] = None) -> torch.Tensor:
+    def loss_grads_unet(self, labels: torch.Tensor, aux_labels: Optional[torch.Tensor], class_w: Optional[torch.Tensor] = None,
+                        cost=None) -> torch.Tensor:
         """UNetLoss (model/training/cost.py:35-65: CE over every pixel, class 0 counted, 0.5 final + 0.5 auxiliary, optional class
         weights) fused with its gradient, under the ragged rule: every document computes what it computes alone, the batch is the
         mean of the documents.  `labels` / `aux_labels` int64 [B,H,W]: each head has its own map; the kernel reads the extents
         itself, so the canvases are not copied and whatever they hold outside the documents is ignored.  `class_w`: fp32 [n_class]
         on the device; only then the per-document class histograms are taken (one launch per head).  Writes d(logits), d(aux) in
-        place and returns the plan's 3-float buffer (total, final, auxiliary)."""
+        place and returns the plan's 3-float buffer (total, final, auxiliary).
+        `cost` (`unet_cost`: None, a dict such as {"cost_name": "focal", "gamma": 2.0} or {"cost_name": "dice", "smooth": 1.0}): the
+        focal or the soft Dice loss under the same rules (msau_unet_cost; Dice always takes the histograms).  None or
+        "cross_entropy": the path above, launch for launch."""
+        cost = unet_cost(cost)
         lg, ax = self.logits, self.aux
         for t in (labels,) + ((aux_labels,) if ax is not None else ()):
             assert t is not None and t.dtype == torch.int64 and t.is_contiguous() and tuple(t.shape) == (self.B, self.H, self.W)
@@ -1871,28 +1913,48 @@ class Plan:
             self.unet_loss_buf = torch.zeros((3,), dtype=torch.float32, device=self.device)
             self.unet_ws = torch.zeros((int(L.load().msau_unet_ce_ws_floats(self.B * self.H * self.W)),), dtype=torch.float32, device=self.device)
             self.unet_hist_k = max(1, min(16, 256 // self.B))
+            # Dice: K is also the slabs per document of its reduction pass.  Two workgroups per compute unit were the best of three
+            # choices in ONE measurement: B = 16 on 320 x 256, 256 compute units (profiles/unet_cost.md: K = 16 / 32 / 64 -> 163 /
+            # 146 / 150 us in bf16).  Any other B or canvas size is unmeasured, and what bounds that pass has not been profiled.
+            self.unet_dice_k = max(1, min(32, 512 // self.B))
             self.unet_hist = None
         ext = self.extents.data_ptr() if self.ragged else None      # level 0: the documents' own (h, w)
-        K, hist = self.unet_hist_k, None
+        dice = cost is not None and cost.kind == L.COST_DICE
+        K, hist = self.unet_dice_k if dice else self.unet_hist_k, None
         if class_w is not None:
             assert class_w.dtype == torch.float32 and class_w.is_contiguous() and class_w.numel() == lg.C and class_w.device == lg.data.device
-            if self.unet_hist is None:
+        if class_w is not None or dice:
+            if self.unet_hist is None or self.unet_hist.shape[2] < K:      # (grows once when a plan's cost changes to Dice)
                 self.unet_hist = torch.zeros((2, self.B, K, lg.C), dtype=torch.int32, device=self.device)
             hist = self.unet_hist.data_ptr()
             for t, lab in enumerate((labels, aux_labels) if ax is not None else (labels,)):
                 L.call("msau_label_hist", s, lab.data_ptr(), ext, hist + 4 * t * self.B * K * lg.C, self.B, self.H, self.W, lg.C, K)
+        if cost is not None:
+            if getattr(self, "unet_cost_ws", None) is None or self.unet_cost_ws[0] != cost.kind:
+                n = int(L.load().msau_unet_cost_ws_floats(cost.kind, self.B, self.H, self.W, lg.C))
+                self.unet_cost_ws = (cost.kind, torch.zeros((n,), dtype=torch.float32, device=self.device))
+            L.call("msau_unet_cost", s, self.dtype, cost.kind, cost.param, lg.data.data_ptr(), _ptr(ax.data) if ax is not None else None,
+                   labels.data_ptr(), aux_labels.data_ptr() if ax is not None else None, ext, _ptr(class_w), hist, K, lg.grad.data_ptr(),
+                   _ptr(ax.grad) if ax is not None else None, self.unet_loss_buf.data_ptr(), self.unet_cost_ws[1].data_ptr(),
+                   self.B, self.H, self.W, lg.C, lg.Cs)
+            return self.unet_loss_buf
         L.call("msau_unet_ce", s, self.dtype, lg.data.data_ptr(), _ptr(ax.data) if ax is not None else None, labels.data_ptr(),
                aux_labels.data_ptr() if ax is not None else None, ext, _ptr(class_w), hist, K, lg.grad.data_ptr(),
                _ptr(ax.grad) if ax is not None else None, self.unet_loss_buf.data_ptr(), self.unet_ws.data_ptr(),
                self.B, self.H, self.W, lg.C, lg.Cs)
         return self.unet_loss_buf
 
-    def unet_eval_launches(self) -> List[Launch]:
+    def unet_eval_launches(self, cost=None) -> List[Launch]:
         """the launch of `eval_unet`, stated as `unet_launches` states those of `loss_grads_unet`: key and algorithmic bytes (per head
-        the int64 label and the pixel's stored logits, read once; the K partial rows and the finish launch are noise beside them)"""
+        the int64 label and the pixel's stored logits, read once; the K partial rows and the finish launch are noise beside them).
+        `cost` as `eval_unet` takes it: Dice reads both once more and the labels a third time (its own histograms)."""
+        cost = unet_cost(cost)
         esz = 4 if self.dtype == L.F32 else 2
         nl = 2 if self.aux is not None else 1
-        return [Launch(0, None, "msau_unet_eval", self.B * self.H * self.W * nl * (8 + self.logits.Cs * esz))]
+        nbytes = self.B * self.H * self.W * nl * (8 + self.logits.Cs * esz)
+        if cost is not None and cost.kind == L.COST_DICE:
+            nbytes += self.B * self.H * self.W * nl * (16 + self.logits.Cs * esz)
+        return [Launch(0, None, "msau_unet_eval" if cost is None else "msau_unet_cost_eval", nbytes)]
 
     def unet_eval_k(self) -> int:
         """workgroups per document of `eval_unet`: enough to give every compute unit two workgroups, never more than the smallest
@@ -1902,13 +1964,16 @@ class Plan:
         rows = int(self._ext_host[0, :, 0].min()) if self.ragged else self.H      # the pinned host copy of set_extents: no sync
         return max(1, min(256, rows, -(-2 * self._cu_count // self.B)))
 
-    def eval_unet(self, labels: torch.Tensor, aux_labels: Optional[torch.Tensor], class_w: Optional[torch.Tensor] = None, out=None):
+    def eval_unet(self, labels: torch.Tensor, aux_labels: Optional[torch.Tensor], class_w: Optional[torch.Tensor] = None, out=None,
+                  cost=None):
         """UNetLoss and the reference's accuracy per document, forward only (msau_unet_eval): after `forward(export=False)` on a
         forward-only plan, on the logits both heads left in the plan (`TrainEngine.step_unet(stats=...)` calls it on the training
         plan's, between the forward and the loss kernel).  `labels` / `aux_labels` / `class_w` as `loss_grads_unet` takes
         them; the kernel reads the extents itself.  -> (doc_loss fp32 [B, 2], doc_counts int32 [B, 2, 2]) on the device, head 0 =
         final, head 1 = auxiliary, counts = (labelled, correct); `out`: a pair of such tensors to write instead of fresh ones.  No
-        gradient buffer is touched and nothing waits for the device."""
+        gradient buffer is touched and nothing waits for the device.  `cost` as `loss_grads_unet` takes it: doc_loss is then the
+        document's loss under that cost (msau_unet_cost_eval), the counts are unchanged."""
+        cost = unet_cost(cost)
         lg, ax = self.logits, self.aux
         for t in (labels,) + ((aux_labels,) if ax is not None else ()):
             assert t is not None and t.dtype == torch.int64 and t.is_contiguous() and tuple(t.shape) == (self.B, self.H, self.W)
@@ -1926,6 +1991,15 @@ class Plan:
         K = self.unet_eval_k()
         if getattr(self, "unet_eval_ws", None) is None:          # for the largest K: the extents, and with them K, change per batch
             self.unet_eval_ws = torch.zeros((int(L.load().msau_unet_eval_ws_bytes(self.B, 256)),), dtype=torch.uint8, device=self.device)
+        if cost is not None:
+            if getattr(self, "unet_cost_eval_ws", None) is None or self.unet_cost_eval_ws[0] != cost.kind:
+                n = int(L.load().msau_unet_cost_eval_ws_bytes(cost.kind, self.B, 256, lg.C))
+                self.unet_cost_eval_ws = (cost.kind, torch.zeros((n,), dtype=torch.uint8, device=self.device))
+            L.call("msau_unet_cost_eval", self._stream(), self.dtype, cost.kind, cost.param, lg.data.data_ptr(),
+                   _ptr(ax.data) if ax is not None else None, labels.data_ptr(), aux_labels.data_ptr() if ax is not None else None,
+                   self.extents.data_ptr() if self.ragged else None, _ptr(class_w), K, doc_loss.data_ptr(), doc_counts.data_ptr(),
+                   self.unet_cost_eval_ws[1].data_ptr(), self.B, self.H, self.W, lg.C, lg.Cs)
+            return doc_loss, doc_counts
         L.call("msau_unet_eval", self._stream(), self.dtype, lg.data.data_ptr(), _ptr(ax.data) if ax is not None else None,
                labels.data_ptr(), aux_labels.data_ptr() if ax is not None else None, self.extents.data_ptr() if self.ragged else None,
                _ptr(class_w), K, doc_loss.data_ptr(), doc_counts.data_ptr(), self.unet_eval_ws.data_ptr(), self.B, self.H, self.W,

@@ -1,12 +1,15 @@
 """`UNetLoss` counterpart (reference: model/training/cost.py:6-65): plain cross entropy over every pixel on
 one-hot targets, 0.5 * final + 0.5 * auxiliary when auxiliary logits are given, accuracy over pixels whose
-target class is not 0.  The CE and its gradient are one HIP kernel (`msau_softmax_ce`)."""
+target class is not 0.  The CE and its gradient are one HIP kernel (`msau_softmax_ce`).  Beyond the reference, which promises
+a Dice cost and returns the prediction for it: `cost_name` "focal" (`gamma`, default 2) and "dice" (`smooth`, default 1) are the
+focal and the soft Dice loss of DESIGN.md 5e, each sample of the batch a document of its own (`msau_unet_cost`)."""
 from __future__ import annotations
 
 import numpy as np
 import torch
 
 from .. import _lib as L
+from ..plan import unet_cost
 
 
 class _SoftmaxCE(torch.autograd.Function):
@@ -69,29 +72,71 @@ class _WeightedSoftmaxCE(torch.autograd.Function):
         return g * (go / sums[1]), None, None
 
 
+class _UnetCost(torch.autograd.Function):
+    """the focal or the soft Dice loss of one head on NCHW fp32 logits (`msau_unet_cost`): every sample is its own document, the
+    loss is the mean of the samples' losses; `cost` a checked msau_amd.plan.UnetCost, `class_w` fp32 [C] on the device or None"""
+
+    @staticmethod
+    def forward(ctx, logits, target, cost, class_w):
+        B, C, H, W = logits.shape
+        dev = logits.device
+        Cs = -(-C // 8) * 8
+        K = 4
+        s = torch.cuda.current_stream().cuda_stream
+        lg = logits.contiguous().float()
+        tg = target.reshape(B, H, W).contiguous().long()
+        nhwc = torch.empty((B, H, W, Cs), dtype=torch.float32, device=dev)
+        dn = torch.empty_like(nhwc)
+        loss3 = torch.empty((3,), dtype=torch.float32, device=dev)
+        ws = torch.empty((int(L.load().msau_unet_cost_ws_floats(cost.kind, B, H, W, C)),), dtype=torch.float32, device=dev)
+        hist = None
+        if class_w is not None or cost.kind == L.COST_DICE:
+            hist = torch.empty((B, K, C), dtype=torch.int32, device=dev)
+            L.call("msau_label_hist", s, tg.data_ptr(), None, hist.data_ptr(), B, H, W, C, K)
+        L.call("msau_nchw_to_nhwc", s, L.F32, lg.data_ptr(), nhwc.data_ptr(), B, C, Cs, H, W)
+        L.call("msau_unet_cost", s, L.F32, cost.kind, cost.param, nhwc.data_ptr(), None, tg.data_ptr(), None, None,
+               class_w.data_ptr() if class_w is not None else None, hist.data_ptr() if hist is not None else None, K, dn.data_ptr(), None,
+               loss3.data_ptr(), ws.data_ptr(), B, H, W, C, Cs)
+        g = torch.empty((B, C, H, W), dtype=torch.float32, device=dev)
+        L.call("msau_nhwc_to_nchw", s, L.F32, dn.data_ptr(), g.data_ptr(), B, C, Cs, H, W)
+        ctx.save_for_backward(g)
+        return loss3[0].clone()
+
+    @staticmethod
+    def backward(ctx, go):
+        (g,) = ctx.saved_tensors
+        return g * go, None, None, None
+
+
 class UNetLoss(torch.nn.Module):
     def __init__(self, kwargs):
         super().__init__()
         self.cost_name = kwargs.get("cost_name", "cross_entropy")
         self.act_name = kwargs.get("act_name", "softmax")
         self.class_weights = kwargs.get("class_weights", None)
-        if self.class_weights is not None and self.cost_name == "cross_entropy":
+        self.cost = unet_cost(kwargs) if self.cost_name in ("focal", "dice") else None
+        if self.class_weights is not None and self.cost_name in ("cross_entropy", "focal", "dice"):
             # the reference keeps them as a CPU tensor inside torch.nn.CrossEntropyLoss (cost.py:26-29); here a buffer that
             # follows the module to the device
             self.register_buffer("class_weights_torch", torch.from_numpy(np.array(self.class_weights, dtype=np.float32)))
 
     def _ce(self, logits, tgt_idx):
-        if self.class_weights is None:
+        """the head's loss under `cost_name` (the cross entropy, or `_UnetCost`)"""
+        cw = None
+        if self.class_weights is not None:
+            cw = self.class_weights_torch.to(logits.device).contiguous()
+            assert cw.numel() == logits.shape[1], "class_weights: one weight per class"
+        if self.cost is not None:
+            return _UnetCost.apply(logits, tgt_idx, self.cost, cw)
+        if cw is None:
             return _SoftmaxCE.apply(logits, tgt_idx)
-        cw = self.class_weights_torch.to(logits.device)
-        assert cw.numel() == logits.shape[1], "class_weights: one weight per class"
-        return _WeightedSoftmaxCE.apply(logits, tgt_idx, cw.contiguous())
+        return _WeightedSoftmaxCE.apply(logits, tgt_idx, cw)
 
     def forward(self, logits, tgt, kwargs):
         """-> (acc, loss, final_loss) exactly as the reference; `tgt` / `aux_tgt` are one-hot [B,C,H,W]"""
         aux_logits = kwargs.get("aux_logits", None)
         aux_tgt = kwargs.get("aux_tgt", None)
-        if self.cost_name != "cross_entropy":
+        if self.cost_name not in ("cross_entropy", "focal", "dice"):
             return torch.softmax(logits, dim=1) if self.act_name == "softmax" else logits
         tgt = torch.argmax(tgt, dim=1)
         with torch.no_grad():

@@ -55,10 +55,16 @@ class KVTrainer:
     `TrainEngine.step_unet` takes them, `engine_kwargs` for the TrainEngine.  `opt_kwargs` (a dict, `{}` included): the options of
     the reference's `get_optimizer`; the engine is then `TrainEngine.from_opt_kwargs(model, opt_kwargs, **engine_kwargs)`, the
     reference `Trainer`'s optimiser -- RMSprop at 1e-3 by default, no gradient clipping.  None: the engine's own default (clip +
-    Adam).  Eager only; under data parallelism every rank would validate every document."""
+    Adam).  `cost_kwargs`: the `cost` of `TrainEngine.step_unet` ({"cost_name": "focal", "gamma": 2.0}, {"cost_name": "dice",
+    "smooth": 1.0}; None: the cross entropy), checked here and given to every training step AND every validation call: the
+    TRAIN / VAL lines and the checkpoint rule run on the loss that is trained.  Eager only; under data parallelism every rank
+    would validate every document."""
 
-    def __init__(self, model, batches, class_weights=None, engine_kwargs={}, opt_kwargs=None):
+    def __init__(self, model, batches, class_weights=None, engine_kwargs={}, opt_kwargs=None, cost_kwargs=None):
+        from ..plan import unet_cost
         self.model, self.batches, self.class_weights = model, batches, class_weights
+        self.cost = unet_cost(cost_kwargs)
+        self._cost_kw = {} if self.cost is None else {"cost": self.cost}      # the cross entropy: the calls as they always were
         self.engine = self._engine(dict(engine_kwargs)) if opt_kwargs is None else self._engine_from_opt(dict(opt_kwargs), dict(engine_kwargs))
 
     def _engine(self, kwargs):
@@ -77,7 +83,7 @@ class KVTrainer:
         """every group of `batches.validation()` through `eval_kv`; one read"""
         rows = _Rows()
         for group in self.batches.validation():
-            rows.add(self.model.eval_kv(group, class_weights=self.class_weights))
+            rows.add(self.model.eval_kv(group, class_weights=self.class_weights, **self._cost_kw))
         return rows.read()
 
     def fit(self, output_path, epochs: int, steps_per_epoch: int, restore_path=None) -> List[dict]:
@@ -104,7 +110,7 @@ class KVTrainer:
             for _ in range(steps_per_epoch):
                 group = next(self.batches)
                 stats = self._stats(len(group))
-                self.engine.step_kv(group, class_weights=self.class_weights, stats=stats)
+                self.engine.step_kv(group, class_weights=self.class_weights, stats=stats, **self._cost_kw)
                 rows.add(stats)
                 shown += len(group)
             train = rows.read()

@@ -70,24 +70,31 @@ def scipy_warp(t, maps):
     return out
 
 
+def cost_of(args):
+    """--cost / --gamma / --smooth as the `cost` of TrainEngine.step_kv / MSAUWrapper.eval_kv and as UNetLoss's kwargs (the trainer
+    routes); None for the cross entropy"""
+    return {"cross_entropy": None, "focal": {"cost_name": "focal", "gamma": args.gamma}, "dice": {"cost_name": "dice", "smooth": args.smooth}}[args.cost]
+
+
 def run_tables(args):
     it = batches(args, args.batch_size)
     eng = TrainEngine(model(it.n_token, args.n_class, args.dtype), lr=args.lr, optimizer=args.optimizer, weight_decay=args.weight_decay,
                       max_norm=None if args.no_clip else 1.0)
     print("optimiser launches:", ", ".join(f"{key} ({nbytes} B)" for key, nbytes in eng.optim_launches()))
     cw = [float(v) for v in args.class_weights.split(",")] if args.class_weights else None
+    cost = cost_of(args)
     for _ in range(args.warmup):
-        eng.step_kv(next(it), class_weights=cw, round_to=args.round_to)
+        eng.step_kv(next(it), class_weights=cw, round_to=args.round_to, cost=cost)
     torch.cuda.synchronize()
     kv_data.STATS.update(calls=0, documents=0, host_painted=0, h2d_bytes=0, host_warped=0)
     losses = []
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        losses.append(eng.step_kv(next(it), class_weights=cw, round_to=args.round_to).clone())
+        losses.append(eng.step_kv(next(it), class_weights=cw, round_to=args.round_to, cost=cost).clone())
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
     docs = args.steps * args.batch_size
-    return dict(route="tables", batch_size=args.batch_size, optimizer=args.optimizer, clip=not args.no_clip, weight_decay=args.weight_decay,
+    return dict(route="tables", cost=args.cost, batch_size=args.batch_size, optimizer=args.optimizer, clip=not args.no_clip, weight_decay=args.weight_decay,
                 optim_launches=[key for key, _ in eng.optim_launches()], docs_per_s=docs / dt,
                 h2d_bytes_per_doc=kv_data.STATS["h2d_bytes"] / docs,
                 host_painted=kv_data.STATS["host_painted"], host_warped=kv_data.STATS["host_warped"], warp=args.warp, loss=[round(float(l[0]), 5) for l in torch.stack(losses).cpu()])
@@ -96,7 +103,7 @@ def run_tables(args):
 def run_trainer(args):
     it = batches(args, 1)
     net = model(it.n_token, args.n_class, args.dtype)
-    crit = UNetLoss({})
+    crit = UNetLoss(cost_of(args) or {})
     opt = {"adam": lambda ps: torch.optim.Adam(ps, lr=args.lr, weight_decay=args.weight_decay),
            "rmsprop": lambda ps: torch.optim.RMSprop(ps, lr=args.lr, weight_decay=args.weight_decay),
            "momentum": lambda ps: torch.optim.SGD(ps, lr=args.lr, momentum=0.9, weight_decay=args.weight_decay)}[args.optimizer](net.parameters())
@@ -131,7 +138,7 @@ def run_trainer(args):
         nbytes += n
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
-    return dict(route="trainer", batch_size=1, warp=args.warp, docs_per_s=docs / dt, h2d_bytes_per_doc=nbytes / docs,
+    return dict(route="trainer", cost=args.cost, batch_size=1, warp=args.warp, docs_per_s=docs / dt, h2d_bytes_per_doc=nbytes / docs,
                 loss=[round(float(l), 5) for l in torch.stack(losses).cpu()][::max(1, args.batch_size)])
 
 
@@ -145,16 +152,16 @@ def run_eval_kv(args, net, docs, batch_size):
     from msau_amd.training.kv_trainer import summarize
     groups = [docs[i:i + batch_size] for i in range(0, len(docs), batch_size)]
     for g in groups[:args.warmup] + groups[-1:]:                          # every canvas of the timed window (the last may be smaller)
-        net.eval_kv(g, round_to=args.round_to)
+        net.eval_kv(g, round_to=args.round_to, cost=cost_of(args))
     torch.cuda.synchronize()
     t0 = time.perf_counter()
-    rows = [net.eval_kv(g, round_to=args.round_to) for g in groups]
+    rows = [net.eval_kv(g, round_to=args.round_to, cost=cost_of(args)) for g in groups]
     s = summarize(torch.cat([r[0] for r in rows]), torch.cat([r[1] for r in rows]))      # the one read: ends the window
     return len(docs) / (time.perf_counter() - t0), s
 
 
 def run_eval_trainer(args, net, docs, n_token):
-    crit = UNetLoss({})
+    crit = UNetLoss(cost_of(args) or {})
     eye_in, eye_out = np.eye(n_token, dtype="B"), np.eye(args.n_class, dtype="B")
 
     def one(t):
@@ -209,7 +216,7 @@ def run_eval(args):
         os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
         with open(args.out, "w") as fh:
             fh.write(text)
-    print(json.dumps(dict(mode="eval", dtype=args.dtype, eval_docs=args.eval_docs, repeats=args.repeats, results=out)))
+    print(json.dumps(dict(mode="eval", cost=args.cost, dtype=args.dtype, eval_docs=args.eval_docs, repeats=args.repeats, results=out)))
 
 
 def main():
@@ -230,6 +237,9 @@ def main():
     ap.add_argument("--scale-max", type=float, default=4.0)
     ap.add_argument("--text-err", type=float, default=0.1)
     ap.add_argument("--class-weights", default="", help="comma-separated, n_class values (tables route)")
+    ap.add_argument("--cost", default="cross_entropy", choices=["cross_entropy", "focal", "dice"], help="the loss of every route, training and --eval")
+    ap.add_argument("--gamma", type=float, default=2.0, help="--cost focal")
+    ap.add_argument("--smooth", type=float, default=1.0, help="--cost dice")
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--warp", default="", choices=["", "affine", "rotate"], help="the generator's augmentation: on the device in the tables "
                     "route, scipy.ndimage on the host in the trainer route")
