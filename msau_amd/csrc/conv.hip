@@ -397,7 +397,7 @@ static int conv_route(int dtype, const msau_conv_desc* d, ConvRoute* r, int fami
     } else if (!rc) {
         const ConvGeom& g = r->g;
         if (g.nslices > 1) r->inst = 0;                                        // more than 128 output channels: slices of the tile kernel
-        else if (asked(CONV_ROWS) && (r->inst = msau_rowconv_case(dtype, d))) r->family = CONV_ROWS;
+        else if (asked(CONV_ROWS) && (r->inst = msau_rowconv_case(dtype, d, g.kchunk, g.rows))) r->family = CONV_ROWS;
         else if (asked(CONV_CHUNKED) && (r->inst = msau_conv_chunked_case(dtype, d, g.cch, g.nchunks, g.CT))) r->family = CONV_CHUNKED;
         else if (asked(CONV_LEAN) && (r->inst = msau_conv_lean_case(dtype, d, g.nchunks, g.CT))) r->family = CONV_LEAN;
         if (r->family == CONV_REFUSED && asked(CONV_TILE) && !(f & kOnlyOthers)) r->family = CONV_TILE;
@@ -483,7 +483,7 @@ extern "C" int msau_conv2d_launch_info(int dtype, const msau_conv_desc* d, int32
 extern "C" int msau_conv2d_rider_slabs(int dtype, const msau_conv_desc* d) {
     ConvRoute r;
     if (!d || !(d->flags & MSAU_CONV_WGRAD) || conv_route(dtype, d, &r) || r.family != CONV_ROWS) return 0;
-    return msau_rowconv_workgroups(d);                   // (the row-streaming coupling instance is the one that carries the rider)
+    return msau_rowconv_workgroups(d, r.inst);           // (the row-streaming coupling instance is the one that carries the rider)
 }
 
 static int tile_launch(hipStream_t s, int dtype, const msau_conv_desc* d, const ConvRoute& r) {

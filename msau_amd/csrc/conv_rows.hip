@@ -1587,17 +1587,26 @@ const RowsEnv& rows_env() {
     return g_env;
 }
 
-// segment height: a wave takes one task; aim for MSAU_ROWS_WAVES tasks in one round, at least 8 rows each.
+// Segment height of every row launch, the arithmetic written here and nowhere else.  A wave takes one task: aim for `target` tasks
+// in one round, i.e. target / (B * nstrips) segments per strip (`sh` > 0, MSAU_ROWS_SH: that height instead); at least `min_rows`
+// rows each; rounded up so that the loop's trips of `trip` rows come out even with `warm` iterations besides the rows; and, where the
+// kernel does not bound its last segment itself (`clamp`), no more than the image's H rows.
+struct SegRule { int min_rows, trip, warm; bool clamp; };
+int segment_height(int target, int B, int nstrips, int H, int sh, SegRule r) {
+    int nseg = target / (B * nstrips);
+    if (nseg < 1) nseg = 1;
+    if (sh <= 0) sh = cdiv(H, nseg);
+    if (sh < r.min_rows) sh = r.min_rows;
+    sh = roundup(sh + r.warm, r.trip) - r.warm;
+    return r.clamp && sh > H ? H : sh;
+}
+
+// ... of the residual pair: MSAU_ROWS_SH / MSAU_ROWS_SH16 are taken as they are (no minimum, no rounding), else trips of 6 rows
 int segment_rows(int B, int H, int nstrips, int warm, bool c16 = false) {
     const RowsEnv& e = rows_env();
     if (e.sh > 0) return e.sh < H ? e.sh : H;
     if (c16 && e.sh16 > 0) return e.sh16 < H ? e.sh16 : H;
-    int nseg = e.waves / (B * nstrips);
-    if (nseg < 1) nseg = 1;
-    int sh = cdiv(H, nseg);
-    if (sh < 10) sh = 10;
-    sh = cdiv(sh + warm, UNR) * UNR - warm;              // `warm` iterations besides the rows: the trips of 6 come out even
-    return sh < H ? sh : H;
+    return segment_height(e.waves, B, nstrips, H, 0, {10, UNR, warm, true});
 }
 
 // ---- the residual pair (msau_conv_pair descriptors).  The number of an instance packs its template arguments; ROWPAIR_TABLE is the
@@ -1699,181 +1708,187 @@ int msau_rowpair_launch(hipStream_t s, const msau_conv_pair_desc* d, const PairR
     return rowpair_instance(r->inst, s, &a);
 }
 
-// ---- single convolutions (msau_conv2d descriptors)
+// ---- single convolutions (msau_conv2d descriptors).  The same contract as the pair's: the number of an instance packs what selects
+// its kernel (rowconv_id), ROWCONV_TABLE is the one list of the instances that exist, rowconv_instance() reads it as the query and as
+// the launch, rowconv_split() is the task split of either kind of kernel.
 namespace {
-template <int NS, int KH, int KW, int EPI, int EPI2 = 0>
-int launch_rowconv8(hipStream_t s, const RowConvArgs& a) {
-    hipLaunchKernelGGL((rowconv8_kernel<NS, KH, KW, EPI, EPI2>), dim3(8 * (a.tasks_per_xcd / 4)), dim3(256), 0, s, a);
-    MSAU_CHECK_LAUNCH("rowconv8_kernel");
+enum { RC_CONV8 = 1, RC_DECONV8 = 2, RC_DECONV16 = 3 };                    // the kernel: rowconv8 <NS, KH, KW, EPI, EPI2, WG>, rowdeconv8, rowdeconv16
+// EPI = flags without MSAU_CONV_WGRAD (15 bits: MSAU_CONV_ELU and above have no instance), WG = that flag, EPI2 = flags2 (6 bits)
+constexpr int rowconv_id(int kind, int ns, int kh, int kw, int epi, int epi2, bool wg) {
+    return kind | (ns - 1) << 2 | kh << 3 | kw << 6 | epi << 9 | epi2 << 24 | wg << 30;
+}
+constexpr int rowconv_kind(int id) { return id & 3; }
+constexpr bool rowconv_wg(int id) { return id >> 30 & 1; }
+// X(KIND, NS, KH, KW, EPI, EPI2, WG)
+#define ROWCONV8(X, NS, K, EPI) X(RC_CONV8, NS, K, K, EPI, 0, false)
+#define ROWCONV_TABLE(X)                                                                                                           \
+    /* 3x3 8 -> 8: the LRN as second output, plain, y accumulates; 3x3 and the coupling 1x1 over concat(8, 8) -> 8 */               \
+    ROWCONV8(X, 1, 3, MSAU_CONV_LRN) ROWCONV8(X, 1, 3, 0) ROWCONV8(X, 1, 3, MSAU_CONV_ACCUM)                                       \
+    ROWCONV8(X, 2, 3, 0) ROWCONV8(X, 2, 1, MSAU_CONV_RELU_OUT)                                                                     \
+    /* 4x4, the end conv (pad 1) and its data gradient (flipped image, pad 2) */                                                   \
+    ROWCONV8(X, 1, 4, 0) ROWCONV8(X, 1, 4, MSAU_CONV_MASK_B) ROWCONV8(X, 1, 4, MSAU_CONV_ACCUM | MSAU_CONV_MASK_B)                 \
+    /* two outputs, the data gradient of a conv over concat(x1, x2), g -> (dx1, dx2), with the flag sets the reference's nets      \
+       produce: 3x3 plain / y accumulates; 1x1 with y2 masked, alone and with the coupling conv's weight gradient as a rider */    \
+    ROWCONV8(X, 1, 3, MSAU_CONV_DOUT) ROWCONV8(X, 1, 3, MSAU_CONV_DOUT | MSAU_CONV_ACCUM)                                          \
+    X(RC_CONV8, 1, 1, 1, MSAU_CONV_DOUT, MSAU_CONV_MASK_B, false) X(RC_CONV8, 1, 1, 1, MSAU_CONV_DOUT, MSAU_CONV_MASK_B, true)     \
+    /* the transposed convs 16 -> 8 and 32 -> 16 (3x3, ups 2) from their live taps */                                              \
+    X(RC_DECONV8, 1, 3, 3, 0, 0, false) X(RC_DECONV16, 1, 3, 3, 0, 0, false)
+
+// what a launch takes besides its instance: the descriptor, its task split and the packed image's row and chunk sizes
+struct RowConvJob { const msau_conv_desc* d; int nstrips, nseg, SH, ntasks, tasks_per_xcd, wrow, wchunk; };
+
+template <int KIND, int NS, int KH, int KW, int EPI, int EPI2, bool WG>
+int launch_rowconv(hipStream_t s, const RowConvJob& j) {
+    const msau_conv_desc* d = j.d;
+    const dim3 grid(8 * (j.tasks_per_xcd / 4)), block(256);
+    if constexpr (KIND == RC_CONV8) {
+        const int row_bytes = d->Wout * 16;
+        const RowConvArgs a{*d, j.nstrips, j.nseg, j.SH, j.ntasks, j.tasks_per_xcd, row_bytes, j.wrow, j.wchunk, (unsigned)d->Hout * (unsigned)row_bytes};
+        hipLaunchKernelGGL((rowconv8_kernel<NS, KH, KW, EPI, EPI2, WG>), grid, block, 0, s, a);
+    } else {
+        const int in_row = d->Win * d->C1 * 2, out_row = d->Wout * d->Cout * 2;
+        const RowDeconvArgs a{*d, j.nstrips, j.nseg, j.SH, j.ntasks, j.tasks_per_xcd, in_row, out_row, (unsigned)d->Hin * (unsigned)in_row, (unsigned)d->Hout * (unsigned)out_row};
+        if constexpr (KIND == RC_DECONV8) hipLaunchKernelGGL(rowdeconv8_kernel, grid, block, 0, s, a);
+        else hipLaunchKernelGGL(rowdeconv16_kernel, grid, block, 0, s, a);
+    }
+    MSAU_CHECK_LAUNCH(KIND == RC_CONV8 ? "rowconv8_kernel" : "rowdeconv_kernel");
     return 0;
 }
+
+// j == nullptr: 1 if instance `id` exists, else 0.  Otherwise: launch it (0, or an error -- never "not mine")
+int rowconv_instance(int id, hipStream_t s, const RowConvJob* j) {
+    switch (id) {
+#define ROWCONV_ROW(KIND, NS, KH, KW, EPI, EPI2, WG) \
+        case rowconv_id(KIND, NS, KH, KW, EPI, EPI2, WG): return j ? launch_rowconv<KIND, NS, KH, KW, EPI, EPI2, WG>(s, *j) : 1;
+        ROWCONV_TABLE(ROWCONV_ROW)
+#undef ROWCONV_ROW
+    }
+    return j ? msau_set_error(MSAU_ERR_ARG, "rowconv: no instance %#x", id) : 0;
+}
+
+// rowconv8: strips of 32 output columns; the transposed convs: of 16 input (= 32 output) columns
+int rowconv_strips(const msau_conv_desc* d, int kind) { return kind == RC_CONV8 ? cdiv(d->Wout, 32) : cdiv(d->Win, 16); }
+
+// The task split of instance `id` on `d`, computed here and nowhere else.  rowconv8 rounds to the rows it holds in registers (NXR); the
+// transposed convs to 8 output rows (4 input rows per loop trip), and bound their last segment themselves: SH stays a multiple of 8.
+void rowconv_split(const msau_conv_desc* d, int id, RowConvJob& j) {
+    const RowsEnv& e = rows_env();
+    const bool conv8 = rowconv_kind(id) == RC_CONV8;
+    j.d = d;
+    j.nstrips = rowconv_strips(d, rowconv_kind(id));
+    j.SH = segment_height(e.waves, d->B, j.nstrips, d->Hout, e.sh, {8, (!conv8 || d->KH == 4) ? 8 : d->KH + MSAU_ROWCONV_PF, 0, conv8});
+    j.nseg = cdiv(d->Hout, j.SH);
+    j.ntasks = d->B * j.nstrips * j.nseg;
+    j.tasks_per_xcd = roundup(cdiv(j.ntasks, 8), 4);
+}
 }  // namespace
-// the row-streaming instance msau_conv2d launches for `d` (the case numbers of msau_rowconv_launch), 0 = none
-int msau_rowconv_case(int dtype, const msau_conv_desc* d) {
+
+// The row-streaming instance msau_conv2d launches for `d` (see rowconv_id), 0 = none.  kchunk / rows: the packed image's geometry.
+// What has no entry in ROWCONV_TABLE is refused there: which flag sets go with which kernel size, a second source beside two outputs
+// or a 4x4 kernel, anything but 3x3 without flags for the transposed convs.
+int msau_rowconv_case(int dtype, const msau_conv_desc* d, int kchunk, int rows) {
     const RowsEnv& e = rows_env();
     if (!e.on || !e.conv || dtype != MSAU_BF16 || (d->flags & (MSAU_CONV_ELU | MSAU_CONV_EXTENT))) return 0;
+    const int f = d->flags, f2 = f & MSAU_CONV_DOUT ? d->flags2 : 0, k = d->KH;    // (flags2 belongs to the second output)
+    if ((d->KH | d->KW) >> 3 || f >> 15 || f2 >> 6) return 0;                 // beyond the fields of rowconv_id: no instance either
+    int kind = RC_CONV8;
     if (d->ups == 2) {                                                     // the 16 -> 8 / 32 -> 16 transposed convs (rowdeconv8 / rowdeconv16)
-        const bool c16 = d->C1 == 16 && d->Cout == 8, c32 = d->C1 == 32 && d->Cout == 16 && e.deconv >= 2;
-        if (!e.deconv || !(c16 || c32) || d->C2 != 0 || d->KH != 3 || d->KW != 3 || d->stride != 1 || d->dil != 1 || d->flags) return 0;
-        if (d->pad_t != 1 || d->pad_l != 1) return 0;
+        kind = d->C1 == 16 && d->Cout == 8 ? RC_DECONV8 : d->C1 == 32 && d->Cout == 16 && e.deconv >= 2 ? RC_DECONV16 : 0;
+        if (!e.deconv || !kind || d->stride != 1 || d->dil != 1 || d->pad_t != 1 || d->pad_l != 1) return 0;
         if ((d->Hout != 2 * d->Hin && d->Hout != 2 * d->Hin - 1) || (d->Wout != 2 * d->Win && d->Wout != 2 * d->Win - 1)) return 0;
         if ((int64_t)d->Hout * d->Wout * d->Cout * 2 >= (1ll << 31)) return 0;
-        if ((int64_t)d->B * cdiv(d->Win, 16) * cdiv(d->Hout, 8) < e.min_tasks) return 0;
-        return c16 ? 12 : 16;
+        // the packed image must be the one the kernels index: conv_geom gives exactly this for the two shapes (profiles/rows_route.md)
+        if (kchunk != (kind == RC_DECONV8 ? 160 : 288) || rows != 16) return 0;
+    } else {
+        if (d->Cout != (f & MSAU_CONV_DOUT ? 16 : 8) || d->C1 != 8 || (d->C2 != 0 && d->C2 != 8) || d->stride != 1 || d->ups != 1 || d->dil != 1) return 0;
+        if (d->Hin != d->Hout || d->Win != d->Wout) return 0;
+        // SAME padding; 4x4: 1 before for the forward, 2 for the data gradient (flipped image)
+        if (d->pad_t != d->pad_l || (k == 4 ? d->pad_t != 1 && d->pad_t != 2 : d->pad_t != k / 2)) return 0;
+        if ((int64_t)d->Hout * d->Wout * 16 >= (1ll << 31)) return 0;
     }
-    const bool dout = d->flags & MSAU_CONV_DOUT;
-    if (d->Cout != (dout ? 16 : 8) || d->C1 != 8 || (d->C2 != 0 && d->C2 != 8) || d->stride != 1 || d->ups != 1 || d->dil != 1) return 0;
-    if (d->Hin != d->Hout || d->Win != d->Wout || d->KH != d->KW) return 0;
-    if ((int64_t)d->Hout * d->Wout * 16 >= (1ll << 31)) return 0;
-    if ((int64_t)d->B * cdiv(d->Wout, 32) * cdiv(d->Hout, 8) < e.min_tasks) return 0;
-    const int f = d->flags, k = d->KH, dual = d->C2 != 0;
-    if (dout) {                                                            // the data gradient of a conv over concat(x1, x2): g -> (dx1, dx2)
-        if (!e.dout || dual || !d->y2) return 0;
-        // the flag sets the reference's nets produce (anything else: the tile kernel's run-time epilogue)
-        const int f1 = f & ~MSAU_CONV_DOUT, f2 = d->flags2;
-        if (k == 3 && d->pad_t == 1 && d->pad_l == 1 && f2 == 0) return f1 == 0 ? 9 : f1 == MSAU_CONV_ACCUM ? 10 : 0;
-        if (k == 1 && d->pad_t == 0 && d->pad_l == 0 && f1 == 0 && f2 == MSAU_CONV_MASK_B && d->mask_b2) return 11;
-        if (k == 1 && d->pad_t == 0 && d->pad_l == 0 && f1 == MSAU_CONV_WGRAD && f2 == MSAU_CONV_MASK_B && d->mask_b2 && d->wg_x1 && d->wg_slabs && e.cplwg) return 13;
-        return 0;
-    }
-    if (k == 3 && !dual && d->pad_t == 1 && d->pad_l == 1) {
-        if (f == MSAU_CONV_LRN) return d->y2 && d->lrn_k > 0.f ? 1 : 0;
-        if (f == 0) return 2;
-        if (f == MSAU_CONV_ACCUM) return 3;
-    }
-    if (k == 3 && dual && d->pad_t == 1 && d->pad_l == 1 && f == 0) return 4;
-    if (k == 1 && dual && d->pad_t == 0 && d->pad_l == 0 && f == MSAU_CONV_RELU_OUT) return 5;
-    if (k == 4 && !dual && d->pad_t == d->pad_l && (d->pad_t == 1 || d->pad_t == 2)) {    // forward: 1; data gradient (flipped image): 2
-        if (f == 0) return 6;
-        if (f == MSAU_CONV_MASK_B) return 7;
-        if (f == (MSAU_CONV_ACCUM | MSAU_CONV_MASK_B)) return 8;
-    }
+    if ((int64_t)d->B * rowconv_strips(d, kind) * cdiv(d->Hout, 8) < e.min_tasks) return 0;    // too little work to fill the device
+    // the operands and the switches of the fused outputs
+    if ((f & MSAU_CONV_DOUT) && !(e.dout && d->y2 && (!(f2 & MSAU_CONV_MASK_B) || d->mask_b2))) return 0;
+    if ((f & MSAU_CONV_WGRAD) && !(e.cplwg && d->wg_x1 && d->wg_slabs)) return 0;
+    if ((f & MSAU_CONV_LRN) && !(d->y2 && d->lrn_k > 0.f)) return 0;
+    const int id = rowconv_id(kind, d->C2 ? 2 : 1, d->KH, d->KW, f & ~MSAU_CONV_WGRAD, f2, f & MSAU_CONV_WGRAD);
+    return rowconv_instance(id, nullptr, nullptr) ? id : 0;
+}
+
+// workgroups of the launch of instance `inst` on this descriptor (= the slabs an MSAU_CONV_WGRAD launch writes)
+int msau_rowconv_workgroups(const msau_conv_desc* d, int inst) {
+    RowConvJob j;
+    rowconv_split(d, inst, j);
+    return 8 * (j.tasks_per_xcd / 4);
+}
+
+int msau_rowconv_launch(hipStream_t s, const msau_conv_desc* d, int kchunk, int rows, int inst) {
+    RowConvJob j;
+    rowconv_split(d, inst, j);
+    j.wrow = kchunk;
+    j.wchunk = rows * kchunk;
+    const int wgs = 8 * (j.tasks_per_xcd / 4);
+    if (rowconv_wg(inst))                                                  // the rider writes one slab per workgroup
+        MSAU_CHECK_ARG(wgs == d->wg_nslabs, "conv2d: MSAU_CONV_WGRAD launch has %d workgroups, the caller allocated %d slabs "
+                       "(msau_conv2d_rider_slabs under other MSAU_ROWS_* settings?)", wgs, d->wg_nslabs);
+    return rowconv_instance(inst, s, &j);
+}
+
+// ---- weight gradients (msau_conv2d_wgrad descriptors): rowwgrad8_kernel<RELU, KS>, the same contract
+namespace {
+constexpr int rowwgrad_id(bool relu, int ks) { return 2 * ks + relu; }
+// X(RELU, KS)
+#define ROWWGRAD_TABLE(X) X(false, 3) X(true, 3) X(false, 4) X(true, 4)
+
+template <bool RELU, int KS>
+int launch_rowwgrad(hipStream_t s, const RowWgradArgs& a) {
+    hipLaunchKernelGGL((rowwgrad8_kernel<RELU, KS>), dim3(a.d.nslabs), dim3(64 * WG_WAVES), 0, s, a);    // a persistent workgroup per slab
+    MSAU_CHECK_LAUNCH("rowwgrad8_kernel");
     return 0;
 }
 
-namespace {
-// task split of a rowconv8 launch (3x3 / 1x1 / 4x4 instances)
-void rowconv_split(const msau_conv_desc* d, RowConvArgs& a) {
-    a.nstrips = cdiv(d->Wout, 32);
-    const int unr = d->KH == 4 ? 8 : d->KH + MSAU_ROWCONV_PF;
+// a == nullptr: 1 if instance `id` exists, else 0.  Otherwise: launch it (0, or an error -- never "not mine")
+int rowwgrad_instance(int id, hipStream_t s, const RowWgradArgs* a) {
+    switch (id) {
+#define ROWWGRAD_ROW(RELU, KS) case rowwgrad_id(RELU, KS): return a ? launch_rowwgrad<RELU, KS>(s, *a) : 1;
+        ROWWGRAD_TABLE(ROWWGRAD_ROW)
+#undef ROWWGRAD_ROW
+    }
+    return a ? msau_set_error(MSAU_ERR_ARG, "rowwgrad: no instance %d", id) : 0;
+}
+
+// The task split of a launch, computed here and nowhere else.  One round: at most one task per wave (nslabs workgroups x 8 waves), as
+// many as that allows up to MSAU_ROWS_WAVES; segments of at least 9 rows, a multiple of the kernel's rows.
+void rowwgrad_split(const msau_wgrad_desc* d, RowWgradArgs& a) {
     const RowsEnv& e = rows_env();
-    int nseg = e.waves / (d->B * a.nstrips);
-    if (nseg < 1) nseg = 1;
-    int sh = e.sh > 0 ? e.sh : cdiv(d->Hout, nseg);
-    if (sh < 8) sh = 8;
-    sh = roundup(sh, unr);
-    a.SH = sh < d->Hout ? sh : d->Hout;
+    a.nstrips = cdiv(d->Wout, 30);
+    a.SH = segment_height(WG_WAVES * d->nslabs < e.waves ? WG_WAVES * d->nslabs : e.waves, d->B, a.nstrips, d->Hout, e.sh, {9, d->KH, 0, true});
     a.nseg = cdiv(d->Hout, a.SH);
     a.ntasks = d->B * a.nstrips * a.nseg;
-    a.tasks_per_xcd = roundup(cdiv(a.ntasks, 8), 4);
-}
-}  // namespace
-
-// workgroups of a rowconv8 launch of this descriptor (= the slabs an MSAU_CONV_WGRAD launch writes)
-int msau_rowconv_workgroups(const msau_conv_desc* d) {
-    RowConvArgs a;
-    rowconv_split(d, a);
-    return 8 * (a.tasks_per_xcd / 4);
-}
-
-int msau_rowconv_launch(hipStream_t s, const msau_conv_desc* d, int kchunk, int rows, int which) {
-    if (which == 12 || which == 16) {
-        MSAU_CHECK_ARG(kchunk == (which == 12 ? 160 : 288) && rows == 16, "rowdeconv: packed image of another geometry (kchunk %d, rows %d)", kchunk, rows);
-        RowDeconvArgs a;
-        a.d = *d;
-        a.nstrips = cdiv(d->Win, 16);
-        const RowsEnv& e = rows_env();
-        int nseg = e.waves / (d->B * a.nstrips);
-        if (nseg < 1) nseg = 1;
-        int sh = e.sh > 0 ? e.sh : cdiv(d->Hout, nseg);
-        if (sh < 8) sh = 8;
-        a.SH = roundup(sh, 8);                                             // (4 input rows per loop trip)
-        a.nseg = cdiv(d->Hout, a.SH);
-        a.ntasks = d->B * a.nstrips * a.nseg;
-        a.tasks_per_xcd = roundup(cdiv(a.ntasks, 8), 4);
-        a.in_row_bytes = d->Win * d->C1 * 2;
-        a.out_row_bytes = d->Wout * d->Cout * 2;
-        a.in_img_bytes = (unsigned)d->Hin * (unsigned)a.in_row_bytes;
-        a.out_img_bytes = (unsigned)d->Hout * (unsigned)a.out_row_bytes;
-        if (which == 12) hipLaunchKernelGGL(rowdeconv8_kernel, dim3(8 * (a.tasks_per_xcd / 4)), dim3(256), 0, s, a);
-        else hipLaunchKernelGGL(rowdeconv16_kernel, dim3(8 * (a.tasks_per_xcd / 4)), dim3(256), 0, s, a);
-        MSAU_CHECK_LAUNCH("rowdeconv_kernel");
-        return 0;
-    }
-    RowConvArgs a;
-    a.d = *d;
-    rowconv_split(d, a);
     a.row_bytes = d->Wout * 16;
     a.img_bytes = (unsigned)d->Hout * (unsigned)a.row_bytes;
-    a.wrow = kchunk;
-    a.wchunk = rows * kchunk;
-    switch (which) {
-        case 1: return launch_rowconv8<1, 3, 3, MSAU_CONV_LRN>(s, a);
-        case 2: return launch_rowconv8<1, 3, 3, 0>(s, a);
-        case 3: return launch_rowconv8<1, 3, 3, MSAU_CONV_ACCUM>(s, a);
-        case 4: return launch_rowconv8<2, 3, 3, 0>(s, a);
-        case 5: return launch_rowconv8<2, 1, 1, MSAU_CONV_RELU_OUT>(s, a);
-        case 6: return launch_rowconv8<1, 4, 4, 0>(s, a);
-        case 7: return launch_rowconv8<1, 4, 4, MSAU_CONV_MASK_B>(s, a);
-        case 8: return launch_rowconv8<1, 4, 4, MSAU_CONV_ACCUM | MSAU_CONV_MASK_B>(s, a);
-        case 9: return launch_rowconv8<1, 3, 3, MSAU_CONV_DOUT>(s, a);
-        case 10: return launch_rowconv8<1, 3, 3, MSAU_CONV_DOUT | MSAU_CONV_ACCUM>(s, a);
-        case 11: return launch_rowconv8<1, 1, 1, MSAU_CONV_DOUT, MSAU_CONV_MASK_B>(s, a);
-        case 13:
-            MSAU_CHECK_ARG(8 * (a.tasks_per_xcd / 4) == d->wg_nslabs, "conv2d: MSAU_CONV_WGRAD launch has %d workgroups, the caller allocated %d slabs "
-                           "(msau_conv2d_rider_slabs under other MSAU_ROWS_* settings?)", 8 * (a.tasks_per_xcd / 4), d->wg_nslabs);
-            hipLaunchKernelGGL((rowconv8_kernel<1, 1, 1, MSAU_CONV_DOUT, MSAU_CONV_MASK_B, true>), dim3(8 * (a.tasks_per_xcd / 4)), dim3(256), 0, s, a);
-            MSAU_CHECK_LAUNCH("rowconv8_kernel");
-            return 0;
-    }
-    return msau_set_error(MSAU_ERR_ARG, "rowconv: no instance");
+    a.kext = d->KH == 4 ? 144 : 80;
 }
-
-// ---- weight gradients (msau_conv2d_wgrad descriptors)
-// the number of the instance <RELU, KS> of rowwgrad8_kernel
-constexpr int rowwgrad_id(bool relu, int ks) { return 2 * ks + relu; }
+}  // namespace
 
 // The row-streaming instance msau_conv2d_wgrad launches for `d`, 0 = none.  cch / nchunks / kextc: the generic geometry.
 int msau_rowwgrad_case(int dtype, const msau_wgrad_desc* d, int cch, int nchunks, int kextc) {
     const RowsEnv& e = rows_env();
     if (!e.on || !e.wgrad || dtype != MSAU_BF16) return 0;
-    if (d->C1 != 8 || d->C2 != 0 || d->Cout != 8 || (d->KH != 3 && d->KH != 4) || d->KW != d->KH || d->dil != 1 || d->stride != 1) return 0;
+    if (d->C1 != 8 || d->C2 != 0 || d->Cout != 8 || d->KW != d->KH || d->dil != 1 || d->stride != 1) return 0;
     if (d->pad_t != 1 || d->pad_l != 1 || d->Hin != d->Hout || d->Win != d->Wout) return 0;        // (4x4: the SAME padding, 1 before / 2 after)
     if (d->flags & ~MSAU_CONV_RELU_IN) return 0;
     if (cch != 8 || nchunks != 1 || kextc != (d->KH == 4 ? 144 : 80) || d->nslabs < 1) return 0;
     if (d->KH == 4 && !e.wgrad4) return 0;
     if ((int64_t)d->Hout * d->Wout * 16 >= (1ll << 31)) return 0;
     if ((int64_t)d->B * cdiv(d->Wout, 30) * cdiv(d->Hout, 8) < e.min_tasks) return 0;
-    return rowwgrad_id(d->flags & MSAU_CONV_RELU_IN, d->KH);
+    const int id = rowwgrad_id(d->flags & MSAU_CONV_RELU_IN, d->KH);
+    return rowwgrad_instance(id, nullptr, nullptr) ? id : 0;
 }
 
-int msau_rowwgrad_launch(hipStream_t s, const msau_wgrad_desc* d, int which) {
+int msau_rowwgrad_launch(hipStream_t s, const msau_wgrad_desc* d, int inst) {
     RowWgradArgs a;
     a.d = *d;
-    a.nstrips = cdiv(d->Wout, 30);
-    const RowsEnv& e = rows_env();
-    // one round: at most one task per wave (nslabs workgroups x 8 waves), as many as that allows up to MSAU_ROWS_WAVES
-    int target = WG_WAVES * d->nslabs;
-    if (target > e.waves) target = e.waves;
-    int nseg = target / (d->B * a.nstrips);
-    if (nseg < 1) nseg = 1;
-    int sh = e.sh > 0 ? e.sh : cdiv(d->Hout, nseg);
-    if (sh < 9) sh = 9;
-    sh = roundup(sh, d->KH);
-    a.SH = sh < d->Hout ? sh : d->Hout;
-    a.nseg = cdiv(d->Hout, a.SH);
-    a.ntasks = d->B * a.nstrips * a.nseg;
-    a.row_bytes = d->Wout * 16;
-    a.img_bytes = (unsigned)d->Hout * (unsigned)a.row_bytes;
-    a.kext = d->KH == 4 ? 144 : 80;
-    const dim3 grid(d->nslabs), block(64 * WG_WAVES);
-    switch (which) {
-        case rowwgrad_id(false, 3): hipLaunchKernelGGL((rowwgrad8_kernel<false, 3>), grid, block, 0, s, a); break;
-        case rowwgrad_id(true, 3): hipLaunchKernelGGL((rowwgrad8_kernel<true, 3>), grid, block, 0, s, a); break;
-        case rowwgrad_id(false, 4): hipLaunchKernelGGL((rowwgrad8_kernel<false, 4>), grid, block, 0, s, a); break;
-        case rowwgrad_id(true, 4): hipLaunchKernelGGL((rowwgrad8_kernel<true, 4>), grid, block, 0, s, a); break;
-        default: return msau_set_error(MSAU_ERR_ARG, "rowwgrad: no instance %d", which);
-    }
-    MSAU_CHECK_LAUNCH("rowwgrad8_kernel");
-    return 0;
+    rowwgrad_split(d, a);
+    return rowwgrad_instance(inst, s, &a);
 }

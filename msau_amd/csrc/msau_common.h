@@ -50,11 +50,13 @@ int msau_ownerconv_takes(int dtype, const msau_conv_desc* d);
 int msau_ownerconv_fwd(hipStream_t s, int dtype, const msau_conv_desc* d);
 // The instance families of msau_conv2d besides the tile kernel (conv_route in conv.hip picks one; DESIGN.md, "conv2d routing").
 // <family>_case: the number of the instance that runs the descriptor, 0 = none; pure host arithmetic.  <family>_launch: launches
-// exactly that instance -- a case it has no instance for is an MSAU_ERR_ARG error, never "try the next family".
-// conv_rows.hip: row-streaming instances for the single convolutions of the 8-channel level
-int msau_rowconv_case(int dtype, const msau_conv_desc* d);
-int msau_rowconv_launch(hipStream_t s, const msau_conv_desc* d, int kchunk, int rows, int which);
-int msau_rowconv_workgroups(const msau_conv_desc* d);
+// exactly that instance -- a case it has no instance for is an MSAU_ERR_ARG error, never "try the next family".  The number packs
+// what selects the instance's kernel; the family's one table of instances answers "exists" for _case and is the launch's switch.
+// conv_rows.hip: row-streaming instances for the single convolutions of the 8-channel level and the two transposed convs above it
+// (kchunk / rows: the packed image).  _workgroups: the grid of instance `inst` on `d`, from the task split the launch uses
+int msau_rowconv_case(int dtype, const msau_conv_desc* d, int kchunk, int rows);
+int msau_rowconv_launch(hipStream_t s, const msau_conv_desc* d, int kchunk, int rows, int inst);
+int msau_rowconv_workgroups(const msau_conv_desc* d, int inst);
 // conv_lean.hip: the chunked-K instances and the compile-time-specialised instances for the hot layer shapes
 // (cch / kchunk / nchunks / CT: the generic geometry = the packed image)
 int msau_conv_chunked_case(int dtype, const msau_conv_desc* d, int cch, int nchunks, int CT);
@@ -79,7 +81,7 @@ int msau_wgrad_lean_case(int dtype, const msau_wgrad_desc* d, int cch, int kextc
 int msau_wgrad_lean_launch(hipStream_t s, int dtype, const msau_wgrad_desc* const* ds, int n, const WRoute* r);
 // conv_rows.hip: the row-streaming 8 -> 8 instances <RELU, KS>
 int msau_rowwgrad_case(int dtype, const msau_wgrad_desc* d, int cch, int nchunks, int kextc);
-int msau_rowwgrad_launch(hipStream_t s, const msau_wgrad_desc* d, int which);
+int msau_rowwgrad_launch(hipStream_t s, const msau_wgrad_desc* d, int inst);
 // ownerconv.hip: the first conv fed with box lists (MSAU_CONV_OWNER); one instance.  _case reads no pointer: the context behind
 // d->x1 is the launch's to check
 int msau_ownerconv_wgrad_case(int dtype, const msau_wgrad_desc* d, int cch, int nchunks, int kextc);
