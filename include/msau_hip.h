@@ -953,6 +953,37 @@ int msau_unet_cost_eval(void* stream, int dtype, int kind, float param, const vo
                         int32_t* doc_counts, void* ws, int B, int H, int W, int C, int Cs);
 
 /* ------------------------------------------------------------------------------------------
+ * The masked cost: the masked cross entropy of msau_masked_ce_multi -- the loss of TrainEngine.step and
+ * MSAUWrapper.loss -- with class weights and under the costs above.  Both heads are scored against ONE label map; the active pixels
+ * A_b of document b lie inside its extent (extent [B][2] = (h, w), NULL: the whole canvas) and have a label in [1, C): label 0, a
+ * negative label and a label >= C are inactive.  v = class_w (NULL: ones), p / p_t / nll as above.
+ *   MSAU_COST_CE    : L_b = sum_{A_b} v_y nll / D_b,  D_b = sum_{A_b} v_y (without weights: the number of labelled pixels); param unread.
+ *   MSAU_COST_FOCAL : L_b = sum_{A_b} v_y (1 - p_t)^gamma nll / D_b;  gamma = 0 gives MSAU_COST_CE's bits.
+ *   MSAU_COST_DICE  : the Dice formulas above with I_c, P_c, Y_c over A_b; all C classes count and Y_0 = 0.
+ * loss3 = (mean_b (L_b(final) + L_b(aux)), mean_b L_b(final), mean_b L_b(aux)): head weights 1 and 1; aux NULL: one head, loss3[2] = 0,
+ * daux untouched.  A document without an active pixel, with D_b = 0 or with V = 0 has loss 0 and gradient 0, and B still divides.
+ * dlogits / daux: every stored channel of every pixel is written, exactly 0 at inactive pixels, outside the extents and in the
+ * padded channels.  The kernels are msau_unet_cost's, compiled for one label map (read once per pixel for both heads), first
+ * active class 1 and head weight 1; heads of up to 32 stored channels keep a pixel in registers, wider ones read it from the cache,
+ * with equal bits.  No floating-point atomics, no memset, every summation order fixed.
+ * hist_partial / K: msau_label_hist's rows of `labels` (1 <= K <= 64).  Dice and class weights need them (MSAU_ERR_ARG without);
+ * the unweighted cross entropy and focal loss take them when given, and otherwise this call takes a histogram of its own into ws.
+ * msau_masked_cost_eval: forward only, per document: doc_loss[b][t] = L_b(head t), doc_counts[b][t] = (labelled, correct) as
+ * msau_unet_eval counts them; K workgroups per document (1 <= K <= 256); Dice takes its own histogram (min(K, 64) rows) into ws.
+ * msau_masked_cost_ws_floats = msau_unet_ce_ws_floats(B*H*W) + 16 B C (CE, focal) or 2 B + 4 B C + 256 B C (Dice);
+ * msau_masked_cost_eval_ws_bytes = msau_unet_eval_ws_bytes(B, K), for Dice + 4 (4 B K C + B min(K, 64) C).
+ * Every argument error is MSAU_ERR_ARG before anything is launched.
+ * ------------------------------------------------------------------------------------------ */
+int64_t msau_masked_cost_ws_floats(int kind, int B, int H, int W, int C);
+int msau_masked_cost(void* stream, int dtype, int kind, float param, const void* logits, const void* aux, const int64_t* labels,
+                     const int32_t* extent, const float* class_w, const int32_t* hist_partial, int K,
+                     void* dlogits, void* daux, float* loss3, float* ws, int B, int H, int W, int C, int Cs);
+int64_t msau_masked_cost_eval_ws_bytes(int kind, int B, int K, int C);
+int msau_masked_cost_eval(void* stream, int dtype, int kind, float param, const void* logits, const void* aux, const int64_t* labels,
+                          const int32_t* extent, const float* class_w, int K, float* doc_loss,
+                          int32_t* doc_counts, void* ws, int B, int H, int W, int C, int Cs);
+
+/* ------------------------------------------------------------------------------------------
  * Key-value training, the generator's affine / rotation augmentation (data_generator/data_generator_text.py:303-344,
  * utils/image_util.py:38-55; msau_amd/training/kv_warp.py states what is computed, csrc/warp.hip how).
  *   msau_kv_warp_train : the canvases msau_kv_paint_train leaves (ids int32, labels / aux_labels int64 [B][H][W], src_sizes int32

@@ -242,6 +242,10 @@ _SIGNATURES = {
     "msau_unet_cost": (C.c_int, [vp, C.c_int, C.c_int, f32] + [vp] * 7 + [C.c_int, vp, vp, vp, vp] + [C.c_int] * 5),
     "msau_unet_cost_eval_ws_bytes": (i64, [C.c_int] * 4),
     "msau_unet_cost_eval": (C.c_int, [vp, C.c_int, C.c_int, f32] + [vp] * 6 + [C.c_int, vp, vp, vp] + [C.c_int] * 5),
+    "msau_masked_cost_ws_floats": (i64, [C.c_int] * 5),
+    "msau_masked_cost": (C.c_int, [vp, C.c_int, C.c_int, f32] + [vp] * 6 + [C.c_int, vp, vp, vp, vp] + [C.c_int] * 5),
+    "msau_masked_cost_eval_ws_bytes": (i64, [C.c_int] * 4),
+    "msau_masked_cost_eval": (C.c_int, [vp, C.c_int, C.c_int, f32] + [vp] * 5 + [C.c_int, vp, vp, vp] + [C.c_int] * 5),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)

@@ -320,18 +320,21 @@ __global__ __launch_bounds__(256) void label_hist_kernel(const int64_t* __restri
 
 // inv[t * B + b] = 1 / (B * D_b(head t)), 0 for a document without weight: D_b is the extent's area, or with class weights
 // sum_c cw[c] * hist_t[b][c], the classes added in index order (hist_t = hist + t * B * K * C, its K rows added first)
+// MASKED (the masked cost: one label map, the classes from 1): always from the one histogram, D_b = sum_{c >= 1} cw[c] * hist[b][c]
+// (cw absent: the number of labelled pixels); the caller passes NL = 1
+template <bool MASKED>
 __device__ __forceinline__ void unet_ce_denominators(float* inv, const int32_t* __restrict__ extent, const float* __restrict__ cw,
                                                      const int32_t* __restrict__ hist, int NL, int B, int H, int W, int C, int K) {
     for (int i = threadIdx.x; i < NL * B; i += blockDim.x) {
         const int t = i / B, b = i - t * B;
         float d;
-        if (cw) {
+        if (MASKED || cw) {
             const int32_t* h = hist + ((int64_t)t * B + b) * K * C;
             d = 0.f;
-            for (int c = 0; c < C; ++c) {
+            for (int c = MASKED ? 1 : 0; c < C; ++c) {
                 int n = 0;
                 for (int k = 0; k < K; ++k) n += h[k * C + c];
-                d += cw[c] * (float)n;
+                d += (cw ? cw[c] : 1.f) * (float)n;
             }
         } else {
             const int eh = extent ? min(max(extent[2 * b], 0), H) : H, ew = extent ? min(max(extent[2 * b + 1], 0), W) : W;
@@ -357,7 +360,9 @@ __device__ __forceinline__ void unet_ce_block_sums(float l0, float l1, float* re
 // A thread's weight of head t at pixel p of document b: hw_t * cw[lab] / (B * D_b(t)) inside the extent with lab in [0, C), else 0;
 // the loss partials carry the weight WITHOUT hw_t (loss3[1], loss3[2] are the heads' own losses).
 // FOCAL: the focal loss with parameter gamma (focal_weights); otherwise gamma is not read.
-template <typename T, int NL, int CS8, bool FOCAL>
+// MASKED: the masked cost of TrainEngine.step -- both heads against lab0, whose label, extent test and weight are
+// taken once per pixel; the active classes start at 1; the head weight is 1.
+template <typename T, int NL, int CS8, bool FOCAL, bool MASKED>
 __global__ void unet_ce_kernel(const T* __restrict__ l0, const T* __restrict__ l1, const int64_t* __restrict__ lab0,
                                const int64_t* __restrict__ lab1, const int32_t* __restrict__ extent, const float* __restrict__ cw,
                                const int32_t* __restrict__ hist, int K, T* __restrict__ d0, T* __restrict__ d1,
@@ -365,8 +370,8 @@ __global__ void unet_ce_kernel(const T* __restrict__ l0, const T* __restrict__ l
     constexpr int Cs = CS8 * 8;
     __shared__ float red[2 * kWaves];
     __shared__ float inv[2 * kCeMaxB];
-    unet_ce_denominators(inv, extent, cw, hist, NL, B, H, W, C, K);
-    const float hwt = NL == 2 ? 0.5f : 1.f;
+    unet_ce_denominators<MASKED>(inv, extent, cw, hist, MASKED ? 1 : NL, B, H, W, C, K);
+    const float hwt = (NL == 2 && !MASKED) ? 0.5f : 1.f;
     const int hw = H * W;
     float local[2] = {0.f, 0.f};
     const int64_t total = (int64_t)B * hw;
@@ -374,12 +379,17 @@ __global__ void unet_ce_kernel(const T* __restrict__ l0, const T* __restrict__ l
         const int b = (int)((unsigned)p / (unsigned)hw);               // total < 2^31 (checked by the host)
         const int j = (int)p - b * hw;
         const bool in = extent ? pos_in_extent(j, W, extent[2 * b], extent[2 * b + 1]) : true;
+        bool on = false;
+        int lab = -1;
+        float w = 0.f;
 #pragma unroll
         for (int t = 0; t < NL; ++t) {
-            const int64_t lab64 = (t ? lab1 : lab0)[p];
-            const bool on = in && lab64 >= 0 && lab64 < C;
-            const int lab = on ? (int)lab64 : -1;
-            const float w = on ? inv[t * B + b] * (cw ? cw[lab] : 1.f) : 0.f;
+            if (!MASKED || t == 0) {
+                const int64_t lab64 = (t ? lab1 : lab0)[p];
+                on = in && lab64 >= (MASKED ? 1 : 0) && lab64 < C;
+                lab = on ? (int)lab64 : -1;
+                w = on ? inv[t * B + b] * (cw ? cw[lab] : 1.f) : 0.f;
+            }
             float x[Cs];
             float xl;
             const float lse = pixel_lse<T, CS8>((t ? l1 : l0) + p * Cs, C, lab, x, xl);
@@ -394,7 +404,7 @@ __global__ void unet_ce_kernel(const T* __restrict__ l0, const T* __restrict__ l
 }
 
 // Any class count (Cs > 32): the logits of a pixel are read three times from the cache.
-template <typename T, bool FOCAL>
+template <typename T, bool FOCAL, bool MASKED>
 __global__ void unet_ce_wide_kernel(const T* __restrict__ l0, const T* __restrict__ l1, const int64_t* __restrict__ lab0,
                                     const int64_t* __restrict__ lab1, const int32_t* __restrict__ extent, const float* __restrict__ cw,
                                     const int32_t* __restrict__ hist, int K, T* __restrict__ d0, T* __restrict__ d1,
@@ -402,8 +412,8 @@ __global__ void unet_ce_wide_kernel(const T* __restrict__ l0, const T* __restric
     __shared__ float red[2 * kWaves];
     __shared__ float inv[2 * kCeMaxB];
     const int NL = l1 ? 2 : 1;
-    unet_ce_denominators(inv, extent, cw, hist, NL, B, H, W, C, K);
-    const float hwt = NL == 2 ? 0.5f : 1.f;
+    unet_ce_denominators<MASKED>(inv, extent, cw, hist, MASKED ? 1 : NL, B, H, W, C, K);
+    const float hwt = (NL == 2 && !MASKED) ? 0.5f : 1.f;
     const int hw = H * W;
     float local[2] = {0.f, 0.f};
     const int64_t total = (int64_t)B * hw;
@@ -411,12 +421,17 @@ __global__ void unet_ce_wide_kernel(const T* __restrict__ l0, const T* __restric
         const int b = (int)((unsigned)p / (unsigned)hw);
         const int j = (int)p - b * hw;
         const bool in = extent ? pos_in_extent(j, W, extent[2 * b], extent[2 * b + 1]) : true;
+        bool on = false;
+        int lab = -1;
+        float w = 0.f;
         for (int t = 0; t < NL; ++t) {
             const T* l = (t ? l1 : l0) + p * Cs;
-            const int64_t lab64 = (t ? lab1 : lab0)[p];
-            const bool on = in && lab64 >= 0 && lab64 < C;
-            const int lab = on ? (int)lab64 : -1;
-            const float w = on ? inv[t * B + b] * (cw ? cw[lab] : 1.f) : 0.f;
+            if (!MASKED || t == 0) {
+                const int64_t lab64 = (t ? lab1 : lab0)[p];
+                on = in && lab64 >= (MASKED ? 1 : 0) && lab64 < C;
+                lab = on ? (int)lab64 : -1;
+                w = on ? inv[t * B + b] * (cw ? cw[lab] : 1.f) : 0.f;
+            }
             const float lse = pixel_lse_wide(l, C);
             const bool act = on && w != 0.f;
             const float xl = act ? (float)l[lab] : 0.f;
@@ -430,6 +445,8 @@ __global__ void unet_ce_wide_kernel(const T* __restrict__ l0, const T* __restric
 }
 
 // the follow-up: the block partials of each head added in ordered_sum_kernel_t's order -> loss3 = (total, final, auxiliary), written
+// MASKED: the total is final + auxiliary (head weights 1 and 1)
+template <bool MASKED>
 __global__ __launch_bounds__(256) void unet_ce_finish_kernel(const float* __restrict__ ws, int n, int two, float* __restrict__ loss3) {
     __shared__ float red[8];
     float s0 = 0.f, s1 = 0.f;
@@ -440,7 +457,8 @@ __global__ __launch_bounds__(256) void unet_ce_finish_kernel(const float* __rest
     if (threadIdx.x == 0) {
         const float f = add_waves<4, true>(red);
         const float a = two ? add_waves<4, true>(red + 4) : 0.f;
-        loss3[0] = two ? 0.5f * f + 0.5f * a : f;
+        if (MASKED) loss3[0] = two ? f + a : f;
+        else loss3[0] = two ? 0.5f * f + 0.5f * a : f;
         loss3[1] = f;
         loss3[2] = a;
     }
@@ -505,7 +523,8 @@ struct UnetEvalSlab {
     __device__ __forceinline__ int offset(int i, int W) const { const int y = i / ew; return (r0 + y) * W + (i - y * ew); }
 };
 
-template <typename T, int NL, int CS8, bool FOCAL>
+// MASKED: both heads against lab0, read once; the active classes start at 1
+template <typename T, int NL, int CS8, bool FOCAL, bool MASKED>
 __global__ __launch_bounds__(256) void unet_eval_kernel(const T* __restrict__ l0, const T* __restrict__ l1,
                                                         const int64_t* __restrict__ lab0, const int64_t* __restrict__ lab1,
                                                         const int32_t* __restrict__ extent, const float* __restrict__ cw,
@@ -518,11 +537,15 @@ __global__ __launch_bounds__(256) void unet_eval_kernel(const T* __restrict__ l0
     int cnt[2][2] = {{0, 0}, {0, 0}};
     for (int i = threadIdx.x; i < slab.n; i += 256) {
         const int64_t p = base + slab.offset(i, W);
+        bool on = false;
+        int lab = -1;
 #pragma unroll
         for (int t = 0; t < NL; ++t) {
-            const int64_t lab64 = (t ? lab1 : lab0)[p];
-            const bool on = lab64 >= 0 && lab64 < C;
-            const int lab = on ? (int)lab64 : -1;
+            if (!MASKED || t == 0) {
+                const int64_t lab64 = (t ? lab1 : lab0)[p];
+                on = lab64 >= (MASKED ? 1 : 0) && lab64 < C;
+                lab = on ? (int)lab64 : -1;
+            }
             float x[Cs];
             float xl;
             const float lse = pixel_lse<T, CS8>((t ? l1 : l0) + p * Cs, C, lab, x, xl);
@@ -538,7 +561,7 @@ __global__ __launch_bounds__(256) void unet_eval_kernel(const T* __restrict__ l0
 }
 
 // Any class count (Cs > 32): the logits of a pixel are read from the cache.
-template <typename T, bool FOCAL>
+template <typename T, bool FOCAL, bool MASKED>
 __global__ __launch_bounds__(256) void unet_eval_wide_kernel(const T* __restrict__ l0, const T* __restrict__ l1,
                                                              const int64_t* __restrict__ lab0, const int64_t* __restrict__ lab1,
                                                              const int32_t* __restrict__ extent, const float* __restrict__ cw,
@@ -551,11 +574,15 @@ __global__ __launch_bounds__(256) void unet_eval_wide_kernel(const T* __restrict
     int cnt[2][2] = {{0, 0}, {0, 0}};
     for (int i = threadIdx.x; i < slab.n; i += 256) {
         const int64_t p = base + slab.offset(i, W);
+        bool on = false;
+        int lab = -1;
         for (int t = 0; t < NL; ++t) {
             const T* l = (t ? l1 : l0) + p * Cs;
-            const int64_t lab64 = (t ? lab1 : lab0)[p];
-            const bool on = lab64 >= 0 && lab64 < C;
-            const int lab = on ? (int)lab64 : -1;
+            if (!MASKED || t == 0) {
+                const int64_t lab64 = (t ? lab1 : lab0)[p];
+                on = lab64 >= (MASKED ? 1 : 0) && lab64 < C;
+                lab = on ? (int)lab64 : -1;
+            }
             const float lse = pixel_lse_wide(l, C);
             int pred = 0;
             float bv = -INFINITY;
@@ -612,7 +639,8 @@ __device__ __forceinline__ void dice_block_rows(const float (&I)[N], const float
 }
 
 // part[((t * B + b) * K + k)][2][C] is WRITTEN by workgroup k of document b for head t; a thread adds its pixels in slab order
-template <typename T, int NL, int CS8>
+// MASKED: both heads against lab0; the active classes start at 1 (I_0 = 0, P_0 is summed as every class's)
+template <typename T, int NL, int CS8, bool MASKED>
 __global__ __launch_bounds__(256) void unet_dice_sums_kernel(const T* __restrict__ l0, const T* __restrict__ l1,
                                                              const int64_t* __restrict__ lab0, const int64_t* __restrict__ lab1,
                                                              const int32_t* __restrict__ extent, float* __restrict__ part, int B, int H,
@@ -629,8 +657,8 @@ __global__ __launch_bounds__(256) void unet_dice_sums_kernel(const T* __restrict
         for (int c = 0; c < Cs; ++c) I[c] = P[c] = 0.f;
         for (int i = threadIdx.x; i < slab.n; i += 256) {
             const int64_t p = base + slab.offset(i, W);
-            const int64_t lab64 = (t ? lab1 : lab0)[p];
-            if (lab64 < 0 || lab64 >= C) continue;
+            const int64_t lab64 = (t && !MASKED ? lab1 : lab0)[p];
+            if (lab64 < (MASKED ? 1 : 0) || lab64 >= C) continue;
             const int lab = (int)lab64;
             float x[Cs];
             float xl;
@@ -647,7 +675,7 @@ __global__ __launch_bounds__(256) void unet_dice_sums_kernel(const T* __restrict
 }
 
 // Any class count (Cs > 32): kDiceChunk classes per sweep of the slab, the logits of a pixel read from the cache in every sweep
-template <typename T>
+template <typename T, bool MASKED>
 __global__ __launch_bounds__(256) void unet_dice_sums_wide_kernel(const T* __restrict__ l0, const T* __restrict__ l1,
                                                                   const int64_t* __restrict__ lab0, const int64_t* __restrict__ lab1,
                                                                   const int32_t* __restrict__ extent, float* __restrict__ part, int B,
@@ -664,8 +692,8 @@ __global__ __launch_bounds__(256) void unet_dice_sums_wide_kernel(const T* __res
             for (int c = 0; c < kDiceChunk; ++c) I[c] = P[c] = 0.f;
             for (int i = threadIdx.x; i < slab.n; i += 256) {
                 const int64_t p = base + slab.offset(i, W);
-                const int64_t lab64 = (t ? lab1 : lab0)[p];
-                if (lab64 < 0 || lab64 >= C) continue;
+                const int64_t lab64 = (t && !MASKED ? lab1 : lab0)[p];
+                if (lab64 < (MASKED ? 1 : 0) || lab64 >= C) continue;
                 const int lab = (int)lab64;
                 const T* l = (t ? l1 : l0) + p * Cs;
                 const float lse = pixel_lse_wide(l, C);
@@ -684,6 +712,9 @@ __global__ __launch_bounds__(256) void unet_dice_sums_wide_kernel(const T* __res
 // The coefficient step: grid (B, heads), thread c takes class c (C <= 256).  The K rows of `part` and the Kh rows of the head's label
 // histogram are added in index order; tab[(t * B + b) * C + c] = (hit, miss) when tab is given; the document's loss, the classes
 // added lanes-then-waves, times `scale` -> doc_loss[b * sb + t * st].  Every output is written.
+// MASKED: one histogram for both heads, Y_0 = 0 whatever the histogram counted at label 0, and a document without a labelled pixel
+// has loss 0 (its table is unread: no pixel of it is active).
+template <bool MASKED>
 __global__ __launch_bounds__(256) void unet_dice_coef_kernel(const float* __restrict__ part, int K, const int32_t* __restrict__ hist, int Kh,
                                                              const float* __restrict__ cw, float eps, float2* __restrict__ tab,
                                                              float* __restrict__ doc_loss, int sb, int st, float scale, int B, int C) {
@@ -692,19 +723,21 @@ __global__ __launch_bounds__(256) void unet_dice_coef_kernel(const float* __rest
     float V = 0.f;                                                   // every thread the same sum, classes in index order
     for (int i = 0; i < C; ++i) V += cw ? cw[i] : 1.f;
     float term = 0.f;
+    int n = 0;
     if (c < C) {
         const float* rows = part + ((int64_t)t * B + b) * K * 2 * C;
-        const int32_t* h = hist + ((int64_t)t * B + b) * Kh * C;
+        const int32_t* h = hist + ((int64_t)(MASKED ? 0 : t) * B + b) * Kh * C;
         float I = 0.f, P = 0.f;
-        int n = 0;
         for (int k = 0; k < K; ++k) { I += rows[(int64_t)k * 2 * C + c]; P += rows[(int64_t)k * 2 * C + C + c]; }
         for (int k = 0; k < Kh; ++k) n += h[k * C + c];
+        if (MASKED && c == 0) n = 0;
         float hit, miss;
         msau_dice_coef(I, P, (float)n, eps, V > 0.f ? (cw ? cw[c] : 1.f) / V : 0.f, &term, &hit, &miss);
         if (tab) tab[((int64_t)t * B + b) * C + c] = make_float2(hit, miss);
     }
+    const bool labelled = MASKED ? __syncthreads_or(n > 0) != 0 : true;
     const float s = block_sum<4, true>(term, red);
-    if (threadIdx.x == 0) doc_loss[b * sb + t * st] = scale * msau_dice_loss(V, s);
+    if (threadIdx.x == 0) doc_loss[b * sb + t * st] = labelled ? scale * msau_dice_loss(V, s) : 0.f;
 }
 
 // The pixel's Dice gradient g[j] = sc * p_j * (a_j - sum_c a_c p_c), a_c = hit_c at the label, else miss_c (tab: the document's C
@@ -758,23 +791,28 @@ __device__ __forceinline__ void dice_grad_store_wide(T* __restrict__ dst, const 
 }
 
 // The gradient pass, of unet_ce_kernel's shape: every pixel of the canvas, both heads, sc = head weight / B
-template <typename T, int NL, int CS8>
+// MASKED: as in unet_ce_kernel -- lab0 read once for both heads, the active classes from 1, head weight 1
+template <typename T, int NL, int CS8, bool MASKED>
 __global__ void unet_dice_grad_kernel(const T* __restrict__ l0, const T* __restrict__ l1, const int64_t* __restrict__ lab0,
                                       const int64_t* __restrict__ lab1, const int32_t* __restrict__ extent, const float2* __restrict__ tab,
                                       T* __restrict__ d0, T* __restrict__ d1, int B, int H, int W, int C) {
     constexpr int Cs = CS8 * 8;
-    const float sc = (NL == 2 ? 0.5f : 1.f) / (float)B;
+    const float sc = ((NL == 2 && !MASKED) ? 0.5f : 1.f) / (float)B;
     const int hw = H * W;
     const int64_t total = (int64_t)B * hw;
     for (int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; p < total; p += (int64_t)gridDim.x * blockDim.x) {
         const int b = (int)((unsigned)p / (unsigned)hw);               // total < 2^31 (checked by the host)
         const int j = (int)p - b * hw;
         const bool in = extent ? pos_in_extent(j, W, extent[2 * b], extent[2 * b + 1]) : true;
+        bool on = false;
+        int lab = -1;
 #pragma unroll
         for (int t = 0; t < NL; ++t) {
-            const int64_t lab64 = (t ? lab1 : lab0)[p];
-            const bool on = in && lab64 >= 0 && lab64 < C;
-            const int lab = on ? (int)lab64 : -1;
+            if (!MASKED || t == 0) {
+                const int64_t lab64 = (t ? lab1 : lab0)[p];
+                on = in && lab64 >= (MASKED ? 1 : 0) && lab64 < C;
+                lab = on ? (int)lab64 : -1;
+            }
             float x[Cs];
             float xl;
             const float lse = pixel_lse<T, CS8>((t ? l1 : l0) + p * Cs, C, lab, x, xl);
@@ -783,25 +821,30 @@ __global__ void unet_dice_grad_kernel(const T* __restrict__ l0, const T* __restr
     }
 }
 
-template <typename T>
+template <typename T, bool MASKED>
 __global__ void unet_dice_grad_wide_kernel(const T* __restrict__ l0, const T* __restrict__ l1, const int64_t* __restrict__ lab0,
                                            const int64_t* __restrict__ lab1, const int32_t* __restrict__ extent,
                                            const float2* __restrict__ tab, T* __restrict__ d0, T* __restrict__ d1, int B, int H, int W,
                                            int C, int Cs) {
     const int NL = l1 ? 2 : 1;
-    const float sc = (NL == 2 ? 0.5f : 1.f) / (float)B;
+    const float sc = ((NL == 2 && !MASKED) ? 0.5f : 1.f) / (float)B;
     const int hw = H * W;
     const int64_t total = (int64_t)B * hw;
     for (int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; p < total; p += (int64_t)gridDim.x * blockDim.x) {
         const int b = (int)((unsigned)p / (unsigned)hw);
         const int j = (int)p - b * hw;
         const bool in = extent ? pos_in_extent(j, W, extent[2 * b], extent[2 * b + 1]) : true;
+        bool on = false;
+        int lab = -1;
         for (int t = 0; t < NL; ++t) {
             const T* l = (t ? l1 : l0) + p * Cs;
-            const int64_t lab64 = (t ? lab1 : lab0)[p];
-            const bool on = in && lab64 >= 0 && lab64 < C;
+            if (!MASKED || t == 0) {
+                const int64_t lab64 = (t ? lab1 : lab0)[p];
+                on = in && lab64 >= (MASKED ? 1 : 0) && lab64 < C;
+                lab = on ? (int)lab64 : -1;
+            }
             const float lse = pixel_lse_wide(l, C);
-            dice_grad_store_wide((t ? d1 : d0) + p * Cs, l, lse, tab + ((int64_t)t * B + b) * C, sc, on ? (int)lab64 : -1, C, Cs, on);
+            dice_grad_store_wide((t ? d1 : d0) + p * Cs, l, lse, tab + ((int64_t)t * B + b) * C, sc, lab, C, Cs, on);
         }
     }
 }
@@ -996,29 +1039,37 @@ extern "C" int msau_label_hist(void* stream, const int64_t* labels, const int32_
 static int unet_ce_blocks(int64_t npix) { return grid_for(npix, 2048); }
 extern "C" int64_t msau_unet_ce_ws_floats(int64_t npix_total) { return 2 * unet_ce_blocks(npix_total); }
 
-// msau_unet_ce (FOCAL false, gamma unread) and the focal loss of msau_unet_cost: the same checks, the same two launches.  `fn`
-// names the entry point in the messages.
-template <bool FOCAL>
-static int unet_ce_run(const char* fn, float gamma, void* stream, int dtype, const void* logits, const void* aux, const int64_t* labels,
-                       const int64_t* aux_labels, const int32_t* extent, const float* class_w, const int32_t* hist_partial, int K,
-                       void* dlogits, void* daux, float* loss3, float* ws, int B, int H, int W, int C, int Cs) {
+// the argument checks of every training entry point of the family, before anything is launched.  `fn` names the entry point.
+static int unet_train_check(const char* fn, const void* logits, const void* aux, const int64_t* labels, const int64_t* aux_labels,
+                            const float* class_w, const int32_t* hist_partial, int K, const void* dlogits, const void* daux,
+                            const float* loss3, const float* ws, int B, int H, int W, int C, int Cs) {
     MSAU_CHECK_ARG(logits && labels && dlogits && loss3 && ws && (!aux || (daux && aux_labels)), "%s: null pointer", fn);
     MSAU_CHECK_ARG(!class_w || (hist_partial && K >= 1 && K <= 64), "%s: class weights need the label histograms (1 <= K <= 64)", fn);
     MSAU_CHECK_ARG(B > 0 && B <= kCeMaxB && H > 0 && W > 0 && (int64_t)B * H * W < (1ll << 31) && C > 0 && C <= Cs && Cs % 8 == 0 && Cs <= 256,
                    "%s: bad dims (B <= %d, B*H*W < 2^31, n_class <= 256)", fn, kCeMaxB);
+    return 0;
+}
+
+// msau_unet_ce (FOCAL false, gamma unread), the focal loss of msau_unet_cost and (MASKED) both of msau_masked_cost: the same checks,
+// the same two launches.  `fn` names the entry point in the messages.
+template <bool FOCAL, bool MASKED>
+static int unet_ce_run(const char* fn, float gamma, void* stream, int dtype, const void* logits, const void* aux, const int64_t* labels,
+                       const int64_t* aux_labels, const int32_t* extent, const float* class_w, const int32_t* hist_partial, int K,
+                       void* dlogits, void* daux, float* loss3, float* ws, int B, int H, int W, int C, int Cs) {
+    if (int e = unet_train_check(fn, logits, aux, labels, aux_labels, class_w, hist_partial, K, dlogits, daux, loss3, ws, B, H, W, C, Cs)) return e;
     hipStream_t s = static_cast<hipStream_t>(stream);
     const int nb = unet_ce_blocks((int64_t)B * H * W);
-#define UNET_CE(T, NL, C8) hipLaunchKernelGGL((unet_ce_kernel<T, NL, C8, FOCAL>), dim3(nb), dim3(kThreads), 0, s, static_cast<const T*>(logits), \
+#define UNET_CE(T, NL, C8) hipLaunchKernelGGL((unet_ce_kernel<T, NL, C8, FOCAL, MASKED>), dim3(nb), dim3(kThreads), 0, s, static_cast<const T*>(logits), \
         static_cast<const T*>(aux), labels, aux_labels, extent, class_w, hist_partial, K, static_cast<T*>(dlogits), static_cast<T*>(daux), \
         ws, B, H, W, C, gamma)
-#define UNET_CE_WIDE(T) hipLaunchKernelGGL((unet_ce_wide_kernel<T, FOCAL>), dim3(nb), dim3(kThreads), 0, s, static_cast<const T*>(logits), \
+#define UNET_CE_WIDE(T) hipLaunchKernelGGL((unet_ce_wide_kernel<T, FOCAL, MASKED>), dim3(nb), dim3(kThreads), 0, s, static_cast<const T*>(logits), \
         static_cast<const T*>(aux), labels, aux_labels, extent, class_w, hist_partial, K, static_cast<T*>(dlogits), static_cast<T*>(daux), \
         ws, B, H, W, C, Cs, gamma)
     LOSS_LADDER_32(dtype, aux, Cs, UNET_CE, UNET_CE_WIDE);
 #undef UNET_CE_WIDE
 #undef UNET_CE
     MSAU_CHECK_LAUNCH(fn);
-    hipLaunchKernelGGL(unet_ce_finish_kernel, dim3(1), dim3(256), 0, s, ws, nb, aux ? 1 : 0, loss3);
+    hipLaunchKernelGGL(unet_ce_finish_kernel<MASKED>, dim3(1), dim3(256), 0, s, ws, nb, aux ? 1 : 0, loss3);
     MSAU_CHECK_LAUNCH("unet_ce_finish");
     return 0;
 }
@@ -1026,11 +1077,12 @@ static int unet_ce_run(const char* fn, float gamma, void* stream, int dtype, con
 extern "C" int msau_unet_ce(void* stream, int dtype, const void* logits, const void* aux, const int64_t* labels,
                             const int64_t* aux_labels, const int32_t* extent, const float* class_w, const int32_t* hist_partial, int K,
                             void* dlogits, void* daux, float* loss3, float* ws, int B, int H, int W, int C, int Cs) {
-    return unet_ce_run<false>("unet_ce", 0.f, stream, dtype, logits, aux, labels, aux_labels, extent, class_w, hist_partial, K, dlogits, daux,
-                              loss3, ws, B, H, W, C, Cs);
+    return unet_ce_run<false, false>("unet_ce", 0.f, stream, dtype, logits, aux, labels, aux_labels, extent, class_w, hist_partial, K, dlogits,
+                                     daux, loss3, ws, B, H, W, C, Cs);
 }
 
-// the cost of msau_unet_cost / msau_unet_cost_eval: checked before anything else, and without a device
+// the cost of msau_unet_cost / msau_unet_cost_eval / msau_masked_cost / msau_masked_cost_eval: checked before anything else, and
+// without a device
 static int unet_cost_check(const char* fn, int kind, float param) {
     MSAU_CHECK_ARG(kind == MSAU_COST_CE || kind == MSAU_COST_FOCAL || kind == MSAU_COST_DICE, "%s: unknown cost %d", fn, kind);
     MSAU_CHECK_ARG(kind != MSAU_COST_FOCAL || (param >= 0.f && param < INFINITY), "%s: focal gamma = %g (finite, >= 0)", fn, (double)param);
@@ -1039,12 +1091,13 @@ static int unet_cost_check(const char* fn, int kind, float param) {
 }
 
 // the Dice sums of both heads: part[heads][B][K][2][C] written
+template <bool MASKED>
 static int launch_dice_sums(hipStream_t s, int dtype, const void* logits, const void* aux, const int64_t* labels, const int64_t* aux_labels,
                             const int32_t* extent, float* part, int K, int B, int H, int W, int C, int Cs) {
     const dim3 grid(K, B);
-#define DICE_SUMS(T, NL, C8) hipLaunchKernelGGL((unet_dice_sums_kernel<T, NL, C8>), grid, dim3(256), 0, s, static_cast<const T*>(logits), \
+#define DICE_SUMS(T, NL, C8) hipLaunchKernelGGL((unet_dice_sums_kernel<T, NL, C8, MASKED>), grid, dim3(256), 0, s, static_cast<const T*>(logits), \
         static_cast<const T*>(aux), labels, aux_labels, extent, part, B, H, W, C)
-#define DICE_SUMS_WIDE(T) hipLaunchKernelGGL((unet_dice_sums_wide_kernel<T>), grid, dim3(256), 0, s, static_cast<const T*>(logits), \
+#define DICE_SUMS_WIDE(T) hipLaunchKernelGGL((unet_dice_sums_wide_kernel<T, MASKED>), grid, dim3(256), 0, s, static_cast<const T*>(logits), \
         static_cast<const T*>(aux), labels, aux_labels, extent, part, B, H, W, C, Cs)
     LOSS_LADDER_32(dtype, aux, Cs, DICE_SUMS, DICE_SUMS_WIDE);
 #undef DICE_SUMS_WIDE
@@ -1056,11 +1109,42 @@ static int launch_dice_sums(hipStream_t s, int dtype, const void* logits, const 
 // Dice training workspace, in floats: [2 B] the documents' losses / B, [2 B C] (hit, miss) pairs, [2 B 64 2 C] the slab rows (K <= 64)
 static int64_t dice_tab_at(int B) { return 2 * (int64_t)B; }
 static int64_t dice_part_at(int B, int C) { return dice_tab_at(B) + 4 * (int64_t)B * C; }
+static int64_t dice_ws_floats(int B, int C) { return dice_part_at(B, C) + 2 * (int64_t)B * 64 * 2 * C; }
 
 extern "C" int64_t msau_unet_cost_ws_floats(int kind, int B, int H, int W, int C) {
     if (B <= 0 || H <= 0 || W <= 0 || C <= 0) return 0;
-    if (kind == MSAU_COST_DICE) return dice_part_at(B, C) + 2 * (int64_t)B * 64 * 2 * C;
+    if (kind == MSAU_COST_DICE) return dice_ws_floats(B, C);
     return msau_unet_ce_ws_floats((int64_t)B * H * W);
+}
+
+// The Dice loss of msau_unet_cost and (MASKED) of msau_masked_cost, after the cost's own check: the sums, the coefficient step, the
+// finish launch and the gradient pass.  MASKED: hist_partial is the one label map's.
+template <bool MASKED>
+static int unet_dice_run(const char* fn, float eps, void* stream, int dtype, const void* logits, const void* aux, const int64_t* labels,
+                         const int64_t* aux_labels, const int32_t* extent, const float* class_w, const int32_t* hist_partial, int K,
+                         void* dlogits, void* daux, float* loss3, float* ws, int B, int H, int W, int C, int Cs) {
+    if (int e = unet_train_check(fn, logits, aux, labels, aux_labels, class_w, hist_partial, K, dlogits, daux, loss3, ws, B, H, W, C, Cs)) return e;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const int nl = aux ? 2 : 1;
+    float* part = ws + dice_part_at(B, C);
+    float2* tab = reinterpret_cast<float2*>(ws + dice_tab_at(B));
+    if (int e = launch_dice_sums<MASKED>(s, dtype, logits, aux, labels, aux_labels, extent, part, K, B, H, W, C, Cs)) return e;
+    // the documents' losses / B of head t -> ws[t * B + b]: unet_ce_finish_kernel then adds each head's B values as it adds block partials
+    hipLaunchKernelGGL(unet_dice_coef_kernel<MASKED>, dim3(B, nl), dim3(256), 0, s, part, K, hist_partial, K, class_w, eps, tab, ws, 1, B,
+                       1.f / (float)B, B, C);
+    MSAU_CHECK_LAUNCH("unet_dice_coef");
+    hipLaunchKernelGGL(unet_ce_finish_kernel<MASKED>, dim3(1), dim3(256), 0, s, ws, B, aux ? 1 : 0, loss3);
+    MSAU_CHECK_LAUNCH("unet_ce_finish");
+    const int nb = unet_ce_blocks((int64_t)B * H * W);
+#define DICE_GRAD(T, NL, C8) hipLaunchKernelGGL((unet_dice_grad_kernel<T, NL, C8, MASKED>), dim3(nb), dim3(kThreads), 0, s, static_cast<const T*>(logits), \
+        static_cast<const T*>(aux), labels, aux_labels, extent, tab, static_cast<T*>(dlogits), static_cast<T*>(daux), B, H, W, C)
+#define DICE_GRAD_WIDE(T) hipLaunchKernelGGL((unet_dice_grad_wide_kernel<T, MASKED>), dim3(nb), dim3(kThreads), 0, s, static_cast<const T*>(logits), \
+        static_cast<const T*>(aux), labels, aux_labels, extent, tab, static_cast<T*>(dlogits), static_cast<T*>(daux), B, H, W, C, Cs)
+    LOSS_LADDER_32(dtype, aux, Cs, DICE_GRAD, DICE_GRAD_WIDE);
+#undef DICE_GRAD_WIDE
+#undef DICE_GRAD
+    MSAU_CHECK_LAUNCH("unet_dice_grad");
+    return 0;
 }
 
 extern "C" int msau_unet_cost(void* stream, int dtype, int kind, float param, const void* logits, const void* aux, const int64_t* labels,
@@ -1071,40 +1155,54 @@ extern "C" int msau_unet_cost(void* stream, int dtype, int kind, float param, co
     if (kind == MSAU_COST_CE)
         return msau_unet_ce(stream, dtype, logits, aux, labels, aux_labels, extent, class_w, hist_partial, K, dlogits, daux, loss3, ws, B, H, W, C, Cs);
     if (kind == MSAU_COST_FOCAL)
-        return unet_ce_run<true>("unet_cost", param, stream, dtype, logits, aux, labels, aux_labels, extent, class_w, hist_partial, K, dlogits,
-                                 daux, loss3, ws, B, H, W, C, Cs);
-    MSAU_CHECK_ARG(logits && labels && dlogits && loss3 && ws && (!aux || (daux && aux_labels)), "unet_cost: null pointer");
-    MSAU_CHECK_ARG(B > 0 && B <= kCeMaxB && H > 0 && W > 0 && (int64_t)B * H * W < (1ll << 31) && C > 0 && C <= Cs && Cs % 8 == 0 && Cs <= 256,
-                   "unet_cost: bad dims (B <= %d, B*H*W < 2^31, n_class <= 256)", kCeMaxB);
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    const int nl = aux ? 2 : 1;
-    float* part = ws + dice_part_at(B, C);
-    float2* tab = reinterpret_cast<float2*>(ws + dice_tab_at(B));
-    if (int e = launch_dice_sums(s, dtype, logits, aux, labels, aux_labels, extent, part, K, B, H, W, C, Cs)) return e;
-    // the documents' losses / B of head t -> ws[t * B + b]: unet_ce_finish_kernel then adds each head's B values as it adds block partials
-    hipLaunchKernelGGL(unet_dice_coef_kernel, dim3(B, nl), dim3(256), 0, s, part, K, hist_partial, K, class_w, param, tab, ws, 1, B,
-                       1.f / (float)B, B, C);
-    MSAU_CHECK_LAUNCH("unet_dice_coef");
-    hipLaunchKernelGGL(unet_ce_finish_kernel, dim3(1), dim3(256), 0, s, ws, B, aux ? 1 : 0, loss3);
-    MSAU_CHECK_LAUNCH("unet_ce_finish");
-    const int nb = unet_ce_blocks((int64_t)B * H * W);
-#define DICE_GRAD(T, NL, C8) hipLaunchKernelGGL((unet_dice_grad_kernel<T, NL, C8>), dim3(nb), dim3(kThreads), 0, s, static_cast<const T*>(logits), \
-        static_cast<const T*>(aux), labels, aux_labels, extent, tab, static_cast<T*>(dlogits), static_cast<T*>(daux), B, H, W, C)
-#define DICE_GRAD_WIDE(T) hipLaunchKernelGGL((unet_dice_grad_wide_kernel<T>), dim3(nb), dim3(kThreads), 0, s, static_cast<const T*>(logits), \
-        static_cast<const T*>(aux), labels, aux_labels, extent, tab, static_cast<T*>(dlogits), static_cast<T*>(daux), B, H, W, C, Cs)
-    LOSS_LADDER_32(dtype, aux, Cs, DICE_GRAD, DICE_GRAD_WIDE);
-#undef DICE_GRAD_WIDE
-#undef DICE_GRAD
-    MSAU_CHECK_LAUNCH("unet_dice_grad");
-    return 0;
+        return unet_ce_run<true, false>("unet_cost", param, stream, dtype, logits, aux, labels, aux_labels, extent, class_w, hist_partial, K,
+                                        dlogits, daux, loss3, ws, B, H, W, C, Cs);
+    return unet_dice_run<false>("unet_cost", param, stream, dtype, logits, aux, labels, aux_labels, extent, class_w, hist_partial, K, dlogits,
+                                daux, loss3, ws, B, H, W, C, Cs);
+}
+
+// The masked cost: the loss of TrainEngine.step / MSAUWrapper.loss under a cost and class weights.  Both heads are
+// scored against ONE label map over the pixels with a label in [1, C), head weights 1 and 1.  The cross entropy and the focal loss
+// without class weights need only the documents' numbers of labelled pixels: when no histogram is given, this call takes one itself,
+// kMaskedHistK rows per document, into the tail of its workspace.
+constexpr int kMaskedHistK = 16;
+
+extern "C" int64_t msau_masked_cost_ws_floats(int kind, int B, int H, int W, int C) {
+    if (B <= 0 || H <= 0 || W <= 0 || C <= 0) return 0;
+    if (kind == MSAU_COST_DICE) return dice_ws_floats(B, C);
+    return msau_unet_ce_ws_floats((int64_t)B * H * W) + (int64_t)B * kMaskedHistK * C;
+}
+
+extern "C" int msau_masked_cost(void* stream, int dtype, int kind, float param, const void* logits, const void* aux, const int64_t* labels,
+                                const int32_t* extent, const float* class_w, const int32_t* hist_partial, int K, void* dlogits, void* daux,
+                                float* loss3, float* ws, int B, int H, int W, int C, int Cs) {
+    if (int e = unet_cost_check("masked_cost", kind, param)) return e;
+    MSAU_CHECK_ARG(kind != MSAU_COST_DICE || (hist_partial && K >= 1 && K <= 64), "masked_cost: dice needs the label histograms (1 <= K <= 64)");
+    MSAU_CHECK_ARG(!hist_partial || (K >= 1 && K <= 64), "masked_cost: K = %d rows of the label histograms (1 <= K <= 64)", K);
+    if (kind == MSAU_COST_DICE)
+        return unet_dice_run<true>("masked_cost", param, stream, dtype, logits, aux, labels, labels, extent, class_w, hist_partial, K, dlogits,
+                                   daux, loss3, ws, B, H, W, C, Cs);
+    if (!hist_partial) {
+        if (int e = unet_train_check("masked_cost", logits, aux, labels, labels, class_w, hist_partial, K, dlogits, daux, loss3, ws, B, H, W, C, Cs)) return e;
+        MSAU_CHECK_ARG(C <= kHistMaxC, "masked_cost: n_class <= %d", kHistMaxC);
+        int32_t* own = reinterpret_cast<int32_t*>(ws + msau_unet_ce_ws_floats((int64_t)B * H * W));
+        if (int e = msau_label_hist(stream, labels, extent, own, B, H, W, C, kMaskedHistK)) return e;
+        hist_partial = own;
+        K = kMaskedHistK;
+    }
+    if (kind == MSAU_COST_FOCAL)
+        return unet_ce_run<true, true>("masked_cost", param, stream, dtype, logits, aux, labels, labels, extent, class_w, hist_partial, K, dlogits,
+                                       daux, loss3, ws, B, H, W, C, Cs);
+    return unet_ce_run<false, true>("masked_cost", 0.f, stream, dtype, logits, aux, labels, labels, extent, class_w, hist_partial, K, dlogits,
+                                    daux, loss3, ws, B, H, W, C, Cs);
 }
 
 extern "C" int64_t msau_unet_eval_ws_bytes(int B, int K) {
     return B > 0 && K > 0 ? (int64_t)B * K * (int64_t)sizeof(UnetEvalRow) : 0;
 }
 
-// msau_unet_eval (FOCAL false, gamma unread) and the focal rows of msau_unet_cost_eval
-template <bool FOCAL>
+// msau_unet_eval (FOCAL false, gamma unread), the focal rows of msau_unet_cost_eval and (MASKED) the rows of msau_masked_cost_eval
+template <bool FOCAL, bool MASKED>
 static int unet_eval_run(const char* fn, float gamma, void* stream, int dtype, const void* logits, const void* aux, const int64_t* labels,
                          const int64_t* aux_labels, const int32_t* extent, const float* class_w, int K, float* doc_loss,
                          int32_t* doc_counts, void* ws, int B, int H, int W, int C, int Cs) {
@@ -1115,9 +1213,9 @@ static int unet_eval_run(const char* fn, float gamma, void* stream, int dtype, c
     hipStream_t s = static_cast<hipStream_t>(stream);
     UnetEvalRow* rows = static_cast<UnetEvalRow*>(ws);
     const dim3 grid(K, B);
-#define UNET_EVAL(T, NL, C8) hipLaunchKernelGGL((unet_eval_kernel<T, NL, C8, FOCAL>), grid, dim3(256), 0, s, static_cast<const T*>(logits), \
+#define UNET_EVAL(T, NL, C8) hipLaunchKernelGGL((unet_eval_kernel<T, NL, C8, FOCAL, MASKED>), grid, dim3(256), 0, s, static_cast<const T*>(logits), \
         static_cast<const T*>(aux), labels, aux_labels, extent, class_w, rows, H, W, C, gamma)
-#define UNET_EVAL_WIDE(T) hipLaunchKernelGGL((unet_eval_wide_kernel<T, FOCAL>), grid, dim3(256), 0, s, static_cast<const T*>(logits), \
+#define UNET_EVAL_WIDE(T) hipLaunchKernelGGL((unet_eval_wide_kernel<T, FOCAL, MASKED>), grid, dim3(256), 0, s, static_cast<const T*>(logits), \
         static_cast<const T*>(aux), labels, aux_labels, extent, class_w, rows, H, W, C, Cs, gamma)
     LOSS_LADDER_32(dtype, aux, Cs, UNET_EVAL, UNET_EVAL_WIDE);
 #undef UNET_EVAL_WIDE
@@ -1131,28 +1229,33 @@ static int unet_eval_run(const char* fn, float gamma, void* stream, int dtype, c
 extern "C" int msau_unet_eval(void* stream, int dtype, const void* logits, const void* aux, const int64_t* labels,
                               const int64_t* aux_labels, const int32_t* extent, const float* class_w, int K, float* doc_loss,
                               int32_t* doc_counts, void* ws, int B, int H, int W, int C, int Cs) {
-    return unet_eval_run<false>("unet_eval", 0.f, stream, dtype, logits, aux, labels, aux_labels, extent, class_w, K, doc_loss, doc_counts, ws,
-                                B, H, W, C, Cs);
+    return unet_eval_run<false, false>("unet_eval", 0.f, stream, dtype, logits, aux, labels, aux_labels, extent, class_w, K, doc_loss, doc_counts,
+                                       ws, B, H, W, C, Cs);
 }
 
-// Dice evaluation workspace, in bytes: msau_unet_eval's rows, then [2 B K 2 C] floats of slab rows, then [2 B min(K, 64) C] int32
-// of label histograms
+// Dice evaluation workspace, in bytes: msau_unet_eval's rows, then [2 B K 2 C] floats of slab rows, then [heads B min(K, 64) C] int32
+// of label histograms (heads: 2 label maps under UNetLoss, 1 under the masked cost)
 static int dice_eval_kh(int K) { return K < 64 ? K : 64; }
-extern "C" int64_t msau_unet_cost_eval_ws_bytes(int kind, int B, int K, int C) {
+static int64_t cost_eval_ws_bytes(int kind, int B, int K, int C, int maps) {
     const int64_t rows = msau_unet_eval_ws_bytes(B, K);
     if (kind != MSAU_COST_DICE || rows == 0 || C <= 0) return rows;
-    return rows + 4 * (2 * (int64_t)B * K * 2 * C + 2 * (int64_t)B * dice_eval_kh(K) * C);
+    return rows + 4 * (2 * (int64_t)B * K * 2 * C + maps * (int64_t)B * dice_eval_kh(K) * C);
 }
+extern "C" int64_t msau_unet_cost_eval_ws_bytes(int kind, int B, int K, int C) { return cost_eval_ws_bytes(kind, B, K, C, 2); }
+extern "C" int64_t msau_masked_cost_eval_ws_bytes(int kind, int B, int K, int C) { return cost_eval_ws_bytes(kind, B, K, C, 1); }
 
-extern "C" int msau_unet_cost_eval(void* stream, int dtype, int kind, float param, const void* logits, const void* aux,
-                                   const int64_t* labels, const int64_t* aux_labels, const int32_t* extent, const float* class_w, int K,
-                                   float* doc_loss, int32_t* doc_counts, void* ws, int B, int H, int W, int C, int Cs) {
-    if (int e = unet_cost_check("unet_cost_eval", kind, param)) return e;
+// msau_unet_cost_eval and (MASKED: aux_labels = labels) msau_masked_cost_eval
+template <bool MASKED>
+static int unet_cost_eval_run(const char* fn, void* stream, int dtype, int kind, float param, const void* logits, const void* aux,
+                              const int64_t* labels, const int64_t* aux_labels, const int32_t* extent, const float* class_w, int K,
+                              float* doc_loss, int32_t* doc_counts, void* ws, int B, int H, int W, int C, int Cs) {
+    if (int e = unet_cost_check(fn, kind, param)) return e;
     if (kind == MSAU_COST_FOCAL)
-        return unet_eval_run<true>("unet_cost_eval", param, stream, dtype, logits, aux, labels, aux_labels, extent, class_w, K, doc_loss,
-                                   doc_counts, ws, B, H, W, C, Cs);
+        return unet_eval_run<true, MASKED>(fn, param, stream, dtype, logits, aux, labels, aux_labels, extent, class_w, K, doc_loss,
+                                           doc_counts, ws, B, H, W, C, Cs);
     // the counts (and, for the cross entropy, the losses) are msau_unet_eval's own
-    if (int e = msau_unet_eval(stream, dtype, logits, aux, labels, aux_labels, extent, class_w, K, doc_loss, doc_counts, ws, B, H, W, C, Cs)) return e;
+    if (int e = unet_eval_run<false, MASKED>(MASKED ? fn : "unet_eval", 0.f, stream, dtype, logits, aux, labels, aux_labels, extent, class_w, K,
+                                             doc_loss, doc_counts, ws, B, H, W, C, Cs)) return e;
     if (kind == MSAU_COST_CE) return 0;
     // Dice: the sums over the same K slabs, the label histograms taken here, and the coefficient step writes doc_loss[b][t] over the
     // cross entropy's (head 1 of a one-head call keeps msau_unet_eval's 0)
@@ -1160,13 +1263,27 @@ extern "C" int msau_unet_cost_eval(void* stream, int dtype, int kind, float para
     const int nl = aux ? 2 : 1, Kh = dice_eval_kh(K);
     float* part = reinterpret_cast<float*>(static_cast<char*>(ws) + msau_unet_eval_ws_bytes(B, K));
     int32_t* hist = reinterpret_cast<int32_t*>(part + 2 * (int64_t)B * K * 2 * C);
-    for (int t = 0; t < nl; ++t)
+    for (int t = 0; t < (MASKED ? 1 : nl); ++t)
         if (int e = msau_label_hist(stream, t ? aux_labels : labels, extent, hist + (int64_t)t * B * Kh * C, B, H, W, C, Kh)) return e;
-    if (int e = launch_dice_sums(s, dtype, logits, aux, labels, aux_labels, extent, part, K, B, H, W, C, Cs)) return e;
-    hipLaunchKernelGGL(unet_dice_coef_kernel, dim3(B, nl), dim3(256), 0, s, part, K, hist, Kh, class_w, param, static_cast<float2*>(nullptr),
-                       doc_loss, 2, 1, 1.f, B, C);
+    if (int e = launch_dice_sums<MASKED>(s, dtype, logits, aux, labels, aux_labels, extent, part, K, B, H, W, C, Cs)) return e;
+    hipLaunchKernelGGL(unet_dice_coef_kernel<MASKED>, dim3(B, nl), dim3(256), 0, s, part, K, hist, Kh, class_w, param,
+                       static_cast<float2*>(nullptr), doc_loss, 2, 1, 1.f, B, C);
     MSAU_CHECK_LAUNCH("unet_dice_coef");
     return 0;
+}
+
+extern "C" int msau_unet_cost_eval(void* stream, int dtype, int kind, float param, const void* logits, const void* aux,
+                                   const int64_t* labels, const int64_t* aux_labels, const int32_t* extent, const float* class_w, int K,
+                                   float* doc_loss, int32_t* doc_counts, void* ws, int B, int H, int W, int C, int Cs) {
+    return unet_cost_eval_run<false>("unet_cost_eval", stream, dtype, kind, param, logits, aux, labels, aux_labels, extent, class_w, K, doc_loss,
+                                     doc_counts, ws, B, H, W, C, Cs);
+}
+
+extern "C" int msau_masked_cost_eval(void* stream, int dtype, int kind, float param, const void* logits, const void* aux,
+                                     const int64_t* labels, const int32_t* extent, const float* class_w, int K, float* doc_loss,
+                                     int32_t* doc_counts, void* ws, int B, int H, int W, int C, int Cs) {
+    return unet_cost_eval_run<true>("masked_cost_eval", stream, dtype, kind, param, logits, aux, labels, labels, extent, class_w, K, doc_loss,
+                                    doc_counts, ws, B, H, W, C, Cs);
 }
 
 extern "C" int msau_softmax_ce(void* stream, int dtype, const void* logits, const int64_t* labels, void* dlogits,

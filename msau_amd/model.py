@@ -211,6 +211,49 @@ class _MaskedCEFunction(torch.autograd.Function):
         return g_logits, g_aux, None
 
 
+class _MaskedCostFunction(torch.autograd.Function):
+    """MSAUWrapper.loss under a cost and class weights on NCHW fp32 logits: one msau_masked_cost for both heads, every
+    sample a document of its own; `kind` / `param` a checked cost's, `class_w` fp32 [C] on the device or None.  The conversion
+    launches are those of training/cost.py's _UnetCost."""
+
+    @staticmethod
+    def forward(ctx, logits, aux, label, kind, param, class_w):
+        B, C, H, W = logits.shape
+        dev = logits.device
+        Cs = -(-C // 8) * 8
+        K = 4
+        s = torch.cuda.current_stream().cuda_stream
+        label = label.reshape(B, H, W).contiguous().long()
+        loss3 = torch.empty((3,), dtype=torch.float32, device=dev)
+        ws = torch.empty((int(L.load().msau_masked_cost_ws_floats(kind, B, H, W, C)),), dtype=torch.float32, device=dev)
+        hist = None
+        if class_w is not None or kind == L.COST_DICE:
+            hist = torch.empty((B, K, C), dtype=torch.int32, device=dev)
+            L.call("msau_label_hist", s, label.data_ptr(), None, hist.data_ptr(), B, H, W, C, K)
+        heads = [t for t in (logits, aux) if t is not None]
+        nhwc = [torch.empty((B, H, W, Cs), dtype=torch.float32, device=dev) for _ in heads]
+        dn = [torch.empty_like(x) for x in nhwc]
+        for t, x in zip(heads, nhwc):
+            L.call("msau_nchw_to_nhwc", s, L.F32, t.contiguous().float().data_ptr(), x.data_ptr(), B, C, Cs, H, W)
+        two = aux is not None
+        L.call("msau_masked_cost", s, L.F32, kind, param, nhwc[0].data_ptr(), nhwc[1].data_ptr() if two else None, label.data_ptr(), None,
+               class_w.data_ptr() if class_w is not None else None, hist.data_ptr() if hist is not None else None, K, dn[0].data_ptr(),
+               dn[1].data_ptr() if two else None, loss3.data_ptr(), ws.data_ptr(), B, H, W, C, Cs)
+        grads = []
+        for d in dn:
+            g = torch.empty((B, C, H, W), dtype=torch.float32, device=dev)
+            L.call("msau_nhwc_to_nchw", s, L.F32, d.data_ptr(), g.data_ptr(), B, C, Cs, H, W)
+            grads.append(g)
+        ctx.save_for_backward(*grads)
+        ctx.has_aux = two
+        return loss3[0].clone()
+
+    @staticmethod
+    def backward(ctx, go):
+        saved = ctx.saved_tensors
+        return saved[0] * go, saved[1] * go if ctx.has_aux else None, None, None, None, None
+
+
 def _device_class_weights(holder, class_weights, n_class: int, device) -> Optional[torch.Tensor]:
     """the class weights on the device, uploaded again only when they change; `holder` (a TrainEngine, a MSAUWrapper) keeps the
     last upload in `_cw`"""
@@ -702,10 +745,38 @@ class MSAUWrapper(nn.Module):
     def load_weights(self, path):
         self.load_state_dict(torch.load(path, map_location=self._flat.device))
 
-    def loss(self, out_grid, out_grid_aux, label_mask):
+    def loss(self, out_grid, out_grid_aux, label_mask, cost=None, class_weights=None):
         """Masked CE of final + aux logits over pixels with label != 0 (model/model.py:446-459).
-        Accepts label_mask [B,H,W] (the reference: B = 1): per-sample masked mean, then mean over B."""
-        return _MaskedCEFunction.apply(out_grid, out_grid_aux, label_mask)
+        Accepts label_mask [B,H,W] (the reference: B = 1): per-sample masked mean, then mean over B.
+        `cost` (msau_amd.plan.unet_cost: {"cost_name": "focal", "gamma": 2.0}, {"cost_name": "dice", "smooth": 1.0}) and
+        `class_weights` (n_class values): the masked loss under that cost and with those weights, what
+        `TrainEngine(cost=..., class_weights=...)` trains.  Neither: the masked CE as ever."""
+        cost = unet_cost(cost)
+        if cost is None and class_weights is None:
+            return _MaskedCEFunction.apply(out_grid, out_grid_aux, label_mask)
+        cw = _device_class_weights(self, class_weights, self.n_class, out_grid.device)
+        kind, param = (cost.kind, cost.param) if cost is not None else (L.COST_CE, 0.0)
+        return _MaskedCostFunction.apply(out_grid, out_grid_aux, label_mask, kind, param, cw)
+
+    @torch.no_grad()
+    def eval_loss(self, inp, labels, sizes=None, *, cost=None, class_weights=None):
+        """Validation of the masked loss on the device: the forward-only plan fed with `inp` (NCHW, as `forward` takes it; `sizes`
+        for a ragged batch), then per document the loss of `loss` / `TrainEngine.step` under `cost` and `class_weights` and the
+        accuracy counts, in one call (msau_masked_cost_eval) on the logits both heads left in the plan.  -> (doc_loss fp32 [B, 2],
+        doc_counts int32 [B, 2, 2]) on the device, as `eval_unet` returns them: head 0 = final, 1 = auxiliary, counts = (labelled,
+        correct).  Nothing is exported and nothing waits for the device.  `cost=None`: the masked CE's per-document loss."""
+        cost = unet_cost(cost)
+        cw = _device_class_weights(self, class_weights, self.n_class, self._flat.device)
+        self._need_gpu(inp)
+        x = inp.contiguous().float()
+        B, _, H, W = x.shape
+        if sizes is not None:
+            sizes = self._check_sizes(x, sizes)
+        labels = labels.reshape(B, H, W).contiguous().long()
+        plan = self._plan_for(x, training=False, ragged=sizes is not None)
+        plan.set_extents(sizes)
+        plan.forward(self._flat, x, export=False)
+        return plan.eval_masked(labels, cw, cost=cost)
 
 
 # A stream capture is in "global" mode: a device synchronisation (or a graph's destruction) from ANY Python context while it runs --
@@ -825,11 +896,17 @@ class TrainEngine:
     `optimizer` "adam" | "rmsprop" | "momentum", `weight_decay`, `alpha` (RMSprop), `momentum` (SGD) and `max_norm=None` (or
     <= 0: no clipping) give the optimisers of the reference's `get_optimizer` (model/training/optimizer.py; `from_opt_kwargs`
     takes its options): torch.optim's arithmetic in one fused launch (msau_optim_step), two with clipping or under Adam.  The
-    default -- Adam, no weight decay -- is msau_clip_adam_step as ever."""
+    default -- Adam, no weight decay -- is msau_clip_adam_step as ever.
+
+    `cost` (msau_amd.plan.unet_cost: {"cost_name": "focal", "gamma": 2.0}, {"cost_name": "dice", "smooth": 1.0}) and `class_weights`
+    (n_class values) put the masked loss of `step` / `step_ids` / `step_nhwc` / `step_boxes` / `step_prefetched` under that cost and
+    those weights (`set_cost` changes them); the default is the masked CE, launch for launch."""
 
     def __init__(self, model: MSAUWrapper, lr: float = 1e-4, betas=(0.9, 0.999), eps: float = 1e-8,
                  max_norm: Optional[float] = 1.0, process_group=None, use_graph: bool = False, *, optimizer: str = "adam",
-                 weight_decay: float = 0.0, alpha: float = 0.99, momentum: float = 0.9):
+                 weight_decay: float = 0.0, alpha: float = 0.99, momentum: float = 0.9, cost=None, class_weights=None):
+        self._cost = unet_cost(cost)                     # (checked first thing: a bad cost is a ValueError before a GPU is needed)
+        self._cost_cw = None
         if optimizer not in OPTIMIZERS:
             raise ValueError(f"optimizer {optimizer!r}: TrainEngine knows {sorted(OPTIMIZERS)}")
         self.model, self.lr, self.betas, self.eps, self.max_norm = model, lr, betas, eps, max_norm
@@ -880,6 +957,7 @@ class TrainEngine:
         TrainEngine._tokens += 1
         self._token = TrainEngine._tokens
         weakref.finalize(self, TrainEngine._drop_graphs, weakref.ref(model), self._token)
+        self._cost_cw = _device_class_weights(self, class_weights, model.n_class, flat.device)
 
     _tokens = 0
 
@@ -910,6 +988,20 @@ class TrainEngine:
         if weight_decay is not None: self.weight_decay = float(weight_decay)
         if alpha is not None: self.alpha = float(alpha)
         if momentum is not None: self.momentum = float(momentum)
+        self._invalidate_graphs()
+
+    def set_cost(self, cost, class_weights=None):
+        """The cost and the class weights of the masked loss -- of `step` (eager and captured), `step_ids`, `step_nhwc`,
+        `step_boxes` and `step_prefetched`: `cost` as `msau_amd.plan.unet_cost` takes it (None or {"cost_name": "cross_entropy"}
+        without weights: the masked CE, launch for launch), `class_weights` a sequence or tensor of n_class values (uploaded here) or
+        None.  DESIGN.md 5d.  The cost's parameter and the workspace pointers are frozen into a captured sweep: the engine's graphs
+        are dropped.  `step_unet*` / `step_kv` keep their own per-call `cost`.  Configuration, not state: `state_dict` does not
+        hold it."""
+        cost = unet_cost(cost)
+        cw = None
+        if class_weights is not None:
+            cw = _device_class_weights(self, class_weights, self.model.n_class, self.model._flat.device)
+        self._cost, self._cost_cw = cost, cw
         self._invalidate_graphs()
 
     @classmethod
@@ -981,7 +1073,8 @@ class TrainEngine:
     def _fwd_bwd(self, plan: Plan, x, labels, ids=None, nhwc_ready=False, owner=None, nhwc_clean=False, loss_grads=None):
         plan.forward(self.model._flat, x, export=False, ids=ids, nhwc_ready=nhwc_ready, owner=owner, single_stream=self.use_graph,
                      nhwc_clean=nhwc_clean)
-        loss = plan.loss_grads(labels) if loss_grads is None else loss_grads(plan)     # (step_unet: another loss, same sweeps)
+        # the engine's cost and class weights (set_cost): the default issues today's launches.  (step_unet: another loss, same sweeps)
+        loss = plan.loss_grads(labels, self._cost, self._cost_cw) if loss_grads is None else loss_grads(plan)
         # MSAU_DP_BUCKETS=1: ONE all-reduce of the whole flat gradient after the backward instead of a bucket per stage
         # issued while the earlier stages' backward still runs (fewer launches and joins, no overlap)
         self._ar_native = False

@@ -1841,10 +1841,107 @@ class Plan:
                 if maskb:       # output produced through a ReLU and consumed by nothing else (op-level tests only)
                     act.grad.mul_(act.data > 0)
 
-    def loss_grads(self, labels: torch.Tensor) -> torch.Tensor:
-        """Masked CE (model/model.py:446-459, batch rule SURVEY 8e) fused with its gradient: writes d(logits), d(aux)
-        in place and returns the loss as a 1-element device tensor.  One launch for final + aux."""
+    def cost_hist_k(self, dice: bool) -> int:
+        """rows per document of the label histograms a cost takes (msau_label_hist's K).  Dice: K is also the slabs per document of
+        its reduction pass.  Two workgroups per compute unit were the best of three choices in ONE measurement: B = 16 on 320 x 256,
+        256 compute units (profiles/unet_cost.md: K = 16 / 32 / 64 -> 163 / 146 / 150 us in bf16).  Any other B or canvas size is
+        unmeasured, and what bounds that pass has not been profiled."""
+        return max(1, min(32, 512 // self.B)) if dice else max(1, min(16, 256 // self.B))
+
+    def masked_cost_launches(self, weighted: bool, cost=None) -> List[Launch]:
+        """the launches of `loss_grads(labels, cost, class_w)`, stated as `unet_launches` states those of `loss_grads_unet`: key and
+        algorithmic bytes.  The default (no cost or "cross_entropy", no weights) is what `_boundary_launches` states: the label
+        counts and the masked CE.  Anything else is msau_masked_cost: the label and both heads' logits read and both gradients
+        written; class weights or Dice put msau_label_hist in front (one launch: one label map), otherwise the call counts the
+        labelled pixels itself (the labels once more); Dice reads label and logits once more (the reduction behind its gradient
+        pass)."""
+        cost = unet_cost(cost)
+        esz = 4 if self.dtype == L.F32 else 2
+        HW, lg = self.H * self.W, self.logits
+        nl = 2 if self.aux is not None else 1
+        if cost is None and not weighted:
+            return [Launch(0, None, "msau_label_counts", self.B * HW * 8),
+                    Launch(0, None, "msau_masked_ce_multi" if lg.Cs <= 16 else "msau_masked_ce", self.B * HW * (8 + nl * 2 * lg.Cs * esz))]
+        dice = cost is not None and cost.kind == L.COST_DICE
+        out = [Launch(0, None, "msau_label_hist", self.B * HW * 8)] if weighted or dice else []
+        nbytes = self.B * HW * (8 + nl * 2 * lg.Cs * esz)
+        if dice:
+            nbytes += self.B * HW * (8 + nl * lg.Cs * esz)
+        elif not weighted:
+            nbytes += self.B * HW * 8
+        out.append(Launch(0, None, "msau_masked_cost", nbytes))
+        return out
+
+    def _loss_grads_cost(self, labels: torch.Tensor, cost: Optional[UnetCost], class_w: Optional[torch.Tensor]) -> torch.Tensor:
+        """`loss_grads` under a cost or class weights (msau_masked_cost)"""
+        lg, ax = self.logits, self.aux
+        assert ax is None or (ax.C, ax.Cs, ax.H, ax.W) == (lg.C, lg.Cs, lg.H, lg.W), "the auxiliary head must have the final head's shape"
+        assert (lg.H, lg.W) == (self.H, self.W)
+        kind, param = (cost.kind, cost.param) if cost is not None else (L.COST_CE, 0.0)
+        s = self._stream()
+        if getattr(self, "masked_loss3", None) is None:
+            self.masked_loss3 = torch.zeros((3,), dtype=torch.float32, device=self.device)
+            self.masked_hist = None
+        ext = self.extents.data_ptr() if self.ragged else None      # level 0: the documents' own (h, w)
+        dice = kind == L.COST_DICE
+        K, hist = self.cost_hist_k(dice), None
+        if class_w is not None:
+            assert class_w.dtype == torch.float32 and class_w.is_contiguous() and class_w.numel() == lg.C and class_w.device == lg.data.device
+        if class_w is not None or dice:
+            if self.masked_hist is None or self.masked_hist.shape[1] < K:      # (grows once when a plan's cost changes to Dice)
+                self.masked_hist = torch.zeros((self.B, K, lg.C), dtype=torch.int32, device=self.device)
+            hist = self.masked_hist.data_ptr()
+            L.call("msau_label_hist", s, labels.data_ptr(), ext, hist, self.B, self.H, self.W, lg.C, K)
+        if getattr(self, "masked_cost_ws", None) is None or self.masked_cost_ws[0] != dice:
+            n = int(L.load().msau_masked_cost_ws_floats(kind, self.B, self.H, self.W, lg.C))
+            self.masked_cost_ws = (dice, torch.zeros((n,), dtype=torch.float32, device=self.device))
+        L.call("msau_masked_cost", s, self.dtype, kind, param, lg.data.data_ptr(), _ptr(ax.data) if ax is not None else None,
+               labels.data_ptr(), ext, _ptr(class_w), hist, K, lg.grad.data_ptr(), _ptr(ax.grad) if ax is not None else None,
+               self.masked_loss3.data_ptr(), self.masked_cost_ws[1].data_ptr(), self.B, self.H, self.W, lg.C, lg.Cs)
+        return self.masked_loss3[:1]
+
+    def eval_masked(self, labels: torch.Tensor, class_w: Optional[torch.Tensor] = None, out=None, cost=None):
+        """The masked loss and the accuracy counts per document, forward only (msau_masked_cost_eval): the counterpart of
+        `eval_unet` for the loss of `loss_grads` -- after `forward(export=False)` on a forward-only plan, on the logits both heads
+        left in the plan, both against `labels` (int64 [B,H,W]; the kernel reads the extents itself).  `class_w` and `cost` as
+        `loss_grads` takes them; None: the masked CE's per-document loss.  -> (doc_loss fp32 [B, 2], doc_counts int32 [B, 2, 2]) on
+        the device, as `eval_unet` returns them; `out`: a pair of such tensors to write.  No gradient buffer is touched and nothing
+        waits for the device."""
+        cost = unet_cost(cost)
+        lg, ax = self.logits, self.aux
         assert labels.dtype == torch.int64 and labels.is_contiguous() and tuple(labels.shape) == (self.B, self.H, self.W)
+        assert ax is None or (ax.C, ax.Cs, ax.H, ax.W) == (lg.C, lg.Cs, lg.H, lg.W), "the auxiliary head must have the final head's shape"
+        assert (lg.H, lg.W) == (self.H, self.W)
+        if class_w is not None:
+            assert class_w.dtype == torch.float32 and class_w.is_contiguous() and class_w.numel() == lg.C and class_w.device == lg.data.device
+        if out is None:
+            out = (torch.empty((self.B, 2), dtype=torch.float32, device=self.device),
+                   torch.empty((self.B, 2, 2), dtype=torch.int32, device=self.device))
+        doc_loss, doc_counts = out
+        assert doc_loss.dtype == torch.float32 and doc_loss.is_contiguous() and tuple(doc_loss.shape) == (self.B, 2) \
+            and doc_counts.dtype == torch.int32 and doc_counts.is_contiguous() and tuple(doc_counts.shape) == (self.B, 2, 2) \
+            and doc_loss.device == doc_counts.device == lg.data.device, "out: (fp32 [B, 2], int32 [B, 2, 2]) on the model's device"
+        kind, param = (cost.kind, cost.param) if cost is not None else (L.COST_CE, 0.0)
+        dice = kind == L.COST_DICE
+        if getattr(self, "masked_eval_ws", None) is None or self.masked_eval_ws[0] != dice:      # for the largest K, as eval_unet's
+            n = int(L.load().msau_masked_cost_eval_ws_bytes(kind, self.B, 256, lg.C))
+            self.masked_eval_ws = (dice, torch.zeros((n,), dtype=torch.uint8, device=self.device))
+        L.call("msau_masked_cost_eval", self._stream(), self.dtype, kind, param, lg.data.data_ptr(), _ptr(ax.data) if ax is not None else None,
+               labels.data_ptr(), self.extents.data_ptr() if self.ragged else None, _ptr(class_w), self.unet_eval_k(), doc_loss.data_ptr(),
+               doc_counts.data_ptr(), self.masked_eval_ws[1].data_ptr(), self.B, self.H, self.W, lg.C, lg.Cs)
+        return doc_loss, doc_counts
+
+    def loss_grads(self, labels: torch.Tensor, cost=None, class_w: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """Masked CE (model/model.py:446-459, batch rule SURVEY 8e) fused with its gradient: writes d(logits), d(aux)
+        in place and returns the loss as a 1-element device tensor.  One launch for final + aux.
+        `cost` (`unet_cost`) and `class_w` (fp32 [n_class] on the device): the masked loss under the focal or the soft Dice cost and
+        with class weights (msau_masked_cost, which reads the extents of a ragged plan itself: whatever the label canvas
+        holds outside the documents is ignored).  The three values (total, final, auxiliary) stay readable as `masked_loss3`, the
+        total is returned.  With neither -- also with "cross_entropy" by name -- the launches are those below, unchanged."""
+        assert labels.dtype == torch.int64 and labels.is_contiguous() and tuple(labels.shape) == (self.B, self.H, self.W)
+        cost = unet_cost(cost)
+        if cost is not None or class_w is not None:
+            return self._loss_grads_cost(labels, cost, class_w)
         s = self._stream()
         HW = self.H * self.W
         if self.ragged:                                  # the label canvas: 0 (= not counted) outside the documents
@@ -1912,11 +2009,7 @@ class Plan:
         if getattr(self, "unet_loss_buf", None) is None:
             self.unet_loss_buf = torch.zeros((3,), dtype=torch.float32, device=self.device)
             self.unet_ws = torch.zeros((int(L.load().msau_unet_ce_ws_floats(self.B * self.H * self.W)),), dtype=torch.float32, device=self.device)
-            self.unet_hist_k = max(1, min(16, 256 // self.B))
-            # Dice: K is also the slabs per document of its reduction pass.  Two workgroups per compute unit were the best of three
-            # choices in ONE measurement: B = 16 on 320 x 256, 256 compute units (profiles/unet_cost.md: K = 16 / 32 / 64 -> 163 /
-            # 146 / 150 us in bf16).  Any other B or canvas size is unmeasured, and what bounds that pass has not been profiled.
-            self.unet_dice_k = max(1, min(32, 512 // self.B))
+            self.unet_hist_k, self.unet_dice_k = self.cost_hist_k(False), self.cost_hist_k(True)
             self.unet_hist = None
         ext = self.extents.data_ptr() if self.ragged else None      # level 0: the documents' own (h, w)
         dice = cost is not None and cost.kind == L.COST_DICE

@@ -81,6 +81,12 @@ def make_model(args):
     return MSAUWrapper(args.channels, 5, kw).to(torch.device("cuda", 0))
 
 
+def _cost(args):
+    """--cost NAME as TrainEngine takes it (the cost's default parameter); cross_entropy: None, the default path"""
+    name = getattr(args, "cost", "cross_entropy")
+    return None if name == "cross_entropy" else {"cost_name": name}
+
+
 def run(args, use_graph):
     import torch
     from msau_amd import TrainEngine
@@ -88,7 +94,7 @@ def run(args, use_graph):
     m = make_model(args)
     shapes = doc_shapes(args.docs)
     m.max_cached_plans = 2 * len(shapes) + 2
-    eng = TrainEngine(m, lr=1e-4, use_graph=use_graph)
+    eng = TrainEngine(m, lr=1e-4, use_graph=use_graph, cost=_cost(args))
     docs = [(d["mask"].to(dev), d["label"].to(dev)) for d in make_docs(args)]
     torch.cuda.synchronize()
     res = {}
@@ -136,7 +142,7 @@ def run_ragged(args, B, use_graph=False):
         steps.append((x.to(dev), lab.to(dev), sizes))
     canvases = sorted({(int(x.shape[0]), int(x.shape[2]), int(x.shape[3])) for x, _, _ in steps})
     m.max_cached_plans = 2 * len(canvases) + 2
-    eng = TrainEngine(m, lr=1e-4, use_graph=use_graph)
+    eng = TrainEngine(m, lr=1e-4, use_graph=use_graph, cost=_cost(args))
     torch.cuda.synchronize()
     res = {}
     t0 = time.perf_counter()
@@ -397,6 +403,8 @@ def main():
     ap.add_argument("--boxes", action="store_true", help="with --ragged: ragged batches from box lists against the host-painted canvas (only this runs)")
     ap.add_argument("--repeats", type=int, default=5, help="--boxes / --entities: interleaved repeats (at least 5)")
     ap.add_argument("--entities", action="store_true", help="with --eval: entity-level predictions, device route against host route (only this runs)")
+    ap.add_argument("--cost", choices=["cross_entropy", "focal", "dice"], default="cross_entropy",
+                    help="the cost of the masked loss in the batch-1 and the ragged training loops (TrainEngine(cost=...))")
     args = ap.parse_args()
     if args.entities:
         if not args.eval:

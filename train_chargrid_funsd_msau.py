@@ -13,6 +13,10 @@ the documents' losses); --eval-batch-size N evaluates in ragged batches.  The ev
 --entity-level adds the entity-level figures: every annotated entity box gets the class most of its pixels predict
 (MSAUWrapper.box_predictions, counted on the device as well) and a second accuracy / report is printed over entities.
 
+--cost {cross_entropy,focal,dice} (--gamma, --smooth) and --class-weights w0,w1,... train the masked loss under the focal or the
+soft Dice cost and with class weights; the epoch print then carries the validation loss under the same cost
+(MSAUWrapper.eval_loss, on the device).  The defaults are the reference's masked cross entropy.
+
 Two step implementations, selected with --loop:
   engine     (default) msau_amd.TrainEngine: fused masked-CE + clip + Adam, no per-step host sync
   reference  model(V) -> model.loss -> loss.backward() -> clip_grad_norm_ -> optimizer.step(), line for line
@@ -109,10 +113,36 @@ def evaluate(dataset, model, args, name="Validation", testing=False, max_num_exa
     return result
 
 
+def cost_of(args):
+    """-> (cost, class_weights) as TrainEngine / MSAUWrapper.loss / eval_loss take them, from --cost / --gamma / --smooth / --class-weights"""
+    name = getattr(args, "cost", "cross_entropy")
+    cost = {"cost_name": "focal", "gamma": args.gamma} if name == "focal" else {"cost_name": "dice", "smooth": args.smooth} if name == "dice" else None
+    return cost, getattr(args, "class_weights", None)
+
+
+def validation_loss(dataset, model, args, batch_size=None):
+    """the mean over the documents of the loss that is trained (final + auxiliary head, under --cost and --class-weights), forward
+    only and summed on the device (MSAUWrapper.eval_loss): the host reads one number"""
+    model.eval()
+    device = model.flat_parameters.device
+    cost, cw = cost_of(args)
+    bs = batch_size if batch_size is not None else getattr(args, "eval_batch_size", 1)
+    total = torch.zeros((), device=device)
+    if bs == 1:
+        for data in dataset:
+            total += model.eval_loss(data["mask"].float().to(device), data["label"].long().to(device), cost=cost, class_weights=cw)[0].sum()
+    else:
+        for idx in ragged.batches(dataset, bs):
+            x, lab, sizes = ragged.pack([dataset[i] for i in idx])
+            total += model.eval_loss(x.to(device), lab.to(device), sizes, cost=cost, class_weights=cw)[0].sum()
+    return float(total) / max(len(dataset), 1)
+
+
 def train(dataset, model, args, val_dataset=None, test_dataset=None, labels_map=None):
     device = model.flat_parameters.device
+    cost, class_weights = cost_of(args)
     if args.loop == "engine":
-        engine = TrainEngine(model, lr=args.lr, max_norm=float(args.clip))
+        engine = TrainEngine(model, lr=args.lr, max_norm=float(args.clip), cost=cost, class_weights=class_weights)
         optimizer = None
     else:
         optimizer = torch.optim.Adam(filter(lambda p: p.requires_grad, model.parameters()), lr=args.lr)
@@ -140,7 +170,7 @@ def train(dataset, model, args, val_dataset=None, test_dataset=None, labels_map=
             else:
                 model.zero_grad()
                 _, ypred, ypred_aux = model(V, sizes)
-                loss = model.loss(ypred, ypred_aux, label)
+                loss = model.loss(ypred, ypred_aux, label, cost=cost, class_weights=class_weights)
                 loss.backward()
                 torch.nn.utils.clip_grad_norm_(model.parameters(), float(args.clip))
                 optimizer.step()
@@ -153,6 +183,7 @@ def train(dataset, model, args, val_dataset=None, test_dataset=None, labels_map=
         evaluate(dataset, model, args, name="Train", max_num_examples=100)
         if val_dataset:
             vr = evaluate(val_dataset, model, args, name="Validation")
+            print("Validation  loss:", validation_loss(val_dataset, model, args))
             val_accs.append(vr["acc"])
             if vr["acc"] > best_val["acc"] - 1e-7:
                 best_val = {"acc": vr["acc"], "epoch": epoch, "loss": avg_loss}
@@ -185,9 +216,19 @@ def parse_args(argv=None):
     ap.add_argument("--eval-batch-size", type=int, default=1, help="documents per evaluation forward (ragged batches when > 1)")
     ap.add_argument("--entity-level", action="store_true",
                     help="also report accuracy / precision / recall over the annotated entity boxes (each box votes with its pixels)")
+    ap.add_argument("--cost", choices=["cross_entropy", "focal", "dice"], default="cross_entropy",
+                    help="the masked loss's cost: the reference's cross entropy, the focal loss (--gamma) or the soft Dice loss (--smooth)")
+    ap.add_argument("--gamma", type=float, default=2.0, help="focal: the exponent of (1 - p_t), >= 0")
+    ap.add_argument("--smooth", type=float, default=1.0, help="dice: the smoothing term, > 0")
+    ap.add_argument("--class-weights", default=None, help="w0,w1,...: one weight per class (class 0 = unlabelled first)")
     args = ap.parse_args(argv)
     if args.batch_size < 1 or args.eval_batch_size < 1:
         ap.error("--batch-size and --eval-batch-size must be >= 1")
+    if args.class_weights is not None:
+        try:
+            args.class_weights = [float(w) for w in args.class_weights.split(",")]
+        except ValueError:
+            ap.error("--class-weights: numbers separated by commas")
     args.bmname, args.hidden_dim, args.dataset, args.method = None, 500, "invoice", "GCN"
     return args
 
