@@ -1,8 +1,9 @@
 // Everything that reads logits against labels or turns logits into probabilities: label counts and histograms, the masked cross
 // entropy and its two-head form, the weighted CE, UNetLoss for training and per-document evaluation, the confusion counts and the
-// two softmax heads.  A pixel's log-sum-exp, the gradient store and the workgroup sum are each stated once below and used by every
-// kernel of the family: that, not a comment, is what makes the register and the cache forms (and the training and the evaluation
-// kernels) agree bit for bit.  Accumulation in fp32, every summation order fixed.
+// two softmax heads.  Every loss is one kernel; how it holds a pixel's logits -- in registers or re-read from the cache -- is the type
+// Pixel<T, CS8> below, the only place where the two forms differ.  The CE and the Dice gradient, the label / extent / weight rules and
+// the workgroup sum are each stated once and used by every kernel of the family: that, not a comment, is what makes the register and
+// the cache form (and the training and the evaluation kernels) agree bit for bit.  Accumulation in fp32, every summation order fixed.
 #include "msau_common.h"
 #include "loss_cost.h"
 
@@ -11,68 +12,136 @@ namespace {
 // =============================================================================================
 // the family's shared statements
 // =============================================================================================
-// A pixel's softmax statistics.  Register form: the pixel's Cs = 8 * CS8 stored values -> x[] (every index a compile-time
-// constant: the array stays in registers), xl = x[lab] (0 when lab is not a channel), returns the log-sum-exp over the C real
-// classes: max, then the __expf sum in channel order (the padded channels add + 0.f onto a positive sum), mx + __logf(se).
+// strictly greater: the first maximum wins; a NaN counts as the maximum, as in torch.argmax
+__device__ __forceinline__ void first_max(float v, int c, float& bv, int& best) {
+    if (v > bv || (v != v && bv == bv)) { bv = v; best = c; }
+}
+
+// How a pixel's logits are held is a type, Pixel<T, CS8>; every kernel below is written once against it.  The type has no members:
+// what a thread holds of a pixel is a `Pixel::Held h` of the kernel's own, and the operations are static --
+//   load(h, px, Cs, C, lab, xl)   the pixel's Cs stored values at px -> the log-sum-exp over the C real classes: max, then the __expf
+//                              sum in channel order, mx + __logf(se); the register form leaves x[lab] in xl (0 when lab is no channel)
+//   label_logit(h, lab, active, xl)   the logit at the label: the register form hands back load's xl; the cache form READS l[lab]
+//                              wherever `active` is set (0 elsewhere), so lab must be a channel there.  A separate operation so that a
+//                              kernel can state `active` after the load, where it is used: computed before it, the large register
+//                              instances of unet_ce_kernel came out with other code
+//   channels(C), logit(h, c)   a visit of the real channels in channel order is `for (c = 0; c < channels(C); ++c) if (c < C) ... logit(h, c)`
+//                              under `#pragma unroll kUnroll`: the register form visits all Cs with every index a constant, the cache form
+//                              loops over C
+//   prob(h, c, lse)            the probability of real channel c, __expf(logit - lse)
+//   store(h, dst, C, active, g)   all Cs stored channels of a gradient: g(c) in the real channels of an active pixel, exact zeros in the
+//                              padded channels and everywhere on an inactive pixel
+//   store_dot(h, dst, lse, C, active, a, g)   the same with s = sum_c a_c * prob(c) taken first, by fmaf in channel order: g(p_c, a_c, s);
+//                              a_c = a(c, real), which reads memory only where `real` (a real channel of an active pixel) and is 0 elsewhere
+// Why it is written this way and not as an object with a callback per visit (profiles/loss_forms.md): the register form's Held is a
+// plain array and the visiting loop stands in the kernel, which is the shape the compiler saw before there was a type; an array
+// inside a struct, a member function around load, or the first maximum's running pair local to a callee each changed the code of
+// large instances.
+// Register form (CS8 > 0): the Cs = 8 * CS8 stored values sit in x[], every index a compile-time constant so that the array stays in
+// registers; 16-byte loads and stores; the padded channels add + 0.f onto a positive sum (and fmaf(0, 0, s) onto s); store_dot turns
+// x[] into the probabilities once and keeps the a(c).
 template <typename T, int CS8>
-__device__ __forceinline__ float pixel_lse(const T* __restrict__ px, int C, int lab, float (&x)[CS8 * 8], float& xl) {
-    constexpr int Cs = CS8 * 8;
-    float mx = -INFINITY;
-    xl = 0.f;
+struct Pixel {
+    static constexpr int kCs = CS8 * 8;
+    static constexpr int kUnroll = kCs;
+    static constexpr int kDiceChunk = kCs;                           // the Dice sums take every class in one sweep of the slab
+    typedef float Held[kCs];
+    static __device__ __forceinline__ int dice_sweeps(int) { return 1; }
+    static __device__ __forceinline__ float load(Held& x, const T* __restrict__ px, int, int C, int lab, float& xl) {
+        float mx = -INFINITY;
+        xl = 0.f;
 #pragma unroll
-    for (int c0 = 0; c0 < Cs; c0 += 8) {
-        typename Vec8<T>::type v = load8<T>(px + c0);
+        for (int c0 = 0; c0 < kCs; c0 += 8) {
+            typename Vec8<T>::type v = load8<T>(px + c0);
 #pragma unroll
-        for (int jj = 0; jj < 8; ++jj) {
-            x[c0 + jj] = (float)v[jj];
-            if (c0 + jj < C) mx = fmaxf(mx, x[c0 + jj]);
-            xl = (c0 + jj == lab) ? x[c0 + jj] : xl;
+            for (int jj = 0; jj < 8; ++jj) {
+                x[c0 + jj] = (float)v[jj];
+                if (c0 + jj < C) mx = fmaxf(mx, x[c0 + jj]);
+                xl = (c0 + jj == lab) ? x[c0 + jj] : xl;
+            }
+        }
+        float se = 0.f;
+#pragma unroll
+        for (int c = 0; c < kCs; ++c) se += c < C ? __expf(x[c] - mx) : 0.f;
+        return mx + __logf(se);
+    }
+    static __device__ __forceinline__ float label_logit(const Held&, int, bool, float xl) { return xl; }
+    static __device__ __forceinline__ int channels(int) { return kCs; }
+    static __device__ __forceinline__ float logit(const Held& x, int c) { return x[c]; }
+    static __device__ __forceinline__ float prob(const Held& x, int c, float lse) { return __expf(x[c] - lse); }
+    template <typename G>
+    static __device__ __forceinline__ void store(const Held&, T* __restrict__ dst, int C, bool active, G g) {
+#pragma unroll
+        for (int c0 = 0; c0 < kCs; c0 += 8) {
+            typename Vec8<T>::type o;
+#pragma unroll
+            for (int jj = 0; jj < 8; ++jj) {
+                float v = 0.f;
+                if (active && c0 + jj < C) v = g(c0 + jj);
+                o[jj] = (T)v;
+            }
+            store8<T>(dst + c0, o);
         }
     }
-    float se = 0.f;
+    template <typename A, typename G>
+    static __device__ __forceinline__ void store_dot(Held& x, T* __restrict__ dst, float lse, int C, bool active, A a, G g) {
+        float ac[kCs];
+        float s = 0.f;
 #pragma unroll
-    for (int c = 0; c < Cs; ++c) se += c < C ? __expf(x[c] - mx) : 0.f;
-    return mx + __logf(se);
-}
+        for (int c = 0; c < kCs; ++c) {
+            const bool real = active && c < C;
+            ac[c] = a(c, real);
+            x[c] = real ? prob(x, c, lse) : 0.f;
+            s = fmaf(ac[c], x[c], s);
+        }
+        store(x, dst, C, active, [&](int c) { return g(x[c], ac[c], s); });
+    }
+};
 
-// Cache-read form (any class count): the pixel's C values are read twice, nothing is kept.
+// Cache form (CS8 = 0; any class count): nothing is kept, the pixel's logits are read again through l[c] wherever they are used.
 template <typename T>
-__device__ __forceinline__ float pixel_lse_wide(const T* __restrict__ l, int C) {
-    float mx = -INFINITY;
-    for (int c = 0; c < C; ++c) mx = fmaxf(mx, (float)l[c]);
-    float se = 0.f;
-    for (int c = 0; c < C; ++c) se += __expf((float)l[c] - mx);
-    return mx + __logf(se);
-}
+struct Pixel<T, 0> {
+    static constexpr int kCs = 0;                                    // the stored channel count is the kernel's run-time Cs
+    static constexpr int kUnroll = 1;
+    static constexpr int kDiceChunk = 32;                            // classes a thread sums per sweep of its slab
+    struct Held { const T* __restrict__ l; int Cs; };
+    static __device__ __forceinline__ int dice_sweeps(int C) { return (C + kDiceChunk - 1) / kDiceChunk; }
+    static __device__ __forceinline__ float load(Held& h, const T* __restrict__ l, int Cs, int C, int, float& xl) {
+        h.l = l;
+        h.Cs = Cs;
+        float mx = -INFINITY;
+        for (int c = 0; c < C; ++c) mx = fmaxf(mx, (float)l[c]);
+        float se = 0.f;
+        for (int c = 0; c < C; ++c) se += __expf((float)l[c] - mx);
+        xl = 0.f;
+        return mx + __logf(se);
+    }
+    static __device__ __forceinline__ float label_logit(const Held& h, int lab, bool active, float) { return active ? (float)h.l[lab] : 0.f; }
+    static __device__ __forceinline__ int channels(int C) { return C; }
+    static __device__ __forceinline__ float logit(const Held& h, int c) { return (float)h.l[c]; }
+    static __device__ __forceinline__ float prob(const Held& h, int c, float lse) { return __expf((float)h.l[c] - lse); }
+    template <typename G>
+    static __device__ __forceinline__ void store(const Held& h, T* __restrict__ dst, int C, bool active, G g) {
+        for (int c = 0; c < h.Cs; ++c) {
+            float v = 0.f;
+            if (active && c < C) v = g(c);
+            dst[c] = (T)v;
+        }
+    }
+    template <typename A, typename G>
+    static __device__ __forceinline__ void store_dot(Held& h, T* __restrict__ dst, float lse, int C, bool active, A a, G g) {
+        float s = 0.f;
+        if (active)
+            for (int c = 0; c < C; ++c) s = fmaf(a(c, true), prob(h, c, lse), s);
+        store(h, dst, C, active, [&](int c) { return g(prob(h, c, lse), a(c, true), s); });
+    }
+};
 
-// The pixel's gradient g[c] = w * (softmax[c] - onehot[c]) over the real classes of an active pixel, zero in the padded channels and
-// everywhere on an inactive one; all Cs stored channels are written.  Register form: x[] as pixel_lse left it.
+// The pixel's CE gradient g[c] = w * (softmax[c] - onehot[c]).
 template <typename T, int CS8>
-__device__ __forceinline__ void ce_grad_store(T* __restrict__ dst, const float (&x)[CS8 * 8], float lse, float w, int lab, int C,
+__device__ __forceinline__ void ce_grad_store(T* __restrict__ dst, const typename Pixel<T, CS8>::Held& h, float lse, float w, int lab, int C,
                                               bool active) {
-#pragma unroll
-    for (int c0 = 0; c0 < CS8 * 8; c0 += 8) {
-        typename Vec8<T>::type o;
-#pragma unroll
-        for (int jj = 0; jj < 8; ++jj) {
-            const int c = c0 + jj;
-            float g = 0.f;
-            if (active && c < C) g = w * (__expf(x[c] - lse) - (c == lab ? 1.f : 0.f));
-            o[jj] = (T)g;
-        }
-        store8<T>(dst + c0, o);
-    }
-}
-
-// Cache-read form: the pixel's logits are read once more from l.
-template <typename T>
-__device__ __forceinline__ void ce_grad_store_wide(T* __restrict__ dst, const T* __restrict__ l, float lse, float w, int lab, int C,
-                                                   int Cs, bool active) {
-    for (int c = 0; c < Cs; ++c) {
-        float g = 0.f;
-        if (active && c < C) g = w * (__expf((float)l[c] - lse) - (c == lab ? 1.f : 0.f));
-        dst[c] = (T)g;
-    }
+    Pixel<T, CS8>::store(h, dst, C, active, [&](int c) { return w * (Pixel<T, CS8>::prob(h, c, lse) - (c == lab ? 1.f : 0.f)); });
 }
 
 // The focal loss as two factors on the CE weight w of an active pixel (msau_focal_factor, loss_cost.h): the loss term is
@@ -112,11 +181,6 @@ __device__ __forceinline__ V block_sum(V v, V* red) {
 }
 
 constexpr int kWaves = kThreads / 64;                                // of the 256-thread CE kernels
-
-// strictly greater: the first maximum wins; a NaN counts as the maximum, as in torch.argmax
-__device__ __forceinline__ void first_max(float v, int c, float& bv, int& best) {
-    if (v > bv || (v != v && bv == bv)) { bv = v; best = c; }
-}
 
 // =============================================================================================
 // masked cross entropy (model/model.py:446-459), batch rule of SURVEY 8(e)
@@ -187,15 +251,17 @@ __device__ __forceinline__ void ce_block_sums(float local, float local_w, bool w
     }
 }
 
-// One head, the logits of a pixel in registers (Cs = 8 * CS8 <= 16).  ALL: every label in [0, C) counts and the weight is `scale`
-// (plain softmax CE); otherwise the labels in [1, C) count with scale / counts[b].
+// One head; the host takes the register form up to 16 stored channels and the cache form beyond (e.g. the 17-class key-value head).
+// ALL: every label in [0, C) counts and the weight is `scale` (plain softmax CE); otherwise the labels in [1, C) count with
+// scale / counts[b].
 // cw (ALL only): per-class weights of torch.nn.CrossEntropyLoss(weight) (model/training/cost.py:24-31): every pixel's term and
 // gradient are multiplied by cw[label]; the sum of those weights -- the loss's denominator -- goes to the second half of partials
 template <typename T, bool ALL, int CS8>
 __global__ void masked_ce_kernel(const T* __restrict__ logits, const int64_t* __restrict__ labels,
                                  const int32_t* __restrict__ counts, T* __restrict__ dlogits, float* __restrict__ partials,
-                                 int B, int64_t hw, int C, float scale, const float* __restrict__ cw) {
-    constexpr int Cs = CS8 * 8;
+                                 int B, int64_t hw, int C, float scale, const float* __restrict__ cw, int Cs) {
+    using Px = Pixel<T, CS8>;
+    const int cs = Px::kCs ? Px::kCs : Cs;                             // a pixel's stride: stated as a constant in the register form
     __shared__ float red[kWaves];
     float local = 0.f, local_w = 0.f;
     const int64_t total = (int64_t)B * hw;
@@ -205,34 +271,12 @@ __global__ void masked_ce_kernel(const T* __restrict__ logits, const int64_t* __
         const bool on = ALL ? (lab >= 0 && lab < C) : (lab > 0 && lab < C);
         float w = on ? (ALL ? scale : scale / (float)max(counts[b], 1)) : 0.f;
         if (ALL && cw && on) { const float c = cw[(int)lab]; w *= c; local_w += c; }
-        float x[Cs];
+        typename Px::Held h;
         float xl;
-        const float lse = pixel_lse<T, CS8>(logits + p * Cs, C, (int)lab, x, xl);
+        const float lse = Px::load(h, logits + p * cs, Cs, C, (int)lab, xl);
+        xl = Px::label_logit(h, (int)lab, on, xl);
         if (on) local += w * (lse - xl);
-        ce_grad_store<T, CS8>(dlogits + p * Cs, x, lse, w, (int)lab, C, on);
-    }
-    ce_block_sums(local, local_w, ALL && cw, red, partials);
-}
-
-// Any class count (Cs > 16: e.g. the 17-class key-value head): the logits of a pixel are read three times from the
-// cache instead of being held in registers.
-template <typename T, bool ALL>
-__global__ void masked_ce_wide_kernel(const T* __restrict__ logits, const int64_t* __restrict__ labels,
-                                      const int32_t* __restrict__ counts, T* __restrict__ dlogits, float* __restrict__ partials,
-                                      int B, int64_t hw, int C, int Cs, float scale, const float* __restrict__ cw) {
-    __shared__ float red[kWaves];
-    float local = 0.f, local_w = 0.f;
-    const int64_t total = (int64_t)B * hw;
-    for (int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; p < total; p += (int64_t)gridDim.x * blockDim.x) {
-        const int b = (int)(p / hw);
-        const int64_t lab = labels[p];
-        const bool on = ALL ? (lab >= 0 && lab < C) : (lab > 0 && lab < C);
-        float w = on ? (ALL ? scale : scale / (float)max(counts[b], 1)) : 0.f;
-        if (ALL && cw && on) { const float c = cw[(int)lab]; w *= c; local_w += c; }
-        const T* l = logits + p * Cs;
-        const float lse = pixel_lse_wide(l, C);
-        if (on) local += w * (lse - (float)l[lab]);
-        ce_grad_store_wide(dlogits + p * Cs, l, lse, w, (int)lab, C, Cs, on);
+        ce_grad_store<T, CS8>(dlogits + p * cs, h, lse, w, (int)lab, C, on);
     }
     ce_block_sums(local, local_w, ALL && cw, red, partials);
 }
@@ -246,6 +290,7 @@ template <typename T, int NL, int CS8>
 __global__ void masked_ce_multi_kernel(const T* __restrict__ l0, const T* __restrict__ l1, const int64_t* __restrict__ labels,
                                        const int32_t* __restrict__ counts, T* __restrict__ d0, T* __restrict__ d1,
                                        float* __restrict__ ws, float* __restrict__ loss, int B, int hw, int C, float scale, int K) {
+    using Px = Pixel<T, CS8>;
     constexpr int Cs = CS8 * 8;
     __shared__ float red[kWaves];
     __shared__ int cnt[kCeMaxB];                                       // per-sample counts: the K partial counts added up (B <= kCeMaxB)
@@ -267,11 +312,11 @@ __global__ void masked_ce_multi_kernel(const T* __restrict__ l0, const T* __rest
         const float w = on ? scale / (float)max(in_lds ? cnt[b] : counts[b], 1) : 0.f;
 #pragma unroll
         for (int t = 0; t < NL; ++t) {
-            float x[Cs];
+            typename Px::Held h;
             float xl;
-            const float lse = pixel_lse<T, CS8>((t ? l1 : l0) + p * Cs, C, lab, x, xl);
+            const float lse = Px::load(h, (t ? l1 : l0) + p * Cs, Cs, C, lab, xl);
             if (on) local += w * (lse - xl);
-            ce_grad_store<T, CS8>((t ? d1 : d0) + p * Cs, x, lse, w, lab, C, on);
+            ce_grad_store<T, CS8>((t ? d1 : d0) + p * Cs, h, lse, w, lab, C, on);
         }
     }
     const float s = block_sum<kWaves, false>(local, red);
@@ -356,7 +401,7 @@ __device__ __forceinline__ void unet_ce_block_sums(float l0, float l1, float* re
     }
 }
 
-// Both heads in one launch, the logits of a pixel in registers (Cs = 8 * CS8 <= 32: every index is a compile-time constant).
+// Both heads in one launch; the host takes the register form up to 32 stored channels and the cache form beyond.
 // A thread's weight of head t at pixel p of document b: hw_t * cw[lab] / (B * D_b(t)) inside the extent with lab in [0, C), else 0;
 // the loss partials carry the weight WITHOUT hw_t (loss3[1], loss3[2] are the heads' own losses).
 // FOCAL: the focal loss with parameter gamma (focal_weights); otherwise gamma is not read.
@@ -366,12 +411,15 @@ template <typename T, int NL, int CS8, bool FOCAL, bool MASKED>
 __global__ void unet_ce_kernel(const T* __restrict__ l0, const T* __restrict__ l1, const int64_t* __restrict__ lab0,
                                const int64_t* __restrict__ lab1, const int32_t* __restrict__ extent, const float* __restrict__ cw,
                                const int32_t* __restrict__ hist, int K, T* __restrict__ d0, T* __restrict__ d1,
-                               float* __restrict__ ws, int B, int H, int W, int C, float gamma) {
-    constexpr int Cs = CS8 * 8;
+                               float* __restrict__ ws, int B, int H, int W, int C, float gamma, int Cs) {
+    using Px = Pixel<T, CS8>;
+    const int cs = Px::kCs ? Px::kCs : Cs;                             // a pixel's stride: stated as a constant in the register form
     __shared__ float red[2 * kWaves];
     __shared__ float inv[2 * kCeMaxB];
-    unet_ce_denominators<MASKED>(inv, extent, cw, hist, MASKED ? 1 : NL, B, H, W, C, K);
-    const float hwt = (NL == 2 && !MASKED) ? 0.5f : 1.f;
+    constexpr int kHeadUnroll = NL ? NL : 1;                           // NL = 0 (the cache form): the head count is read at run time, the loop stays a loop
+    const int nl = NL ? NL : (l1 ? 2 : 1);
+    unet_ce_denominators<MASKED>(inv, extent, cw, hist, MASKED ? 1 : nl, B, H, W, C, K);
+    const float hwt = (nl == 2 && !MASKED) ? 0.5f : 1.f;
     const int hw = H * W;
     float local[2] = {0.f, 0.f};
     const int64_t total = (int64_t)B * hw;
@@ -382,63 +430,23 @@ __global__ void unet_ce_kernel(const T* __restrict__ l0, const T* __restrict__ l
         bool on = false;
         int lab = -1;
         float w = 0.f;
-#pragma unroll
-        for (int t = 0; t < NL; ++t) {
+#pragma unroll kHeadUnroll
+        for (int t = 0; t < nl; ++t) {
             if (!MASKED || t == 0) {
                 const int64_t lab64 = (t ? lab1 : lab0)[p];
                 on = in && lab64 >= (MASKED ? 1 : 0) && lab64 < C;
                 lab = on ? (int)lab64 : -1;
                 w = on ? inv[t * B + b] * (cw ? cw[lab] : 1.f) : 0.f;
             }
-            float x[Cs];
+            typename Px::Held h;
             float xl;
-            const float lse = pixel_lse<T, CS8>((t ? l1 : l0) + p * Cs, C, lab, x, xl);
+            const float lse = Px::load(h, (t ? l1 : l0) + p * cs, Cs, C, lab, xl);
             const bool act = on && w != 0.f;
+            xl = Px::label_logit(h, lab, act, xl);
             float wl = w, wg = w;
             if (FOCAL && act) focal_weights(w, lse, xl, gamma, wl, wg);
             if (act) local[t] += wl * (lse - xl);
-            ce_grad_store<T, CS8>((t ? d1 : d0) + p * Cs, x, lse, hwt * wg, lab, C, act);
-        }
-    }
-    unet_ce_block_sums(local[0], local[1], red, ws);
-}
-
-// Any class count (Cs > 32): the logits of a pixel are read three times from the cache.
-template <typename T, bool FOCAL, bool MASKED>
-__global__ void unet_ce_wide_kernel(const T* __restrict__ l0, const T* __restrict__ l1, const int64_t* __restrict__ lab0,
-                                    const int64_t* __restrict__ lab1, const int32_t* __restrict__ extent, const float* __restrict__ cw,
-                                    const int32_t* __restrict__ hist, int K, T* __restrict__ d0, T* __restrict__ d1,
-                                    float* __restrict__ ws, int B, int H, int W, int C, int Cs, float gamma) {
-    __shared__ float red[2 * kWaves];
-    __shared__ float inv[2 * kCeMaxB];
-    const int NL = l1 ? 2 : 1;
-    unet_ce_denominators<MASKED>(inv, extent, cw, hist, MASKED ? 1 : NL, B, H, W, C, K);
-    const float hwt = (NL == 2 && !MASKED) ? 0.5f : 1.f;
-    const int hw = H * W;
-    float local[2] = {0.f, 0.f};
-    const int64_t total = (int64_t)B * hw;
-    for (int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; p < total; p += (int64_t)gridDim.x * blockDim.x) {
-        const int b = (int)((unsigned)p / (unsigned)hw);
-        const int j = (int)p - b * hw;
-        const bool in = extent ? pos_in_extent(j, W, extent[2 * b], extent[2 * b + 1]) : true;
-        bool on = false;
-        int lab = -1;
-        float w = 0.f;
-        for (int t = 0; t < NL; ++t) {
-            const T* l = (t ? l1 : l0) + p * Cs;
-            if (!MASKED || t == 0) {
-                const int64_t lab64 = (t ? lab1 : lab0)[p];
-                on = in && lab64 >= (MASKED ? 1 : 0) && lab64 < C;
-                lab = on ? (int)lab64 : -1;
-                w = on ? inv[t * B + b] * (cw ? cw[lab] : 1.f) : 0.f;
-            }
-            const float lse = pixel_lse_wide(l, C);
-            const bool act = on && w != 0.f;
-            const float xl = act ? (float)l[lab] : 0.f;
-            float wl = w, wg = w;
-            if (FOCAL && act) focal_weights(w, lse, xl, gamma, wl, wg);
-            if (act) local[t] += wl * (lse - xl);
-            ce_grad_store_wide((t ? d1 : d0) + p * Cs, l, lse, hwt * wg, lab, C, Cs, act);
+            ce_grad_store<T, CS8>((t ? d1 : d0) + p * cs, h, lse, hwt * wg, lab, C, act);
         }
     }
     unet_ce_block_sums(local[0], local[1], red, ws);
@@ -528,8 +536,12 @@ template <typename T, int NL, int CS8, bool FOCAL, bool MASKED>
 __global__ __launch_bounds__(256) void unet_eval_kernel(const T* __restrict__ l0, const T* __restrict__ l1,
                                                         const int64_t* __restrict__ lab0, const int64_t* __restrict__ lab1,
                                                         const int32_t* __restrict__ extent, const float* __restrict__ cw,
-                                                        UnetEvalRow* __restrict__ rows, int H, int W, int C, float gamma) {
-    constexpr int Cs = CS8 * 8;
+                                                        UnetEvalRow* __restrict__ rows, int H, int W, int C, float gamma, int Cs) {
+    using Px = Pixel<T, CS8>;
+    const int cs = Px::kCs ? Px::kCs : Cs;                             // a pixel's stride: stated as a constant in the register form
+    constexpr int kChannelUnroll = Px::kUnroll;
+    constexpr int kHeadUnroll = NL ? NL : 1;                           // NL = 0 (the cache form): the head count is read at run time, the loop stays a loop
+    const int nl = NL ? NL : (l1 ? 2 : 1);
     const int b = blockIdx.y, k = blockIdx.x, K = gridDim.x;
     const UnetEvalSlab slab(extent, b, k, K, H, W);
     const int64_t base = (int64_t)b * H * W;
@@ -539,55 +551,23 @@ __global__ __launch_bounds__(256) void unet_eval_kernel(const T* __restrict__ l0
         const int64_t p = base + slab.offset(i, W);
         bool on = false;
         int lab = -1;
-#pragma unroll
-        for (int t = 0; t < NL; ++t) {
+#pragma unroll kHeadUnroll
+        for (int t = 0; t < nl; ++t) {
             if (!MASKED || t == 0) {
                 const int64_t lab64 = (t ? lab1 : lab0)[p];
                 on = lab64 >= (MASKED ? 1 : 0) && lab64 < C;
                 lab = on ? (int)lab64 : -1;
             }
-            float x[Cs];
+            typename Px::Held h;
             float xl;
-            const float lse = pixel_lse<T, CS8>((t ? l1 : l0) + p * Cs, C, lab, x, xl);
+            const float lse = Px::load(h, (t ? l1 : l0) + p * cs, Cs, C, lab, xl);
+            xl = Px::label_logit(h, lab, on, xl);
             int pred = 0;
             float bv = -INFINITY;
-#pragma unroll
-            for (int c = 0; c < Cs; ++c)
-                if (c < C) first_max(x[c], c, bv, pred);
+#pragma unroll kChannelUnroll
+            for (int c = 0; c < Px::channels(C); ++c)
+                if (c < C) first_max(Px::logit(h, c), c, bv, pred);
             unet_eval_add<FOCAL>(lab, on, lse, xl, pred, cw, gamma, num[t], den[t], cnt[t][0], cnt[t][1]);
-        }
-    }
-    unet_eval_block_row(num, den, cnt, rows + (int64_t)b * K + k);
-}
-
-// Any class count (Cs > 32): the logits of a pixel are read from the cache.
-template <typename T, bool FOCAL, bool MASKED>
-__global__ __launch_bounds__(256) void unet_eval_wide_kernel(const T* __restrict__ l0, const T* __restrict__ l1,
-                                                             const int64_t* __restrict__ lab0, const int64_t* __restrict__ lab1,
-                                                             const int32_t* __restrict__ extent, const float* __restrict__ cw,
-                                                             UnetEvalRow* __restrict__ rows, int H, int W, int C, int Cs, float gamma) {
-    const int b = blockIdx.y, k = blockIdx.x, K = gridDim.x;
-    const int NL = l1 ? 2 : 1;
-    const UnetEvalSlab slab(extent, b, k, K, H, W);
-    const int64_t base = (int64_t)b * H * W;
-    float num[2] = {0.f, 0.f}, den[2] = {0.f, 0.f};
-    int cnt[2][2] = {{0, 0}, {0, 0}};
-    for (int i = threadIdx.x; i < slab.n; i += 256) {
-        const int64_t p = base + slab.offset(i, W);
-        bool on = false;
-        int lab = -1;
-        for (int t = 0; t < NL; ++t) {
-            const T* l = (t ? l1 : l0) + p * Cs;
-            if (!MASKED || t == 0) {
-                const int64_t lab64 = (t ? lab1 : lab0)[p];
-                on = lab64 >= (MASKED ? 1 : 0) && lab64 < C;
-                lab = on ? (int)lab64 : -1;
-            }
-            const float lse = pixel_lse_wide(l, C);
-            int pred = 0;
-            float bv = -INFINITY;
-            for (int c = 0; c < C; ++c) first_max((float)l[c], c, bv, pred);
-            unet_eval_add<FOCAL>(lab, on, lse, on ? (float)l[lab] : 0.f, pred, cw, gamma, num[t], den[t], cnt[t][0], cnt[t][1]);
         }
     }
     unet_eval_block_row(num, den, cnt, rows + (int64_t)b * K + k);
@@ -619,8 +599,6 @@ __global__ __launch_bounds__(256) void unet_eval_finish_kernel(const UnetEvalRow
 // (unet_dice_coef_kernel: the K rows in index order, Y_c from msau_label_hist's rows, msau_dice_coef of loss_cost.h), and for
 // training the gradient pass (unet_dice_grad_kernel, of unet_ce_kernel's shape) that reads the (hit, miss) table from global memory.
 // =============================================================================================
-constexpr int kDiceChunk = 32;                                       // classes a thread of the cache form sums per sweep of its slab
-
 // The workgroup's sums of N classes -> row[0][c0 + c] = I, row[1][c0 + c] = P (row: [2][C]) for c0 + c < C: lanes by shuffle, the four
 // waves paired.  red: 2 * N * 4 floats; may be called again after it returns.
 template <int N>
@@ -638,73 +616,46 @@ __device__ __forceinline__ void dice_block_rows(const float (&I)[N], const float
     __syncthreads();
 }
 
-// part[((t * B + b) * K + k)][2][C] is WRITTEN by workgroup k of document b for head t; a thread adds its pixels in slab order
+// part[((t * B + b) * K + k)][2][C] is WRITTEN by workgroup k of document b for head t; a thread adds its pixels in slab order,
+// Pixel::kDiceChunk classes per sweep of the slab (the register form: all of them in one sweep)
 // MASKED: both heads against lab0; the active classes start at 1 (I_0 = 0, P_0 is summed as every class's)
 template <typename T, int NL, int CS8, bool MASKED>
 __global__ __launch_bounds__(256) void unet_dice_sums_kernel(const T* __restrict__ l0, const T* __restrict__ l1,
                                                              const int64_t* __restrict__ lab0, const int64_t* __restrict__ lab1,
                                                              const int32_t* __restrict__ extent, float* __restrict__ part, int B, int H,
-                                                             int W, int C) {
-    constexpr int Cs = CS8 * 8;
-    __shared__ float red[2 * Cs * 4];
+                                                             int W, int C, int Cs) {
+    using Px = Pixel<T, CS8>;
+    const int cs = Px::kCs ? Px::kCs : Cs;                             // a pixel's stride: stated as a constant in the register form
+    constexpr int N = Px::kDiceChunk;
+    __shared__ float red[2 * N * 4];
+    constexpr int kHeadUnroll = NL ? NL : 1;                           // NL = 0 (the cache form): the head count is read at run time, the loop stays a loop
+    const int nl = NL ? NL : (l1 ? 2 : 1);
     const int b = blockIdx.y, k = blockIdx.x, K = gridDim.x;
     const UnetEvalSlab slab(extent, b, k, K, H, W);
     const int64_t base = (int64_t)b * H * W;
+#pragma unroll kHeadUnroll
+    for (int t = 0; t < nl; ++t) {
+        for (int sweep = 0; sweep < Px::dice_sweeps(C); ++sweep) {
+            const int c0 = sweep * N;
+            float I[N], P[N];
 #pragma unroll
-    for (int t = 0; t < NL; ++t) {
-        float I[Cs], P[Cs];
-#pragma unroll
-        for (int c = 0; c < Cs; ++c) I[c] = P[c] = 0.f;
-        for (int i = threadIdx.x; i < slab.n; i += 256) {
-            const int64_t p = base + slab.offset(i, W);
-            const int64_t lab64 = (t && !MASKED ? lab1 : lab0)[p];
-            if (lab64 < (MASKED ? 1 : 0) || lab64 >= C) continue;
-            const int lab = (int)lab64;
-            float x[Cs];
-            float xl;
-            const float lse = pixel_lse<T, CS8>((t ? l1 : l0) + p * Cs, C, lab, x, xl);
-#pragma unroll
-            for (int c = 0; c < Cs; ++c) {
-                const float pc = c < C ? __expf(x[c] - lse) : 0.f;
-                P[c] += pc;
-                I[c] += c == lab ? pc : 0.f;
-            }
-        }
-        dice_block_rows<Cs>(I, P, red, part + (((int64_t)t * B + b) * K + k) * 2 * C, 0, C);
-    }
-}
-
-// Any class count (Cs > 32): kDiceChunk classes per sweep of the slab, the logits of a pixel read from the cache in every sweep
-template <typename T, bool MASKED>
-__global__ __launch_bounds__(256) void unet_dice_sums_wide_kernel(const T* __restrict__ l0, const T* __restrict__ l1,
-                                                                  const int64_t* __restrict__ lab0, const int64_t* __restrict__ lab1,
-                                                                  const int32_t* __restrict__ extent, float* __restrict__ part, int B,
-                                                                  int H, int W, int C, int Cs) {
-    __shared__ float red[2 * kDiceChunk * 4];
-    const int b = blockIdx.y, k = blockIdx.x, K = gridDim.x;
-    const int NL = l1 ? 2 : 1;
-    const UnetEvalSlab slab(extent, b, k, K, H, W);
-    const int64_t base = (int64_t)b * H * W;
-    for (int t = 0; t < NL; ++t) {
-        for (int c0 = 0; c0 < C; c0 += kDiceChunk) {
-            float I[kDiceChunk], P[kDiceChunk];
-#pragma unroll
-            for (int c = 0; c < kDiceChunk; ++c) I[c] = P[c] = 0.f;
+            for (int c = 0; c < N; ++c) I[c] = P[c] = 0.f;
             for (int i = threadIdx.x; i < slab.n; i += 256) {
                 const int64_t p = base + slab.offset(i, W);
                 const int64_t lab64 = (t && !MASKED ? lab1 : lab0)[p];
                 if (lab64 < (MASKED ? 1 : 0) || lab64 >= C) continue;
                 const int lab = (int)lab64;
-                const T* l = (t ? l1 : l0) + p * Cs;
-                const float lse = pixel_lse_wide(l, C);
+                typename Px::Held h;
+                float xl;
+                const float lse = Px::load(h, (t ? l1 : l0) + p * cs, Cs, C, lab, xl);
 #pragma unroll
-                for (int c = 0; c < kDiceChunk; ++c) {
-                    const float pc = c0 + c < C ? __expf((float)l[c0 + c] - lse) : 0.f;
+                for (int c = 0; c < N; ++c) {
+                    const float pc = c0 + c < C ? Px::prob(h, c0 + c, lse) : 0.f;
                     P[c] += pc;
                     I[c] += c0 + c == lab ? pc : 0.f;
                 }
             }
-            dice_block_rows<kDiceChunk>(I, P, red, part + (((int64_t)t * B + b) * K + k) * 2 * C, c0, C);
+            dice_block_rows<N>(I, P, red, part + (((int64_t)t * B + b) * K + k) * 2 * C, c0, C);
         }
     }
 }
@@ -741,53 +692,13 @@ __global__ __launch_bounds__(256) void unet_dice_coef_kernel(const float* __rest
 }
 
 // The pixel's Dice gradient g[j] = sc * p_j * (a_j - sum_c a_c p_c), a_c = hit_c at the label, else miss_c (tab: the document's C
-// (hit, miss) pairs), the sum by fmaf in channel order; zero in the padded channels and everywhere on an inactive pixel; all Cs
-// stored channels are written.  Register form: x[] as pixel_lse left it (it leaves holding the probabilities).
+// (hit, miss) pairs).
 template <typename T, int CS8>
-__device__ __forceinline__ void dice_grad_store(T* __restrict__ dst, float (&x)[CS8 * 8], float lse, const float2* __restrict__ tab,
-                                                float sc, int lab, int C, bool active) {
-    float a[CS8 * 8];
-    float s = 0.f;
-#pragma unroll
-    for (int c = 0; c < CS8 * 8; ++c) {
-        const bool real = active && c < C;
-        const float2 hm = real ? tab[c] : make_float2(0.f, 0.f);
-        x[c] = real ? __expf(x[c] - lse) : 0.f;
-        a[c] = c == lab ? hm.x : hm.y;
-        s = fmaf(a[c], x[c], s);
-    }
-#pragma unroll
-    for (int c0 = 0; c0 < CS8 * 8; c0 += 8) {
-        typename Vec8<T>::type o;
-#pragma unroll
-        for (int jj = 0; jj < 8; ++jj) {
-            const int c = c0 + jj;
-            float g = 0.f;
-            if (active && c < C) g = sc * (x[c] * (a[c] - s));
-            o[jj] = (T)g;
-        }
-        store8<T>(dst + c0, o);
-    }
-}
-
-// Cache-read form: the pixel's logits and the table are read twice.
-template <typename T>
-__device__ __forceinline__ void dice_grad_store_wide(T* __restrict__ dst, const T* __restrict__ l, float lse, const float2* __restrict__ tab,
-                                                     float sc, int lab, int C, int Cs, bool active) {
-    float s = 0.f;
-    if (active)
-        for (int c = 0; c < C; ++c) {
-            const float2 hm = tab[c];
-            s = fmaf(c == lab ? hm.x : hm.y, __expf((float)l[c] - lse), s);
-        }
-    for (int c = 0; c < Cs; ++c) {
-        float g = 0.f;
-        if (active && c < C) {
-            const float2 hm = tab[c];
-            g = sc * (__expf((float)l[c] - lse) * ((c == lab ? hm.x : hm.y) - s));
-        }
-        dst[c] = (T)g;
-    }
+__device__ __forceinline__ void dice_grad_store(T* __restrict__ dst, typename Pixel<T, CS8>::Held& h, float lse, const float2* __restrict__ tab, float sc, int lab,
+                                                int C, bool active) {
+    // (the table entry is selected from outside the condition it is loaded under: the loads of a pixel's channels stay in flight together)
+    Pixel<T, CS8>::store_dot(h, dst, lse, C, active, [&](int c, bool real) { const float2 hm = real ? tab[c] : make_float2(0.f, 0.f); return c == lab ? hm.x : hm.y; },
+                 [&](float p, float a, float s) { return sc * (p * (a - s)); });
 }
 
 // The gradient pass, of unet_ce_kernel's shape: every pixel of the canvas, both heads, sc = head weight / B
@@ -795,9 +706,12 @@ __device__ __forceinline__ void dice_grad_store_wide(T* __restrict__ dst, const 
 template <typename T, int NL, int CS8, bool MASKED>
 __global__ void unet_dice_grad_kernel(const T* __restrict__ l0, const T* __restrict__ l1, const int64_t* __restrict__ lab0,
                                       const int64_t* __restrict__ lab1, const int32_t* __restrict__ extent, const float2* __restrict__ tab,
-                                      T* __restrict__ d0, T* __restrict__ d1, int B, int H, int W, int C) {
-    constexpr int Cs = CS8 * 8;
-    const float sc = ((NL == 2 && !MASKED) ? 0.5f : 1.f) / (float)B;
+                                      T* __restrict__ d0, T* __restrict__ d1, int B, int H, int W, int C, int Cs) {
+    using Px = Pixel<T, CS8>;
+    const int cs = Px::kCs ? Px::kCs : Cs;                             // a pixel's stride: stated as a constant in the register form
+    constexpr int kHeadUnroll = NL ? NL : 1;                           // NL = 0 (the cache form): the head count is read at run time, the loop stays a loop
+    const int nl = NL ? NL : (l1 ? 2 : 1);
+    const float sc = ((nl == 2 && !MASKED) ? 0.5f : 1.f) / (float)B;
     const int hw = H * W;
     const int64_t total = (int64_t)B * hw;
     for (int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; p < total; p += (int64_t)gridDim.x * blockDim.x) {
@@ -806,45 +720,17 @@ __global__ void unet_dice_grad_kernel(const T* __restrict__ l0, const T* __restr
         const bool in = extent ? pos_in_extent(j, W, extent[2 * b], extent[2 * b + 1]) : true;
         bool on = false;
         int lab = -1;
-#pragma unroll
-        for (int t = 0; t < NL; ++t) {
+#pragma unroll kHeadUnroll
+        for (int t = 0; t < nl; ++t) {
             if (!MASKED || t == 0) {
                 const int64_t lab64 = (t ? lab1 : lab0)[p];
                 on = in && lab64 >= (MASKED ? 1 : 0) && lab64 < C;
                 lab = on ? (int)lab64 : -1;
             }
-            float x[Cs];
+            typename Px::Held h;
             float xl;
-            const float lse = pixel_lse<T, CS8>((t ? l1 : l0) + p * Cs, C, lab, x, xl);
-            dice_grad_store<T, CS8>((t ? d1 : d0) + p * Cs, x, lse, tab + ((int64_t)t * B + b) * C, sc, lab, C, on);
-        }
-    }
-}
-
-template <typename T, bool MASKED>
-__global__ void unet_dice_grad_wide_kernel(const T* __restrict__ l0, const T* __restrict__ l1, const int64_t* __restrict__ lab0,
-                                           const int64_t* __restrict__ lab1, const int32_t* __restrict__ extent,
-                                           const float2* __restrict__ tab, T* __restrict__ d0, T* __restrict__ d1, int B, int H, int W,
-                                           int C, int Cs) {
-    const int NL = l1 ? 2 : 1;
-    const float sc = ((NL == 2 && !MASKED) ? 0.5f : 1.f) / (float)B;
-    const int hw = H * W;
-    const int64_t total = (int64_t)B * hw;
-    for (int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; p < total; p += (int64_t)gridDim.x * blockDim.x) {
-        const int b = (int)((unsigned)p / (unsigned)hw);
-        const int j = (int)p - b * hw;
-        const bool in = extent ? pos_in_extent(j, W, extent[2 * b], extent[2 * b + 1]) : true;
-        bool on = false;
-        int lab = -1;
-        for (int t = 0; t < NL; ++t) {
-            const T* l = (t ? l1 : l0) + p * Cs;
-            if (!MASKED || t == 0) {
-                const int64_t lab64 = (t ? lab1 : lab0)[p];
-                on = in && lab64 >= (MASKED ? 1 : 0) && lab64 < C;
-                lab = on ? (int)lab64 : -1;
-            }
-            const float lse = pixel_lse_wide(l, C);
-            dice_grad_store_wide((t ? d1 : d0) + p * Cs, l, lse, tab + ((int64_t)t * B + b) * C, sc, lab, C, Cs, on);
+            const float lse = Px::load(h, (t ? l1 : l0) + p * cs, Cs, C, lab, xl);
+            dice_grad_store<T, CS8>((t ? d1 : d0) + p * cs, h, lse, tab + ((int64_t)t * B + b) * C, sc, lab, C, on);
         }
     }
 }
@@ -939,23 +825,25 @@ __global__ void softmax_argmax_nhwc_kernel(const T* __restrict__ logits, float* 
 }  // namespace
 
 // The family's instance ladder, stated once: dtype -> T, a second head -> NL = 2, Cs -> the register form with Cs = 8 * CS8, or
-// what lies beyond it (the cache form, where there is one).  REG(T, NL, CS8) and WIDE(T) are the caller's launch expressions.
-#define LOSS_REG(dtype, two, REG, C8)                                                     \
+// what lies beyond it (the cache form, CS8 = 0, where there is one: it reads the head count at run time, NL = 0).  LAUNCH(T, NL, CS8)
+// is the caller's one launch expression.
+#define LOSS_FORM(dtype, two, LAUNCH, C8)                                                 \
     do {                                                                                  \
-        if (two) { DISPATCH_T(dtype, REG(float, 2, C8), REG(bf16_t, 2, C8)); }            \
-        else { DISPATCH_T(dtype, REG(float, 1, C8), REG(bf16_t, 1, C8)); }                \
+        if (two) { DISPATCH_T(dtype, LAUNCH(float, 2, C8), LAUNCH(bf16_t, 2, C8)); }      \
+        else { DISPATCH_T(dtype, LAUNCH(float, 1, C8), LAUNCH(bf16_t, 1, C8)); }          \
     } while (0)
-#define LOSS_LADDER_16(dtype, two, Cs, REG, BEYOND)                                       \
+#define LOSS_CACHE(dtype, LAUNCH) DISPATCH_T(dtype, LAUNCH(float, 0, 0), LAUNCH(bf16_t, 0, 0))
+#define LOSS_LADDER_16(dtype, two, Cs, LAUNCH, BEYOND)                                    \
     do {                                                                                  \
-        if ((Cs) == 8) LOSS_REG(dtype, two, REG, 1);                                      \
-        else if ((Cs) == 16) LOSS_REG(dtype, two, REG, 2);                                \
+        if ((Cs) == 8) LOSS_FORM(dtype, two, LAUNCH, 1);                                  \
+        else if ((Cs) == 16) LOSS_FORM(dtype, two, LAUNCH, 2);                            \
         else { BEYOND; }                                                                  \
     } while (0)
-#define LOSS_LADDER_32(dtype, two, Cs, REG, WIDE)                                         \
-    LOSS_LADDER_16(dtype, two, Cs, REG,                                                   \
-                   if ((Cs) == 24) LOSS_REG(dtype, two, REG, 3);                          \
-                   else if ((Cs) == 32) LOSS_REG(dtype, two, REG, 4);                     \
-                   else DISPATCH_T(dtype, WIDE(float), WIDE(bf16_t)))
+#define LOSS_LADDER_32(dtype, two, Cs, LAUNCH)                                            \
+    LOSS_LADDER_16(dtype, two, Cs, LAUNCH,                                                \
+                   if ((Cs) == 24) LOSS_FORM(dtype, two, LAUNCH, 3);                      \
+                   else if ((Cs) == 32) LOSS_FORM(dtype, two, LAUNCH, 4);                 \
+                   else LOSS_CACHE(dtype, LAUNCH))
 
 extern "C" int msau_label_counts(void* stream, const int64_t* labels, int32_t* counts, int B, int64_t hw) {
     MSAU_CHECK_ARG(labels && counts && B > 0 && hw > 0, "label_counts: bad args");
@@ -981,13 +869,10 @@ extern "C" int64_t msau_ce_ws_floats(int64_t npix_total) { return 2 * ce_blocks(
 template <bool ALL>
 static int launch_masked_ce(hipStream_t s, const char* name, int dtype, const void* logits, const int64_t* labels, const int32_t* counts,
                             void* dlogits, float* ws, int nb, int B, int64_t hw, int C, int Cs, float scale, const float* cw) {
-#define CE_REG(T, NL, C8) hipLaunchKernelGGL((masked_ce_kernel<T, ALL, C8>), dim3(nb), dim3(kThreads), 0, s, static_cast<const T*>(logits), \
-        labels, counts, static_cast<T*>(dlogits), ws, B, hw, C, scale, cw)
-#define CE_WIDE(T) hipLaunchKernelGGL((masked_ce_wide_kernel<T, ALL>), dim3(nb), dim3(kThreads), 0, s, static_cast<const T*>(logits), \
-        labels, counts, static_cast<T*>(dlogits), ws, B, hw, C, Cs, scale, cw)
-    LOSS_LADDER_16(dtype, false, Cs, CE_REG, DISPATCH_T(dtype, CE_WIDE(float), CE_WIDE(bf16_t)));
-#undef CE_WIDE
-#undef CE_REG
+#define CE(T, NL, C8) hipLaunchKernelGGL((masked_ce_kernel<T, ALL, C8>), dim3(nb), dim3(kThreads), 0, s, static_cast<const T*>(logits), \
+        labels, counts, static_cast<T*>(dlogits), ws, B, hw, C, scale, cw, Cs)
+    LOSS_LADDER_16(dtype, false, Cs, CE, LOSS_CACHE(dtype, CE));
+#undef CE
     MSAU_CHECK_LAUNCH(name);
     return 0;
 }
@@ -1061,12 +946,8 @@ static int unet_ce_run(const char* fn, float gamma, void* stream, int dtype, con
     const int nb = unet_ce_blocks((int64_t)B * H * W);
 #define UNET_CE(T, NL, C8) hipLaunchKernelGGL((unet_ce_kernel<T, NL, C8, FOCAL, MASKED>), dim3(nb), dim3(kThreads), 0, s, static_cast<const T*>(logits), \
         static_cast<const T*>(aux), labels, aux_labels, extent, class_w, hist_partial, K, static_cast<T*>(dlogits), static_cast<T*>(daux), \
-        ws, B, H, W, C, gamma)
-#define UNET_CE_WIDE(T) hipLaunchKernelGGL((unet_ce_wide_kernel<T, FOCAL, MASKED>), dim3(nb), dim3(kThreads), 0, s, static_cast<const T*>(logits), \
-        static_cast<const T*>(aux), labels, aux_labels, extent, class_w, hist_partial, K, static_cast<T*>(dlogits), static_cast<T*>(daux), \
-        ws, B, H, W, C, Cs, gamma)
-    LOSS_LADDER_32(dtype, aux, Cs, UNET_CE, UNET_CE_WIDE);
-#undef UNET_CE_WIDE
+        ws, B, H, W, C, gamma, Cs)
+    LOSS_LADDER_32(dtype, aux, Cs, UNET_CE);
 #undef UNET_CE
     MSAU_CHECK_LAUNCH(fn);
     hipLaunchKernelGGL(unet_ce_finish_kernel<MASKED>, dim3(1), dim3(256), 0, s, ws, nb, aux ? 1 : 0, loss3);
@@ -1096,11 +977,8 @@ static int launch_dice_sums(hipStream_t s, int dtype, const void* logits, const 
                             const int32_t* extent, float* part, int K, int B, int H, int W, int C, int Cs) {
     const dim3 grid(K, B);
 #define DICE_SUMS(T, NL, C8) hipLaunchKernelGGL((unet_dice_sums_kernel<T, NL, C8, MASKED>), grid, dim3(256), 0, s, static_cast<const T*>(logits), \
-        static_cast<const T*>(aux), labels, aux_labels, extent, part, B, H, W, C)
-#define DICE_SUMS_WIDE(T) hipLaunchKernelGGL((unet_dice_sums_wide_kernel<T, MASKED>), grid, dim3(256), 0, s, static_cast<const T*>(logits), \
         static_cast<const T*>(aux), labels, aux_labels, extent, part, B, H, W, C, Cs)
-    LOSS_LADDER_32(dtype, aux, Cs, DICE_SUMS, DICE_SUMS_WIDE);
-#undef DICE_SUMS_WIDE
+    LOSS_LADDER_32(dtype, aux, Cs, DICE_SUMS);
 #undef DICE_SUMS
     MSAU_CHECK_LAUNCH("unet_dice_sums");
     return 0;
@@ -1137,11 +1015,8 @@ static int unet_dice_run(const char* fn, float eps, void* stream, int dtype, con
     MSAU_CHECK_LAUNCH("unet_ce_finish");
     const int nb = unet_ce_blocks((int64_t)B * H * W);
 #define DICE_GRAD(T, NL, C8) hipLaunchKernelGGL((unet_dice_grad_kernel<T, NL, C8, MASKED>), dim3(nb), dim3(kThreads), 0, s, static_cast<const T*>(logits), \
-        static_cast<const T*>(aux), labels, aux_labels, extent, tab, static_cast<T*>(dlogits), static_cast<T*>(daux), B, H, W, C)
-#define DICE_GRAD_WIDE(T) hipLaunchKernelGGL((unet_dice_grad_wide_kernel<T, MASKED>), dim3(nb), dim3(kThreads), 0, s, static_cast<const T*>(logits), \
         static_cast<const T*>(aux), labels, aux_labels, extent, tab, static_cast<T*>(dlogits), static_cast<T*>(daux), B, H, W, C, Cs)
-    LOSS_LADDER_32(dtype, aux, Cs, DICE_GRAD, DICE_GRAD_WIDE);
-#undef DICE_GRAD_WIDE
+    LOSS_LADDER_32(dtype, aux, Cs, DICE_GRAD);
 #undef DICE_GRAD
     MSAU_CHECK_LAUNCH("unet_dice_grad");
     return 0;
@@ -1214,11 +1089,8 @@ static int unet_eval_run(const char* fn, float gamma, void* stream, int dtype, c
     UnetEvalRow* rows = static_cast<UnetEvalRow*>(ws);
     const dim3 grid(K, B);
 #define UNET_EVAL(T, NL, C8) hipLaunchKernelGGL((unet_eval_kernel<T, NL, C8, FOCAL, MASKED>), grid, dim3(256), 0, s, static_cast<const T*>(logits), \
-        static_cast<const T*>(aux), labels, aux_labels, extent, class_w, rows, H, W, C, gamma)
-#define UNET_EVAL_WIDE(T) hipLaunchKernelGGL((unet_eval_wide_kernel<T, FOCAL, MASKED>), grid, dim3(256), 0, s, static_cast<const T*>(logits), \
-        static_cast<const T*>(aux), labels, aux_labels, extent, class_w, rows, H, W, C, Cs, gamma)
-    LOSS_LADDER_32(dtype, aux, Cs, UNET_EVAL, UNET_EVAL_WIDE);
-#undef UNET_EVAL_WIDE
+        static_cast<const T*>(aux), labels, aux_labels, extent, class_w, rows, H, W, C, gamma, Cs)
+    LOSS_LADDER_32(dtype, aux, Cs, UNET_EVAL);
 #undef UNET_EVAL
     MSAU_CHECK_LAUNCH(fn);
     hipLaunchKernelGGL(unet_eval_finish_kernel, dim3((2 * B + 255) / 256), dim3(256), 0, s, rows, B, K, doc_loss, doc_counts);

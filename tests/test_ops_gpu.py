@@ -452,6 +452,63 @@ def test_masked_ce_register_form_equals_cache_form(dtype):
         assert float(a[..., C:].float().abs().max()) == 0.0 and float(b[..., C:].float().abs().max()) == 0.0
 
 
+@pytest.mark.parametrize("dtype", ["fp32", "bf16"])
+def test_one_head_ce_gives_the_same_bits_on_every_rung(dtype):
+    """the same 5 real logits stored at Cs = 8 and 16 (the two register instances of the one-head CE) and at Cs = 24 (its cache form),
+    the padded channels holding different random values: msau_masked_ce, msau_softmax_ce and msau_softmax_ce_weighted give the same
+    loss bits and the same gradient bits in the real channels, zeros in the padded ones; msau_masked_ce_multi (register instances only:
+    Cs = 8 and 16; one head and two, counts_k 1 and 4) likewise"""
+    torch.manual_seed(5)
+    B, H, W, C = 3, 37, 29, 5
+    td = torch.float32 if dtype == "fp32" else torch.bfloat16
+    dt = L.F32 if dtype == "fp32" else L.BF16
+    real = [(torch.randn(B, H, W, C) * 2).to(td) for _ in range(2)]
+    labels = torch.randint(-1, C + 1, (B, H, W), dtype=torch.int64)       # 0, -1 and C occur: not labelled
+    labels[1] = 0                                                         # a sample without labelled pixels
+    labels = labels.cuda()
+    cw = torch.rand(C) + 0.5
+    cw[2] = 0.0
+    cw = cw.cuda()
+    s = torch.cuda.current_stream().cuda_stream
+    counts, split = torch.zeros(B, dtype=torch.int32, device="cuda"), torch.zeros(B, 4, dtype=torch.int32, device="cuda")
+    L.call("msau_label_counts", s, labels.data_ptr(), counts.data_ptr(), B, H * W)
+    L.call("msau_label_counts_split", s, labels.data_ptr(), split.data_ptr(), B, H * W, 4)
+    ws = torch.zeros(int(max(L.load().msau_ce_ws_floats(B * H * W), L.load().msau_ce_multi_ws_floats(B * H * W))), device="cuda")
+    got = {}
+    for Cs in (8, 16, 24):
+        lg = [(torch.randn(B, H, W, Cs) * 2).to(td) for _ in range(2)]
+        for x, r in zip(lg, real):
+            x[..., :C] = r
+        lg = [x.cuda() for x in lg]
+        d = [torch.full_like(lg[0], 9.0) for _ in range(11)]              # three one-head calls, then four (final, auxiliary) pairs
+        losses = [torch.zeros(2, device="cuda") for _ in range(7)]
+        L.call("msau_masked_ce", s, dt, lg[0].data_ptr(), labels.data_ptr(), counts.data_ptr(), d[0].data_ptr(), losses[0].data_ptr(), ws.data_ptr(),
+               B, H * W, C, Cs, 1.0 / B)
+        L.call("msau_softmax_ce", s, dt, lg[0].data_ptr(), labels.data_ptr(), d[1].data_ptr(), losses[1].data_ptr(), ws.data_ptr(),
+               B, H * W, C, Cs, 1.0 / (B * H * W))
+        L.call("msau_softmax_ce_weighted", s, dt, lg[0].data_ptr(), labels.data_ptr(), cw.data_ptr(), d[2].data_ptr(), losses[2].data_ptr(),
+               ws.data_ptr(), B, H * W, C, Cs)
+        n = 3
+        if Cs <= 16:
+            for i, (two, k) in enumerate(((False, 1), (True, 1), (False, 4), (True, 4))):
+                L.call("msau_masked_ce_multi", s, dt, lg[0].data_ptr(), lg[1].data_ptr() if two else None, labels.data_ptr(),
+                       (counts if k == 1 else split).data_ptr(), d[3 + 2 * i].data_ptr(), d[4 + 2 * i].data_ptr() if two else None,
+                       losses[3 + i].data_ptr(), ws.data_ptr(), B, H * W, C, Cs, 1.0 / B, k)
+            n = 7
+        torch.cuda.synchronize()
+        got[Cs] = ([x.cpu() for x in losses[:n]], [x.cpu() for x in d[:3 + 2 * (n - 3)]])
+    assert len(got[8][0]) == len(got[16][0]) == 7 and len(got[24][0]) == 3
+    for Cs in (16, 24):
+        for i, (a, b) in enumerate(zip(got[8][0], got[Cs][0])):
+            assert torch.equal(a, b) and bool(torch.isfinite(a).all()) and float(a[0]) > 0, (Cs, i, a, b)
+        for i, (a, b) in enumerate(zip(got[8][1], got[Cs][1])):
+            if i in (4, 8):                                                   # the absent head of a one-head call is not written
+                assert bool((a == 9.0).all()) and bool((b == 9.0).all()), (Cs, i)
+                continue
+            assert torch.equal(a[..., :C], b[..., :C]) and float(a[..., :C].float().abs().max()) > 0, (Cs, i)
+            assert float(a[..., C:].float().abs().max()) == 0.0 and float(b[..., C:].float().abs().max()) == 0.0, (Cs, i)
+
+
 @pytest.mark.parametrize("dtype", DT)
 @pytest.mark.parametrize("k,cin,cout", [(1, 192, 64), (3, 192, 64), (1, 136, 8)])
 def test_data_gradient_wider_than_128_channels(dtype, k, cin, cout):

@@ -151,7 +151,7 @@ def _assert_against_host(what, tol, C, ext, got, ref, with_aux):
 
 # ---- 1: the training call against the host statement ------------------------------------------------------------------------------
 @pytest.mark.parametrize("dtype", ["fp32", "bf16"])
-@pytest.mark.parametrize("C", [5, 12, 17, 40])
+@pytest.mark.parametrize("C", [5, 8, 12, 17, 40])                                # 8: C == Cs in a register instance
 @pytest.mark.parametrize("kind", [U.FOCAL, U.DICE])
 def test_unet_cost_equals_float64_host(kind, C, dtype):
     tol = 1e-5 if dtype == "fp32" else 1e-2
@@ -222,6 +222,38 @@ def test_register_form_equals_cache_form(kind, dtype):
                     assert float(a[..., C:].float().abs().max()) == 0.0 and float(b_[..., C:].float().abs().max()) == 0.0, what
                 e_r, e_w = reg.evaluate(KIND[kind], param, with_aux, weighted, K), wide.evaluate(KIND[kind], param, with_aux, weighted, K)
                 assert torch.equal(e_r[0], e_w[0]) and torch.equal(e_r[1], e_w[1]), what
+
+
+RUNGS = (8, 16, 24, 32, 40)                                                   # every register instance (Cs = 8 * CS8 <= 32) and the cache form
+
+
+@pytest.mark.parametrize("dtype", ["fp32", "bf16"])
+@pytest.mark.parametrize("C", [5, 8])
+def test_every_rung_gives_the_same_bits(C, dtype):
+    """the same C real logits stored at every rung of the instance ladder, the padded channels holding different random values (C = 8:
+    the first rung has none): the cross entropy, the focal and the Dice loss give the same three loss bits, the same gradient bits in the
+    real channels, zeros in the padded ones, and the same evaluation rows and counts"""
+    K = 4
+    for ragged in (False, True):
+        rungs = {Cs: _Dev(C, dtype, ragged, K, Cs) for Cs in RUNGS}
+        for kind, param in ((L.COST_CE, 0.0), (L.COST_FOCAL, PARAMS[U.FOCAL][1]), (L.COST_DICE, PARAMS[U.DICE][1])):
+            for with_aux in (True, False):
+                for weighted in (False, True):
+                    first = None
+                    for Cs, case in rungs.items():
+                        what = (kind, C, dtype, ragged, with_aux, weighted, Cs)
+                        (l3, d), (rows, cnt) = case.train(kind, param, with_aux, weighted), case.evaluate(kind, param, with_aux, weighted, K)
+                        assert bool(torch.isfinite(l3).all()) and float(l3[0]) > 0, (what, l3)
+                        for x in d[:2 if with_aux else 1]:
+                            assert float(x[..., :C].float().abs().max()) > 0, what
+                            assert Cs == C or float(x[..., C:].float().abs().max()) == 0.0, what
+                        if first is None:
+                            first = (l3, d, rows, cnt)
+                            continue
+                        assert torch.equal(l3, first[0]), (what, l3, first[0])
+                        for x, y in list(zip(d, first[1]))[:2 if with_aux else 1]:
+                            assert torch.equal(x[..., :C], y[..., :C]), what
+                        assert torch.equal(rows, first[2]) and torch.equal(cnt, first[3]), (what, rows, first[2])
 
 
 # ---- 4: evaluation ----------------------------------------------------------------------------------------------------------------
