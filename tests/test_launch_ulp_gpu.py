@@ -26,6 +26,7 @@ from msau_amd import _lib as L
 from msau_amd.model import MSAUWrapper, TrainEngine
 from msau_amd.plan import AttnCoreOp, ConvOp, LrnOp, PoolOp
 from oracle import msau_oracle as O
+from tests.elementwise_util import lrn_bwd_ref, ulp_bf16          # (the LRN backward and its terms for any n: one statement)
 
 pytestmark = pytest.mark.gpu
 ACC = 3e-5                 # fp32 accumulation slack, relative to the sum of |terms| of an output element
@@ -35,11 +36,6 @@ def nchw(t, C, samples=None):
     if samples is not None:
         t = t[list(samples)]
     return t[..., :C].permute(0, 3, 1, 2).double().cpu().contiguous()
-
-
-def ulp_bf16(v):
-    a = v.abs().clamp_min(2.0 ** -120)
-    return torch.pow(2.0, torch.floor(torch.log2(a)) - 7)
 
 
 def assert_rounded(got, ref, slack, what, half_ulps=1, mag=None):
@@ -66,21 +62,6 @@ def conv_ref(op, sd, inp, w=None, b=None):
         pb, pr = (k - 1) * d - op.pad_t, (k - 1) * d - op.pad_l
         return F.conv2d(F.pad(inp, (op.pad_l, pr, op.pad_t, pb)), w, b, dilation=d)
     return O.deconv(inp, w, b, (op.out.H, op.out.W))
-
-
-def lrn_bwd_ref(a, dy):
-    """-> (da, sum of |terms|): da_c = dy_c d_c^-b - a_c (2 alpha b / n) sum_{c' : c in window(c')} dy_c' a_c' d_c'^(-b-1); the kernels
-    take the window sums as differences of fp32 prefix sums over ALL channels, so the terms of the bound are those of the whole sum"""
-    n, alpha, beta = a.shape[1], 1e-4, 0.75
-    ar = a.clone().requires_grad_(True)
-    O.lrn(ar, n).backward(dy)
-    # d = |a / y|^(1/beta)   (|.| BEFORE the clamp: a negative y used to be clamped to 1e-300, which made d huge and the bound of
-    # every element with a < 0 -- half of an LRN input -- collapse to the bare half ulp; the bench-shape case then tripped over two
-    # exact ties among 1.4 M elements)
-    d = (a.abs() / O.lrn(a, n).abs().clamp_min(1e-300)).where(a != 0, torch.ones_like(a)) ** (1.0 / beta)
-    t1 = dy.abs() * d ** -beta
-    t2 = a.abs() * (2 * alpha * beta / n) * (dy.abs() * a.abs() * d ** (-beta - 1)).sum(1, keepdim=True)
-    return ar.grad, t1 + t2
 
 
 class Checker:

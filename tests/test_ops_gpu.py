@@ -4,9 +4,11 @@ relative to the tensor's max (fp32 MFMA sums in a different order than MKL-DNN);
 import numpy as np
 import pytest
 import torch
+import torch.nn.functional as F
 
 from msau_amd import _lib as L
 from oracle import msau_oracle as O
+from tests import elementwise_util as EU
 from tests.golden_util import err, load_ops, rel_err
 from tests.hip_harness import Act, AttnCoreOp, ConvOp, LrnOp, PoolOp, run_graph
 
@@ -166,7 +168,14 @@ def test_pool_golden(dtype):
     if dtype == L.F32:
         assert np.array_equal(y.numpy(), g["pool.y"]) and np.array_equal(dx.numpy(), g["pool.gx"])   # bit exact
     else:
-        assert rel_err(y, g["pool.y"]) < 1e-2
+        # a max pool selects: exact on the bf16-rounded operands (the first maximum in row-major order where two of them tie)
+        xb = torch.tensor(x).bfloat16().float().permute(0, 2, 3, 1)
+        ry, ridx = EU.pool_fwd(xb)
+        assert torch.equal(ry.permute(0, 3, 1, 2), F.max_pool2d(F.pad(xb.permute(0, 3, 1, 2), (0, xb.shape[2] % 2, 0, xb.shape[1] % 2)), 2, 2))
+        assert torch.equal(y, ry.permute(0, 3, 1, 2)), "y is not the pool of the bf16-rounded input"
+        gb = torch.tensor(g["pool.gy"]).bfloat16().float().permute(0, 2, 3, 1)
+        rdx = EU.pool_scatter(gb, ridx, xb.shape[1], xb.shape[2]).permute(0, 3, 1, 2)
+        assert torch.equal(dx, rdx), "dx is not the scatter of the bf16-rounded output gradient"
 
 
 @pytest.mark.parametrize("dtype", DT)
