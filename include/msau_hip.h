@@ -1012,6 +1012,36 @@ int msau_kv_warp_train(void* stream, int dtype, const int32_t* ids, const int64_
                        int n_token, int Cs, int n_class, void* grid, int64_t* labels_out, int64_t* aux_out, int32_t* flags,
                        int32_t* ws);
 
+/* ------------------------------------------------------------------------------------------
+ * Key-value training, the generator's elastic augmentation (data_generator/data_generator_text.py:309-344,
+ * utils/image_util.py:58-90; msau_amd/training/kv_warp.py "the elastic warp" states what is computed, csrc/warp.hip how).
+ *   msau_kv_elastic_train : the canvases msau_kv_paint_train leaves (as for msau_kv_warp_train) resampled as scipy's
+ *                   map_coordinates(order=1, mode "constant", cval 0) resamples the generator's one-hot planes x 255, thresholded
+ *                   at > 64 after scipy's uint8 rounding.  fields uint8 [B][H][W][2] = (fy, fx) on the source canvas, alphas double
+ *                   [B][2] = (alpha_y, alpha_x): output pixel (oy, ox) of document b reads the source at
+ *                   (oy + fy * alpha_y, ox + fx * alpha_x), float64, the product rounded, then the sum.  A document's output
+ *                   extent is its source size (h, w), clipped to (Ho, Wo).  All device memory.
+ *                     grid [B][Ho][Wo][Cs] in `dtype`: channel c < n_token is 1 iff the bilinear grey level of the plane
+ *                       [ids == c], (1-uy)((1-ux) p00 + ux p01) + uy((1-ux) p10 + ux p11) in float64 in this order, is >= 64.5 --
+ *                       at most three channels of a pixel -- every other element 0: the channels from n_token on, pixels whose
+ *                       source lies outside [0, h-1] x [0, w-1], outside (h, w) and in the padding
+ *                     labels_out / aux_out int64 [B][Ho][Wo]: 1 if the plane [labels == 1] is set, else the smallest set plane in
+ *                       [2, n_class), else 0; -1 outside (h, w)
+ *                     flags int32 [B]: 0, or bit 1: an alpha of the document is not finite, nothing of it was resampled (zeros
+ *                       and 0 labels inside its extent); bit 0 cannot occur
+ *                   Every element of the four outputs is written exactly once, nothing is cleared first, no atomics: equal inputs
+ *                   give equal bits.  Everything a pixel's planes depend on is float64 with no fused multiply-add, so the outputs
+ *                   equal the float64 statement (`kv_warp.elastic_host`) bit for bit.  A tap never leaves the document: floor + 1
+ *                   is clamped to n - 1, where its weight is 0.  Negative alphas are legal.  ws: int32
+ *                   [msau_kv_elastic_train_ws_ints(B, Ho, Wo)], one word per 16 x 16 tile.  Two launches (the tiles; the flags).
+ *                   B <= 65535, B*H*W < 2^31, B*Ho*Wo < 2^31, n_token <= Cs, Cs % 8 == 0, n_token and n_class <= 32767, grid 16-byte aligned.
+ * ------------------------------------------------------------------------------------------ */
+int64_t msau_kv_elastic_train_ws_ints(int B, int Ho, int Wo);
+int msau_kv_elastic_train(void* stream, int dtype, const int32_t* ids, const int64_t* labels, const int64_t* aux_labels,
+                          const int32_t* src_sizes, const uint8_t* fields, const double* alphas, int B, int H, int W, int Ho, int Wo,
+                          int n_token, int Cs, int n_class, void* grid, int64_t* labels_out, int64_t* aux_out, int32_t* flags,
+                          int32_t* ws);
+
 #ifdef __cplusplus
 }
 #endif

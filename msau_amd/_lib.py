@@ -233,6 +233,8 @@ _SIGNATURES = {
     "msau_kv_paint_train": (C.c_int, [vp] * 7 + [C.c_int] * 3 + [vp, vp, vp]),
     "msau_kv_warp_train_ws_ints": (i64, [C.c_int] * 3),
     "msau_kv_warp_train": (C.c_int, [vp, C.c_int] + [vp] * 6 + [C.c_int] * 8 + [vp] * 5),
+    "msau_kv_elastic_train_ws_ints": (i64, [C.c_int] * 3),
+    "msau_kv_elastic_train": (C.c_int, [vp, C.c_int] + [vp] * 6 + [C.c_int] * 8 + [vp] * 5),
     "msau_label_hist": (C.c_int, [vp, vp, vp, vp] + [C.c_int] * 5),
     "msau_unet_ce_ws_floats": (i64, [i64]),
     "msau_unet_ce": (C.c_int, [vp, C.c_int] + [vp] * 7 + [C.c_int, vp, vp, vp, vp] + [C.c_int] * 5),

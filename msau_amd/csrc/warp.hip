@@ -357,7 +357,206 @@ WP_DEV void wp_body(const WpCtx& c, const WpLds& s) {
     WP_PHASE(wp_ph_store);
 }
 
+// ---- the elastic warp: msau_kv_elastic_train ---------------------------------------------------------------------------------------------
+// The generator's elastic_transform (utils/image_util.py:58-90; kv_warp.py "the elastic warp"): output pixel (oy, ox)
+// of every one-hot plane x 255 is scipy's map_coordinates(order=1, mode "constant") at
+//   sy = oy + fy[oy, ox] * alpha_y,  sx = ox + fx[oy, ox] * alpha_x     (float64, the product rounded, then the sum; fields uint8)
+// 0 outside [0, h-1] x [0, w-1], else with uy = sy - floor(sy), ux = sx - floor(sx), p = 255 [canvas(tap) == c]
+//   grey = (1 - uy) * ((1 - ux) * p00 + ux * p01) + uy * ((1 - ux) * p10 + ux * p11)       (this order, nothing fused)
+// on the taps floor(s) and floor(s) + 1, the latter clamped to n - 1 where its weight is 0; the plane is set iff grey >= 64.5 (scipy
+// stores grey + 0.5 truncated, the generator keeps > 64).  The four weights sum to 1 and a set plane needs 0.2529 of them, so at most
+// three planes of a pixel are set: the WP_MAXSET slots always suffice.  The output has the source's extent.
+//
+// Same tiles, same outputs and same rules as above (every element written once by one lane, no atomics, a word per tile folded by the
+// flags kernel) with another phase 2: a lane reads its pixel's two field bytes and the 4 taps of each canvas straight from global
+// memory -- neighbouring lanes read neighbouring addresses, and 12 reads per pixel earn no staging -- and evaluates the grey level of
+// each of the at most 4 distinct tap values in float64, exactly as the host statement does: the outputs equal it to the bit.  No LDS
+// beyond the set slots that phase 3 (wp_ph_store, unchanged) reads.  An alpha that is not finite flags the document
+// (WP_FLAG_MATRIX) and nothing of it is resampled; a negative one is legal, its coordinates simply fall outside.
+#define WE_LDS_INTS (WP_THREADS * WP_MAXSET + 4)
+
+struct WeCtx {
+    WpCtx c;                        // what phase 3 reads, and the source planes and extents (ho == h, wo == w, clipped to the canvases)
+    const uint8_t* fld;             // the document's [H][W][2] = (fy, fx)
+    double alpha_y, alpha_x;
+};
+
+struct WeTaps { double vy, uy, vx, ux; size_t at[4]; };             // weights of floor / floor + 1 per axis; addresses of p00, p01, p10, p11
+
+// A product that is to be rounded before it is added to.  The library is built with -ffp-contract=fast, under which the backend
+// fuses a multiplication into the addition it feeds wherever it still sees it, whatever the pragma says; an empty asm statement
+// that takes the product in and out of its register hides it (no instruction is emitted).  The plain C++ form is built with
+// -ffp-contract=off.
+WP_DEV double we_rounded(double v) {
+#ifndef MSAU_WARP_CPU
+    asm("" : "+v"(v));
+#endif
+    return v;
+}
+
+// o + f * alpha, the product rounded, then the sum (kv_warp.elastic_coords)
+WP_DEV double we_coord(double o, double f, double alpha) {
+#ifdef __clang__
+#pragma clang fp contract(off)
+#endif
+    const double d = we_rounded(f * alpha);
+    return o + d;
+}
+
+WP_DEV void we_axis(double s, int n, int& q0, int& q1, double& v, double& u) {
+#ifdef __clang__
+#pragma clang fp contract(off)
+#endif
+    const double fl = floor(s);
+    q0 = (int)fl;
+    q1 = q0 + 1 < n ? q0 + 1 : n - 1;
+    u = s - fl;
+    v = 1.0 - u;
+}
+
+// the grey level of plane [canvas == v] from the four tap values, in the statement's order
+WP_DEV double we_grey(const WeTaps& t, const int* tap, int v) {
+#ifdef __clang__
+#pragma clang fp contract(off)
+#endif
+    const double p00 = tap[0] == v ? 255.0 : 0.0, p01 = tap[1] == v ? 255.0 : 0.0;
+    const double p10 = tap[2] == v ? 255.0 : 0.0, p11 = tap[3] == v ? 255.0 : 0.0;
+    const double a0 = we_rounded(t.vx * p00), a1 = we_rounded(t.ux * p01), b0 = we_rounded(t.vx * p10), b1 = we_rounded(t.ux * p11);
+    const double top = a0 + a1, bot = b0 + b1;
+    const double y0 = we_rounded(t.vy * top), y1 = we_rounded(t.uy * bot);
+    return y0 + y1;
+}
+
+// the distinct tap values in [first, limit) whose plane is set -> out[0 .. n), n <= 4 (by the weights, n <= 3)
+WP_DEV int we_set_values(const WeTaps& t, const int* tap, int first, int limit, int* out) {
+    int n = 0;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const int v = tap[k];
+        bool seen = v < first || v >= limit;
+#pragma unroll
+        for (int q = 0; q < k; ++q) seen = seen || tap[q] == v;
+        if (seen) continue;
+        if (we_grey(t, tap, v) >= 64.5) out[n++] = v;
+    }
+    return n;
+}
+
+WP_DEV int we_label_of(const WeTaps& t, const int* tap, int n_class) {
+    int got[4];
+    const int n = we_set_values(t, tap, 1, n_class, got);
+    int best = 0x7fffffff;
+    for (int k = 0; k < n; ++k) {
+        if (got[k] == 1) return 1;
+        best = got[k] < best ? got[k] : best;
+    }
+    return best != 0x7fffffff ? best : 0;
+}
+
+WP_DEV void we_ctx(WeCtx& e, int dtype, const int32_t* ids, const int64_t* lab, const int64_t* aux, const int32_t* src_sizes,
+                   const uint8_t* fields, const double* alphas, int b, int ty, int tx, int tiles_x, int tiles, int H, int W, int Ho,
+                   int Wo, int n_token, int Cs, int n_class, void* grid, int64_t* lab_out, int64_t* aux_out, int32_t* tile_flags) {
+    WpCtx& c = e.c;
+    const size_t src = (size_t)b * H * W, dst = (size_t)b * Ho * Wo;
+    c.ids = ids + src; c.lab = lab + src; c.aux = aux + src;
+    e.fld = fields + 2 * src;
+    const int h = src_sizes[2 * b], w = src_sizes[2 * b + 1];
+    c.h = h < 0 ? 0 : (h > H ? H : h); c.w = w < 0 ? 0 : (w > W ? W : w); c.W = W;
+    c.ho = c.h > Ho ? Ho : c.h; c.wo = c.w > Wo ? Wo : c.w; c.Ho = Ho; c.Wo = Wo;
+    e.alpha_y = alphas[2 * (size_t)b]; e.alpha_x = alphas[2 * (size_t)b + 1];
+    c.m00 = c.m11 = 1.0; c.m01 = c.m10 = c.o0 = c.o1 = 0.0;
+    c.finite = wp_finite(e.alpha_y) && wp_finite(e.alpha_x);
+    c.ty0 = ty * WP_TILE; c.tx0 = tx * WP_TILE;
+    c.y0 = c.x0 = 0; c.th = c.tw = 0; c.any = c.h >= 1 && c.w >= 1; c.staged = false;
+    c.n_token = n_token; c.n_class = n_class; c.Cs = Cs; c.dtype = dtype;
+    c.grid = (char*)grid + dst * Cs * (dtype == 0 ? 4 : 2);
+    c.lab_out = lab_out + dst; c.aux_out = aux_out + dst;
+    c.tile_flag = tile_flags + (size_t)b * tiles + (size_t)ty * tiles_x + tx;
+}
+
+// ---- phase 2 of the elastic warp: one output pixel per lane, taps from global memory ---------------------------------------------------
+WP_DEV void we_ph_pixel(const WeCtx& e, const WpLds& s, int tid) {
+    const WpCtx& c = e.c;
+    if (tid == 0) s.flag[0] = c.finite ? 0 : WP_FLAG_MATRIX;         // (the only store to the flag: a pixel cannot overflow its slots)
+    const int oy = c.ty0 + tid / WP_TILE, ox = c.tx0 + tid % WP_TILE;
+    int set[WP_MAXSET] = {-1, -1, -1, -1};
+    int64_t lab = -1, aux = -1;
+    if (oy < c.ho && ox < c.wo) {                                     // inside the document: oy < h <= H, ox < w <= W
+        lab = 0; aux = 0;
+        if (c.finite) {
+            const uint8_t* f = e.fld + ((size_t)oy * c.W + ox) * 2;
+            const double sy = we_coord((double)oy, (double)f[0], e.alpha_y), sx = we_coord((double)ox, (double)f[1], e.alpha_x);
+            if (sy >= 0.0 && sy <= (double)(c.h - 1) && sx >= 0.0 && sx <= (double)(c.w - 1)) {
+                WeTaps t;
+                int j0, j1, i0, i1;
+                we_axis(sy, c.h, j0, j1, t.vy, t.uy);                 // 0 <= j0 <= j1 <= h - 1
+                we_axis(sx, c.w, i0, i1, t.vx, t.ux);
+                t.at[0] = (size_t)j0 * c.W + i0; t.at[1] = (size_t)j0 * c.W + i1;
+                t.at[2] = (size_t)j1 * c.W + i0; t.at[3] = (size_t)j1 * c.W + i1;
+                int tap[4], got[4];
+#pragma unroll
+                for (int k = 0; k < 4; ++k) tap[k] = wp_value(c.ids[t.at[k]]);
+                const int n = we_set_values(t, tap, 0, c.n_token, got);
+#pragma unroll
+                for (int k = 0; k < WP_MAXSET; ++k) set[k] = k < n ? got[k] : -1;
+#pragma unroll
+                for (int k = 0; k < 4; ++k) tap[k] = wp_value(c.lab[t.at[k]]);
+                lab = we_label_of(t, tap, c.n_class);
+#pragma unroll
+                for (int k = 0; k < 4; ++k) tap[k] = wp_value(c.aux[t.at[k]]);
+                aux = we_label_of(t, tap, c.n_class);
+            }
+        }
+    }
+    int* mine = s.set + tid * WP_MAXSET;
+#pragma unroll
+    for (int k = 0; k < WP_MAXSET; ++k) mine[k] = set[k];
+    if (oy < c.Ho && ox < c.Wo) {
+        const size_t at = (size_t)oy * c.Wo + ox;
+        c.lab_out[at] = lab; c.aux_out[at] = aux;
+    }
+}
+
+WP_DEV void we_carve(WpLds& s, int* base) {
+    s.ids = s.lab = s.aux = s.cand = 0;                             // nothing is staged and no lane keeps a list
+    s.set = base; s.flag = base + WP_THREADS * WP_MAXSET;
+}
+
+WP_DEV void we_body(const WeCtx& e, const WpLds& s) {
+    { const WeCtx& c = e; WP_PHASE(we_ph_pixel); }
+    { const WpCtx& c = e.c; WP_PHASE(wp_ph_store); }
+}
+
 #ifdef MSAU_WARP_CPU
+extern "C" int64_t msau_kv_elastic_train_ws_ints(int B, int Ho, int Wo) {
+    return (int64_t)B * ((Ho + WP_TILE - 1) / WP_TILE) * ((Wo + WP_TILE - 1) / WP_TILE);
+}
+
+// the launch, lane by lane on the host: same arguments as msau_kv_elastic_train without the stream
+extern "C" int msau_kv_elastic_train_cpu(int dtype, const int32_t* ids, const int64_t* labels, const int64_t* aux_labels,
+                                         const int32_t* src_sizes, const uint8_t* fields, const double* alphas, int B, int H, int W, int Ho,
+                                         int Wo, int n_token, int Cs, int n_class, void* grid, int64_t* labels_out, int64_t* aux_out,
+                                         int32_t* flags, int32_t* ws) {
+    if (n_token > WP_VALUE_MAX + 1 || n_class > WP_VALUE_MAX + 1) return 2;
+    int lds[WE_LDS_INTS];
+    const int tiles_y = (Ho + WP_TILE - 1) / WP_TILE, tiles_x = (Wo + WP_TILE - 1) / WP_TILE, tiles = tiles_x * tiles_y;
+    for (int b = 0; b < B; ++b) {
+        for (int ty = 0; ty < tiles_y; ++ty)
+            for (int tx = 0; tx < tiles_x; ++tx) {
+                WeCtx e;
+                we_ctx(e, dtype, ids, labels, aux_labels, src_sizes, fields, alphas, b, ty, tx, tiles_x, tiles, H, W, Ho, Wo, n_token,
+                       Cs, n_class, grid, labels_out, aux_out, ws);
+                WpLds s;
+                we_carve(s, lds);
+                we_body(e, s);
+            }
+        int f = 0;
+        for (int t = 0; t < tiles; ++t) f |= ws[(size_t)b * tiles + t];
+        flags[b] = f;
+    }
+    return 0;
+}
+
 extern "C" int64_t msau_kv_warp_train_ws_ints(int B, int Ho, int Wo) {
     return (int64_t)B * ((Ho + WP_TILE - 1) / WP_TILE) * ((Wo + WP_TILE - 1) / WP_TILE);
 }
@@ -448,6 +647,50 @@ extern "C" int msau_kv_warp_train(void* stream, int dtype, const int32_t* ids, c
     hipLaunchKernelGGL(kv_warp_train_kernel, dim3(tiles_x, tiles_y, B), dim3(WP_THREADS), 0, st, dtype, ids, labels, aux_labels,
                        src_sizes, warps, dst_sizes, H, W, Ho, Wo, n_token, Cs, n_class, grid, labels_out, aux_out, ws);
     MSAU_CHECK_LAUNCH("kv_warp_train");
+    hipLaunchKernelGGL(kv_warp_flags_kernel, dim3(B), dim3(64), 0, st, ws, tiles_x * tiles_y, flags);
+    MSAU_CHECK_LAUNCH("kv_warp_flags");
+    return 0;
+}
+
+__global__ void __launch_bounds__(WP_THREADS)
+kv_elastic_train_kernel(int dtype, const int32_t* ids, const int64_t* labels, const int64_t* aux_labels, const int32_t* src_sizes,
+                        const uint8_t* fields, const double* alphas, int H, int W, int Ho, int Wo, int n_token, int Cs, int n_class,
+                        void* grid, int64_t* labels_out, int64_t* aux_out, int32_t* ws) {
+    __shared__ int we_lds[WE_LDS_INTS];
+    WeCtx e;
+    we_ctx(e, dtype, ids, labels, aux_labels, src_sizes, fields, alphas, (int)blockIdx.z, (int)blockIdx.y, (int)blockIdx.x,
+           (int)gridDim.x, (int)(gridDim.x * gridDim.y), H, W, Ho, Wo, n_token, Cs, n_class, grid, labels_out, aux_out, ws);
+    WpLds s;
+    we_carve(s, we_lds);
+    we_body(e, s);
+}
+
+extern "C" int64_t msau_kv_elastic_train_ws_ints(int B, int Ho, int Wo) { return msau_kv_warp_train_ws_ints(B, Ho, Wo); }
+
+extern "C" int msau_kv_elastic_train(void* stream, int dtype, const int32_t* ids, const int64_t* labels, const int64_t* aux_labels,
+                                     const int32_t* src_sizes, const uint8_t* fields, const double* alphas, int B, int H, int W, int Ho,
+                                     int Wo, int n_token, int Cs, int n_class, void* grid, int64_t* labels_out, int64_t* aux_out,
+                                     int32_t* flags, int32_t* ws) {
+    MSAU_CHECK_ARG(ids && labels && aux_labels && src_sizes && fields && alphas && grid && labels_out && aux_out && flags && ws,
+                   "kv_elastic_train: null pointer");
+    MSAU_CHECK_ARG(dtype == 0 || dtype == 1, "kv_elastic_train: dtype %d is neither MSAU_F32 nor MSAU_BF16", dtype);
+    MSAU_CHECK_ARG(B > 0 && B <= 65535 && H > 0 && W > 0 && Ho > 0 && Wo > 0 && (int64_t)B * H * W < (1ll << 31)
+                   && (int64_t)B * Ho * Wo < (1ll << 31), "kv_elastic_train: bad shape B = %d, H = %d, W = %d, Ho = %d, Wo = %d", B, H, W, Ho,
+                   Wo);
+    MSAU_CHECK_ARG(cdiv(Ho, WP_TILE) <= 65535, "kv_elastic_train: Ho = %d is more than 65535 tiles", Ho);
+    MSAU_CHECK_ARG(n_token > 0 && n_class > 0 && Cs > 0 && Cs % 8 == 0 && n_token <= Cs && n_token <= WP_VALUE_MAX + 1
+                   && n_class <= WP_VALUE_MAX + 1,
+                   "kv_elastic_train: n_token = %d, Cs = %d, n_class = %d (need n_token <= Cs, Cs %% 8 == 0, both counts <= 32767)", n_token,
+                   Cs, n_class);
+    MSAU_CHECK_ARG((uintptr_t)grid % 16 == 0 && ((uintptr_t)labels | (uintptr_t)aux_labels | (uintptr_t)labels_out | (uintptr_t)aux_out
+                                                 | (uintptr_t)alphas) % 8 == 0
+                   && ((uintptr_t)ids | (uintptr_t)src_sizes | (uintptr_t)flags | (uintptr_t)ws) % 4 == 0,
+                   "kv_elastic_train: the input must be 16-byte aligned, every other array to its element size");
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const int tiles_x = cdiv(Wo, WP_TILE), tiles_y = cdiv(Ho, WP_TILE);
+    hipLaunchKernelGGL(kv_elastic_train_kernel, dim3(tiles_x, tiles_y, B), dim3(WP_THREADS), 0, st, dtype, ids, labels, aux_labels,
+                       src_sizes, fields, alphas, H, W, Ho, Wo, n_token, Cs, n_class, grid, labels_out, aux_out, ws);
+    MSAU_CHECK_LAUNCH("kv_elastic_train");
     hipLaunchKernelGGL(kv_warp_flags_kernel, dim3(B), dim3(64), 0, st, ws, tiles_x * tiles_y, flags);
     MSAU_CHECK_LAUNCH("kv_warp_flags");
     return 0;

@@ -1277,25 +1277,31 @@ class TrainEngine:
         canvas (rounded up to `round_to`).  Tables without a warp in such a group take the identity.  The launch leaves one flag
         per document, which the host reads before the sweep (the one wait of this path); a flagged document is warped by
         `kv_warp.warp_host` and uploaded (kv_data.STATS["host_warped"]).  A group without warps takes the path above, launch for
-        launch."""
+        launch.  A group whose warps are `kv_warp.Elastic` (the generator's elastic augmentation, `KVTrainBatches(...,
+        imresize="pillow")`) takes the same route through msau_kv_elastic_train, tables without a warp as `identity_elastic`, a
+        flagged document through `kv_warp.elastic_host`; a group that mixes the two kinds is a ValueError."""
         self._eager("step_kv")
         cost = unet_cost(cost)
-        from .training import kv_data
+        from .training import kv_data, kv_warp
+        elastic = any(isinstance(t.warp, kv_warp.Elastic) for t in tables)
+        if elastic and any(isinstance(t.warp, kv_warp.Warp) for t in tables):         # (on the host, before anything is launched)
+            raise ValueError("step_kv: a group mixes affine / rotation warps with elastic ones; a group takes one kind (and tables without)")
         dev = self.model._flat.device
         ids, labels, aux_labels, sizes = kv_data.paint_train_device(tables, round_to=round_to, device=dev)
         if all(t.warp is None for t in tables):
             return self.step_unet(ids, labels, aux_labels, sizes=sizes, class_weights=class_weights, stats=stats, cost=cost)
-        from .training import kv_warp
         m = self.model
         cw = self._class_weights(class_weights, m.n_class)
-        warps = [kv_warp.identity_warp(t.shape) if t.warp is None else t.warp for t in tables]
+        identity, launch, upload = ((kv_warp.identity_elastic, kv_warp.elastic_train_device, kv_warp.upload_host_elastic) if elastic else
+                                    (kv_warp.identity_warp, kv_warp.warp_train_device, kv_warp.upload_host_warp))
+        warps = [identity(t.shape) if t.warp is None else t.warp for t in tables]
         wsizes, (Ho, Wo) = kv_warp.warped_canvas(warps, round_to=round_to)
         B = len(tables)
         plan = m._plan(B, Ho, Wo, dev, True, m._check_sizes_for(torch.from_numpy(wsizes), B, Ho, Wo))
         grid = plan.input_nhwc
-        wl, wa, flags = kv_warp.warp_train_device(ids, labels, aux_labels, sizes, warps, grid, m.channels, m.n_class, plan.dtype)
+        wl, wa, flags = launch(ids, labels, aux_labels, sizes, warps, grid, m.channels, m.n_class, plan.dtype)
         for b in torch.nonzero(flags.cpu()).reshape(-1).tolist():
-            kv_warp.upload_host_warp(b, tables[b], warps[b], grid, wl, wa, m.channels, m.n_class)
+            upload(b, tables[b], warps[b], grid, wl, wa, m.channels, m.n_class)
             kv_data.STATS["host_warped"] += 1
         # (the kernel and the host warp leave zeros outside the warped extents: nothing to clear)
         return self._step_unet(plan, wl, wa, cw, stats, cost, nhwc_ready=True, nhwc_clean=True)

@@ -14,18 +14,19 @@ generator's expressions in the generator's order, so a table under `random.Rando
 loop of the generator: the fallback for a document whose table is not `ok` (STATS counts them) and what the gather is tested
 against.  The generator's affine and rotation warps are a table's optional `warp` (msau_amd/training/kv_warp.py): `KVTrainBatches`
 draws them when `kwargs_dat` asks for them and `TrainEngine.step_kv` resamples the painted canvases on the device
-(csrc/warp.hip, `msau_kv_warp_train`).  The elastic warp is not here."""
+(csrc/warp.hip, `msau_kv_warp_train`).  The generator's elastic warp is a `kv_warp.Elastic` in the same slot, drawn
+when `KVTrainBatches(..., imresize="pillow")` names the restatement of its removed resize, and resampled by `msau_kv_elastic_train`."""
 from __future__ import annotations
 
 import json
 import random
 from dataclasses import dataclass
-from typing import List, Optional, Sequence, Tuple
+from typing import List, Optional, Sequence, Tuple, Union
 
 import numpy as np
 
 from ..inference import glyphs as G
-from .kv_warp import Warp, affine_warp, mod90_angle, rotate_warp
+from .kv_warp import ELASTIC_GRID, Elastic, Warp, affine_warp, elastic_field, mod90_angle, rotate_warp
 
 LABEL_INTS = 2
 
@@ -47,7 +48,7 @@ class TrainTable:
     line_rec: Optional[np.ndarray]      # int32 [n_lines, 8] as glyphs.GlyphTable; None when the table cannot represent the document
     glyph_rec: Optional[np.ndarray]     # int16 [n_glyphs, 4]
     reason: str = ""                    # why not, when it cannot
-    warp: Optional[Warp] = None         # the generator's affine or rotation augmentation of the painted document, if any
+    warp: Optional[Union[Warp, Elastic]] = None     # the generator's affine, rotation or elastic augmentation of the painted document, if any
 
     @property
     def ok(self) -> bool:
@@ -247,11 +248,19 @@ class KVTrainBatches:
     rotation the generator's `uniform(-20, 20)`.  `rotateMod90_tr` maps that angle as the generator does, which -- as written there
     -- always yields -45 degrees (kv_warp.mod90_angle); the oddity is kept.  With every flag off not one extra draw is taken.
     Refused with NotImplementedError: `affine_tr` together with a rotation (the generator re-interpolates the grey-level planes of the
-    first warp, which the id canvases cannot express), `elastic_tr` (the generator's version needs `scipy.misc.imresize`, which no
-    current scipy has) and the `*_val` flags (validation is not augmented here)."""
+    first warp, which the id canvases cannot express) and the `*_val` flags (validation is not augmented here).
+
+    `elastic_tr` (with the generator's keys `elastic_val_x` and `elastic_value_y`, both 0.0002 by default; `elastic_val` is the
+    validation flag) needs `scipy.misc.imresize`, which no current scipy has.  `imresize="pillow"` names its restatement
+    (kv_warp.imresize_bicubic: `bytescale` + Pillow's bicubic resize) and turns the flag on; without it `elastic_tr` is refused with
+    NotImplementedError, any other value is a ValueError.  A table then carries a `kv_warp.Elastic`: one `getrandbits(32)` per
+    document, after the table's own draws, seeds the `RandomState` of its two fields.  A document under 25 pixels on a side -- on
+    which the generator itself fails -- still takes its draw and keeps `warp is None`.  `elastic_tr` together with `affine_tr`,
+    `rotate_tr` or `rotateMod90_tr` is refused (the generator re-interpolates grey-level planes there)."""
 
     def __init__(self, paths: Sequence[str], charset_path: str, n_class: int, batch_size: int, scale_min: float = 2.0,
-                 scale_max: float = 4.0, text_err: float = 0.1, shuffle: bool = True, seed: int = 0, kwargs_dat: Optional[dict] = None):
+                 scale_max: float = 4.0, text_err: float = 0.1, shuffle: bool = True, seed: int = 0, kwargs_dat: Optional[dict] = None,
+                 imresize: Optional[str] = None):
         if len(paths) == 0 or batch_size < 1:
             raise ValueError("KVTrainBatches: needs at least one document and batch_size >= 1")
         kw = dict(kwargs_dat or {})
@@ -260,9 +269,18 @@ class KVTrainBatches:
         if self.affine and (self.rotate or self.rotate_mod90):
             raise NotImplementedError("KVTrainBatches: affine_tr together with rotate_tr / rotateMod90_tr -- the generator rotates the "
                                       "grey-level planes the affine warp interpolated, which cannot be computed from the id canvases")
-        if kw.get("elastic_tr", False):
+        if imresize not in (None, "pillow"):
+            raise ValueError(f"KVTrainBatches: imresize = {imresize!r}; the one restatement of scipy.misc.imresize is \"pillow\"")
+        self.elastic = bool(kw.get("elastic_tr", False))
+        self.elastic_value_x, self.elastic_value_y = float(kw.get("elastic_val_x", 0.0002)), float(kw.get("elastic_value_y", 0.0002))
+        if self.elastic and imresize is None:
             raise NotImplementedError("KVTrainBatches: elastic_tr -- the generator's elastic_transform needs scipy.misc.imresize, which "
-                                      "no current scipy has")
+                                      "no current scipy has; pass imresize=\"pillow\" to take its restatement with Pillow "
+                                      "(kv_warp.imresize_bicubic)")
+        if self.elastic and (self.affine or self.rotate or self.rotate_mod90):
+            raise NotImplementedError("KVTrainBatches: elastic_tr together with affine_tr / rotate_tr / rotateMod90_tr -- the generator "
+                                      "re-interpolates the grey-level planes of the first warp, which cannot be computed from the id "
+                                      "canvases")
         on = [k for k in ("affine_val", "elastic_val", "rotate_val", "rotateMod90_val") if kw.get(k, False)]
         if on:
             raise NotImplementedError(f"KVTrainBatches: {', '.join(on)} -- validation tables are not augmented")
@@ -298,6 +316,10 @@ class KVTrainBatches:
         elif self.rotate or self.rotate_mod90:
             angle = self.rng.uniform(-20, 20)
             t.warp = rotate_warp(t.shape, mod90_angle(angle) if self.rotate_mod90 else angle)
+        elif self.elastic:
+            rs = np.random.RandomState(self.rng.getrandbits(32))            # (drawn whatever the size: the stream does not depend on it)
+            if min(t.shape) >= ELASTIC_GRID:
+                t.warp = elastic_field(t.shape, self.elastic_value_x, self.elastic_value_y, rs)
         return t
 
     def validation(self, scale: float = 3.0) -> List[List[TrainTable]]:

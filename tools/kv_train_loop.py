@@ -13,7 +13,10 @@ the loss trajectory, and one JSON line.  The two routes see the same jitter sett
 differ (the engine clips the gradient norm), so the trajectories are to be read side by side, not compared digit for digit.
 --warp affine|rotate turns on the generator's augmentation (kwargs_dat affine_tr / rotate_tr): the tables route resamples the painted
 canvases on the device (msau_kv_warp_train), the trainer route warps the one-hot planes x 255 with scipy.ndimage on the host, plane
-by plane, as the generator does -- the comparison that `--warp` is about.
+by plane, as the generator does -- the comparison that `--warp` is about.  --warp elastic is the generator's elastic_tr
+(`KVTrainBatches(..., imresize="pillow")`: the fields are drawn on the host with Pillow, msau_kv_elastic_train resamples; the trainer
+route calls scipy's map_coordinates(order=1) per plane).  --time-launch adds, for the tables route under a --warp, the device time of
+the warp launch alone on the last group (events around --steps calls, upload included) and the host time of a document's draw.
 Not the headline metric (bench.py is); numbers are quoted in DESIGN.md 5e and profiles/kv_train.md.
 
 --eval times VALIDATION instead (forward only, loss and accuracy per document), again two routes over the same deterministic tables
@@ -51,21 +54,25 @@ def model(n_token, n_class, dtype):
 
 
 def batches(args, batch_size):
-    kwargs_dat = {"affine": {"affine_tr": True}, "rotate": {"rotate_tr": True}}.get(args.warp, {})
+    kwargs_dat = {"affine": {"affine_tr": True}, "rotate": {"rotate_tr": True}, "elastic": {"elastic_tr": True}}.get(args.warp, {})
     return KVTrainBatches(args.layouts, args.charset, args.n_class, batch_size, args.scale_min, args.scale_max, args.text_err,
-                          shuffle=True, seed=args.seed, kwargs_dat=kwargs_dat)
+                          shuffle=True, seed=args.seed, kwargs_dat=kwargs_dat, imresize="pillow" if args.warp == "elastic" else None)
 
 
 def scipy_warp(t, maps):
     """the generator's host route for a table's warp: the one-hot maps [h, w, c] x 255 as uint8, every plane through scipy's cubic
     spline, thresholded at > 64; the targets made one-hot again (1 first, then the smallest set class, else 0)"""
     from scipy import ndimage
-    from msau_amd.training.kv_warp import _label_of
+    from msau_amd.training.kv_warp import Elastic, _label_of, elastic_coords
+    if isinstance(t.warp, Elastic):                                         # (order 1, at the elastic warp's coordinates)
+        coords = elastic_coords(t.warp)
+        warp_plane = lambda plane: ndimage.map_coordinates(plane, coords, order=1)
+    else:
+        warp_plane = lambda plane: ndimage.affine_transform(plane, t.warp.matrix, offset=t.warp.offset, output_shape=t.warp.out_shape)
     out = []
     for k, m in enumerate(maps):
         planes = m * np.uint8(255)
-        res = np.stack([ndimage.affine_transform(planes[:, :, d], t.warp.matrix, offset=t.warp.offset, output_shape=t.warp.out_shape)
-                        for d in range(planes.shape[2])], axis=2) > 64
+        res = np.stack([warp_plane(planes[:, :, d]) for d in range(planes.shape[2])], axis=2) > 64
         out.append(res.astype("B") if k == 0 else np.eye(m.shape[2], dtype="B")[_label_of(res)])
     return out
 
@@ -94,10 +101,41 @@ def run_tables(args):
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
     docs = args.steps * args.batch_size
-    return dict(route="tables", cost=args.cost, batch_size=args.batch_size, optimizer=args.optimizer, clip=not args.no_clip, weight_decay=args.weight_decay,
+    extra = time_launch(args, eng, it) if args.time_launch and args.warp else {}
+    return dict(**extra, route="tables", cost=args.cost, batch_size=args.batch_size, optimizer=args.optimizer, clip=not args.no_clip, weight_decay=args.weight_decay,
                 optim_launches=[key for key, _ in eng.optim_launches()], docs_per_s=docs / dt,
                 h2d_bytes_per_doc=kv_data.STATS["h2d_bytes"] / docs,
                 host_painted=kv_data.STATS["host_painted"], host_warped=kv_data.STATS["host_warped"], warp=args.warp, loss=[round(float(l[0]), 5) for l in torch.stack(losses).cpu()])
+
+
+def time_launch(args, eng, it):
+    """the warp launch of one group alone, as step_kv issues it (upload of its records, the tiles, the flags): device events around
+    --steps calls; and the host time of a document's warp draw"""
+    from msau_amd.training import kv_warp
+    tables = next(it)
+    t0 = time.perf_counter()
+    for t in tables:
+        it._augment(t)
+    draw_ms = (time.perf_counter() - t0) * 1e3 / len(tables)
+    elastic = args.warp == "elastic"
+    ident, launch = (kv_warp.identity_elastic, kv_warp.elastic_train_device) if elastic else (kv_warp.identity_warp, kv_warp.warp_train_device)
+    warps = [ident(t.shape) if t.warp is None else t.warp for t in tables]
+    ids, labels, aux, sizes = kv_data.paint_train_device(tables, round_to=args.round_to, device=eng.model._flat.device)
+    wsizes, (Ho, Wo) = kv_warp.warped_canvas(warps, round_to=args.round_to)
+    grid = eng.input_nhwc(len(tables), Ho, Wo)
+    m = eng.model
+    dtype = m._plan_for_shape(len(tables), Ho, Wo, grid.device, True).dtype
+    go = lambda: launch(ids, labels, aux, sizes, warps, grid, m.channels, m.n_class, dtype)
+    for _ in range(3):
+        go()
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    a.record()
+    for _ in range(args.steps):
+        go()
+    b.record()
+    torch.cuda.synchronize()
+    return dict(warp_launch_ms=a.elapsed_time(b) / args.steps, warp_canvas=[len(tables), int(ids.shape[1]), int(ids.shape[2]), Ho, Wo],
+                warp_pixels=int(wsizes.prod(axis=1).sum()), warp_draw_ms_per_doc=draw_ms)
 
 
 def run_trainer(args):
@@ -241,8 +279,9 @@ def main():
     ap.add_argument("--gamma", type=float, default=2.0, help="--cost focal")
     ap.add_argument("--smooth", type=float, default=1.0, help="--cost dice")
     ap.add_argument("--seed", type=int, default=0)
-    ap.add_argument("--warp", default="", choices=["", "affine", "rotate"], help="the generator's augmentation: on the device in the tables "
-                    "route, scipy.ndimage on the host in the trainer route")
+    ap.add_argument("--warp", default="", choices=["", "affine", "rotate", "elastic"], help="the generator's augmentation: on the device in the "
+                    "tables route, scipy.ndimage on the host in the trainer route")
+    ap.add_argument("--time-launch", action="store_true", help="tables route with --warp: also time the warp launch alone and the draw")
     ap.add_argument("--round-to", type=int, default=32, help="canvas sizes are rounded up to a multiple (fewer distinct plans)")
     ap.add_argument("--routes", default="tables,trainer")
     ap.add_argument("--eval", action="store_true", help="time validation (eval_kv against the Trainer's route) instead of training")
@@ -260,6 +299,9 @@ def main():
         print(f"{r['route']:8s} batch {r['batch_size']:3d}: {r['docs_per_s']:9.1f} documents/s (whole step)  "
               f"{r['h2d_bytes_per_doc']:12.0f} bytes uploaded per document")
         print(f"{'':8s} loss: {r['loss']}")
+        if "warp_launch_ms" in r:
+            print(f"{'':8s} warp launch alone: {r['warp_launch_ms']:.3f} ms (B, H, W, Ho, Wo = {r['warp_canvas']}, {r['warp_pixels']} pixels inside); "
+                  f"draw on the host: {r['warp_draw_ms_per_doc']:.3f} ms per document; step: {1e3 * r['batch_size'] / r['docs_per_s']:.2f} ms")
     print(json.dumps(dict(dtype=args.dtype, steps=args.steps, results=out)))
 
 
