@@ -842,6 +842,27 @@ int msau_kv_regions_large(void* stream, const uint8_t* argmax, const uint16_t* l
                           const int32_t* box_off, const int32_t* extent, int B, int H, int W, int n_class, const int32_t* docs,
                           int n_docs, const int64_t* ws_off, int32_t* workspace, int64_t workspace_ints, int32_t* header,
                           int32_t* regions, int cap_regions, int32_t* pairs, int cap_pairs, int32_t* overflow);
+/*   msau_kv_regions_scored, msau_kv_regions_large_scored : the two calls above with a confidence per region.  Everything they
+ *                            write they write as above (header, regions, pairs and overflow are the same words), plus
+ *                              probs   fp32 [B][H][W][n_class] on the canvas: the head's probabilities (head_probs), read as stored
+ *                              scores  int64 [B][cap_regions]: row r of document b belongs to the region record in row r of
+ *                                      `regions`: the sum over the region's pixels (those of the closed mask, so the gap pixels
+ *                                      the closing added count with the probability they have) of q(p) = rint(p * 65536), p =
+ *                                      probs[b][y][x][c] of the region's class c, rounded to nearest even (the product by 2^16 is
+ *                                      exact).  The mean probability of the region is scores / (65536 * pixels).  An integer
+ *                                      sum, independent of arrival order: at most 24 576 * 65 536 < 2^31 in the LDS form, up to
+ *                                      2^47 in the large form, summed in 64 bits in both.  Every row a class reserves is written,
+ *                                      no other row is touched; a flagged document's rows are to be ignored.
+ *                            NULL probs or scores are refused (MSAU_ERR_ARG). */
+int msau_kv_regions_scored(void* stream, const uint8_t* argmax, const float* probs, const uint16_t* line_ids, const uint16_t* char_pos,
+                           const int32_t* boxes, const int32_t* box_off, const int32_t* extent, int B, int H, int W, int n_class,
+                           int32_t* header, int32_t* regions, int cap_regions, int32_t* pairs, int cap_pairs, int64_t* scores,
+                           int32_t* overflow);
+int msau_kv_regions_large_scored(void* stream, const uint8_t* argmax, const float* probs, const uint16_t* line_ids, const uint16_t* char_pos,
+                                 const int32_t* boxes, const int32_t* box_off, const int32_t* extent, int B, int H, int W, int n_class,
+                                 const int32_t* docs, int n_docs, const int64_t* ws_off, int32_t* workspace, int64_t workspace_ints,
+                                 int32_t* header, int32_t* regions, int cap_regions, int32_t* pairs, int cap_pairs, int64_t* scores,
+                                 int32_t* overflow);
 
 /* ------------------------------------------------------------------------------------------
  * Mask painter for key-value inference (inference/kv_model.py:83-148 `_generate_masks_from_label`, the per-pixel part):

@@ -229,6 +229,9 @@ _SIGNATURES = {
     "msau_kv_regions": (C.c_int, [vp] * 7 + [C.c_int] * 4 + [vp, vp, C.c_int, vp, C.c_int, vp]),
     "msau_kv_regions_large": (C.c_int, [vp] * 7 + [C.c_int] * 4 + [C.POINTER(i32), C.c_int, C.POINTER(i64), vp, i64]
                               + [vp, vp, C.c_int, vp, C.c_int, vp]),
+    "msau_kv_regions_scored": (C.c_int, [vp] * 8 + [C.c_int] * 4 + [vp, vp, C.c_int, vp, C.c_int, vp, vp]),
+    "msau_kv_regions_large_scored": (C.c_int, [vp] * 8 + [C.c_int] * 4 + [C.POINTER(i32), C.c_int, C.POINTER(i64), vp, i64]
+                                     + [vp, vp, C.c_int, vp, C.c_int, vp, vp]),
     "msau_kv_paint": (C.c_int, [vp] * 6 + [C.c_int] * 3 + [vp, vp, vp]),
     "msau_kv_paint_train": (C.c_int, [vp] * 7 + [C.c_int] * 3 + [vp, vp, vp]),
     "msau_kv_warp_train_ws_ints": (i64, [C.c_int] * 3),

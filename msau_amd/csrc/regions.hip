@@ -11,6 +11,9 @@
 //                                   indexed alike; everything else as here)
 //   pairs    4 x uint32 [RG_HASH]   open-addressing hash keyed (k << 16) | v, sorted in place (bitonic) before it is written
 //   comps    6 x int32 [RG_MAXK]    first pixel, box, count
+// The scored form (rg_body<true>) adds, per component, the sum over its pixels of q(p) = rint(p * 65536), p the probability of the
+// workgroup's class at the pixel (fp32 [B][H][W][n_class] on the canvas): 64-bit integers in two of the component tables, which
+// are dead once rg_ph_write has run, written to scores[roff + k] beside the region record of the same row.
 // Every loop is a counted loop whose bound follows from the document's pixel count (or from the sizes of the LDS tables); a
 // document that does not fit, a table that is full and a labelling that has not converged set the document's overflow flag
 // and end the workgroup.  The results are integers and do not depend on arrival order: the component numbers are ranks of root
@@ -20,6 +23,7 @@
 // The body is written as phases between workgroup barriers; with -DMSAU_REGIONS_CPU the same phases compile as plain C++ and
 // the lanes of a phase run one after another (tests/test_regions_cpu.py builds that form with the host compiler).
 #ifdef MSAU_REGIONS_CPU
+#include <math.h>
 #include <stdint.h>
 #include <stdlib.h>
 #include <string.h>
@@ -28,9 +32,11 @@
 RG_DEV int rg_amin(int* p, int v) { int o = *p; if (v < o) *p = v; return o; }
 RG_DEV int rg_amax(int* p, int v) { int o = *p; if (v > o) *p = v; return o; }
 RG_DEV int rg_aadd(int* p, int v) { int o = *p; *p = o + v; return o; }
+RG_DEV void rg_aadd64(long long* p, long long v) { *p += v; }
 RG_DEV int rg_aor(int* p, int v) { int o = *p; *p = o | v; return o; }
 RG_DEV unsigned rg_acas(unsigned* p, unsigned cmp, unsigned v) { unsigned o = *p; if (o == cmp) *p = v; return o; }
 RG_DEV int rg_ld(const int* p) { return *p; }
+RG_DEV int rg_rint(float v) { return (int)lrintf(v); }                    // to nearest even (the default rounding mode)
 #define RG_SYNC() do { } while (0)
 #else
 #include "msau_common.h"
@@ -39,10 +45,12 @@ RG_DEV int rg_ld(const int* p) { return *p; }
 RG_DEV int rg_amin(int* p, int v) { return atomicMin(p, v); }
 RG_DEV int rg_amax(int* p, int v) { return atomicMax(p, v); }
 RG_DEV int rg_aadd(int* p, int v) { return atomicAdd(p, v); }
+RG_DEV void rg_aadd64(long long* p, long long v) { atomicAdd((unsigned long long*)p, (unsigned long long)v); }
 RG_DEV int rg_aor(int* p, int v) { return atomicOr(p, v); }
 RG_DEV unsigned rg_acas(unsigned* p, unsigned cmp, unsigned v) { return atomicCAS(p, cmp, v); }
 // a label another wave may change in the same phase: never from a register or (large form) from the L1, always a value written
 RG_DEV int rg_ld(const int* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+RG_DEV int rg_rint(float v) { return __float2int_rn(v); }                 // to nearest even
 #define RG_SYNC() __syncthreads()
 #endif
 // a uniform exit: every lane reads the flags, THEN a barrier, so that no lane of the next phase can change them under a reader
@@ -72,12 +80,16 @@ struct RgCtx {                      // one (document, class)
     int32_t* regions;               // the document's slices of the output lists
     int32_t* pairs;
     int cap_regions, cap_pairs;
+    const float* probs;             // the scored form only: the document's probabilities, pixel (y, x) class k at (y * W + x) * n_class + k
+    int64_t* scores;                //                       the document's rows [cap_regions], beside `regions`
+    int n_class;
 };
 
 struct RgLds {
     int* L;                                          // [RG_MAXPIX] in LDS, or [h * w] of the workspace (large form)
     unsigned* hk; int* hn; int* hmn; int* hmx;       // [RG_HASH]
     int* cfirst; int* cy0; int* cy1; int* cx0; int* cx1; int* ccnt;   // [RG_MAXK]
+    long long* sum;                                  // [RG_MAXK] over cy0 and cy1, once rg_ph_write has read them (scored form)
     int* scan;                                       // [RG_THREADS]
     int* part;                                       // [32]
     int* misc;                                       // [RG_MISC]
@@ -93,7 +105,7 @@ RG_DEV void rg_carve(RgLds& s, int* L, int* base) {
     s.hmn = base; base += RG_HASH;
     s.hmx = base; base += RG_HASH;
     s.cfirst = base; base += RG_MAXK;
-    s.cy0 = base; base += RG_MAXK;
+    s.cy0 = base; s.sum = (long long*)base; base += RG_MAXK;
     s.cy1 = base; base += RG_MAXK;
     s.cx0 = base; base += RG_MAXK;
     s.cx1 = base; base += RG_MAXK;
@@ -335,7 +347,43 @@ RG_DEV void rg_ph_write(const RgCtx& c, const RgLds& s, int tid) {
     }
 }
 
+// ---- the scored form's phases, behind rg_ph_write ------------------------------------------------------------------
+// q(p) = rint(p * 65536): the scale is a power of two, so the product is exact and the conversion is the only rounding
+RG_DEV int rg_quant(float p) { return rg_rint(p * 65536.0f); }
+
+RG_DEV void rg_ph_score_zero(const RgCtx& c, const RgLds& s, int tid) {
+    const int nc = s.misc[RG_NCOMP];
+    for (int k = tid; k < nc; k += RG_THREADS) s.sum[k] = 0;
+}
+
+// lane t owns pixels [t * chunk, (t + 1) * chunk) as in rg_ph_count: it sums a run of one component locally and adds the run's
+// sum when the component changes.  A component of RG_LARGE_MAXPIX pixels at p = 1 sums to less than 2^47.
+RG_DEV void rg_ph_score_sum(const RgCtx& c, const RgLds& s, int tid) {
+    const int npix = c.h * c.w, chunk = (npix + RG_THREADS - 1) / RG_THREADS;
+    int cur = -1;
+    long long run = 0;
+    for (int i = 0; i < chunk; ++i) {
+        const int p = tid * chunk + i;
+        if (p >= npix) break;
+        if (s.L[p] == RG_BG) continue;
+        const int k = rg_comp(s, p), y = p / c.w, x = p - y * c.w;
+        if (k != cur) {
+            if (cur >= 0) rg_aadd64(s.sum + cur, run);
+            cur = k; run = 0;
+        }
+        run += rg_quant(c.probs[((size_t)y * c.W + x) * c.n_class + c.c]);
+    }
+    if (cur >= 0) rg_aadd64(s.sum + cur, run);
+}
+
+// every row this class reserved, and no other
+RG_DEV void rg_ph_score_write(const RgCtx& c, const RgLds& s, int tid) {
+    const int nc = s.misc[RG_NCOMP], roff = s.misc[RG_ROFF];
+    for (int k = tid; k < nc; k += RG_THREADS) c.scores[roff + k] = s.sum[k];
+}
+
 // -> the overflow bits of this (document, class); 0 = its slices and its header row are written
+template <bool SCORED>
 RG_DEV int rg_body(const RgCtx& c, const RgLds& s) {
     RG_PHASE(rg_ph_init);
     RG_PHASE(rg_ph_link_left);
@@ -358,6 +406,11 @@ RG_DEV int rg_body(const RgCtx& c, const RgLds& s) {
     RG_PHASE(rg_ph_reserve);
     RG_CHECK();
     RG_PHASE(rg_ph_write);
+    if constexpr (SCORED) {
+        RG_PHASE(rg_ph_score_zero);
+        RG_PHASE(rg_ph_score_sum);
+        RG_PHASE(rg_ph_score_write);
+    }
     return 0;
 }
 
@@ -379,6 +432,12 @@ RG_DEV void rg_ctx(RgCtx& c, int b, int cc, const uint8_t* argmax, const uint16_
     c.hdr = header + 4 * (size_t)b * n_class;
     c.regions = regions + (size_t)b * cap_regions * RG_REGION_INTS; c.cap_regions = cap_regions;
     c.pairs = pairs + (size_t)b * cap_pairs * RG_PAIR_INTS; c.cap_pairs = cap_pairs;
+}
+
+// ... and what the scored form reads and writes besides
+RG_DEV void rg_ctx_scores(RgCtx& c, int b, const float* probs, int H, int W, int n_class, int64_t* scores, int cap_regions) {
+    c.probs = probs + (size_t)b * H * W * n_class; c.n_class = n_class;
+    c.scores = scores + (size_t)b * cap_regions;
 }
 
 // ---- the large form ------------------------------------------------------------------------------------------------
@@ -413,10 +472,11 @@ RG_DEV int64_t rg_large_pixels(int64_t share, int n_class) {
 }
 
 #ifdef MSAU_REGIONS_CPU
-// the launch, lane by lane on the host: same arguments as msau_kv_regions without the stream
-extern "C" int msau_kv_regions_cpu(const uint8_t* argmax, const uint16_t* line_ids, const uint16_t* char_pos, const int32_t* boxes,
-                                   const int32_t* box_off, const int32_t* extent, int B, int H, int W, int n_class, int32_t* header,
-                                   int32_t* regions, int cap_regions, int32_t* pairs, int cap_pairs, int32_t* overflow) {
+// the launch, lane by lane on the host (probs and scores: the scored form's, NULL otherwise)
+template <bool SCORED>
+static int rg_cpu_lds(const uint8_t* argmax, const float* probs, const uint16_t* line_ids, const uint16_t* char_pos, const int32_t* boxes,
+                      const int32_t* box_off, const int32_t* extent, int B, int H, int W, int n_class, int32_t* header, int32_t* regions,
+                      int cap_regions, int32_t* pairs, int cap_pairs, int64_t* scores, int32_t* overflow) {
     int* lds = (int*)malloc(sizeof(int) * RG_LDS_INTS);
     if (!lds) return 1;
     memset(header, 0, sizeof(int32_t) * 4 * (size_t)B * n_class);
@@ -425,21 +485,24 @@ extern "C" int msau_kv_regions_cpu(const uint8_t* argmax, const uint16_t* line_i
         for (int cc = 2; cc < n_class; ++cc) {
             RgCtx c;
             rg_ctx(c, b, cc, argmax, line_ids, char_pos, boxes, box_off, extent, H, W, n_class, header, regions, cap_regions, pairs, cap_pairs);
+            if (SCORED) rg_ctx_scores(c, b, probs, H, W, n_class, scores, cap_regions);
             RgLds s;
             rg_carve(s, lds, lds + RG_MAXPIX);
             int f = rg_precheck(c.h, c.w, H, W, c.n_lines, RG_MAXPIX);
-            if (!f) f = rg_body(c, s);
+            if (!f) f = rg_body<SCORED>(c, s);
             overflow[b] |= f;
         }
     free(lds);
     return 0;
 }
-// the large launch, lane by lane on the host: same arguments as msau_kv_regions_large without the stream; 2 = refused arguments
-extern "C" int msau_kv_regions_large_cpu(const uint8_t* argmax, const uint16_t* line_ids, const uint16_t* char_pos, const int32_t* boxes,
-                                         const int32_t* box_off, const int32_t* extent, int B, int H, int W, int n_class,
-                                         const int32_t* docs, int n_docs, const int64_t* ws_off, int32_t* workspace, int64_t workspace_ints,
-                                         int32_t* header, int32_t* regions, int cap_regions, int32_t* pairs, int cap_pairs, int32_t* overflow) {
+// the large launch, lane by lane on the host; 2 = refused arguments
+template <bool SCORED>
+static int rg_cpu_large(const uint8_t* argmax, const float* probs, const uint16_t* line_ids, const uint16_t* char_pos, const int32_t* boxes,
+                        const int32_t* box_off, const int32_t* extent, int B, int H, int W, int n_class, const int32_t* docs, int n_docs,
+                        const int64_t* ws_off, int32_t* workspace, int64_t workspace_ints, int32_t* header, int32_t* regions,
+                        int cap_regions, int32_t* pairs, int cap_pairs, int64_t* scores, int32_t* overflow) {
     if (!(argmax && line_ids && char_pos && boxes && box_off && workspace && header && regions && pairs && overflow)) return 2;
+    if (SCORED && !(probs && scores)) return 2;
     if (!(B > 0 && H > 0 && W > 0 && (int64_t)H * W < (1ll << 31) && n_class >= 1 && n_class <= 255 && cap_regions >= 1 && cap_pairs >= 1)) return 2;
     if (rg_large_args(B, H, W, n_class, docs, n_docs, ws_off, workspace_ints, extent, 1)) return 2;
     int* lds = (int*)malloc(sizeof(int) * RG_TABLE_INTS);
@@ -452,11 +515,12 @@ extern "C" int msau_kv_regions_large_cpu(const uint8_t* argmax, const uint16_t* 
         for (int cc = 2; cc < n_class; ++cc) {
             RgCtx c;
             rg_ctx(c, b, cc, argmax, line_ids, char_pos, boxes, box_off, extent, H, W, n_class, header, regions, cap_regions, pairs, cap_pairs);
+            if (SCORED) rg_ctx_scores(c, b, probs, H, W, n_class, scores, cap_regions);
             RgLds s;
             int f = rg_precheck(c.h, c.w, H, W, c.n_lines, rg_large_pixels(share, n_class));
             if (!f) {
                 rg_carve(s, workspace + ws_off[i] + (int64_t)(cc - 2) * c.h * c.w, lds);
-                f = rg_body(c, s);
+                f = rg_body<SCORED>(c, s);
             }
             overflow[b] |= f;
         }
@@ -464,45 +528,114 @@ extern "C" int msau_kv_regions_large_cpu(const uint8_t* argmax, const uint16_t* 
     free(lds);
     return 0;
 }
+// same arguments as msau_kv_regions / msau_kv_regions_large / their scored forms without the stream
+extern "C" int msau_kv_regions_cpu(const uint8_t* argmax, const uint16_t* line_ids, const uint16_t* char_pos, const int32_t* boxes,
+                                   const int32_t* box_off, const int32_t* extent, int B, int H, int W, int n_class, int32_t* header,
+                                   int32_t* regions, int cap_regions, int32_t* pairs, int cap_pairs, int32_t* overflow) {
+    return rg_cpu_lds<false>(argmax, 0, line_ids, char_pos, boxes, box_off, extent, B, H, W, n_class, header, regions, cap_regions, pairs,
+                             cap_pairs, 0, overflow);
+}
+extern "C" int msau_kv_regions_scored_cpu(const uint8_t* argmax, const float* probs, const uint16_t* line_ids, const uint16_t* char_pos,
+                                          const int32_t* boxes, const int32_t* box_off, const int32_t* extent, int B, int H, int W,
+                                          int n_class, int32_t* header, int32_t* regions, int cap_regions, int32_t* pairs, int cap_pairs,
+                                          int64_t* scores, int32_t* overflow) {
+    if (!(probs && scores)) return 2;
+    return rg_cpu_lds<true>(argmax, probs, line_ids, char_pos, boxes, box_off, extent, B, H, W, n_class, header, regions, cap_regions, pairs,
+                            cap_pairs, scores, overflow);
+}
+extern "C" int msau_kv_regions_large_cpu(const uint8_t* argmax, const uint16_t* line_ids, const uint16_t* char_pos, const int32_t* boxes,
+                                         const int32_t* box_off, const int32_t* extent, int B, int H, int W, int n_class,
+                                         const int32_t* docs, int n_docs, const int64_t* ws_off, int32_t* workspace, int64_t workspace_ints,
+                                         int32_t* header, int32_t* regions, int cap_regions, int32_t* pairs, int cap_pairs, int32_t* overflow) {
+    return rg_cpu_large<false>(argmax, 0, line_ids, char_pos, boxes, box_off, extent, B, H, W, n_class, docs, n_docs, ws_off, workspace,
+                               workspace_ints, header, regions, cap_regions, pairs, cap_pairs, 0, overflow);
+}
+extern "C" int msau_kv_regions_large_scored_cpu(const uint8_t* argmax, const float* probs, const uint16_t* line_ids, const uint16_t* char_pos,
+                                                const int32_t* boxes, const int32_t* box_off, const int32_t* extent, int B, int H, int W,
+                                                int n_class, const int32_t* docs, int n_docs, const int64_t* ws_off, int32_t* workspace,
+                                                int64_t workspace_ints, int32_t* header, int32_t* regions, int cap_regions, int32_t* pairs,
+                                                int cap_pairs, int64_t* scores, int32_t* overflow) {
+    return rg_cpu_large<true>(argmax, probs, line_ids, char_pos, boxes, box_off, extent, B, H, W, n_class, docs, n_docs, ws_off, workspace,
+                              workspace_ints, header, regions, cap_regions, pairs, cap_pairs, scores, overflow);
+}
 extern "C" int msau_kv_regions_limits(int32_t* out) {
     out[0] = RG_MAXPIX; out[1] = RG_MAXK; out[2] = RG_HASH; out[3] = RG_REGION_INTS; out[4] = RG_PAIR_INTS; out[5] = RG_MAXLINES;
     return 0;
 }
 #else
 
+// one workgroup of the LDS form: (document blockIdx.y, class 2 + blockIdx.x), the labels and the tables in `lds`
+template <bool SCORED>
+RG_DEV void rg_lds_form(int* lds, const uint8_t* argmax, const float* probs, const uint16_t* line_ids, const uint16_t* char_pos,
+                        const int32_t* boxes, const int32_t* box_off, const int32_t* extent, int H, int W, int n_class, int32_t* header,
+                        int32_t* regions, int cap_regions, int32_t* pairs, int cap_pairs, int64_t* scores, int32_t* overflow) {
+    const int b = blockIdx.y;
+    RgCtx c;
+    rg_ctx(c, b, 2 + (int)blockIdx.x, argmax, line_ids, char_pos, boxes, box_off, extent, H, W, n_class, header, regions, cap_regions, pairs, cap_pairs);
+    if constexpr (SCORED) rg_ctx_scores(c, b, probs, H, W, n_class, scores, cap_regions);
+    RgLds s;
+    rg_carve(s, lds, lds + RG_MAXPIX);
+    int f = rg_precheck(c.h, c.w, H, W, c.n_lines, RG_MAXPIX);     // uniform over the workgroup, like every exit of rg_body
+    if (!f) f = rg_body<SCORED>(c, s);
+    if (f && threadIdx.x == 0) atomicOr(overflow + b, f);
+}
+
 __global__ void __launch_bounds__(RG_THREADS)
 kv_regions_kernel(const uint8_t* argmax, const uint16_t* line_ids, const uint16_t* char_pos, const int32_t* boxes, const int32_t* box_off,
                   const int32_t* extent, int H, int W, int n_class, int32_t* header, int32_t* regions, int cap_regions, int32_t* pairs,
                   int cap_pairs, int32_t* overflow) {
     extern __shared__ int rg_lds[];
-    const int b = blockIdx.y;
-    RgCtx c;
-    rg_ctx(c, b, 2 + (int)blockIdx.x, argmax, line_ids, char_pos, boxes, box_off, extent, H, W, n_class, header, regions, cap_regions, pairs, cap_pairs);
-    RgLds s;
-    rg_carve(s, rg_lds, rg_lds + RG_MAXPIX);
-    int f = rg_precheck(c.h, c.w, H, W, c.n_lines, RG_MAXPIX);     // uniform over the workgroup, like every exit of rg_body
-    if (!f) f = rg_body(c, s);
-    if (f && threadIdx.x == 0) atomicOr(overflow + b, f);
+    rg_lds_form<false>(rg_lds, argmax, nullptr, line_ids, char_pos, boxes, box_off, extent, H, W, n_class, header, regions, cap_regions, pairs,
+                       cap_pairs, nullptr, overflow);
+}
+
+__global__ void __launch_bounds__(RG_THREADS)
+kv_regions_scored_kernel(const uint8_t* argmax, const float* probs, const uint16_t* line_ids, const uint16_t* char_pos, const int32_t* boxes,
+                         const int32_t* box_off, const int32_t* extent, int H, int W, int n_class, int32_t* header, int32_t* regions,
+                         int cap_regions, int32_t* pairs, int cap_pairs, int64_t* scores, int32_t* overflow) {
+    extern __shared__ int rg_lds[];
+    rg_lds_form<true>(rg_lds, argmax, probs, line_ids, char_pos, boxes, box_off, extent, H, W, n_class, header, regions, cap_regions, pairs,
+                      cap_pairs, scores, overflow);
 }
 
 // The large form: the labels of (document ld.doc[blockIdx.y], class 2 + blockIdx.x) in that pair's own h * w int32 of the
 // workspace, the tables in LDS, the phases of rg_body as they are.  Only this workgroup touches its share, and only between its
 // own barriers: see DESIGN.md 5b for why plain accesses and rg_ld's L2 loads see what they must.
+template <bool SCORED>
+RG_DEV void rg_large_form(int* tables, const uint8_t* argmax, const float* probs, const uint16_t* line_ids, const uint16_t* char_pos,
+                          const int32_t* boxes, const int32_t* box_off, const int32_t* extent, int H, int W, int n_class,
+                          const RgLargeDocs& ld, int32_t* workspace, int32_t* header, int32_t* regions, int cap_regions, int32_t* pairs,
+                          int cap_pairs, int64_t* scores, int32_t* overflow) {
+    const int i = blockIdx.y, b = ld.doc[i];
+    RgCtx c;
+    rg_ctx(c, b, 2 + (int)blockIdx.x, argmax, line_ids, char_pos, boxes, box_off, extent, H, W, n_class, header, regions, cap_regions, pairs, cap_pairs);
+    if constexpr (SCORED) rg_ctx_scores(c, b, probs, H, W, n_class, scores, cap_regions);
+    RgLds s;
+    int f = rg_precheck(c.h, c.w, H, W, c.n_lines, rg_large_pixels(ld.share[i], n_class));
+    if (!f) {
+        rg_carve(s, workspace + ld.off[i] + (int64_t)blockIdx.x * c.h * c.w, tables);
+        f = rg_body<SCORED>(c, s);
+    }
+    if (f && threadIdx.x == 0) atomicOr(overflow + b, f);
+}
+
 __global__ void __launch_bounds__(RG_THREADS)
 kv_regions_large_kernel(const uint8_t* argmax, const uint16_t* line_ids, const uint16_t* char_pos, const int32_t* boxes, const int32_t* box_off,
                         const int32_t* extent, int H, int W, int n_class, RgLargeDocs ld, int32_t* workspace, int32_t* header,
                         int32_t* regions, int cap_regions, int32_t* pairs, int cap_pairs, int32_t* overflow) {
     __shared__ int rg_tables[RG_TABLE_INTS];
-    const int i = blockIdx.y, b = ld.doc[i];
-    RgCtx c;
-    rg_ctx(c, b, 2 + (int)blockIdx.x, argmax, line_ids, char_pos, boxes, box_off, extent, H, W, n_class, header, regions, cap_regions, pairs, cap_pairs);
-    RgLds s;
-    int f = rg_precheck(c.h, c.w, H, W, c.n_lines, rg_large_pixels(ld.share[i], n_class));
-    if (!f) {
-        rg_carve(s, workspace + ld.off[i] + (int64_t)blockIdx.x * c.h * c.w, rg_tables);
-        f = rg_body(c, s);
-    }
-    if (f && threadIdx.x == 0) atomicOr(overflow + b, f);
+    rg_large_form<false>(rg_tables, argmax, nullptr, line_ids, char_pos, boxes, box_off, extent, H, W, n_class, ld, workspace, header, regions,
+                         cap_regions, pairs, cap_pairs, nullptr, overflow);
+}
+
+__global__ void __launch_bounds__(RG_THREADS)
+kv_regions_large_scored_kernel(const uint8_t* argmax, const float* probs, const uint16_t* line_ids, const uint16_t* char_pos,
+                               const int32_t* boxes, const int32_t* box_off, const int32_t* extent, int H, int W, int n_class, RgLargeDocs ld,
+                               int32_t* workspace, int32_t* header, int32_t* regions, int cap_regions, int32_t* pairs, int cap_pairs,
+                               int64_t* scores, int32_t* overflow) {
+    __shared__ __attribute__((aligned(8))) int rg_tables[RG_TABLE_INTS];      // (the 64-bit sums lie over two of the tables)
+    rg_large_form<true>(rg_tables, argmax, probs, line_ids, char_pos, boxes, box_off, extent, H, W, n_class, ld, workspace, header, regions,
+                        cap_regions, pairs, cap_pairs, scores, overflow);
 }
 
 // the listed documents' header rows and overflow words, as msau_kv_regions leaves them before its launch
@@ -518,42 +651,55 @@ extern "C" int msau_kv_regions_limits(int32_t* out) {
     return 0;
 }
 
-extern "C" int msau_kv_regions(void* stream, const uint8_t* argmax, const uint16_t* line_ids, const uint16_t* char_pos, const int32_t* boxes,
-                               const int32_t* box_off, const int32_t* extent, int B, int H, int W, int n_class, int32_t* header,
-                               int32_t* regions, int cap_regions, int32_t* pairs, int cap_pairs, int32_t* overflow) {
-    MSAU_CHECK_ARG(argmax && line_ids && char_pos && boxes && box_off && header && regions && pairs && overflow, "kv_regions: null pointer");
-    MSAU_CHECK_ARG(B > 0 && B <= 65535 && H > 0 && W > 0 && (int64_t)H * W < (1ll << 31), "kv_regions: bad shape B = %d, H = %d, W = %d", B, H, W);
-    MSAU_CHECK_ARG(n_class >= 1 && n_class <= 255, "kv_regions: n_class = %d, must be in [1, 255]", n_class);
-    MSAU_CHECK_ARG(cap_regions >= 1 && cap_pairs >= 1 && cap_regions < (1 << 24) && cap_pairs < (1 << 24), "kv_regions: bad capacities");
+// msau_kv_regions (`who` = "kv_regions") and its scored form
+template <bool SCORED>
+static int rg_launch_lds(const char* who, void* stream, const uint8_t* argmax, const float* probs, const uint16_t* line_ids,
+                         const uint16_t* char_pos, const int32_t* boxes, const int32_t* box_off, const int32_t* extent, int B, int H, int W,
+                         int n_class, int32_t* header, int32_t* regions, int cap_regions, int32_t* pairs, int cap_pairs, int64_t* scores,
+                         int32_t* overflow) {
+    MSAU_CHECK_ARG(argmax && line_ids && char_pos && boxes && box_off && header && regions && pairs && overflow, "%s: null pointer", who);
+    MSAU_CHECK_ARG(!SCORED || (probs && scores), "%s: null probs or scores", who);
+    MSAU_CHECK_ARG(B > 0 && B <= 65535 && H > 0 && W > 0 && (int64_t)H * W < (1ll << 31), "%s: bad shape B = %d, H = %d, W = %d", who, B, H, W);
+    MSAU_CHECK_ARG(n_class >= 1 && n_class <= 255, "%s: n_class = %d, must be in [1, 255]", who, n_class);
+    MSAU_CHECK_ARG(cap_regions >= 1 && cap_pairs >= 1 && cap_regions < (1 << 24) && cap_pairs < (1 << 24), "%s: bad capacities", who);
     static_assert(sizeof(int) * RG_LDS_INTS <= MSAU_LDS_LIMIT, "kv_regions: the tables must fit the LDS");
     hipStream_t s = static_cast<hipStream_t>(stream);
     hipError_t e = hipMemsetAsync(header, 0, sizeof(int32_t) * 4 * (size_t)B * n_class, s);
     if (e == hipSuccess) e = hipMemsetAsync(overflow, 0, sizeof(int32_t) * (size_t)B, s);
-    if (e != hipSuccess) return msau_set_error(MSAU_ERR_HIP, "kv_regions: hipMemsetAsync: %s", hipGetErrorString(e));
+    if (e != hipSuccess) return msau_set_error(MSAU_ERR_HIP, "%s: hipMemsetAsync: %s", who, hipGetErrorString(e));
     if (n_class < 3) return 0;
-    static bool attr_set = false;
+    const void* kern = SCORED ? reinterpret_cast<const void*>(&kv_regions_scored_kernel) : reinterpret_cast<const void*>(&kv_regions_kernel);
+    static bool attr_set = false;                                  // (one per form)
     if (!attr_set) {
-        e = hipFuncSetAttribute(reinterpret_cast<const void*>(&kv_regions_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, MSAU_LDS_LIMIT);
-        if (e != hipSuccess) return msau_set_error(MSAU_ERR_HIP, "kv_regions: hipFuncSetAttribute: %s", hipGetErrorString(e));
+        e = hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, MSAU_LDS_LIMIT);
+        if (e != hipSuccess) return msau_set_error(MSAU_ERR_HIP, "%s: hipFuncSetAttribute: %s", who, hipGetErrorString(e));
         attr_set = true;
     }
-    hipLaunchKernelGGL(kv_regions_kernel, dim3(n_class - 2, B), dim3(RG_THREADS), sizeof(int) * RG_LDS_INTS, s, argmax, line_ids, char_pos, boxes,
-                       box_off, extent, H, W, n_class, header, regions, cap_regions, pairs, cap_pairs, overflow);
-    MSAU_CHECK_LAUNCH("kv_regions");
+    if constexpr (SCORED)
+        hipLaunchKernelGGL(kv_regions_scored_kernel, dim3(n_class - 2, B), dim3(RG_THREADS), sizeof(int) * RG_LDS_INTS, s, argmax, probs, line_ids,
+                           char_pos, boxes, box_off, extent, H, W, n_class, header, regions, cap_regions, pairs, cap_pairs, scores, overflow);
+    else
+        hipLaunchKernelGGL(kv_regions_kernel, dim3(n_class - 2, B), dim3(RG_THREADS), sizeof(int) * RG_LDS_INTS, s, argmax, line_ids, char_pos, boxes,
+                           box_off, extent, H, W, n_class, header, regions, cap_regions, pairs, cap_pairs, overflow);
+    MSAU_CHECK_LAUNCH(who);
     return 0;
 }
 
-extern "C" int msau_kv_regions_large(void* stream, const uint8_t* argmax, const uint16_t* line_ids, const uint16_t* char_pos, const int32_t* boxes,
-                                     const int32_t* box_off, const int32_t* extent, int B, int H, int W, int n_class, const int32_t* docs,
-                                     int n_docs, const int64_t* ws_off, int32_t* workspace, int64_t workspace_ints, int32_t* header,
-                                     int32_t* regions, int cap_regions, int32_t* pairs, int cap_pairs, int32_t* overflow) {
+// msau_kv_regions_large (`who` = "kv_regions_large") and its scored form
+template <bool SCORED>
+static int rg_launch_large(const char* who, void* stream, const uint8_t* argmax, const float* probs, const uint16_t* line_ids,
+                           const uint16_t* char_pos, const int32_t* boxes, const int32_t* box_off, const int32_t* extent, int B, int H, int W,
+                           int n_class, const int32_t* docs, int n_docs, const int64_t* ws_off, int32_t* workspace, int64_t workspace_ints,
+                           int32_t* header, int32_t* regions, int cap_regions, int32_t* pairs, int cap_pairs, int64_t* scores,
+                           int32_t* overflow) {
     MSAU_CHECK_ARG(argmax && line_ids && char_pos && boxes && box_off && workspace && header && regions && pairs && overflow,
-                   "kv_regions_large: null pointer");
-    MSAU_CHECK_ARG(B > 0 && B <= 65535 && H > 0 && W > 0 && (int64_t)H * W < (1ll << 31), "kv_regions_large: bad shape B = %d, H = %d, W = %d", B, H, W);
-    MSAU_CHECK_ARG(n_class >= 1 && n_class <= 255, "kv_regions_large: n_class = %d, must be in [1, 255]", n_class);
-    MSAU_CHECK_ARG(cap_regions >= 1 && cap_pairs >= 1 && cap_regions < (1 << 24) && cap_pairs < (1 << 24), "kv_regions_large: bad capacities");
+                   "%s: null pointer", who);
+    MSAU_CHECK_ARG(!SCORED || (probs && scores), "%s: null probs or scores", who);
+    MSAU_CHECK_ARG(B > 0 && B <= 65535 && H > 0 && W > 0 && (int64_t)H * W < (1ll << 31), "%s: bad shape B = %d, H = %d, W = %d", who, B, H, W);
+    MSAU_CHECK_ARG(n_class >= 1 && n_class <= 255, "%s: n_class = %d, must be in [1, 255]", who, n_class);
+    MSAU_CHECK_ARG(cap_regions >= 1 && cap_pairs >= 1 && cap_regions < (1 << 24) && cap_pairs < (1 << 24), "%s: bad capacities", who);
     const char* bad = rg_large_args(B, H, W, n_class, docs, n_docs, ws_off, workspace_ints, nullptr, extent == nullptr);
-    MSAU_CHECK_ARG(!bad, "kv_regions_large: %s", bad);
+    MSAU_CHECK_ARG(!bad, "%s: %s", who, bad);
     static_assert(sizeof(int) * RG_TABLE_INTS <= 64 * 1024, "kv_regions_large: the tables are a static LDS array");
     static_assert(sizeof(RgLargeDocs) <= 1024, "kv_regions_large: the document list is a kernel argument");
     hipStream_t s = static_cast<hipStream_t>(stream);
@@ -568,10 +714,47 @@ extern "C" int msau_kv_regions_large(void* stream, const uint8_t* argmax, const 
         hipLaunchKernelGGL(kv_regions_large_reset_kernel, dim3(n), dim3(256), 0, s, ld, n_class, header, overflow);
         MSAU_CHECK_LAUNCH("kv_regions_large (reset)");
         if (n_class < 3) continue;
-        hipLaunchKernelGGL(kv_regions_large_kernel, dim3(n_class - 2, n), dim3(RG_THREADS), 0, s, argmax, line_ids, char_pos, boxes, box_off,
-                           extent, H, W, n_class, ld, workspace, header, regions, cap_regions, pairs, cap_pairs, overflow);
-        MSAU_CHECK_LAUNCH("kv_regions_large");
+        if constexpr (SCORED)
+            hipLaunchKernelGGL(kv_regions_large_scored_kernel, dim3(n_class - 2, n), dim3(RG_THREADS), 0, s, argmax, probs, line_ids, char_pos, boxes,
+                               box_off, extent, H, W, n_class, ld, workspace, header, regions, cap_regions, pairs, cap_pairs, scores, overflow);
+        else
+            hipLaunchKernelGGL(kv_regions_large_kernel, dim3(n_class - 2, n), dim3(RG_THREADS), 0, s, argmax, line_ids, char_pos, boxes, box_off,
+                               extent, H, W, n_class, ld, workspace, header, regions, cap_regions, pairs, cap_pairs, overflow);
+        MSAU_CHECK_LAUNCH(who);
     }
     return 0;
 }
+
+extern "C" int msau_kv_regions(void* stream, const uint8_t* argmax, const uint16_t* line_ids, const uint16_t* char_pos, const int32_t* boxes,
+                               const int32_t* box_off, const int32_t* extent, int B, int H, int W, int n_class, int32_t* header,
+                               int32_t* regions, int cap_regions, int32_t* pairs, int cap_pairs, int32_t* overflow) {
+    return rg_launch_lds<false>("kv_regions", stream, argmax, nullptr, line_ids, char_pos, boxes, box_off, extent, B, H, W, n_class, header,
+                                regions, cap_regions, pairs, cap_pairs, nullptr, overflow);
+}
+
+extern "C" int msau_kv_regions_scored(void* stream, const uint8_t* argmax, const float* probs, const uint16_t* line_ids,
+                                      const uint16_t* char_pos, const int32_t* boxes, const int32_t* box_off, const int32_t* extent, int B,
+                                      int H, int W, int n_class, int32_t* header, int32_t* regions, int cap_regions, int32_t* pairs,
+                                      int cap_pairs, int64_t* scores, int32_t* overflow) {
+    return rg_launch_lds<true>("kv_regions_scored", stream, argmax, probs, line_ids, char_pos, boxes, box_off, extent, B, H, W, n_class, header,
+                               regions, cap_regions, pairs, cap_pairs, scores, overflow);
+}
+
+extern "C" int msau_kv_regions_large(void* stream, const uint8_t* argmax, const uint16_t* line_ids, const uint16_t* char_pos, const int32_t* boxes,
+                                     const int32_t* box_off, const int32_t* extent, int B, int H, int W, int n_class, const int32_t* docs,
+                                     int n_docs, const int64_t* ws_off, int32_t* workspace, int64_t workspace_ints, int32_t* header,
+                                     int32_t* regions, int cap_regions, int32_t* pairs, int cap_pairs, int32_t* overflow) {
+    return rg_launch_large<false>("kv_regions_large", stream, argmax, nullptr, line_ids, char_pos, boxes, box_off, extent, B, H, W, n_class, docs,
+                                  n_docs, ws_off, workspace, workspace_ints, header, regions, cap_regions, pairs, cap_pairs, nullptr, overflow);
+}
+
+extern "C" int msau_kv_regions_large_scored(void* stream, const uint8_t* argmax, const float* probs, const uint16_t* line_ids,
+                                            const uint16_t* char_pos, const int32_t* boxes, const int32_t* box_off, const int32_t* extent,
+                                            int B, int H, int W, int n_class, const int32_t* docs, int n_docs, const int64_t* ws_off,
+                                            int32_t* workspace, int64_t workspace_ints, int32_t* header, int32_t* regions, int cap_regions,
+                                            int32_t* pairs, int cap_pairs, int64_t* scores, int32_t* overflow) {
+    return rg_launch_large<true>("kv_regions_large_scored", stream, argmax, probs, line_ids, char_pos, boxes, box_off, extent, B, H, W, n_class,
+                                 docs, n_docs, ws_off, workspace, workspace_ints, header, regions, cap_regions, pairs, cap_pairs, scores, overflow);
+}
 #endif
+

@@ -22,6 +22,11 @@ forward and the region kernel read, and the host builds a per-pixel array only f
 
 `large_documents=True` (with `device_post=True`, with or without `device_masks`) sends a page of more pixels than the region
 kernel holds in LDS through that kernel's large form (labels in device memory) and not through the host fallback.  Same results.
+
+`confidence=True` (predict, predict_batch, run_test; on every path above) gives each field a score beside its text: the mean
+probability of the field's class over the pixels of its kept regions (msau_amd.inference.regions.field_confidences).  On the
+device paths the scored form of the region kernel sums the probabilities where the head left them; on the host path
+`regions_host(..., probs=)` sums the copy that path already has.  Integer sums and one division: the same float on every path.
 """
 from __future__ import annotations
 
@@ -33,7 +38,7 @@ import torch
 
 from .generic_util import read_json_gt, sort_box_reading_order, to_categorical  # noqa: F401  (API parity)
 from .morph_util import IoU, area, connected_components, intersect_boxes, r_closing, union_boxes, ycenter
-from .postprocess import CLASS_NAMES, post_process_kv  # noqa: F401
+from .postprocess import CLASS_NAMES, post_process_kv, post_process_kv_scored  # noqa: F401
 
 
 def _obj_box(o):
@@ -268,16 +273,30 @@ class KVModel:
                 eval_results[value_id]["num_label"] += 1
         return correct_answers
 
-    def _run_regions(self, docs_masks, large=False):
+    def _fallback_table(self, amax, b, host_masks, boxes, confidence):
+        """the table of document `b`, whose overflow flag is set, from `regions_host` on its crop of the class map (and, with
+        `confidence`, of the probabilities), copied back for that document alone -> (table, scores or None)"""
+        from . import regions as R
+        h, w = host_masks[0].shape
+        cls = amax[b, :h, :w].cpu().numpy()
+        R.STATS["fallbacks"] += 1
+        R.STATS["d2h_bytes"] += cls.nbytes
+        if not confidence:
+            return R.regions_host(cls, host_masks[1], host_masks[2], boxes, self.n_class), None
+        probs = np.ascontiguousarray(self.net.last_head_probs[b, :h, :w].cpu().numpy())
+        R.STATS["d2h_bytes"] += probs.nbytes
+        return R.regions_host(cls, host_masks[1], host_masks[2], boxes, self.n_class, probs=probs)
+
+    def _run_regions(self, docs_masks, large=False, confidence=False):
         """`device_post`: the masks of a group of documents -> per document its region table.  One forward (dense at one
         document, ragged otherwise) with the region kernel behind it; a document whose overflow flag is set (more pixels, regions
         or pairs than the kernel's tables hold) gets its table from `regions_host` on its crop of the class map, copied back for
-        that document alone -- the same table, never an approximation.  `large`: more pixels are no overflow (`regions_device`)."""
+        that document alone -- the same table, never an approximation.  `large`: more pixels are no overflow (`regions_device`).
+        -> (tables, scores): scores is None without `confidence`, else per document its regions' sums (scored form of the kernel)."""
         if not torch.cuda.is_available():
             raise RuntimeError("KVModel.predict runs the network through libmsau_hip.so on an MI355X; no GPU is "
                                "visible and there is no CPU fallback")
         from ..data.ragged import pack_ids, pack_masks
-        from . import regions as R
         boxes = [[l["box"] for l in m[3]] for m in docs_masks]
         if len(docs_masks) == 1:
             m = docs_masks[0]
@@ -288,16 +307,13 @@ class KVModel:
             ids, sizes = pack_ids([m[0] for m in docs_masks])
             line_ids, _ = pack_masks([m[1] for m in docs_masks])
             char_pos, _ = pack_masks([m[2] for m in docs_masks])
-        tables, flags, amax = self.net.predict_regions(ids=ids.cuda(), sizes=sizes, line_ids=line_ids, char_pos=char_pos,
-                                                       boxes=boxes, large=large)
+        tables, flags, amax, *scores = self.net.predict_regions(ids=ids.cuda(), sizes=sizes, line_ids=line_ids, char_pos=char_pos,
+                                                                boxes=boxes, large=large, **({"scores": True} if confidence else {}))
+        scores = scores[0] if confidence else [None] * len(docs_masks)
         for b, m in enumerate(docs_masks):
             if flags[b] != 0:
-                h, w = m[0].shape
-                cls = amax[b, :h, :w].cpu().numpy()
-                R.STATS["fallbacks"] += 1
-                R.STATS["d2h_bytes"] += cls.nbytes
-                tables[b] = R.regions_host(cls, m[1], m[2], boxes[b], self.n_class)
-        return tables
+                tables[b], scores[b] = self._fallback_table(amax, b, m[:3], boxes[b], confidence)
+        return tables, scores if confidence else None
 
     def _doc_for_paint(self, json_path):
         """`device_masks`: -> (masks, glyph table) of a document; `masks` is the tuple of `_generate_masks_from_label` with None
@@ -308,15 +324,15 @@ class KVModel:
             return self._generate_masks_from_label(json_path), table
         return (None, None, None, table.lines, table.scale, table.bg_pad, table.text_bbox), table
 
-    def _run_regions_painted(self, docs, json_paths, large=False):
+    def _run_regions_painted(self, docs, json_paths, large=False, confidence=False):
         """`_run_regions` with the masks painted on the device: docs = [(masks, glyph table)] of `_doc_for_paint`.  One upload of
         the group's tables and one launch paint the canvases; a document without a table has its host masks copied into them.  A
-        document whose overflow flag is set has its masks painted on the host then, for `regions_host`."""
+        document whose overflow flag is set has its masks painted on the host then, for `regions_host`.  -> (tables, scores) as
+        `_run_regions`."""
         if not torch.cuda.is_available():
             raise RuntimeError("KVModel.predict runs the network through libmsau_hip.so on an MI355X; no GPU is "
                                "visible and there is no CPU fallback")
         from . import glyphs as G
-        from . import regions as R
         boxes = [[l["box"] for l in m[3]] for m, _ in docs]
         single = len(docs) == 1
         records, offsets, sizes, canvas = G.pack_tables([t for _, t in docs], round_to=1 if single else 16)
@@ -324,33 +340,43 @@ class KVModel:
         for b, (m, t) in enumerate(docs):
             if not t.ok:
                 G.upload_host_masks((ids, line_ids, char_pos), b, m[:3])
-        tables, flags, amax = self.net.predict_regions(ids=ids, sizes=None if single else torch.from_numpy(sizes),
-                                                       line_ids=line_ids, char_pos=char_pos, boxes=boxes, large=large)
+        tables, flags, amax, *scores = self.net.predict_regions(ids=ids, sizes=None if single else torch.from_numpy(sizes),
+                                                                line_ids=line_ids, char_pos=char_pos, boxes=boxes, large=large,
+                                                                **({"scores": True} if confidence else {}))
+        scores = scores[0] if confidence else [None] * len(docs)
         for b, (m, t) in enumerate(docs):
             if flags[b] != 0:
                 host = m[:3] if m[0] is not None else self._generate_masks_from_label(json_paths[b])[:3]
-                h, w = host[0].shape
-                cls = amax[b, :h, :w].cpu().numpy()
-                R.STATS["fallbacks"] += 1
-                R.STATS["d2h_bytes"] += cls.nbytes
-                tables[b] = R.regions_host(cls, host[1], host[2], boxes[b], self.n_class)
-        return tables
+                tables[b], scores[b] = self._fallback_table(amax, b, host, boxes[b], confidence)
+        return tables, scores if confidence else None
 
-    def _finish_regions(self, masks, table, correct_answers, eval_results):
-        """`_finish` from a region table"""
-        from .regions import fields_from_regions
-        values = fields_from_regions(table, masks[3], self.n_class)
-        kv_results = post_process_kv(values)
+    def _finish_regions(self, masks, table, correct_answers, eval_results, scores=None):
+        """`_finish` from a region table (and, for `confidence`, its regions' sums)"""
+        from .regions import field_confidences, fields_from_regions, select_regions
+        if scores is None:
+            values = fields_from_regions(table, masks[3], self.n_class)
+            kv_results = post_process_kv(values)
+        else:
+            selection = select_regions(table, masks[3], self.n_class)   # once for both
+            values = fields_from_regions(table, masks[3], self.n_class, selection)
+            kv_results = post_process_kv_scored(values, field_confidences(table, scores, masks[3], self.n_class, selection))
         if eval_results is not None:
             self._count_predictions(values, self.n_class, eval_results, correct_answers)
         return kv_results
 
-    def _finish(self, masks, a_pred, a_cls, correct_answers, eval_results):
-        """post-processing of one document's prediction -> kv_results"""
+    def _finish(self, masks, a_pred, a_cls, correct_answers, eval_results, confidence=False):
+        """post-processing of one document's prediction -> kv_results; `confidence`: the fields' scores from `regions_host` on
+        the same prediction (its table selects the regions `_extract_value` keeps)"""
         _input_im, line_mask, char_mask, label_lines = masks[:4]
         values, _pred_mask = self._extract_value(line_mask, char_mask, label_lines, a_pred, self.n_class,
                                                  pred_class=a_cls.astype(np.int64))
-        kv_results = post_process_kv(values)
+        if not confidence:
+            kv_results = post_process_kv(values)
+        else:
+            from .regions import field_confidences, regions_host
+            table, scores = regions_host(a_cls, line_mask, char_mask, [l["box"] for l in label_lines], self.n_class,
+                                         probs=np.ascontiguousarray(a_pred, dtype=np.float32))
+            kv_results = post_process_kv_scored(values, field_confidences(table, scores, label_lines, self.n_class))
         if eval_results is not None:
             self._count_predictions(values, self.n_class, eval_results, correct_answers)
         return kv_results
@@ -363,41 +389,44 @@ class KVModel:
             raise ValueError("large_documents=True needs device_post=True: it chooses the form of the region kernel")
 
     def predict(self, data, debug_info=None, label_path=None, eval_results=None, device_post=False, device_masks=False,
-                large_documents=False):
+                large_documents=False, confidence=False):
         """data = (layout JSON path, page image or None) -> ({field: text}, debug image).
         The debug rendering of the reference (OpenCV + PIL drawing) is not part of this build: the second result is
         always None; everything that feeds `kv_results` and `eval_results` is computed as in kv_model.py:264-347.
         device_post=True: the field regions are extracted on the device (module docstring); the results are the same.
         device_masks=True (needs device_post): the masks are painted on the device from the glyph table; the results are the same.
-        large_documents=True (needs device_post): a page beyond the region kernel's LDS form stays on the device; the same results."""
+        large_documents=True (needs device_post): a page beyond the region kernel's LDS form stays on the device; the same results.
+        confidence=True (any path): -> ({field: {"text": text, "confidence": float or None}}, None), the texts as without it; the
+        confidence is the mean probability of the field's class over its kept regions (module docstring), None without a field."""
         self._check_flags(device_post, device_masks, large_documents)
         json_path, _debug_im = data
         masks, table = self._doc_for_paint(json_path) if device_masks else (self._generate_masks_from_label(json_path), None)
         input_im, _line_mask, _char_mask, _label_lines, scale, bg_pad, (min_x, min_y, _max_x, _max_y) = masks
         correct_answers = self._read_answers(label_path, scale, (min_x - bg_pad, min_y - bg_pad), eval_results)
-        if device_masks:
-            regions = self._run_regions_painted([(masks, table)], [json_path], large_documents)[0]
-            return self._finish_regions(masks, regions, correct_answers, eval_results), None
         if device_post:
-            return self._finish_regions(masks, self._run_regions([masks], large_documents)[0], correct_answers, eval_results), None
+            tables, scores = (self._run_regions_painted([(masks, table)], [json_path], large_documents, confidence) if device_masks
+                              else self._run_regions([masks], large_documents, confidence))
+            return self._finish_regions(masks, tables[0], correct_answers, eval_results, scores[0] if confidence else None), None
         a_pred, a_cls = self._run_net(input_im)
-        return self._finish(masks, a_pred, a_cls, correct_answers, eval_results), None
+        return self._finish(masks, a_pred, a_cls, correct_answers, eval_results, confidence), None
 
     def predict_batch(self, json_paths, label_paths=None, eval_results=None, device_post=False, device_masks=False,
-                      large_documents=False):
+                      large_documents=False, confidence=False):
         """`predict` for a group of layout JSONs with one network forward: the documents' id masks share a ragged canvas
         (each is computed as it would be alone).  -> [kv_results] in the order of `json_paths`.  The ground truth of the whole
         group is read before the forward, so a label file that cannot be read is reported before any result is returned
         (`run_test` prints each such message next to its own document, as at batch 1).  device_post=True, device_masks=True: as
         in `predict`; the group's glyph tables go up in one copy and one launch paints its canvases.  large_documents=True: as in
-        `predict`, for the pages of the group that need it."""
-        results, notes = self._predict_group(json_paths, label_paths, eval_results, device_post, device_masks, large_documents)
+        `predict`, for the pages of the group that need it.  confidence=True: as in `predict`."""
+        results, notes = self._predict_group(json_paths, label_paths, eval_results, device_post, device_masks, large_documents,
+                                             confidence)
         for doc_notes in notes:
             for n in doc_notes:
                 print(*n)
         return results
 
-    def _predict_group(self, json_paths, label_paths, eval_results, device_post=False, device_masks=False, large_documents=False):
+    def _predict_group(self, json_paths, label_paths, eval_results, device_post=False, device_masks=False, large_documents=False,
+                       confidence=False):
         """predict_batch -> ([kv_results], per document the list of its unprinted messages)"""
         self._check_flags(device_post, device_masks, large_documents)
         docs, notes, painted = [], [], []
@@ -413,16 +442,16 @@ class KVModel:
             docs.append((masks, self._read_answers(label_path, scale, (min_x - bg_pad, min_y - bg_pad), eval_results,
                                                    notes[-1])))
         if device_post:
-            tables = (self._run_regions_painted(painted, json_paths, large_documents) if device_masks
-                      else self._run_regions([masks for masks, _ in docs], large_documents))
-            return [self._finish_regions(masks, table, correct_answers, eval_results)
-                    for (masks, correct_answers), table in zip(docs, tables)], notes
+            tables, scores = (self._run_regions_painted(painted, json_paths, large_documents, confidence) if device_masks
+                              else self._run_regions([masks for masks, _ in docs], large_documents, confidence))
+            return [self._finish_regions(masks, table, correct_answers, eval_results, scores[b] if confidence else None)
+                    for b, ((masks, correct_answers), table) in enumerate(zip(docs, tables))], notes
         outs = self._run_net_batch([masks[0] for masks, _ in docs])
-        return [self._finish(masks, a_pred, a_cls, correct_answers, eval_results)
+        return [self._finish(masks, a_pred, a_cls, correct_answers, eval_results, confidence)
                 for (masks, correct_answers), (a_pred, a_cls) in zip(docs, outs)], notes
 
     def run_test(self, list_inf, out_dir, label_dir=None, img_dir=None, batch_size=1, device_post=False, device_masks=False,
-                 large_documents=False):
+                 large_documents=False, confidence=False):
         """predict every layout JSON of `list_inf`; with `label_dir`, print per-class counts and precision / recall /
         F1 over region boxes (kv_model.py:350-387).  Unlike the reference a missing page image does not skip the
         document, because no debug image is drawn.  batch_size > 1: consecutive groups of `batch_size` documents go through
@@ -430,7 +459,9 @@ class KVModel:
         `list_inf`, and the last group may be shorter.  The counts are kept as `self.eval_results`.  device_post=True: the
         field regions of every document are extracted on the device (module docstring); results and printing are the same.
         device_masks=True (needs device_post): the masks are painted on the device as well; results and printing are the same.
-        large_documents=True (needs device_post): pages beyond the region kernel's LDS form stay on the device; the same again."""
+        large_documents=True (needs device_post): pages beyond the region kernel's LDS form stay on the device; the same again.
+        confidence=True: every result is {field: {"text", "confidence"}} (as in `predict`); `eval_results` and the printed counts
+        are what they are without it."""
         if batch_size < 1:
             raise ValueError(f"batch_size must be >= 1, got {batch_size}")
         self._check_flags(device_post, device_masks, large_documents)
@@ -445,10 +476,11 @@ class KVModel:
                 results = [self.predict((group[0], None), debug_info=("", None),
                                         label_path=label_paths[0] if label_paths is not None else None,
                                         eval_results=eval_results, device_post=device_post, device_masks=device_masks,
-                                        large_documents=large_documents)[0]]
+                                        large_documents=large_documents, confidence=confidence)[0]]
                 notes = [[]]                                     # (printed by predict)
             else:
-                results, notes = self._predict_group(group, label_paths, eval_results, device_post, device_masks, large_documents)
+                results, notes = self._predict_group(group, label_paths, eval_results, device_post, device_masks, large_documents,
+                                                     confidence)
             for basename, result, doc_notes in zip(names, results, notes):
                 for n in doc_notes:
                     print(*n)

@@ -14,3 +14,11 @@ def post_process_kv(values):
         name = CLASS_NAMES[idx - 1][2:] if idx - 1 < len(CLASS_NAMES) else str(idx - 1)
         out[name] = values[idx][0]
     return out
+
+
+def post_process_kv_scored(values, confidences):
+    """`post_process_kv` with a confidence per field: the same names in the same order -> {field name: {"text": text,
+    "confidence": float or None}}; confidences[idx] as `msau_amd.inference.regions.field_confidences` gives them (None for a
+    class without a field)."""
+    return {name: {"text": text, "confidence": confidences[idx]}
+            for idx, (name, text) in zip(range(3, len(values), 2), post_process_kv(values).items())}

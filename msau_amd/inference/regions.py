@@ -13,11 +13,15 @@ The table of one document, for every class c in [2, n_class):
 `fields_from_regions` applies the selection of `_extract_value` to it (main region, extra regions of the multi-line fields,
 claims, text assembly) with the same `np.argsort` calls on the same lists, so ties fall as they do there.  It is O(regions +
 text lines); everything per pixel is in the table.
+
+With probabilities (`regions_host(..., probs=)`, `regions_device(..., probs=)`) every region also gets a score, the integer sum of
+its class's quantised probability over its pixels; `field_confidences` turns the scores of a field's kept regions into the mean
+probability the network gave that field.
 """
 from __future__ import annotations
 
 import ctypes as C
-from typing import Dict, List, Optional, Sequence, Tuple
+from typing import Dict, List, Optional, Sequence
 
 import numpy as np
 from scipy import ndimage as ndi
@@ -39,6 +43,9 @@ STATS = {"calls": 0, "documents": 0, "d2h_bytes": 0, "fallbacks": 0, "large_docu
 # multi-line fields: KVModel.multiple_lines_fields (kv_model.py:155)
 MULTIPLE_LINES_FIELDS = (5, 11)
 
+# a region's score is the sum over its pixels of rint(p * SCORE_ONE), p the probability of the region's class (csrc/regions.hip)
+SCORE_ONE = 65536
+
 
 def closing_1x3(mask: np.ndarray) -> np.ndarray:
     """`r_closing(mask, (1, 3))` written out: dilate then erode along x, zero outside the array.  Columns 0 and w - 1 are
@@ -55,20 +62,38 @@ def closing_1x3(mask: np.ndarray) -> np.ndarray:
     return e
 
 
-def regions_host(cls, line_mask, char_mask, boxes, n_class: int) -> Dict[int, tuple]:
+def quantise(p) -> np.ndarray:
+    """q(p) = rint(p * 65536) as int64, to nearest even: what the scored kernel adds per pixel (p fp32; the product by 2^16 is
+    exact in fp32 and in float64, so both give the same integer)"""
+    return np.rint(np.asarray(p).astype(np.float64) * SCORE_ONE).astype(np.int64)
+
+
+def regions_host(cls, line_mask, char_mask, boxes, n_class: int, probs=None):
     """The region table of one document on the CPU (scipy): `cls` int [h, w] class map, `line_mask` / `char_mask` uint16 [h, w],
     `boxes` the lines' [x1, y1, x2, y2] in grid coordinates (line id v = boxes[v - 1]; boxes are clipped to the document, so a
-    negative coordinate counts as 0).  The statement the kernel is tested against, and the fallback of the device path."""
+    negative coordinate counts as 0).  The statement the kernel is tested against, and the fallback of the device path.
+    With `probs` (fp32 [h, w, n_class], the head's probabilities) -> (table, scores): scores[c] = per component of class c, in
+    `comps` order, the int sum of `quantise(probs[y, x, c])` over its pixels (those of the closed mask: a gap pixel the closing
+    added counts with the probability of c it has)."""
     cls = np.asarray(cls)
     line_mask, char_mask = np.asarray(line_mask), np.asarray(char_mask)
     h, w = cls.shape
-    out = {}
+    if probs is not None:
+        probs = np.asarray(probs)
+        if probs.shape != (h, w, n_class) or probs.dtype != np.float32:
+            raise ValueError(f"probs must be float32 [h, w, n_class] = {(h, w, n_class)}, got {probs.dtype} {probs.shape}")
+    out, scores = {}, {}
     for c in range(2, n_class):
         lab, n = ndi.label(r_closing(cls == c, (1, 3)))
         comps, pairs = [], {}
+        scores[c] = []
         if n:
             ys, xs = np.nonzero(lab)                                    # raster order
             ks = lab[ys, xs].astype(np.int64) - 1
+            if probs is not None:
+                total = np.zeros(n, dtype=np.int64)
+                np.add.at(total, ks, quantise(probs[ys, xs, c]))
+                scores[c] = total.tolist()
             _, first = np.unique(ks, return_index=True)
             count = np.bincount(ks, minlength=n)
             for k, (sy, sx) in enumerate(ndi.find_objects(lab)):
@@ -88,14 +113,69 @@ def regions_host(cls, line_mask, char_mask, boxes, n_class: int) -> Dict[int, tu
                     old = pairs.get((k, li + 1), (0, 65535, 0))
                     pairs[(k, li + 1)] = (old[0], int(v.min()), int(v.max()))
         out[c] = (comps, pairs)
+    return out if probs is None else (out, scores)
+
+
+def fields_from_regions(regions, label_lines, n_class: int, selection=None):
+    """Region table of one document -> the `values` list of `KVModel._extract_value`: per class (text, [main region box],
+    intersection box, union box), ("", None, None, None) for a class without a field.  Sets line["id"] as `_extract_value` does.
+    `selection`: what `select_regions` returned for the same arguments, when the caller has it already."""
+    multi = MULTIPLE_LINES_FIELDS
+    values = [("", None, None, None)] * n_class
+    kept, field_lines, field_boxes, claims = selection or select_regions(regions, label_lines, n_class)
+    for c in range(2, n_class):
+        if len(field_lines[c]) == 0:
+            continue
+        _comps, pairs = regions[c]
+        ordered = sort_box_reading_order([label_lines[i - 1] for i in field_lines[c] if i > 0])
+        text, rects = "", []
+        for line in ordered:
+            rects.append(line["box"])
+            if claims[line["id"]] <= 1:
+                text += line["text"]
+            else:
+                spans = [pairs[(k, line["id"])] for k in kept[c] if (k, line["id"]) in pairs]
+                spans = [p for p in spans if p[2] > 0]
+                if len(spans) == 0:
+                    continue                                            # (also skips the line break below)
+                first, last = min(p[1] for p in spans), max(p[2] for p in spans)
+                if last > len(line["text"]) - 3:
+                    last = len(line["text"]) + 1
+                text += line["text"][first - 2 if first >= 2 else 0: last - 1]
+            if c in multi:
+                text += "\n"
+        if len(text) > 0 and text[-1] == "\n":
+            text = text[:-1]
+        merged = union_boxes(rects)
+        values[c] = (text, [field_boxes[c][-1]], intersect_boxes(field_boxes[c] + [merged]),
+                     union_boxes(field_boxes[c] + [merged]))
+    return values
+
+
+def field_confidences(regions, scores, label_lines, n_class: int, selection=None) -> List[Optional[float]]:
+    """The confidence of every field `fields_from_regions` yields from this table: per class None (no field) or the mean
+    probability of the class over the pixels of its kept regions (the main region and, for a multi-line field, its extra
+    regions), sum(score_k) / (SCORE_ONE * sum(pixels_k)) in float64.  `scores`: per class the regions' integer sums in `comps`
+    order (`regions_host(..., probs=)`, `regions_device(..., probs=)`).  Integers in, one division: the same float on every
+    path that produced the same table.  `selection` as in `fields_from_regions`."""
+    kept, field_lines, _boxes, _claims = selection or select_regions(regions, label_lines, n_class)
+    out: List[Optional[float]] = [None] * n_class
+    for c in range(2, n_class):
+        if len(field_lines[c]) == 0:
+            continue
+        comps = regions[c][0]
+        total = sum(int(scores[c][k]) for k in kept[c])
+        pixels = sum(int(comps[k][6]) for k in kept[c])
+        out[c] = float(np.float64(total) / np.float64(SCORE_ONE * pixels))
     return out
 
 
-def fields_from_regions(regions, label_lines, n_class: int):
-    """Region table of one document -> the `values` list of `KVModel._extract_value`: per class (text, [main region box],
-    intersection box, union box), ("", None, None, None) for a class without a field.  Sets line["id"] as `_extract_value` does."""
+def select_regions(regions, label_lines, n_class: int):
+    """The selection of `_extract_value`, shared by `fields_from_regions` and `field_confidences`: -> (kept, field_lines,
+    field_boxes, claims): per class with a main region its kept regions [main] + extra (indices into `comps`); per class the ids
+    of the lines under them (empty: no field) and the regions' boxes, the main one last; per line id how many fields claim it.
+    Sets line["id"] as `_extract_value` does."""
     multi = MULTIPLE_LINES_FIELDS
-    values = [("", None, None, None)] * n_class
     claims = [0] * (len(label_lines) + 1)
     field_lines = [[] for _ in range(n_class + 1)]
     field_boxes = [[] for _ in range(n_class + 1)]
@@ -136,33 +216,7 @@ def fields_from_regions(regions, label_lines, n_class: int):
         for v in ids:
             claims[v] += 1
         kept[c] = [main] + extra
-    for c in range(2, n_class):
-        if len(field_lines[c]) == 0:
-            continue
-        _comps, pairs = regions[c]
-        ordered = sort_box_reading_order([label_lines[i - 1] for i in field_lines[c] if i > 0])
-        text, rects = "", []
-        for line in ordered:
-            rects.append(line["box"])
-            if claims[line["id"]] <= 1:
-                text += line["text"]
-            else:
-                spans = [pairs[(k, line["id"])] for k in kept[c] if (k, line["id"]) in pairs]
-                spans = [p for p in spans if p[2] > 0]
-                if len(spans) == 0:
-                    continue                                            # (also skips the line break below)
-                first, last = min(p[1] for p in spans), max(p[2] for p in spans)
-                if last > len(line["text"]) - 3:
-                    last = len(line["text"]) + 1
-                text += line["text"][first - 2 if first >= 2 else 0: last - 1]
-            if c in multi:
-                text += "\n"
-        if len(text) > 0 and text[-1] == "\n":
-            text = text[:-1]
-        merged = union_boxes(rects)
-        values[c] = (text, [field_boxes[c][-1]], intersect_boxes(field_boxes[c] + [merged]),
-                     union_boxes(field_boxes[c] + [merged]))
-    return values
+    return kept, field_lines, field_boxes, claims
 
 
 # ---- the device path ------------------------------------------------------------------------------------------------
@@ -209,7 +263,7 @@ def _workspace(dev, n_ints: int):
 
 def regions_device(argmax, line_ids, char_pos, boxes: Sequence, n_class: int, sizes=None,
                    cap_regions: Optional[int] = None, cap_pairs: Optional[int] = None,
-                   large: bool = False) -> Tuple[List[Optional[dict]], List[int]]:
+                   large: bool = False, probs=None):
     """The region tables of a batch, by the kernel, on the current stream (so: behind the forward that wrote `argmax`).
 
     argmax uint8 [B, H, W] on the device (the plan's `head_argmax`, not copied); line_ids / char_pos [B, H, W] on the device,
@@ -221,7 +275,11 @@ def regions_device(argmax, line_ids, char_pos, boxes: Sequence, n_class: int, si
     in a workspace in device memory; without it such a document is flagged OVF_PIXELS.  The per-class limits and the capacities
     hold for them as for the others.
     -> ([table or None per document], [overflow flags per document]); a document with a non-zero flag (OVF_*) has no table:
-    run `regions_host` on its class map.  Reads back the header (16 bytes per class) and the used prefix of the two lists."""
+    run `regions_host` on its class map.  Reads back the header (16 bytes per class) and the used prefix of the two lists.
+    probs: fp32 [B, H, W, n_class] on the device (the plan's `head_probs`, not copied): the scored entry points write, beside
+    every region record, the integer sum of its class's quantised probability over its pixels (`regions_host(..., probs=)` is the
+    statement); the used prefix of those sums (8 bytes per region row) comes back with the regions.
+    -> (tables, flags, scores): scores[b] = {class: [int per region, in `comps` order]}, None for a document with a flag."""
     import torch
     from .. import _lib as L
     if argmax.dim() != 3 or argmax.dtype != torch.uint8 or not argmax.is_cuda:
@@ -234,6 +292,10 @@ def regions_device(argmax, line_ids, char_pos, boxes: Sequence, n_class: int, si
             raise ValueError(f"{name} must be a 16-bit integer [B, H, W] = {(B, H, W)} tensor on {argmax.device}")
     if len(boxes) != B:
         raise ValueError(f"boxes must hold one list per document ({B}), got {len(boxes)}")
+    if probs is not None and (tuple(probs.shape) != (B, H, W, n_class) or probs.dtype != torch.float32 or probs.device != argmax.device
+                              or not probs.is_contiguous()):
+        raise ValueError(f"probs must be a contiguous float32 [B, H, W, n_class] = {(B, H, W, n_class)} tensor on {argmax.device}")
+    scored = probs is not None
     lim = device_limits()
     cap_regions = DEFAULT_CAP_REGIONS if cap_regions is None else int(cap_regions)
     cap_pairs = DEFAULT_CAP_PAIRS if cap_pairs is None else int(cap_pairs)
@@ -254,18 +316,22 @@ def regions_device(argmax, line_ids, char_pos, boxes: Sequence, n_class: int, si
         small[3 * B + 1:] = np.concatenate([np.asarray(b, dtype=np.int64).reshape(-1, 4) for b in boxes if len(b)]).reshape(-1)
     dev = argmax.device
     small_d = torch.from_numpy(small).to(dev, non_blocking=False)
-    key = (dev, B, n_class, cap_regions, cap_pairs)
+    key = (dev, B, n_class, cap_regions, cap_pairs) + (("scored",) if scored else ())
     if key not in _buffers:
         if len(_buffers) >= 8:
             _buffers.clear()
         _buffers[key] = (torch.zeros(B * n_class * 4 + B, dtype=torch.int32, device=dev),
                          torch.zeros((B, cap_regions, lim["region_ints"]), dtype=torch.int32, device=dev),
-                         torch.zeros((B, cap_pairs, lim["pair_ints"]), dtype=torch.int32, device=dev))
-    head_d, reg_d, pair_d = _buffers[key]
+                         torch.zeros((B, cap_pairs, lim["pair_ints"]), dtype=torch.int32, device=dev)) + \
+                        ((torch.zeros((B, cap_regions), dtype=torch.int64, device=dev),) if scored else ())
+    head_d, reg_d, pair_d = _buffers[key][:3]
+    score_d = _buffers[key][3] if scored else None
     base = small_d.data_ptr()
-    L.call("msau_kv_regions", torch.cuda.current_stream().cuda_stream, argmax.data_ptr(), line_ids.data_ptr(), char_pos.data_ptr(),
-           base + 4 * (3 * B + 1), base, base + 4 * (B + 1) if sizes is not None else None, B, H, W, n_class,
-           head_d.data_ptr(), reg_d.data_ptr(), cap_regions, pair_d.data_ptr(), cap_pairs, head_d.data_ptr() + 16 * B * n_class)
+    inputs = (argmax.data_ptr(),) + ((probs.data_ptr(),) if scored else ()) + (line_ids.data_ptr(), char_pos.data_ptr())
+    outputs = (head_d.data_ptr(), reg_d.data_ptr(), cap_regions, pair_d.data_ptr(), cap_pairs) + \
+              ((score_d.data_ptr(),) if scored else ()) + (head_d.data_ptr() + 16 * B * n_class,)
+    L.call("msau_kv_regions_scored" if scored else "msau_kv_regions", torch.cuda.current_stream().cuda_stream, *inputs,
+           base + 4 * (3 * B + 1), base, base + 4 * (B + 1) if sizes is not None else None, B, H, W, n_class, *outputs)
     if large and n_class > 2:
         pixels = [int(h) * int(w) for h, w in sz] if sizes is not None else [H * W] * B
         big = [b for b in range(B) if pixels[b] > lim["max_pixels"]]
@@ -274,10 +340,9 @@ def regions_device(argmax, line_ids, char_pos, boxes: Sequence, n_class: int, si
             ws = _workspace(dev, sum(share))
             docs_a = (C.c_int32 * len(big))(*big)
             off_a = (C.c_int64 * len(big))(*np.concatenate([[0], np.cumsum(share)[:-1]]).tolist())
-            L.call("msau_kv_regions_large", torch.cuda.current_stream().cuda_stream, argmax.data_ptr(), line_ids.data_ptr(),
-                   char_pos.data_ptr(), base + 4 * (3 * B + 1), base, base + 4 * (B + 1) if sizes is not None else None, B, H, W,
-                   n_class, docs_a, len(big), off_a, ws.data_ptr(), sum(share), head_d.data_ptr(), reg_d.data_ptr(), cap_regions,
-                   pair_d.data_ptr(), cap_pairs, head_d.data_ptr() + 16 * B * n_class)
+            L.call("msau_kv_regions_large_scored" if scored else "msau_kv_regions_large", torch.cuda.current_stream().cuda_stream,
+                   *inputs, base + 4 * (3 * B + 1), base, base + 4 * (B + 1) if sizes is not None else None, B, H, W,
+                   n_class, docs_a, len(big), off_a, ws.data_ptr(), sum(share), *outputs)
             STATS["large_documents"] += len(big)
     head = head_d.cpu().numpy()
     header, flags = head[:B * n_class * 4].reshape(B, n_class, 4), head[B * n_class * 4:].tolist()
@@ -285,10 +350,13 @@ def regions_device(argmax, line_ids, char_pos, boxes: Sequence, n_class: int, si
     used_r = max([int(header[b, 0, 0]) for b in ok], default=0)
     used_p = max([int(header[b, 0, 1]) for b in ok], default=0)
     nbytes = head.nbytes
-    reg = pair = None
+    reg = pair = score = None
     if used_r:
         reg = reg_d[:, :used_r].cpu().numpy()
         nbytes += reg.nbytes
+        if scored:
+            score = score_d[:, :used_r].cpu().numpy()
+            nbytes += score.nbytes
     if used_p:
         pair = pair_d[:, :used_p].cpu().numpy()
         nbytes += pair.nbytes
@@ -298,4 +366,8 @@ def regions_device(argmax, line_ids, char_pos, boxes: Sequence, n_class: int, si
     STATS["calls"] += 1
     STATS["documents"] += B
     STATS["d2h_bytes"] += nbytes
-    return docs, flags
+    if not scored:
+        return docs, flags
+    scores = [{c: (score[b, header[b, c, 0]:header[b, c, 0] + header[b, c, 1]].tolist() if score is not None else [])
+               for c in range(2, n_class)} if flags[b] == 0 else None for b in range(B)]
+    return docs, flags, scores

@@ -528,7 +528,7 @@ class MSAUWrapper(nn.Module):
     @torch.no_grad()
     def predict_regions(self, inp: Optional[torch.Tensor] = None, ids: Optional[torch.Tensor] = None, sizes=None, *,
                         line_ids: torch.Tensor, char_pos: torch.Tensor, boxes, cap_regions: Optional[int] = None,
-                        cap_pairs: Optional[int] = None, large: bool = False):
+                        cap_pairs: Optional[int] = None, large: bool = False, scores: bool = False):
         """`predict_nhwc` followed, on the same stream, by the region kernel (csrc/regions.hip) on the class map the head wrote:
         nothing per pixel comes back to the host.  inp / ids / sizes as in `predict_nhwc`; line_ids / char_pos: 16-bit integer
         [B, H, W] tensors on the canvas of the input, zero outside the documents (msau_amd.data.ragged.pack_masks), moved to the
@@ -536,13 +536,21 @@ class MSAUWrapper(nn.Module):
         -> (tables, flags, argmax): per document its region table (msau_amd.inference.regions) or None, per document the
         overflow flags (0 = the table is complete; otherwise run `regions_host` on that document's crop of `argmax`), and the
         plan's uint8 [B, H, W] class map on the device.  large=True: documents beyond the LDS form's pixel limit get their table
-        from the large form of the kernel (`regions_device`).  Eager only: there is no captured-graph form of the region stage."""
+        from the large form of the kernel (`regions_device`).  Eager only: there is no captured-graph form of the region stage.
+        scores=True: the scored form of the kernel reads the head's probabilities where they are (the plan's `head_probs`)
+        -> (tables, flags, argmax, scores), scores as `regions_device(..., probs=)` returns them (None for a flagged document);
+        `self.last_head_probs` is then that fp32 [B, H, W, n_class] buffer, for the caller that has to redo a flagged document on
+        the host (`regions_host(..., probs=)` on its crop).  Like `argmax` it is the plan's own: valid until the next call."""
         from .inference.regions import regions_device
-        _probs, amax = self.predict_nhwc(inp=inp, ids=ids, sizes=sizes)
+        probs, amax = self.predict_nhwc(inp=inp, ids=ids, sizes=sizes)
         dev = amax.device
-        tables, flags = regions_device(amax, line_ids.to(dev), char_pos.to(dev), boxes, self.n_class,
-                                       sizes=None if sizes is None else torch.as_tensor(sizes).tolist(),
-                                       cap_regions=cap_regions, cap_pairs=cap_pairs, large=large)
+        kw = dict(sizes=None if sizes is None else torch.as_tensor(sizes).tolist(), cap_regions=cap_regions, cap_pairs=cap_pairs,
+                  large=large)
+        if scores:
+            self.last_head_probs = probs
+            tables, flags, sums = regions_device(amax, line_ids.to(dev), char_pos.to(dev), boxes, self.n_class, probs=probs, **kw)
+            return tables, flags, amax, sums
+        tables, flags = regions_device(amax, line_ids.to(dev), char_pos.to(dev), boxes, self.n_class, **kw)
         return tables, flags, amax
 
     @torch.no_grad()

@@ -9,7 +9,9 @@ interleaved in one process: (a) predict_batch end to end on the golden layouts w
 (b) the region stage alone on the reference's clean class maps, both arms starting from class maps on the
 device.  With --post B --large: pages of more pixels than the region kernel holds in LDS (generated here, 260 x 190 at the
 model's scale, 57 824 pixels with the painter's margin) through device_post=True without and with large_documents=True (host fallback against the large form of the
-kernel), interleaved, with the fallback counts of each arm.  Reads tests/golden/kv only.
+kernel), interleaved, with the fallback counts of each arm.  With --post B --confidence (with or without --large): one arm more,
+device_post=True with confidence=True (the scored form of the region kernel), and the bytes copied back per document with and
+without the scores.  Reads tests/golden/kv only.
 Not the headline metric (bench.py is); numbers are quoted in DESIGN.md."""
 import argparse
 import json
@@ -81,7 +83,7 @@ def run_ragged(B, n_docs, dtype, iters, warmup, C=60, n_class=17):
     return out
 
 
-def run_post(B, dtype, repeats, n_docs=48):
+def run_post(B, dtype, repeats, n_docs=48, confidence=False):
     import copy
     import numpy as np
     from msau_amd.data.ragged import pack_masks
@@ -121,11 +123,22 @@ def run_post(B, dtype, repeats, n_docs=48):
             "device": lambda: [km.predict_batch(gr, device_post=True) for gr in groups],
             "device_masks": lambda: [km.predict_batch(gr, device_post=True, device_masks=True) for gr in groups]}
     same = arms["host"]() == arms["device"]() == arms["device_masks"]()    # (the warm-up)
+    if confidence:
+        arms["device_scored"] = lambda: [km.predict_batch(gr, device_post=True, confidence=True) for gr in groups]
+        texts = [[{k: v["text"] for k, v in r.items()} for r in grp] for grp in arms["device_scored"]()]
+        same = same and texts == arms["device"]()
     reset()
     ms = {name: [] for name in arms}
+    scored_stats = {"documents": 0, "d2h_bytes": 0}
     for _ in range(repeats):
         for name in arms:
+            before = dict(R.STATS)
             ms[name].append(timed(arms[name]))
+            if name == "device_scored":                                   # kept apart: the figures below are the unscored arms'
+                for k in scored_stats:
+                    scored_stats[k] += R.STATS[k] - before[k]
+                for k in R.STATS:
+                    R.STATS[k] = before[k]
     sizes = [g[f"d{i}.line_mask"].shape for i in range(3)]
     canvas = (-(-max(h for h, _ in sizes) // 16) * 16) * (-(-max(w for _, w in sizes) // 16) * 16) if B > 1 else None
     pixels = canvas if B > 1 else int(np.mean([h * w for h, w in sizes]))
@@ -137,6 +150,9 @@ def run_post(B, dtype, repeats, n_docs=48):
                            "host_d2h_bytes_per_doc": pixels * (4 * n_class + 1),
                            "device_d2h_bytes_per_doc": round(R.STATS["d2h_bytes"] / max(R.STATS["documents"], 1)),
                            "fallbacks": R.STATS["fallbacks"]}
+    if confidence:
+        out["a_end_to_end"]["device_scored_ms_per_doc"] = ms["device_scored"]
+        out["a_end_to_end"]["device_scored_d2h_bytes_per_doc"] = round(scored_stats["d2h_bytes"] / max(scored_stats["documents"], 1))
     t0 = time.perf_counter()
     for f in files:
         km._generate_masks_from_label(f)
@@ -226,7 +242,7 @@ def large_layout(seed, height=260, width=190):
     return {"lines": lines}
 
 
-def run_large(B, dtype, repeats, n_docs=16, bias_class=3, bias=6.0):
+def run_large(B, dtype, repeats, n_docs=16, bias_class=3, bias=6.0, confidence=False):
     """The seeded golden net with the end conv's bias of one field class raised: as it is, its class map has thousands of regions
     per class on such a page and every document overflows the per-class tables in both arms."""
     import tempfile
@@ -264,6 +280,10 @@ def run_large(B, dtype, repeats, n_docs=16, bias_class=3, bias=6.0):
                                                        for gr in groups])
         first = {name: fn() for name, fn in arms.items()}                   # (the warm-up)
         out["same_results"] = all(r == first["fallback"] for r in first.values())
+        if confidence:
+            arms["large_scored"] = lambda: [km.predict_batch(gr, device_post=True, large_documents=True, confidence=True) for gr in groups]
+            texts = [[{k: v["text"] for k, v in r.items()} for r in grp] for grp in arms["large_scored"]()]
+            out["same_results"] = out["same_results"] and texts == first["fallback"]
         out["fields_found"] = sum(1 for grp in first["fallback"] for r in grp for v in r.values() if v)
         ms = {name: [] for name in arms}
         stats = {name: {k: 0 for k in R.STATS} for name in arms}
@@ -297,15 +317,16 @@ def main():
     ap.add_argument("--repeats", type=int, default=5, help="interleaved repeats per arm of --post")
     ap.add_argument("--large", action="store_true", help="with --post: pages beyond the region kernel's LDS form, host fallback against "
                                                          "large_documents=True")
+    ap.add_argument("--confidence", action="store_true", help="with --post: add the scored device path (confidence=True) to the comparison")
     ap.add_argument("--dtypes", default="bf16,fp32", help="with --post --large: the dtypes to run")
     a = ap.parse_args()
     if a.post and a.large:
         for dtype in a.dtypes.split(","):
-            print(json.dumps(run_large(a.post, dtype, a.repeats, min(a.docs, 16))), flush=True)
+            print(json.dumps(run_large(a.post, dtype, a.repeats, min(a.docs, 16), confidence=a.confidence)), flush=True)
         return
     if a.post:
         for dtype in ("bf16", "fp32"):
-            print(json.dumps(run_post(a.post, dtype, a.repeats, a.docs)), flush=True)
+            print(json.dumps(run_post(a.post, dtype, a.repeats, a.docs, confidence=a.confidence)), flush=True)
         return
     if a.ragged:
         for dtype in ("bf16", "fp32"):
