@@ -27,6 +27,7 @@ import torch.nn as nn
 
 from . import _lib as L
 from .plan import Plan, unet_cost
+from .plan_loss import NCHW_HIST_K, nchw_loss
 
 DTYPES = {"fp32": L.F32, "float32": L.F32, "bf16": L.BF16, "bfloat16": L.BF16}
 
@@ -178,73 +179,46 @@ class _MaskedCEFunction(torch.autograd.Function):
     def forward(ctx, logits, aux, label):
         B, C, H, W = logits.shape
         dev = logits.device
-        Cs = -(-C // 8) * 8
         s = torch.cuda.current_stream().cuda_stream
         label = label.reshape(B, H, W).contiguous().long()
         counts = torch.zeros((B,), dtype=torch.int32, device=dev)
         L.call("msau_label_counts", s, label.data_ptr(), counts.data_ptr(), B, H * W)
         loss = torch.zeros((1,), dtype=torch.float32, device=dev)
         ws = torch.zeros((int(L.load().msau_ce_ws_floats(B * H * W)),), dtype=torch.float32, device=dev)
-        grads = []
-        for t in (logits, aux):
-            if t is None:
-                grads.append(None)
-                continue
-            t = t.contiguous().float()
-            nhwc = torch.empty((B, H, W, Cs), dtype=torch.float32, device=dev)
-            dn = torch.empty_like(nhwc)
-            L.call("msau_nchw_to_nhwc", s, L.F32, t.data_ptr(), nhwc.data_ptr(), B, C, Cs, H, W)
-            L.call("msau_masked_ce", s, L.F32, nhwc.data_ptr(), label.data_ptr(), counts.data_ptr(), dn.data_ptr(),
-                   loss.data_ptr(), ws.data_ptr(), B, H * W, C, Cs, 1.0 / B)
-            g = torch.empty((B, C, H, W), dtype=torch.float32, device=dev)
-            L.call("msau_nhwc_to_nchw", s, L.F32, dn.data_ptr(), g.data_ptr(), B, C, Cs, H, W)
-            grads.append(g)
-        ctx.save_for_backward(*[g for g in grads if g is not None])
+
+        def kernel(nhwc, dn, label, hist, B, H, W, C, Cs, s):
+            L.call("msau_masked_ce", s, L.F32, nhwc[0], label, counts.data_ptr(), dn[0], loss.data_ptr(), ws.data_ptr(),
+                   B, H * W, C, Cs, 1.0 / B)
+
+        # head by head (conversion, CE, conversion back): both add to `loss`
+        ctx.save_for_backward(*[nchw_loss((t,), label, kernel)[0] for t in (logits, aux) if t is not None])
         ctx.has_aux = aux is not None
         return loss.reshape(())
 
     @staticmethod
     def backward(ctx, go):
         saved = ctx.saved_tensors
-        g_logits = saved[0] * go
-        g_aux = saved[1] * go if ctx.has_aux else None
-        return g_logits, g_aux, None
+        return saved[0] * go, saved[1] * go if ctx.has_aux else None, None
 
 
 class _MaskedCostFunction(torch.autograd.Function):
     """MSAUWrapper.loss under a cost and class weights on NCHW fp32 logits: one msau_masked_cost for both heads, every
     sample a document of its own; `kind` / `param` a checked cost's, `class_w` fp32 [C] on the device or None.  The conversion
-    launches are those of training/cost.py's _UnetCost."""
+    launches are those of training/cost.py's _UnetCost (msau_amd.plan_loss.nchw_loss)."""
 
     @staticmethod
     def forward(ctx, logits, aux, label, kind, param, class_w):
-        B, C, H, W = logits.shape
-        dev = logits.device
-        Cs = -(-C // 8) * 8
-        K = 4
-        s = torch.cuda.current_stream().cuda_stream
-        label = label.reshape(B, H, W).contiguous().long()
-        loss3 = torch.empty((3,), dtype=torch.float32, device=dev)
-        ws = torch.empty((int(L.load().msau_masked_cost_ws_floats(kind, B, H, W, C)),), dtype=torch.float32, device=dev)
-        hist = None
-        if class_w is not None or kind == L.COST_DICE:
-            hist = torch.empty((B, K, C), dtype=torch.int32, device=dev)
-            L.call("msau_label_hist", s, label.data_ptr(), None, hist.data_ptr(), B, H, W, C, K)
-        heads = [t for t in (logits, aux) if t is not None]
-        nhwc = [torch.empty((B, H, W, Cs), dtype=torch.float32, device=dev) for _ in heads]
-        dn = [torch.empty_like(x) for x in nhwc]
-        for t, x in zip(heads, nhwc):
-            L.call("msau_nchw_to_nhwc", s, L.F32, t.contiguous().float().data_ptr(), x.data_ptr(), B, C, Cs, H, W)
+        loss3 = torch.empty((3,), dtype=torch.float32, device=logits.device)
         two = aux is not None
-        L.call("msau_masked_cost", s, L.F32, kind, param, nhwc[0].data_ptr(), nhwc[1].data_ptr() if two else None, label.data_ptr(), None,
-               class_w.data_ptr() if class_w is not None else None, hist.data_ptr() if hist is not None else None, K, dn[0].data_ptr(),
-               dn[1].data_ptr() if two else None, loss3.data_ptr(), ws.data_ptr(), B, H, W, C, Cs)
-        grads = []
-        for d in dn:
-            g = torch.empty((B, C, H, W), dtype=torch.float32, device=dev)
-            L.call("msau_nhwc_to_nchw", s, L.F32, d.data_ptr(), g.data_ptr(), B, C, Cs, H, W)
-            grads.append(g)
-        ctx.save_for_backward(*grads)
+
+        def kernel(nhwc, dn, label, hist, B, H, W, C, Cs, s):
+            ws = torch.empty((int(L.load().msau_masked_cost_ws_floats(kind, B, H, W, C)),), dtype=torch.float32, device=logits.device)
+            L.call("msau_masked_cost", s, L.F32, kind, param, nhwc[0], nhwc[1] if two else None, label, None,
+                   class_w.data_ptr() if class_w is not None else None, hist, NCHW_HIST_K, dn[0], dn[1] if two else None,
+                   loss3.data_ptr(), ws.data_ptr(), B, H, W, C, Cs)
+
+        ctx.save_for_backward(*nchw_loss((logits, aux) if two else (logits,), label, kernel,
+                                         hist=class_w is not None or kind == L.COST_DICE))
         ctx.has_aux = two
         return loss3[0].clone()
 

@@ -1325,6 +1325,8 @@ class Plan:
                 op._meta()
         for pr in self.pairs:
             pr.late_bind()
+        from .plan_loss import LossSite     # (that module imports this one)
+        self.loss = LossSite(self)          # with a training plan's loss buffers; it states the loss rows of the boundary launches
         boundary = self._boundary_launches()
         # The bottleneck attention of a stage (f, g, h projections + core: model/layers/attention.py:152-162) feeds ONLY the next stage's
         # level-3 coupling (model/model.py:149-150: the decoder consumes the pre-attention tensor), so in the forward sweep it is a side
@@ -1399,18 +1401,10 @@ class Plan:
         for r in frecs + (recs if self.training else []) + boundary:
             n, nbytes, flops = self.launch_meta.get(r.key, (0, 0.0, 0.0))
             self.launch_meta[r.key] = (n + 1, nbytes + r.nbytes, flops + r.flops)
-        HW = self.H * self.W
         lg = self.logits
         self.out_logits = torch.zeros((self.B, lg.C, lg.H, lg.W), dtype=torch.float32, device=self.device)
         self.out_aux = torch.zeros((self.B, self.aux.C, self.aux.H, self.aux.W), dtype=torch.float32,
                                    device=self.device) if self.aux is not None else None
-        if self.training:
-            # label counts: a sample spread over K workgroups (msau_label_counts_split), the K integers added up by the CE launch
-            self.counts_k = max(1, min(16, 256 // self.B)) if self.B <= 1024 and _env_on("MSAU_LABEL_SPLIT") else 1
-            self.counts = torch.zeros((self.B * self.counts_k,), dtype=torch.int32, device=self.device)
-            self.ce_ws = torch.zeros((int(L.load().msau_ce_ws_floats(self.B * HW)),), dtype=torch.float32, device=self.device)
-            self.ce_multi_ws = torch.zeros((int(L.load().msau_ce_multi_ws_floats(self.B * HW)),), dtype=torch.float32, device=self.device)
-            self.loss_buf = torch.zeros((1,), dtype=torch.float32, device=self.device)
 
     def _assign_buffers(self):
         """Forward-only: give every activation a buffer that is free from its producer to its last reader.  Buffers are
@@ -1473,11 +1467,7 @@ class Plan:
         nparam = sum(int(math.prod(shp)) for shp in self.pshape.values())
         out.append(Launch(0, None, "msau_pack_params", nparam * 4 + self._pack_bytes))
         if self.training:
-            HW = self.H * self.W
-            lg = self.logits
-            nl = 2 if self.aux is not None else 1
-            out.append(Launch(0, None, "msau_label_counts", self.B * HW * 8))
-            out.append(Launch(0, None, "msau_masked_ce_multi" if lg.Cs <= 16 else "msau_masked_ce", self.B * HW * (8 + nl * 2 * lg.Cs * esz)))
+            out += self.loss.masked_launches(False)
             self.reduce_bytes = self._slab_elems * 4 + nparam * 4          # (charged to the reduce records of the backward)
             out.append(Launch(0, None, "msau_clip_adam_step", nparam * 4 * 8))       # g twice, p, m, v read; p, m, v written
         return out
@@ -1841,263 +1831,35 @@ class Plan:
                 if maskb:       # output produced through a ReLU and consumed by nothing else (op-level tests only)
                     act.grad.mul_(act.data > 0)
 
-    def cost_hist_k(self, dice: bool) -> int:
-        """rows per document of the label histograms a cost takes (msau_label_hist's K).  Dice: K is also the slabs per document of
-        its reduction pass.  Two workgroups per compute unit were the best of three choices in ONE measurement: B = 16 on 320 x 256,
-        256 compute units (profiles/unet_cost.md: K = 16 / 32 / 64 -> 163 / 146 / 150 us in bf16).  Any other B or canvas size is
-        unmeasured, and what bounds that pass has not been profiled."""
-        return max(1, min(32, 512 // self.B)) if dice else max(1, min(16, 256 // self.B))
+    # ---- the loss site (msau_amd/plan_loss.py): its entry points, their accounting and their launch geometry, under the plan's names
+    def loss_grads(self, labels: torch.Tensor, cost=None, class_w: Optional[torch.Tensor] = None) -> torch.Tensor:
+        return self.loss.loss_grads(labels, cost, class_w)
 
-    def masked_cost_launches(self, weighted: bool, cost=None) -> List[Launch]:
-        """the launches of `loss_grads(labels, cost, class_w)`, stated as `unet_launches` states those of `loss_grads_unet`: key and
-        algorithmic bytes.  The default (no cost or "cross_entropy", no weights) is what `_boundary_launches` states: the label
-        counts and the masked CE.  Anything else is msau_masked_cost: the label and both heads' logits read and both gradients
-        written; class weights or Dice put msau_label_hist in front (one launch: one label map), otherwise the call counts the
-        labelled pixels itself (the labels once more); Dice reads label and logits once more (the reduction behind its gradient
-        pass)."""
-        cost = unet_cost(cost)
-        esz = 4 if self.dtype == L.F32 else 2
-        HW, lg = self.H * self.W, self.logits
-        nl = 2 if self.aux is not None else 1
-        if cost is None and not weighted:
-            return [Launch(0, None, "msau_label_counts", self.B * HW * 8),
-                    Launch(0, None, "msau_masked_ce_multi" if lg.Cs <= 16 else "msau_masked_ce", self.B * HW * (8 + nl * 2 * lg.Cs * esz))]
-        dice = cost is not None and cost.kind == L.COST_DICE
-        out = [Launch(0, None, "msau_label_hist", self.B * HW * 8)] if weighted or dice else []
-        nbytes = self.B * HW * (8 + nl * 2 * lg.Cs * esz)
-        if dice:
-            nbytes += self.B * HW * (8 + nl * lg.Cs * esz)
-        elif not weighted:
-            nbytes += self.B * HW * 8
-        out.append(Launch(0, None, "msau_masked_cost", nbytes))
-        return out
-
-    def _loss_grads_cost(self, labels: torch.Tensor, cost: Optional[UnetCost], class_w: Optional[torch.Tensor]) -> torch.Tensor:
-        """`loss_grads` under a cost or class weights (msau_masked_cost)"""
-        lg, ax = self.logits, self.aux
-        assert ax is None or (ax.C, ax.Cs, ax.H, ax.W) == (lg.C, lg.Cs, lg.H, lg.W), "the auxiliary head must have the final head's shape"
-        assert (lg.H, lg.W) == (self.H, self.W)
-        kind, param = (cost.kind, cost.param) if cost is not None else (L.COST_CE, 0.0)
-        s = self._stream()
-        if getattr(self, "masked_loss3", None) is None:
-            self.masked_loss3 = torch.zeros((3,), dtype=torch.float32, device=self.device)
-            self.masked_hist = None
-        ext = self.extents.data_ptr() if self.ragged else None      # level 0: the documents' own (h, w)
-        dice = kind == L.COST_DICE
-        K, hist = self.cost_hist_k(dice), None
-        if class_w is not None:
-            assert class_w.dtype == torch.float32 and class_w.is_contiguous() and class_w.numel() == lg.C and class_w.device == lg.data.device
-        if class_w is not None or dice:
-            if self.masked_hist is None or self.masked_hist.shape[1] < K:      # (grows once when a plan's cost changes to Dice)
-                self.masked_hist = torch.zeros((self.B, K, lg.C), dtype=torch.int32, device=self.device)
-            hist = self.masked_hist.data_ptr()
-            L.call("msau_label_hist", s, labels.data_ptr(), ext, hist, self.B, self.H, self.W, lg.C, K)
-        if getattr(self, "masked_cost_ws", None) is None or self.masked_cost_ws[0] != dice:
-            n = int(L.load().msau_masked_cost_ws_floats(kind, self.B, self.H, self.W, lg.C))
-            self.masked_cost_ws = (dice, torch.zeros((n,), dtype=torch.float32, device=self.device))
-        L.call("msau_masked_cost", s, self.dtype, kind, param, lg.data.data_ptr(), _ptr(ax.data) if ax is not None else None,
-               labels.data_ptr(), ext, _ptr(class_w), hist, K, lg.grad.data_ptr(), _ptr(ax.grad) if ax is not None else None,
-               self.masked_loss3.data_ptr(), self.masked_cost_ws[1].data_ptr(), self.B, self.H, self.W, lg.C, lg.Cs)
-        return self.masked_loss3[:1]
+    def loss_grads_unet(self, labels: torch.Tensor, aux_labels: Optional[torch.Tensor], class_w=None, cost=None) -> torch.Tensor:
+        return self.loss.loss_grads_unet(labels, aux_labels, class_w, cost)
 
     def eval_masked(self, labels: torch.Tensor, class_w: Optional[torch.Tensor] = None, out=None, cost=None):
-        """The masked loss and the accuracy counts per document, forward only (msau_masked_cost_eval): the counterpart of
-        `eval_unet` for the loss of `loss_grads` -- after `forward(export=False)` on a forward-only plan, on the logits both heads
-        left in the plan, both against `labels` (int64 [B,H,W]; the kernel reads the extents itself).  `class_w` and `cost` as
-        `loss_grads` takes them; None: the masked CE's per-document loss.  -> (doc_loss fp32 [B, 2], doc_counts int32 [B, 2, 2]) on
-        the device, as `eval_unet` returns them; `out`: a pair of such tensors to write.  No gradient buffer is touched and nothing
-        waits for the device."""
-        cost = unet_cost(cost)
-        lg, ax = self.logits, self.aux
-        assert labels.dtype == torch.int64 and labels.is_contiguous() and tuple(labels.shape) == (self.B, self.H, self.W)
-        assert ax is None or (ax.C, ax.Cs, ax.H, ax.W) == (lg.C, lg.Cs, lg.H, lg.W), "the auxiliary head must have the final head's shape"
-        assert (lg.H, lg.W) == (self.H, self.W)
-        if class_w is not None:
-            assert class_w.dtype == torch.float32 and class_w.is_contiguous() and class_w.numel() == lg.C and class_w.device == lg.data.device
-        if out is None:
-            out = (torch.empty((self.B, 2), dtype=torch.float32, device=self.device),
-                   torch.empty((self.B, 2, 2), dtype=torch.int32, device=self.device))
-        doc_loss, doc_counts = out
-        assert doc_loss.dtype == torch.float32 and doc_loss.is_contiguous() and tuple(doc_loss.shape) == (self.B, 2) \
-            and doc_counts.dtype == torch.int32 and doc_counts.is_contiguous() and tuple(doc_counts.shape) == (self.B, 2, 2) \
-            and doc_loss.device == doc_counts.device == lg.data.device, "out: (fp32 [B, 2], int32 [B, 2, 2]) on the model's device"
-        kind, param = (cost.kind, cost.param) if cost is not None else (L.COST_CE, 0.0)
-        dice = kind == L.COST_DICE
-        if getattr(self, "masked_eval_ws", None) is None or self.masked_eval_ws[0] != dice:      # for the largest K, as eval_unet's
-            n = int(L.load().msau_masked_cost_eval_ws_bytes(kind, self.B, 256, lg.C))
-            self.masked_eval_ws = (dice, torch.zeros((n,), dtype=torch.uint8, device=self.device))
-        L.call("msau_masked_cost_eval", self._stream(), self.dtype, kind, param, lg.data.data_ptr(), _ptr(ax.data) if ax is not None else None,
-               labels.data_ptr(), self.extents.data_ptr() if self.ragged else None, _ptr(class_w), self.unet_eval_k(), doc_loss.data_ptr(),
-               doc_counts.data_ptr(), self.masked_eval_ws[1].data_ptr(), self.B, self.H, self.W, lg.C, lg.Cs)
-        return doc_loss, doc_counts
+        return self.loss.eval_masked(labels, class_w, out, cost)
 
-    def loss_grads(self, labels: torch.Tensor, cost=None, class_w: Optional[torch.Tensor] = None) -> torch.Tensor:
-        """Masked CE (model/model.py:446-459, batch rule SURVEY 8e) fused with its gradient: writes d(logits), d(aux)
-        in place and returns the loss as a 1-element device tensor.  One launch for final + aux.
-        `cost` (`unet_cost`) and `class_w` (fp32 [n_class] on the device): the masked loss under the focal or the soft Dice cost and
-        with class weights (msau_masked_cost, which reads the extents of a ragged plan itself: whatever the label canvas
-        holds outside the documents is ignored).  The three values (total, final, auxiliary) stay readable as `masked_loss3`, the
-        total is returned.  With neither -- also with "cross_entropy" by name -- the launches are those below, unchanged."""
-        assert labels.dtype == torch.int64 and labels.is_contiguous() and tuple(labels.shape) == (self.B, self.H, self.W)
-        cost = unet_cost(cost)
-        if cost is not None or class_w is not None:
-            return self._loss_grads_cost(labels, cost, class_w)
-        s = self._stream()
-        HW = self.H * self.W
-        if self.ragged:                                  # the label canvas: 0 (= not counted) outside the documents
-            if getattr(self, "_labels_buf", None) is None:
-                self._labels_buf = torch.zeros_like(labels)
-            self._zero_outside(labels, self._labels_buf, 1, self.H, self.W, 8)
-            labels = self._labels_buf
-        lg, ax = self.logits, self.aux
-        if lg.Cs <= 16 and self.B * HW < (1 << 31) and (ax is None or (ax.C, ax.Cs) == (lg.C, lg.Cs)) \
-                and _env_on("MSAU_CE_MULTI"):
-            K = self.counts_k
-            if K > 1:
-                L.call("msau_label_counts_split", s, labels.data_ptr(), self.counts.data_ptr(), self.B, HW, K, key="msau_label_counts")
-            else:
-                L.call("msau_label_counts", s, labels.data_ptr(), self.counts.data_ptr(), self.B, HW)
-            L.call("msau_masked_ce_multi", s, self.dtype, lg.data.data_ptr(), _ptr(ax.data) if ax is not None else None,
-                   labels.data_ptr(), self.counts.data_ptr(), lg.grad.data_ptr(), _ptr(ax.grad) if ax is not None else None,
-                   self.loss_buf.data_ptr(), self.ce_multi_ws.data_ptr(), self.B, HW, lg.C, lg.Cs, 1.0 / self.B, K)
-            return self.loss_buf
-        L.call("msau_label_counts", s, labels.data_ptr(), self.counts.data_ptr(), self.B, HW)
-        self.loss_buf.zero_()
-        for act in (self.logits, self.aux):
-            if act is None:
-                continue
-            L.call("msau_masked_ce", s, self.dtype, act.data.data_ptr(), labels.data_ptr(), self.counts.data_ptr(),
-                   act.grad.data_ptr(), self.loss_buf.data_ptr(), self.ce_ws.data_ptr(), self.B, HW, act.C, act.Cs,
-                   1.0 / self.B)
-        return self.loss_buf
+    def eval_unet(self, labels: torch.Tensor, aux_labels: Optional[torch.Tensor], class_w=None, out=None, cost=None):
+        return self.loss.eval_unet(labels, aux_labels, class_w, out, cost)
+
+    def masked_cost_launches(self, weighted: bool, cost=None) -> List[Launch]:
+        return self.loss.masked_launches(weighted, cost)
 
     def unet_launches(self, weighted: bool, cost=None) -> List[Launch]:
-        """the launches of `loss_grads_unet`, stated as `_boundary_launches` states those of `loss_grads` (which they replace in a
-        key-value training step): key and algorithmic bytes, for the step's accounting and a profiler's attribution.  `cost` as
-        `loss_grads_unet` takes it: the focal loss moves the cross entropy's bytes under its own key; the Dice loss always takes
-        the histograms and reads label and logits once more (the reduction behind its gradient pass)."""
-        cost = unet_cost(cost)
-        esz = 4 if self.dtype == L.F32 else 2
-        HW, lg = self.H * self.W, self.logits
-        nl = 2 if self.aux is not None else 1
-        dice = cost is not None and cost.kind == L.COST_DICE
-        out = [Launch(0, None, "msau_label_hist", self.B * HW * 8)] * (nl if weighted or dice else 0)
-        nbytes = self.B * HW * nl * (8 + 2 * lg.Cs * esz)
-        if dice:
-            nbytes += self.B * HW * nl * (8 + lg.Cs * esz)
-        out.append(Launch(0, None, "msau_unet_ce" if cost is None else "msau_unet_cost", nbytes))
-        return out
-
-    def loss_grads_unet(self, labels: torch.Tensor, aux_labels: Optional[torch.Tensor], class_w: Optional[torch.Tensor] = None,
-                        cost=None) -> torch.Tensor:
-        """UNetLoss (model/training/cost.py:35-65: CE over every pixel, class 0 counted, 0.5 final + 0.5 auxiliary, optional class
-        weights) fused with its gradient, under the ragged rule: every document computes what it computes alone, the batch is the
-        mean of the documents.  `labels` / `aux_labels` int64 [B,H,W]: each head has its own map; the kernel reads the extents
-        itself, so the canvases are not copied and whatever they hold outside the documents is ignored.  `class_w`: fp32 [n_class]
-        on the device; only then the per-document class histograms are taken (one launch per head).  Writes d(logits), d(aux) in
-        place and returns the plan's 3-float buffer (total, final, auxiliary).
-        `cost` (`unet_cost`: None, a dict such as {"cost_name": "focal", "gamma": 2.0} or {"cost_name": "dice", "smooth": 1.0}): the
-        focal or the soft Dice loss under the same rules (msau_unet_cost; Dice always takes the histograms).  None or
-        "cross_entropy": the path above, launch for launch."""
-        cost = unet_cost(cost)
-        lg, ax = self.logits, self.aux
-        for t in (labels,) + ((aux_labels,) if ax is not None else ()):
-            assert t is not None and t.dtype == torch.int64 and t.is_contiguous() and tuple(t.shape) == (self.B, self.H, self.W)
-        assert ax is None or (ax.C, ax.Cs, ax.H, ax.W) == (lg.C, lg.Cs, lg.H, lg.W), "the auxiliary head must have the final head's shape"
-        assert (lg.H, lg.W) == (self.H, self.W)
-        s = self._stream()
-        if getattr(self, "unet_loss_buf", None) is None:
-            self.unet_loss_buf = torch.zeros((3,), dtype=torch.float32, device=self.device)
-            self.unet_ws = torch.zeros((int(L.load().msau_unet_ce_ws_floats(self.B * self.H * self.W)),), dtype=torch.float32, device=self.device)
-            self.unet_hist_k, self.unet_dice_k = self.cost_hist_k(False), self.cost_hist_k(True)
-            self.unet_hist = None
-        ext = self.extents.data_ptr() if self.ragged else None      # level 0: the documents' own (h, w)
-        dice = cost is not None and cost.kind == L.COST_DICE
-        K, hist = self.unet_dice_k if dice else self.unet_hist_k, None
-        if class_w is not None:
-            assert class_w.dtype == torch.float32 and class_w.is_contiguous() and class_w.numel() == lg.C and class_w.device == lg.data.device
-        if class_w is not None or dice:
-            if self.unet_hist is None or self.unet_hist.shape[2] < K:      # (grows once when a plan's cost changes to Dice)
-                self.unet_hist = torch.zeros((2, self.B, K, lg.C), dtype=torch.int32, device=self.device)
-            hist = self.unet_hist.data_ptr()
-            for t, lab in enumerate((labels, aux_labels) if ax is not None else (labels,)):
-                L.call("msau_label_hist", s, lab.data_ptr(), ext, hist + 4 * t * self.B * K * lg.C, self.B, self.H, self.W, lg.C, K)
-        if cost is not None:
-            if getattr(self, "unet_cost_ws", None) is None or self.unet_cost_ws[0] != cost.kind:
-                n = int(L.load().msau_unet_cost_ws_floats(cost.kind, self.B, self.H, self.W, lg.C))
-                self.unet_cost_ws = (cost.kind, torch.zeros((n,), dtype=torch.float32, device=self.device))
-            L.call("msau_unet_cost", s, self.dtype, cost.kind, cost.param, lg.data.data_ptr(), _ptr(ax.data) if ax is not None else None,
-                   labels.data_ptr(), aux_labels.data_ptr() if ax is not None else None, ext, _ptr(class_w), hist, K, lg.grad.data_ptr(),
-                   _ptr(ax.grad) if ax is not None else None, self.unet_loss_buf.data_ptr(), self.unet_cost_ws[1].data_ptr(),
-                   self.B, self.H, self.W, lg.C, lg.Cs)
-            return self.unet_loss_buf
-        L.call("msau_unet_ce", s, self.dtype, lg.data.data_ptr(), _ptr(ax.data) if ax is not None else None, labels.data_ptr(),
-               aux_labels.data_ptr() if ax is not None else None, ext, _ptr(class_w), hist, K, lg.grad.data_ptr(),
-               _ptr(ax.grad) if ax is not None else None, self.unet_loss_buf.data_ptr(), self.unet_ws.data_ptr(),
-               self.B, self.H, self.W, lg.C, lg.Cs)
-        return self.unet_loss_buf
+        return self.loss.unet_launches(weighted, cost)
 
     def unet_eval_launches(self, cost=None) -> List[Launch]:
-        """the launch of `eval_unet`, stated as `unet_launches` states those of `loss_grads_unet`: key and algorithmic bytes (per head
-        the int64 label and the pixel's stored logits, read once; the K partial rows and the finish launch are noise beside them).
-        `cost` as `eval_unet` takes it: Dice reads both once more and the labels a third time (its own histograms)."""
-        cost = unet_cost(cost)
-        esz = 4 if self.dtype == L.F32 else 2
-        nl = 2 if self.aux is not None else 1
-        nbytes = self.B * self.H * self.W * nl * (8 + self.logits.Cs * esz)
-        if cost is not None and cost.kind == L.COST_DICE:
-            nbytes += self.B * self.H * self.W * nl * (16 + self.logits.Cs * esz)
-        return [Launch(0, None, "msau_unet_eval" if cost is None else "msau_unet_cost_eval", nbytes)]
+        return self.loss.unet_eval_launches(cost)
+
+    def cost_hist_k(self, dice: bool) -> int:
+        return self.loss.hist_k(dice)
 
     def unet_eval_k(self) -> int:
-        """workgroups per document of `eval_unet`: enough to give every compute unit two workgroups, never more than the smallest
-        document has rows (more would only be empty slabs), at most the kernel's 256.  Reasoned, not measured."""
-        if getattr(self, "_cu_count", None) is None:
-            self._cu_count = int(torch.cuda.get_device_properties(self.device).multi_processor_count)
-        rows = int(self._ext_host[0, :, 0].min()) if self.ragged else self.H      # the pinned host copy of set_extents: no sync
-        return max(1, min(256, rows, -(-2 * self._cu_count // self.B)))
+        return self.loss.eval_k()
 
-    def eval_unet(self, labels: torch.Tensor, aux_labels: Optional[torch.Tensor], class_w: Optional[torch.Tensor] = None, out=None,
-                  cost=None):
-        """UNetLoss and the reference's accuracy per document, forward only (msau_unet_eval): after `forward(export=False)` on a
-        forward-only plan, on the logits both heads left in the plan (`TrainEngine.step_unet(stats=...)` calls it on the training
-        plan's, between the forward and the loss kernel).  `labels` / `aux_labels` / `class_w` as `loss_grads_unet` takes
-        them; the kernel reads the extents itself.  -> (doc_loss fp32 [B, 2], doc_counts int32 [B, 2, 2]) on the device, head 0 =
-        final, head 1 = auxiliary, counts = (labelled, correct); `out`: a pair of such tensors to write instead of fresh ones.  No
-        gradient buffer is touched and nothing waits for the device.  `cost` as `loss_grads_unet` takes it: doc_loss is then the
-        document's loss under that cost (msau_unet_cost_eval), the counts are unchanged."""
-        cost = unet_cost(cost)
-        lg, ax = self.logits, self.aux
-        for t in (labels,) + ((aux_labels,) if ax is not None else ()):
-            assert t is not None and t.dtype == torch.int64 and t.is_contiguous() and tuple(t.shape) == (self.B, self.H, self.W)
-        assert ax is None or (ax.C, ax.Cs, ax.H, ax.W) == (lg.C, lg.Cs, lg.H, lg.W), "the auxiliary head must have the final head's shape"
-        assert (lg.H, lg.W) == (self.H, self.W)
-        if class_w is not None:
-            assert class_w.dtype == torch.float32 and class_w.is_contiguous() and class_w.numel() == lg.C and class_w.device == lg.data.device
-        if out is None:
-            out = (torch.empty((self.B, 2), dtype=torch.float32, device=self.device),
-                   torch.empty((self.B, 2, 2), dtype=torch.int32, device=self.device))
-        doc_loss, doc_counts = out
-        assert doc_loss.dtype == torch.float32 and doc_loss.is_contiguous() and tuple(doc_loss.shape) == (self.B, 2) \
-            and doc_counts.dtype == torch.int32 and doc_counts.is_contiguous() and tuple(doc_counts.shape) == (self.B, 2, 2) \
-            and doc_loss.device == doc_counts.device == lg.data.device, "stats: (fp32 [B, 2], int32 [B, 2, 2]) on the model's device"
-        K = self.unet_eval_k()
-        if getattr(self, "unet_eval_ws", None) is None:          # for the largest K: the extents, and with them K, change per batch
-            self.unet_eval_ws = torch.zeros((int(L.load().msau_unet_eval_ws_bytes(self.B, 256)),), dtype=torch.uint8, device=self.device)
-        if cost is not None:
-            if getattr(self, "unet_cost_eval_ws", None) is None or self.unet_cost_eval_ws[0] != cost.kind:
-                n = int(L.load().msau_unet_cost_eval_ws_bytes(cost.kind, self.B, 256, lg.C))
-                self.unet_cost_eval_ws = (cost.kind, torch.zeros((n,), dtype=torch.uint8, device=self.device))
-            L.call("msau_unet_cost_eval", self._stream(), self.dtype, cost.kind, cost.param, lg.data.data_ptr(),
-                   _ptr(ax.data) if ax is not None else None, labels.data_ptr(), aux_labels.data_ptr() if ax is not None else None,
-                   self.extents.data_ptr() if self.ragged else None, _ptr(class_w), K, doc_loss.data_ptr(), doc_counts.data_ptr(),
-                   self.unet_cost_eval_ws[1].data_ptr(), self.B, self.H, self.W, lg.C, lg.Cs)
-            return doc_loss, doc_counts
-        L.call("msau_unet_eval", self._stream(), self.dtype, lg.data.data_ptr(), _ptr(ax.data) if ax is not None else None,
-               labels.data_ptr(), aux_labels.data_ptr() if ax is not None else None, self.extents.data_ptr() if self.ragged else None,
-               _ptr(class_w), K, doc_loss.data_ptr(), doc_counts.data_ptr(), self.unet_eval_ws.data_ptr(), self.B, self.H, self.W,
-               lg.C, lg.Cs)
-        return doc_loss, doc_counts
+    masked_loss3 = property(lambda self: self.loss.masked_loss3)
 
     def set_native_dp(self, comm: int, comm_stream, buckets, flat_grads: torch.Tensor):
         """Data parallelism through the C ABI (msau_allreduce_bucket, csrc/comm.hip): rebuild the backward sequence with one

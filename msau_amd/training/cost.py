@@ -10,6 +10,7 @@ import torch
 
 from .. import _lib as L
 from ..plan import unet_cost
+from ..plan_loss import NCHW_HIST_K, nchw_loss
 
 
 class _SoftmaxCE(torch.autograd.Function):
@@ -17,22 +18,13 @@ class _SoftmaxCE(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, logits, target):
-        B, C, H, W = logits.shape
-        dev = logits.device
-        Cs = -(-C // 8) * 8
-        s = torch.cuda.current_stream().cuda_stream
-        lg = logits.contiguous().float()
-        tg = target.reshape(B, H, W).contiguous().long()
-        nhwc = torch.empty((B, H, W, Cs), dtype=torch.float32, device=dev)
-        dn = torch.empty_like(nhwc)
-        loss = torch.zeros((1,), dtype=torch.float32, device=dev)
-        ws = torch.zeros((int(L.load().msau_ce_ws_floats(B * H * W)),), dtype=torch.float32, device=dev)
-        L.call("msau_nchw_to_nhwc", s, L.F32, lg.data_ptr(), nhwc.data_ptr(), B, C, Cs, H, W)
-        L.call("msau_softmax_ce", s, L.F32, nhwc.data_ptr(), tg.data_ptr(), dn.data_ptr(), loss.data_ptr(), ws.data_ptr(),
-               B, H * W, C, Cs, 1.0 / (B * H * W))
-        g = torch.empty((B, C, H, W), dtype=torch.float32, device=dev)
-        L.call("msau_nhwc_to_nchw", s, L.F32, dn.data_ptr(), g.data_ptr(), B, C, Cs, H, W)
-        ctx.save_for_backward(g)
+        loss = torch.zeros((1,), dtype=torch.float32, device=logits.device)
+
+        def kernel(nhwc, dn, label, hist, B, H, W, C, Cs, s):
+            ws = torch.zeros((int(L.load().msau_ce_ws_floats(B * H * W)),), dtype=torch.float32, device=logits.device)
+            L.call("msau_softmax_ce", s, L.F32, nhwc[0], label, dn[0], loss.data_ptr(), ws.data_ptr(), B, H * W, C, Cs, 1.0 / (B * H * W))
+
+        ctx.save_for_backward(*nchw_loss((logits,), target, kernel))
         return loss.reshape(())
 
     @staticmethod
@@ -48,22 +40,14 @@ class _WeightedSoftmaxCE(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, logits, target, class_w):
-        B, C, H, W = logits.shape
-        dev = logits.device
-        Cs = -(-C // 8) * 8
-        s = torch.cuda.current_stream().cuda_stream
-        lg = logits.contiguous().float()
-        tg = target.reshape(B, H, W).contiguous().long()
-        nhwc = torch.empty((B, H, W, Cs), dtype=torch.float32, device=dev)
-        dn = torch.empty_like(nhwc)
-        sums = torch.zeros((2,), dtype=torch.float32, device=dev)
-        ws = torch.zeros((int(L.load().msau_ce_ws_floats(B * H * W)),), dtype=torch.float32, device=dev)
-        L.call("msau_nchw_to_nhwc", s, L.F32, lg.data_ptr(), nhwc.data_ptr(), B, C, Cs, H, W)
-        L.call("msau_softmax_ce_weighted", s, L.F32, nhwc.data_ptr(), tg.data_ptr(), class_w.data_ptr(), dn.data_ptr(),
-               sums.data_ptr(), ws.data_ptr(), B, H * W, C, Cs)
-        g = torch.empty((B, C, H, W), dtype=torch.float32, device=dev)
-        L.call("msau_nhwc_to_nchw", s, L.F32, dn.data_ptr(), g.data_ptr(), B, C, Cs, H, W)
-        ctx.save_for_backward(g, sums)
+        sums = torch.zeros((2,), dtype=torch.float32, device=logits.device)
+
+        def kernel(nhwc, dn, label, hist, B, H, W, C, Cs, s):
+            ws = torch.zeros((int(L.load().msau_ce_ws_floats(B * H * W)),), dtype=torch.float32, device=logits.device)
+            L.call("msau_softmax_ce_weighted", s, L.F32, nhwc[0], label, class_w.data_ptr(), dn[0], sums.data_ptr(), ws.data_ptr(),
+                   B, H * W, C, Cs)
+
+        ctx.save_for_backward(*nchw_loss((logits,), target, kernel), sums)
         return sums[0] / sums[1]
 
     @staticmethod
@@ -78,28 +62,15 @@ class _UnetCost(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, logits, target, cost, class_w):
-        B, C, H, W = logits.shape
-        dev = logits.device
-        Cs = -(-C // 8) * 8
-        K = 4
-        s = torch.cuda.current_stream().cuda_stream
-        lg = logits.contiguous().float()
-        tg = target.reshape(B, H, W).contiguous().long()
-        nhwc = torch.empty((B, H, W, Cs), dtype=torch.float32, device=dev)
-        dn = torch.empty_like(nhwc)
-        loss3 = torch.empty((3,), dtype=torch.float32, device=dev)
-        ws = torch.empty((int(L.load().msau_unet_cost_ws_floats(cost.kind, B, H, W, C)),), dtype=torch.float32, device=dev)
-        hist = None
-        if class_w is not None or cost.kind == L.COST_DICE:
-            hist = torch.empty((B, K, C), dtype=torch.int32, device=dev)
-            L.call("msau_label_hist", s, tg.data_ptr(), None, hist.data_ptr(), B, H, W, C, K)
-        L.call("msau_nchw_to_nhwc", s, L.F32, lg.data_ptr(), nhwc.data_ptr(), B, C, Cs, H, W)
-        L.call("msau_unet_cost", s, L.F32, cost.kind, cost.param, nhwc.data_ptr(), None, tg.data_ptr(), None, None,
-               class_w.data_ptr() if class_w is not None else None, hist.data_ptr() if hist is not None else None, K, dn.data_ptr(), None,
-               loss3.data_ptr(), ws.data_ptr(), B, H, W, C, Cs)
-        g = torch.empty((B, C, H, W), dtype=torch.float32, device=dev)
-        L.call("msau_nhwc_to_nchw", s, L.F32, dn.data_ptr(), g.data_ptr(), B, C, Cs, H, W)
-        ctx.save_for_backward(g)
+        loss3 = torch.empty((3,), dtype=torch.float32, device=logits.device)
+
+        def kernel(nhwc, dn, label, hist, B, H, W, C, Cs, s):
+            ws = torch.empty((int(L.load().msau_unet_cost_ws_floats(cost.kind, B, H, W, C)),), dtype=torch.float32, device=logits.device)
+            L.call("msau_unet_cost", s, L.F32, cost.kind, cost.param, nhwc[0], None, label, None, None,
+                   class_w.data_ptr() if class_w is not None else None, hist, NCHW_HIST_K, dn[0], None, loss3.data_ptr(), ws.data_ptr(),
+                   B, H, W, C, Cs)
+
+        ctx.save_for_backward(*nchw_loss((logits,), target, kernel, hist=class_w is not None or cost.kind == L.COST_DICE))
         return loss3[0].clone()
 
     @staticmethod

@@ -297,3 +297,25 @@ def test_launch_accounting_and_the_default_path():
             plan.masked_cost_launches(False, {"cost_name": "tversky"})
         assert (plan.cost_hist_k(False), plan.cost_hist_k(True)) == (max(1, min(16, 256 // plan.B)), max(1, min(32, 512 // plan.B)))
         assert PD.launch_lists(plan) == before
+
+
+@pytest.mark.parametrize("name", ["small.f32.train", "small.bf16.train", "cfg1.f32.train", "cfg1.bf16.train"])
+def test_the_boundary_record_takes_its_loss_rows_from_the_loss_site(name):
+    """the loss rows of `_boundary_launches` ARE the default rows of `masked_cost_launches(False)` -- same records, same order, side
+    by side -- on a plan with an auxiliary head (small.*) and on one without (cfg1.*: num_blocks = 1), in both dtypes; the bytes are
+    written out here once more so that the two cannot drift together"""
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("plan_dump", os.path.join(ROOT, "tools", "plan_dump.py"))
+    PD = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(PD)
+    plan = PD.build_plan({c[0]: c for c in PD.cases()}[name], "cpu")
+    assert (plan.aux is not None) == name.startswith("small")
+    rows = plan.masked_cost_launches(False)
+    nl, esz = (2 if plan.aux is not None else 1), (4 if ".f32." in name else 2)
+    px = plan.B * plan.H * plan.W
+    assert [(r.kind, r.args, r.key, r.nbytes, r.flops) for r in rows] == \
+        [(0, None, "msau_label_counts", px * 8, 0.0), (0, None, "msau_masked_ce_multi", px * (8 + nl * 2 * plan.logits.Cs * esz), 0.0)]
+    boundary = plan._boundary_launches()
+    at = [i for i, r in enumerate(boundary) if r.key in {x.key for x in rows}]
+    assert at == list(range(at[0], at[0] + len(rows))) and [boundary[i] for i in at] == rows
+    assert all(plan.launch_meta[r.key] == (1, r.nbytes, 0.0) for r in rows)

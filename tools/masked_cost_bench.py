@@ -19,6 +19,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 
 from msau_amd import _lib as L
+from msau_amd.plan_loss import cost_hist_k
 
 
 def variants(dtype, B, H, W, C, dice_ks, dev):
@@ -33,7 +34,7 @@ def variants(dtype, B, H, W, C, dice_ks, dev):
     cw = (torch.rand(C, generator=g) + 0.5).to(dev)
     lib = L.load()
     s = lambda: torch.cuda.current_stream().cuda_stream
-    Kc = max(1, min(16, 256 // B))                                             # Plan.counts_k / Plan.cost_hist_k(False)
+    Kc = cost_hist_k(B, False)                                                 # also LossSite.counts_k at this B
     counts = torch.zeros(B * Kc, dtype=torch.int32, device=dev)
     loss = torch.zeros(3, device=dev)
     ws_multi = torch.zeros(int(lib.msau_ce_multi_ws_floats(B * H * W)), device=dev)
